@@ -14,8 +14,12 @@ configs[1]: wmask_rnb.conf, 512 rays x (64+64) samples per GPU, 3 lights, fp32.
     python bench.py --gpus 8 --scaling strong --global-rays 4096       # BASELINE config 4 (strong scaling)
     python bench.py --dtype bf16 --samples 256                         # BASELINE config 5's arithmetic (bf16 sweeps)
     python bench.py --mode mesh --resolution 512                       # validate_mesh's SDF grid (forward only)
+    python bench.py --full                                             # + roofline, CPU baseline, `also` legs, ...
+    python bench.py --dump-outputs DIR                                 # + what the last timed step returned, as DIR/*.npy
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
+A plain run sets up, warms up, times the steps and prints the line; everything else it can measure (the per-kernel event
+times behind `roofline`, the CPU baseline, the `also` legs, the pre-staged leg of --device-rays, marching cubes after
+--mode mesh) needs --full.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 """
 from __future__ import annotations
 
@@ -127,6 +131,31 @@ def kernel_classes(lib, steps, peak_tflops, traffic=None, terms=None):
     return out
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: all arrays together
+
+
+def dump_outputs(dirname, named):
+    """--dump-outputs: writes every tensor of `named` ({name: tensor}) as DIR/<name>.npy — floating tensors as float32
+    (float64 stays float64), integer / bool ones as float64 — in at most DUMP_BYTES together.  The smaller arrays are
+    written whole; one larger than its share of what is left becomes a fixed, seeded sample of its elements (flattened, in
+    index order), so two builds run with the same arguments write files that compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    items = sorted(named.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BYTES
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()
+        share = left // (len(items) - i) // t.element_size()
+        if t.numel() > share:
+            idx = torch.randint(0, t.numel(), (share,), generator=torch.Generator().manual_seed(0)).unique()   # (sorted)
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -140,21 +169,24 @@ def parse():
                     help="arithmetic of the SDF-network sweeps (bf16: bf16 operands, fp32 accumulate; config 5)")
     ap.add_argument("--mode", choices=("train", "render", "mesh"), default="train",
                     help="train: full train_rnb step (the metric); render: forward-only NeuSRenderer.render under no_grad "
-                         "(SURVEY 8d 'also'); mesh: validate_mesh's SDF grid + marching cubes")
+                         "(SURVEY 8d 'also'); mesh: validate_mesh's SDF grid (+ marching cubes with --full)")
     ap.add_argument("--device-rays", action="store_true",
                     help="--mode train: draw pixels and gather rays / targets / lights INSIDE the timed step with "
                          "DeviceRays.sample() on HBM-resident synthetic image stacks (SURVEY 8f-2) instead of pre-staged "
-                         "batches; the line also carries the pre-staged time of the same run")
+                         "batches; with --full the line also carries the pre-staged time of the same run")
     ap.add_argument("--stack", default="20x512x612", help="--device-rays: views x H x W of the synthetic capture "
                                                           "(config 5: 200x1024x1024, ~22 GB of HBM)")
     ap.add_argument("--resolution", type=int, default=512, help="--mode mesh: grid points per axis")
-    ap.add_argument("--no-marching-cubes", action="store_true", help="--mode mesh: time the SDF grid only")
+    ap.add_argument("--no-marching-cubes", action="store_true",
+                    help="--mode mesh --full: time the SDF grid only (a run without --full never meshes)")
     ap.add_argument("--warmup-mode", action="store_true", help="render_rnb_warmup instead of render_rnb")
     ap.add_argument("--no-albedo", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed steps of the CPU baseline (median reported; BASELINE.md 3)")
     ap.add_argument("--cpu-warmup", type=int, default=3, help="untimed warm-up steps of the CPU baseline")
-    ap.add_argument("--no-gemm-events", action="store_true")
+    ap.add_argument("--no-gemm-events", action="store_true",
+                    help="--full: no per-launch HIP events in the timed region (`roofline` null); a run without --full "
+                         "records none anyway")
     ap.add_argument("--deterministic", action="store_true", help="ordered reductions instead of fp32 atomics")
     ap.add_argument("--x3", action="store_true", help="request RNB_VARIANT_X3 explicitly (it is the default for the 256-wide shape)")
     ap.add_argument("--f32-mfma", action="store_true", help="A/B knob: native fp32 MFMA sweeps (RNB_VARIANT_F32_MFMA) instead of x3")
@@ -168,12 +200,18 @@ def parse():
     ap.add_argument("--no-x2h", dest="x2h", action="store_false", default=None,
                     help="A/B knob: forward-type sweeps on six bf16 terms like the backward ones (RNB_VARIANT_NO_X2H)")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the short extra legs (no-albedo, bf16 x 256 samples, render, fp32 MFMA) that the default "
+                    help="skip the short extra legs (no-albedo, bf16 x 256 samples, render, fp32 MFMA) that a --full "
                          "--gpus 1 train run appends under `also`")
     ap.add_argument("--also-steps", type=int, default=20, help="timed steps of each `also` leg")
     ap.add_argument("--torch-train-ops", action="store_true",
                     help="loss as the reference's chain of torch ops and torch.optim.Adam(fused=True) instead of "
                          "the library's one-launch loss and flat Adam")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure too: per-kernel event times (`roofline`), the CPU "
+                         "baseline, the `also` legs, the pre-staged leg of --device-rays, marching cubes of --mode mesh")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_BYTES >> 20} MB in all: a fixed, seeded sample of a larger output)")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 3 if a.mode == "mesh" else 50
@@ -413,9 +451,10 @@ def build_model(R, dev, samples, dtype, deterministic, fwd_ti=0, bwd_ti=0, dw_st
     return sdf, devnet, col, ren
 
 
-def measure_train(args, ctx, with_cpu=True):
+def measure_train(args, ctx, with_cpu=True, dump_dir=None):
     """One measurement of `args` on the process group `ctx` (init_distributed): warm-up, K timed steps, the line as a dict on
-    rank 0 (None elsewhere).  Emits nothing and leaves the process group alone."""
+    rank 0 (None elsewhere).  Emits nothing and leaves the process group alone.  With `dump_dir`, rank 0 writes what the
+    last timed step returned there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     world, rank, dev, backend, rehearsal = ctx
@@ -513,7 +552,7 @@ def measure_train(args, ctx, with_cpu=True):
     torch.cuda.synchronize()
     if rank == 0:
         print(f"[bench] warm-up done ({args.warmup} steps)", file=sys.stderr, flush=True)
-    use_events = not args.no_gemm_events and rank == 0
+    use_events = args.full and not args.no_gemm_events and rank == 0
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     barrier()
     if use_events:
@@ -544,8 +583,20 @@ def measure_train(args, ctx, with_cpu=True):
     final_loss = float(loss.detach())
     if rank == 0:
         print(f"[bench] timed region done: {elapsed:.3f} s for {args.steps} steps", file=sys.stderr, flush=True)
+    if dump_dir and rank == 0:
+        # what a caller of the step receives: the render's tensors, and after a train step the loss and the parameters
+        # Adam has just updated, with the gradients it used
+        named = {"out." + k: v for k, v in last_out[0].items() if torch.is_tensor(v)}
+        if not forward_only:
+            named["loss"] = loss
+            for prefix, m in (("sdf", sdf), ("deviation", devnet), ("color", col)):
+                for n, p in m.named_parameters():
+                    named[f"param.{prefix}.{n}"] = p
+                    if p.grad is not None:
+                        named[f"grad.{prefix}.{n}"] = p.grad
+        dump_outputs(dump_dir, named)
     prestaged_ms = None
-    if capture is not None:
+    if capture is not None and args.full:
         # the same steps on pre-staged batches, in the same process: what the in-step ray generation costs
         use_capture[0] = False
         for i in range(3):
@@ -760,8 +811,8 @@ def measure_train(args, ctx, with_cpu=True):
                 "stack": args.stack, "hbm_gb": round(sum(t.numel() * 4 for t in (capture.images, capture.light_directions,
                                                                                   capture.masks)) / 1e9, 2),
                 "ms_per_step_with_in_step_ray_generation": round(ms_per_step, 3),
-                "ms_per_step_prestaged_batches": round(prestaged_ms, 3),
-                "delta_ms": round(ms_per_step - prestaged_ms, 3),
+                "ms_per_step_prestaged_batches": round(prestaged_ms, 3) if prestaged_ms is not None else None,   # (--full)
+                "delta_ms": round(ms_per_step - prestaged_ms, 3) if prestaged_ms is not None else None,
                 "note": "DeviceRays.sample() (2 x torch.randint + rnb_gen_rays_at_view) and the renderer's own torch.rand "
                         "inside the timed step; `value` is this configuration"}
         if rehearsal:
@@ -792,11 +843,11 @@ def run_train(args):
     import torch.distributed as dist
     ctx = init_distributed(args)
     world, rank = ctx[0], ctx[1]
-    line = measure_train(args, ctx, with_cpu=False)
-    plain = (world == 1 and args.mode == "train" and not args.no_also and not args.device_rays and not args.no_albedo
-             and args.dtype == "f32" and not args.f32_mfma and args.x2h is None and not args.warmup_mode and args.rays == 512
-             and args.samples == 128)
-    if plain:
+    line = measure_train(args, ctx, with_cpu=False, dump_dir=args.dump_outputs)
+    with_also = (args.full and world == 1 and args.mode == "train" and not args.no_also and not args.device_rays and not args.no_albedo
+                 and args.dtype == "f32" and not args.f32_mfma and args.x2h is None and not args.warmup_mode and args.rays == 512
+                 and args.samples == 128)
+    if with_also:
         also = []
         for name, kw in ALSO_LEGS:
             la = copy.copy(args)
@@ -821,7 +872,7 @@ def run_train(args):
             print(f"[bench] also: {name}: {l['value']:.0f} {l['unit']}, {l['ms_per_step']} ms/step", file=sys.stderr, flush=True)
         line["also"] = also
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             forward_only = args.mode == "render"
             B = args.rays if args.scaling == "weak" else args.global_rays // world
             cpu = (cpu_baseline_render(B, args.samples, args.cpu_steps, args.cpu_warmup) if forward_only else
@@ -862,7 +913,7 @@ def run_mesh(args):
 
     for _ in range(args.warmup):
         step()
-    use_events = not args.no_gemm_events and rank == 0
+    use_events = args.full and not args.no_gemm_events and rank == 0
     barrier()
     if use_events:
         lib.rnb_profile_enable(1)
@@ -879,10 +930,12 @@ def run_mesh(args):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sdf_grid": u})
     # the step after the grid in validate_mesh (models/renderer.py:31): marching cubes on the volume still in HBM
     # (csrc/mcubes.hip; every rank holds the whole volume after the all-gather, rank 0 meshes it)
     mc = None
-    if rank == 0 and not args.no_marching_cubes:
+    if args.full and rank == 0 and not args.no_marching_cubes:
         v, tri = R.marching_cubes(u, 0.0)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -917,7 +970,7 @@ def run_mesh(args):
                     "flop_per_launch": round(gemm_fl.value / gemm_n.value, 1),
                     "step_frac": round(gemm_fl.value / args.steps / (ms * 1e-3) / 1e12 / peak, 4)}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline_mesh(1 << 20)
         line = {"metric": f"SDF grid points/sec of validate_mesh at {res}^3", "value": round(n * args.steps / elapsed, 1),
                 "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

@@ -345,3 +345,37 @@ def test_x2h_range_report_flags_weights_beyond_the_fp16_scale():
     rep = ren.x2h_range_report()
     assert not rep["ok"] and rep["layer"] == "sdf.lin3" and rep["max_abs_weight"] > 255.0
 
+
+
+def test_bench_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 files, the byte budget held, small arrays written whole and a larger one
+    as the same seeded sample every time (two builds run with the same arguments compare file for file)."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    g = torch.Generator().manual_seed(1)
+    named = {"loss": torch.tensor(0.5), "small": torch.rand(3, 5, generator=g), "half": torch.rand(64, generator=g).bfloat16(),
+             "exact": torch.rand(7, generator=g, dtype=torch.float64), "mask": torch.arange(10) % 2 == 0,
+             "big": torch.rand(1 << 20, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), named)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(k + ".npy" for k in named)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in named}
+    assert sum(a.nbytes for a in got.values()) <= 1 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["exact"].dtype == np.float64 and got["mask"].dtype == np.float64 and got["half"].dtype == np.float32
+    np.testing.assert_array_equal(got["small"], named["small"].numpy())
+    np.testing.assert_array_equal(got["mask"], named["mask"].double().numpy())
+    assert got["loss"].shape == () and float(got["loss"]) == 0.5
+    big = got["big"]
+    assert 0 < big.size < named["big"].numel()
+    # the largest array comes last and takes what the others left: a seeded draw of that many positions, each once, in
+    # index order
+    share = ((1 << 20) - sum(a.nbytes for k, a in got.items() if k != "big")) // 4
+    idx = torch.randint(0, named["big"].numel(), (share,), generator=torch.Generator().manual_seed(0)).unique()
+    assert bool((idx[1:] > idx[:-1]).all())
+    np.testing.assert_array_equal(big, named["big"][idx].numpy())
+    np.testing.assert_array_equal(big, np.load(tmp_path / "b" / "big.npy"))

@@ -5,7 +5,7 @@ set -e
 tag=$1; shift
 out=gpurun_out/ev_$tag
 mkdir -p $out
-python bench.py "$@" > $out/bench.json 2> $out/bench.err
+python bench.py --full "$@" > $out/bench.json 2> $out/bench.err
 tail -c 400 $out/bench.json; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ks -- python bench.py --no-cpu-baseline --steps 20 --warmup 5 --no-gemm-events "$@" > $out/ks.log 2>&1
 python tools/kstats.py $out/ks_kernel_stats.csv 25 30 > $out/kernel_table.txt

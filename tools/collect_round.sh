@@ -27,7 +27,7 @@ head -14 $out/kernel_table_f32.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ksbf -- python bench.py --no-cpu-baseline --no-also --steps 20 --warmup 5 --no-gemm-events --dtype bf16 --samples 256 > $out/ksbf.log 2>&1
 python tools/kstats.py $out/ksbf_kernel_stats.csv 25 30 > $out/kernel_table_bf16.txt
 echo "== bench legs"
-run() { name=$1; shift; echo "== $name: $*"; timeout -k 10 600 python bench.py "$@" > $out/$name.json 2> $out/$name.err; tail -c 200 $out/$name.json; echo; }
+run() { name=$1; shift; echo "== $name: $*"; timeout -k 10 600 python bench.py --full "$@" > $out/$name.json 2> $out/$name.err; tail -c 200 $out/$name.json; echo; }
 run bench_f32 --steps 50 --warmup 10
 run bench_no_x2h --steps 50 --warmup 10 --no-x2h --no-cpu-baseline --no-also
 run bench_render --mode render --steps 50 --warmup 10
