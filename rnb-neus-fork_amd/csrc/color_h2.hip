@@ -173,7 +173,9 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
     }
     pm = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));   // (the only unbounded entries of the encoding)
     // (every wave leaves its own word: nothing to initialise; the layers' flags start from zero behind the same barrier)
-    if (lane == 0) wmx[wave] = __builtin_amdgcn_ballot_w64(pm >= kH2ActLimit) != 0 ? 1.f : 0.f;
+    // (the ballot runs on every lane: under `lane == 0` it would see row 0 of the tile only)
+    const bool any = __builtin_amdgcn_ballot_w64(pm >= kH2ActLimit) != 0;
+    if (lane == 0) wmx[wave] = any ? 1.f : 0.f;
     if (tid < 2) ovf[tid] = 0;
   }
   __syncthreads();

@@ -114,7 +114,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     if constexpr (H2) {   // the only unbounded entries of the encoding are the coordinates themselves
       xm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fabsf(x[2]));
       // (every wave leaves its own word: nothing to initialise; the layers' flags start from zero behind the same barrier)
-      if (lane == 0) wmx[wave] = __builtin_amdgcn_ballot_w64(xm >= kH2ActLimit) != 0 ? 1.f : 0.f;
+      // (the ballot runs on every lane: under `lane == 0` it would see row 0 of the tile only)
+      const bool any = __builtin_amdgcn_ballot_w64(xm >= kH2ActLimit) != 0;
+      if (lane == 0) wmx[wave] = any ? 1.f : 0.f;
       if (tid < 2) ovf[tid] = 0;
     }
   }

@@ -116,7 +116,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
     }
     for (int idx = tid; idx < BT * FEP; idx += NT) GE[idx] = 0.f;
     if constexpr (H2) {   // (every wave leaves its own word: nothing to initialise; see fused_forward_kernel)
-      if (lane == 0) wmx[wave] = __builtin_amdgcn_ballot_w64(m >= kH2ActLimit) != 0 ? 1.f : 0.f;
+      // (the ballot runs on every lane: under `lane == 0` it would see columns 0..3 only)
+      const bool any = __builtin_amdgcn_ballot_w64(m >= kH2ActLimit) != 0;
+      if (lane == 0) wmx[wave] = any ? 1.f : 0.f;
       if (tid < 2) ovf[tid] = 0;
     }
     if constexpr (H2) sm = m;
