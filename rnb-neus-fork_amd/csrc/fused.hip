@@ -451,7 +451,10 @@ bool fused_supported(const Layout& L) {
   if (L.nh < 1) return false;
   for (int l = 0; l < L.nh; ++l)
     if (L.hid[l].Np != FH || (L.hid[l].Kp != FH && l != 0)) return false;
-  if (L.F > FH) return false;
+  // the FB sweep multiplies the feature adjoint as a full 256-column tile against a 256-row W_feat^T: a feature head of
+  // fewer than 225 rows (Fp < 256) read the albedo-input adjoint's PE columns and the next matrix's weights there, and gave
+  // NaN / wrong SDF gradients (feature widths 1 and 128); such shapes take the per-layer path
+  if (L.F > FH || (L.F > 0 && L.Fp != FH)) return false;
   return true;
 }
 

@@ -108,7 +108,11 @@ int make_layout(const rnb_model_desc* d, Layout* L) {
   L->total_all = L->total;
   if (d->variant & RNB_VARIANT_BF16) {
     if (!fused_supported(*L))
-      RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 needs the 256-wide SDF network shape (d_hidden 256, feature width <= 256)");
+      RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 needs the 256-wide SDF network shape (d_hidden 256, feature width 225..256)");
+    // bf16.hip multiplies layer 0 as 64 PE columns (Ep = 64: multires 5 or 6); with Ep = 32 it read past the matrix
+    if (L->Ep != 64) RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 needs 33..40 positional-encoding columns (multires 5 or 6), got %d", L->pe);
+    // a skip connection at layer 1: the albedo weight gradients are 8-11 x further from the bf16 emulation than its fp32 form
+    if (L->skip == 1) RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 does not support a skip connection at layer 1");
     if (d->variant & RNB_VARIANT_GENERIC) RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 and RNB_VARIANT_GENERIC exclude each other");
     L->total_all = L->total + L->total / 2;   // bf16 mirror of the weights behind the fp32 ones
   }

@@ -52,8 +52,11 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _model(R, mc, seed=0, sharpen=False, **variant):
-    if sharpen:
+def _model(R, mc, seed=0, sharpen=False, params=None, **variant):
+    """`params`: the named parameters to build from (else the sharpened fixture's or a geometric init of `seed`)."""
+    if params is not None:
+        p = {k: v.clone() for k, v in params.items()}
+    elif sharpen:
         from tests.golden_util import Golden
         p = Golden("full_main_sharp").params()
         with torch.no_grad():
@@ -178,8 +181,8 @@ def _emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order):
     return out, float(loss), grads
 
 
-def _step(R, mc, B, api="render_rnb", no_albedo=False, sharpen=True, seed=2, tag="", **variant):
-    p, sdf, dev, col, ren = _model(R, mc, seed=seed, sharpen=sharpen, **variant)
+def _step(R, mc, B, api="render_rnb", no_albedo=False, sharpen=True, seed=2, tag="", params=None, **variant):
+    p, sdf, dev, col, ren = _model(R, mc, seed=seed, sharpen=sharpen, params=params, **variant)
     warm = api == "render_rnb_warmup"
     batch = O.synthetic_batch(B, seed=40 + B, step=1, warmup=warm)
     b = {k: v.to(_dev()) for k, v in batch.items()}
