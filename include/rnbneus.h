@@ -190,6 +190,37 @@ int rnb_color_forward(const rnb_model_desc* desc, const float* packed, const flo
                       const float* normals, const float* feats, int64_t n, float* out, void* ws,
                       size_t ws_bytes, rnb_stream_t stream);
 
+/* ---- point-wise network calls with autograd (opt-in: SDFNetwork / RenderingNetwork.set_autograd) ----------------
+ * Replace autograd through the reference's direct calls: SDFNetwork.forward / .sdf / .sdf_hidden_appearance
+ * (models/fields.py:82-112), SDFNetwork.gradient with create_graph=True (:114-127, differentiated once more) and
+ * RenderingNetwork.forward (:177-215), as Runner.validate_mesh_texture (exp_runner.py:584-615) or an eikonal term on free
+ * points uses them.  The forward keeps the render path's per-point state in `ws`; the backward is the render backward
+ * below the composite (FB, RA, the weight gradients, the albedo backward) seeded with the caller's adjoints, plus the
+ * input adjoints.  Every adjoint (NULL = zero) may have any scale: the x2h scales are taken from its recorded maximum.
+ *   flags                 RNB_POINTS_FEATURE (feat_out / feat_bar), RNB_POINTS_NORMAL (nrm_out / nrm_bar; d sdf / d x),
+ *                         RNB_POINTS_COLOR (the albedo-net call); the forward and its backward take the same flags,
+ *                         descriptor, n and ws.  Without RNB_POINTS_NORMAL the reverse sweep's state is not kept.
+ * rnb_points_grad_workspace_bytes : host function; >= rnb_points_workspace_bytes for the same n
+ * rnb_sdf_forward_save  : sdf_out [n]; feat_out [n, d_out-1]; nrm_out [n,3]
+ * rnb_sdf_backward      : sdf_bar [n], feat_bar [n, d_out-1], nrm_bar [n,3] -> packed_grad (written, fp32 part of the
+ *                         packed layout: rnb_weightnorm_bwd maps it to the leaves) and x_bar [n,3] (NULL: not wanted)
+ * rnb_color_forward_save: out [n, d_out] from pts, normals [n,3] and feats [n, d_feature]
+ * rnb_color_backward    : alb_bar [n, d_out] -> packed_grad (albedo rows), feat_bar [n, d_feature], nrm_bar [n,3],
+ *                         pts_bar [n,3] (each optional).  view_dirs are not an input (mode no_view_dir). */
+enum { RNB_POINTS_FEATURE = 1, RNB_POINTS_NORMAL = 2, RNB_POINTS_COLOR = 4 };
+int rnb_points_grad_workspace_bytes(const rnb_model_desc* desc, int64_t n_points, int32_t flags, int64_t* bytes);
+int rnb_sdf_forward_save(const rnb_model_desc* desc, const float* packed, const float* pts, int64_t n,
+                         int32_t flags, float* sdf_out, float* feat_out, float* nrm_out, void* ws, size_t ws_bytes,
+                         rnb_stream_t stream);
+int rnb_sdf_backward(const rnb_model_desc* desc, const float* packed, int64_t n, int32_t flags, const float* sdf_bar,
+                     const float* feat_bar, const float* nrm_bar, float* packed_grad, float* x_bar, void* ws,
+                     size_t ws_bytes, rnb_stream_t stream);
+int rnb_color_forward_save(const rnb_model_desc* desc, const float* packed, const float* pts, const float* normals,
+                           const float* feats, int64_t n, float* out, void* ws, size_t ws_bytes, rnb_stream_t stream);
+int rnb_color_backward(const rnb_model_desc* desc, const float* packed, int64_t n, const float* alb_bar,
+                       float* packed_grad, float* feat_bar, float* nrm_bar, float* pts_bar, void* ws, size_t ws_bytes,
+                       rnb_stream_t stream);
+
 /* ---- SDF grid of validate_mesh --------------------------------------------------------------------
  * extract_fields (models/renderer.py:10-25) with query_func = -sdf_network.sdf (models/renderer.py:1219-1224):
  * volume[ix - x_begin, iy, iz] = out_scale * sdf(X[ix], Y[iy], Z[iz]) for x_begin <= ix < x_end, with

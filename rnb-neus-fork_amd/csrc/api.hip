@@ -155,6 +155,178 @@ RNB_API int rnb_color_forward(const rnb_model_desc* desc, const float* packed, c
 }
 
 // ---------------------------------------------------------------------------------------------------
+// point-wise autograd of the direct network calls (SDFNetwork.forward / .sdf / .gradient, RenderingNetwork.forward)
+// ---------------------------------------------------------------------------------------------------
+// What the forward keeps is the render path's per-point state (carve_points with PM_WITH_BACKWARD); without the normal
+// neither gz_l nor u_l is carved (PM_NO_REVERSE).  The backward is sweep_backward_parts below the composite.
+static int grad_mode(int32_t flags) {
+  int mode = PM_WITH_BACKWARD | ((flags & RNB_POINTS_NORMAL) ? PM_WITH_NORMAL : PM_NO_REVERSE);
+  if (flags & (RNB_POINTS_FEATURE | RNB_POINTS_COLOR)) mode |= PM_WITH_COLOR;
+  return mode;
+}
+
+static int check_points_flags(int32_t flags) {
+  if (flags & ~(RNB_POINTS_FEATURE | RNB_POINTS_NORMAL | RNB_POINTS_COLOR))
+    RNB_FAIL(RNB_E_INVALID, "unknown bits in the point-call flags (0x%x)", flags);
+  return RNB_OK;
+}
+
+RNB_API int rnb_points_grad_workspace_bytes(const rnb_model_desc* desc, int64_t n_points, int32_t flags, int64_t* bytes) {
+  RNB_REQUIRE(bytes, "bytes");
+  if (n_points < 0) RNB_FAIL(RNB_E_INVALID, "n_points < 0");
+  RNB_TRY(check_points_flags(flags));
+  Layout L;
+  RNB_TRY(make_layout(desc, &L));
+  Carver c(nullptr, 0);
+  PointBufs pb;
+  carve_points(L, c, n_points, grad_mode(flags), &pb);
+  Carver cf(nullptr, 0);   // (never below the forward-only calls' workspace: one buffer serves both)
+  carve_points(L, cf, n_points, kPointsMode, &pb);
+  *bytes = (int64_t)(c.off > cf.off ? c.off : cf.off);
+  return RNB_OK;
+}
+
+static int grad_setup(const rnb_model_desc* desc, int64_t n, int32_t flags, void* ws, size_t ws_bytes, Layout* L,
+                      PointBufs* pb) {
+  RNB_TRY(check_points_flags(flags));
+  RNB_TRY(make_layout(desc, L));
+  if (is_bf16(*L)) RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 has no point-wise backward (the render path only)");
+  if ((flags & (RNB_POINTS_FEATURE | RNB_POINTS_COLOR)) && L->F <= 0) RNB_FAIL(RNB_E_INVALID, "model has no feature head");
+  RNB_REQUIRE(ws, "workspace");
+  Carver c(ws, ws_bytes);
+  carve_points(*L, c, n, grad_mode(flags), pb);
+  if (!c.ok) RNB_FAIL(RNB_E_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
+  return RNB_OK;
+}
+
+RNB_API int rnb_sdf_forward_save(const rnb_model_desc* desc, const float* packed, const float* pts, int64_t n,
+                                 int32_t flags, float* sdf_out, float* feat_out, float* nrm_out, void* ws,
+                                 size_t ws_bytes, rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(pts, "pts");
+  RNB_REQUIRE(sdf_out, "sdf_out");
+  if (flags & RNB_POINTS_COLOR) RNB_FAIL(RNB_E_INVALID, "RNB_POINTS_COLOR belongs to rnb_color_forward_save");
+  const bool feat = (flags & RNB_POINTS_FEATURE) != 0, normal = (flags & RNB_POINTS_NORMAL) != 0;
+  if (feat) RNB_REQUIRE(feat_out, "feat_out");
+  if (normal) RNB_REQUIRE(nrm_out, "nrm_out");
+  if (n <= 0) return n == 0 ? RNB_OK : (set_error("n < 0"), RNB_E_INVALID);
+  hipStream_t s = (hipStream_t)stream;
+  Layout L;
+  PointBufs pb;
+  RNB_TRY(grad_setup(desc, n, flags, ws, ws_bytes, &L, &pb));
+  const bool fused = use_fused(L);
+  // state maxima of the x2h weight-gradient jobs: zeroed here (a render's first kernel does it there), grown by the sweeps
+  RNB_CHECK_HIP(hipMemsetAsync(pb.smax, 0, SMAX_SLOTS * sizeof(unsigned), s));
+  RNB_TRY(forward_points(L, packed, pts, n, pb, true, feat, normal && !fused, feat ? feat_out : nullptr, s));
+  if (normal) {
+    if (fused) RNB_TRY(fused_reverse(L, packed, pb, s, true));   // (+ d sdf / d e for the Hessian term of x's adjoint)
+    else RNB_TRY(sweep_reverse(L, packed, pb, s));
+    RNB_TRY(launch_copy_cols(pb.nrm, 4, 3, n, nrm_out, s));
+  }
+  RNB_CHECK_HIP(hipMemcpyAsync(sdf_out, pb.sdf, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return RNB_OK;
+}
+
+RNB_API int rnb_sdf_backward(const rnb_model_desc* desc, const float* packed, int64_t n, int32_t flags,
+                             const float* sdf_bar, const float* feat_bar, const float* nrm_bar, float* packed_grad,
+                             float* x_bar, void* ws, size_t ws_bytes, rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(packed_grad, "packed_grad");
+  if (feat_bar && !(flags & RNB_POINTS_FEATURE)) RNB_FAIL(RNB_E_INVALID, "feat_bar without RNB_POINTS_FEATURE");
+  if (nrm_bar && !(flags & RNB_POINTS_NORMAL)) RNB_FAIL(RNB_E_INVALID, "nrm_bar without RNB_POINTS_NORMAL");
+  if (flags & RNB_POINTS_COLOR) RNB_FAIL(RNB_E_INVALID, "RNB_POINTS_COLOR belongs to rnb_color_backward");
+  if (n < 0) RNB_FAIL(RNB_E_INVALID, "n < 0");
+  hipStream_t s = (hipStream_t)stream;
+  Layout L;
+  RNB_TRY(make_layout(desc, &L));
+  RNB_CHECK_HIP(hipMemsetAsync(packed_grad, 0, (size_t)L.total * sizeof(float), s));
+  if (n == 0) return RNB_OK;
+  PointBufs pb;
+  RNB_TRY(grad_setup(desc, n, flags, ws, ws_bytes, &L, &pb));
+  const int64_t Mp = pb.Mp;
+  // the adjoints' maxima: zeroed (composite_bwd_kernel's job in a render), then grown by every producer; the caller's
+  // feature adjoint is one of them (the feature head's weight-gradient job reads its slot)
+  RNB_CHECK_HIP(hipMemsetAsync(pb.amax, 0, AMAX_SLOTS * sizeof(unsigned), s));
+  RNB_CHECK_HIP(hipMemsetAsync(pb.sbar, 0, (size_t)Mp * sizeof(float), s));
+  if (sdf_bar) RNB_CHECK_HIP(hipMemcpyAsync(pb.sbar, sdf_bar, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (nrm_bar) {
+    RNB_CHECK_HIP(hipMemsetAsync(pb.nbar, 0, (size_t)Mp * 4 * sizeof(float), s));
+    RNB_TRY(launch_fill_cols(nrm_bar, 3, n, Mp, 4, pb.nbar, s));
+  }
+  if (feat_bar) {
+    RNB_CHECK_HIP(hipMemsetAsync(pb.cinb, 0, (size_t)Mp * L.Cinp * sizeof(float), s));
+    RNB_TRY(launch_fill_cols(feat_bar, L.F, n, Mp, L.Cinp, pb.cinb, s));
+    if (is_x2h(L)) RNB_TRY(launch_absmax_rows(pb.cinb, Mp * L.Cinp, pb.amax + AMAX_CINB, s));
+  }
+  BwdParts parts;
+  parts.albedo = false;
+  parts.sdf = true;
+  parts.feat = feat_bar != nullptr;
+  parts.normal = nrm_bar != nullptr;
+  parts.color_inputs = false;
+  RNB_TRY(sweep_backward_parts(L, packed, pb, parts, packed_grad, use_fused(L), s));
+  if (x_bar) RNB_TRY(launch_sdf_xbar(L, packed, pb, parts.normal, x_bar, s));
+  return RNB_OK;
+}
+
+RNB_API int rnb_color_forward_save(const rnb_model_desc* desc, const float* packed, const float* pts,
+                                   const float* normals, const float* feats, int64_t n, float* out, void* ws,
+                                   size_t ws_bytes, rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(pts, "pts");
+  RNB_REQUIRE(normals, "normals");
+  RNB_REQUIRE(feats, "feats");
+  RNB_REQUIRE(out, "out");
+  if (n <= 0) return n == 0 ? RNB_OK : (set_error("n < 0"), RNB_E_INVALID);
+  hipStream_t s = (hipStream_t)stream;
+  Layout L;
+  PointBufs pb;
+  RNB_TRY(grad_setup(desc, n, RNB_POINTS_COLOR, ws, ws_bytes, &L, &pb));
+  const int64_t Mp = pb.Mp;
+  // the inputs, kept for the input adjoints: points -> pb.x, normals -> pb.nrm ([Mp,4], zero padding), features -> cin
+  RNB_CHECK_HIP(hipMemsetAsync(pb.x, 0, (size_t)Mp * 4 * sizeof(float), s));
+  RNB_CHECK_HIP(hipMemsetAsync(pb.nrm, 0, (size_t)Mp * 4 * sizeof(float), s));
+  RNB_CHECK_HIP(hipMemsetAsync(pb.smax, 0, SMAX_SLOTS * sizeof(unsigned), s));
+  RNB_TRY(launch_fill_cols(pts, 3, n, Mp, 4, pb.x, s));
+  RNB_TRY(launch_fill_cols(normals, 3, n, Mp, 4, pb.nrm, s));
+  RNB_TRY(launch_fill_cols(feats, L.F, n, Mp, L.Cinp, pb.cin, s));
+  if (use_fused(L) && color_h2_supported(L)) RNB_TRY(color_h2_forward(L, packed, pb, pts, pb.nrm, s));
+  else RNB_TRY(sweep_color(L, packed, pb, pts, pb.nrm, 4, s));
+  RNB_TRY(launch_copy_cols(pb.alb, 4, L.Co, n, out, s));
+  return RNB_OK;
+}
+
+RNB_API int rnb_color_backward(const rnb_model_desc* desc, const float* packed, int64_t n, const float* alb_bar,
+                               float* packed_grad, float* feat_bar, float* nrm_bar, float* pts_bar, void* ws,
+                               size_t ws_bytes, rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(alb_bar, "alb_bar");
+  RNB_REQUIRE(packed_grad, "packed_grad");
+  if (n < 0) RNB_FAIL(RNB_E_INVALID, "n < 0");
+  hipStream_t s = (hipStream_t)stream;
+  Layout L;
+  RNB_TRY(make_layout(desc, &L));
+  RNB_CHECK_HIP(hipMemsetAsync(packed_grad, 0, (size_t)L.total * sizeof(float), s));
+  if (n == 0) return RNB_OK;
+  PointBufs pb;
+  RNB_TRY(grad_setup(desc, n, RNB_POINTS_COLOR, ws, ws_bytes, &L, &pb));
+  const int64_t Mp = pb.Mp;
+  RNB_CHECK_HIP(hipMemsetAsync(pb.amax, 0, AMAX_SLOTS * sizeof(unsigned), s));
+  RNB_CHECK_HIP(hipMemsetAsync(pb.albbar, 0, (size_t)Mp * 4 * sizeof(float), s));
+  RNB_TRY(launch_fill_cols(alb_bar, L.Co, n, Mp, 4, pb.albbar, s));
+  BwdParts parts;
+  parts.albedo = true;
+  parts.sdf = false;
+  parts.feat = false;
+  parts.normal = false;
+  parts.color_inputs = pts_bar != nullptr || nrm_bar != nullptr;
+  RNB_TRY(sweep_backward_parts(L, packed, pb, parts, packed_grad, use_fused(L), s));
+  if (feat_bar) RNB_TRY(launch_copy_cols(pb.cinb, L.Cinp, L.F, n, feat_bar, s));
+  RNB_TRY(launch_color_input_bwd(L, pb, pts_bar, nrm_bar, s));
+  return RNB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // SDF grid (extract_fields)
 // ---------------------------------------------------------------------------------------------------
 constexpr int64_t kGridChunk = 1 << 20;   // points per pass of the generic (per-layer GEMM) path

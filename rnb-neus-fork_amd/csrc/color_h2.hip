@@ -45,8 +45,9 @@ struct ColH2Args {
   float* cinb;             // [Mp,Cinp]: the feature columns are written (FB sweep, feature head's weight gradient)
   const float* x4;         // [Mp,4]
   const float* nbar;       // [Mp,4]
-  float* geb;              // [Mp,Ep]
+  float* geb;              // [Mp,Ep], or nullptr: the albedo net alone (no nbar_total, no geb)
   int multires, Ep;
+  int keep_pe;             // store cinb's encoding columns F .. F + 63 too (input adjoints of a direct albedo-net call)
   unsigned* amax;          // PointBufs::amax (slots AMAX_ZC + l, AMAX_CINB grown)
   float* dwo_part;         // [tiles][Co][256] column sums of zo^T ac_1 per tile
   float* dbo_part;         // [tiles][Co]
@@ -433,6 +434,13 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
     for (int r = 0; r < 16; ++r) X[(rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * FP + 32 * ct + cl] = pacc[0][0][r] * unscale0;
   }
   lds_barrier();
+  if (g.keep_pe) {
+    for (int idx = tid; idx < CT * 16; idx += 256) {
+      const int r = idx >> 4, c4 = idx & 15;
+      *reinterpret_cast<vf4*>(g.cinb + (size_t)(row0 + r) * g.Cinp + g.F + c4 * 4) = *reinterpret_cast<const vf4*>(X + r * FP + c4 * 4);
+    }
+  }
+  if (g.geb == nullptr) return;
   // ---- nbar_total = nbar + J_pe(n)^T cinb[pe(n)];  geb = J_pe(x) nbar_total -> tile columns 64 ..: four threads per point,
   //      each one octave in four of both encodings (one thread per point left three waves idle through 30 sincos) ----
   {
@@ -544,7 +552,7 @@ int color_h2_forward(const Layout& L, const float* packed, PointBufs& pb, const 
 // floats of the per-tile slabs of the output layer's gradient
 int64_t color_h2_part_floats(const Layout& L, int64_t M) { return (pad_rows(M) / CT) * (int64_t)L.Co * (FH + 1); }
 
-int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s) {
+int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool sdf, bool keep_pe) {
   ColH2Args g;
   col_fill(L, packed, pb, g);
   g.nrm = pb.nrm;
@@ -552,7 +560,8 @@ int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipSt
   g.cinb = pb.cinb;
   g.x4 = pb.x;
   g.nbar = pb.nbar;
-  g.geb = pb.geb;
+  g.geb = sdf ? pb.geb : nullptr;
+  g.keep_pe = keep_pe ? 1 : 0;
   g.multires = L.multires;
   g.Ep = L.Ep;
   g.amax = pb.amax;

@@ -47,6 +47,8 @@ struct FusedBwdArgs {
   unsigned* amax;       // PointBufs::amax (RA: slots AMAX_U + l of the u_l it writes; FB: AMAX_ZB + l), or nullptr
   const H2Tab* h2tab;   // x2h: scales of the fp16 mirror's matrices (hidden layer l: id l, feature head: id nh)
   unsigned* smax;       // x2h R sweep of a render forward: PointBufs::smax (slots SMAX_GZ + l grown by the tile maxima), or nullptr
+  float* ge_out;        // R: [Mp,Ep] d sdf / d e (its first pe columns), or nullptr.  The point-wise autograd of
+                        // SDFNetwork.gradient reads it for the encoding's second-derivative term of x's adjoint
 };
 
 // matrix loop of one layer (weights at float offset `off` of the packed buffer): two alternating weight-register
@@ -233,6 +235,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
       f *= 2.f;
     }
     g.nrm[row * 4] = n[0]; g.nrm[row * 4 + 1] = n[1]; g.nrm[row * 4 + 2] = n[2]; g.nrm[row * 4 + 3] = 0.f;
+    if (g.ge_out != nullptr)
+      for (int c = 0; c < g.pe; ++c) g.ge_out[row * g.Ep + c] = ge[c];
   }
 }
 
@@ -642,9 +646,10 @@ static double hidden_flops(const Layout& L, int64_t M, int first) {
   return fl;
 }
 
-int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s) {
+int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool store_ge) {
   FusedBwdArgs g;
   fill_args(L, packed, pb, g);
+  g.ge_out = store_ge ? pb.ge : nullptr;
   ProfScope prof(hidden_flops(L, pb.M, 0), s, "R_sweep");
   const int ti = bwd_ti(L, is_x3(L) ? 2 : 1), nw = bwd_nw(L, is_x3(L) ? 4 : 8);
   const dim3 grid((unsigned)(pb.Mp / (32 * ti))), block(64 * nw);

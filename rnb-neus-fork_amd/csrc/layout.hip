@@ -158,7 +158,8 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
   pb->sdf = c.take<float>(Mp);
   pb->smax = c.take<unsigned>(SMAX_SLOTS);
   if (mode & (PM_WITH_NORMAL | PM_WITH_COLOR | PM_WITH_BACKWARD)) {
-    for (int l = 0; l < L.nh; ++l) pb->gz[l] = take_state(Mp * L.Hp);
+    if (!(mode & PM_NO_REVERSE))
+      for (int l = 0; l < L.nh; ++l) pb->gz[l] = take_state(Mp * L.Hp);
     for (int l = 0; l < L.nh; ++l) pb->D[l] = take_state(Mp * L.Hp);
     pb->ge = c.take<float>(Mp * L.Ep);
     pb->nrm = c.take<float>(Mp * 4);
@@ -174,7 +175,8 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
     }
   }
   if (mode & PM_WITH_BACKWARD) {
-    for (int l = 1; l <= L.nh; ++l) pb->u[l] = take_state(Mp * L.Hp);
+    if (!(mode & PM_NO_REVERSE))
+      for (int l = 1; l <= L.nh; ++l) pb->u[l] = take_state(Mp * L.Hp);
     for (int l = 0; l < L.nh; ++l) pb->zR[l] = take_state(Mp * L.Hp);
     for (int l = 0; l < L.nh; ++l) pb->zb[l] = take_state(Mp * L.Hp);
     if (bf) {

@@ -461,6 +461,68 @@ __global__ void fill_cols_kernel(const float* __restrict__ src, int ncols, int64
   dst[row * ld + col] = row < M ? src[i] : 0.f;
 }
 
+// ---- input adjoints of the point-wise autograd calls (rnb_sdf_backward / rnb_color_backward) ----------------------
+// x's adjoint of the SDF network (models/fields.py:84, :104, :114-127 under autograd):
+//   xbar = scale * ( J_pe(xs)^T ebar + [normal] sum_k ge_k d^2 pe_k / d xs^2 . nbar ),   xs = scale * x,
+// ebar = d loss / d e (FB's zb_0 W_0 plus the skip layer's encoding columns, launch_sdf_xbar).  The second term is diagonal
+// per coordinate: d^2 sin(f x) = -f^2 sin(f x), d^2 cos(f x) = -f^2 cos(f x), f = 2^k; ge = d sdf / d e from the R sweep.
+__global__ void sdf_xbar_kernel(const float* __restrict__ x4, const float* __restrict__ ebar, const float* __restrict__ ge,
+                                const float* __restrict__ nbar, int Ep, int multires, float scale, int64_t M,
+                                float* __restrict__ xbar) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= M) return;
+  const float* eb = ebar + row * Ep;
+  float acc[3] = {eb[0], eb[1], eb[2]};
+  float f = 1.f;
+  int c = 3;
+  for (int k = 0; k < multires; ++k) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      float sn, co;
+      sincosf(x4[row * 4 + d] * f, &sn, &co);
+      acc[d] += f * (eb[c + d] * co - eb[c + 3 + d] * sn);
+      if (ge != nullptr) {
+        const float* g = ge + row * Ep;
+        acc[d] -= f * f * (g[c + d] * sn + g[c + 3 + d] * co) * nbar[row * 4 + d];
+      }
+    }
+    c += 6;
+    f *= 2.f;
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) xbar[row * 3 + d] = scale * acc[d];
+}
+
+// adjoints of the albedo net's encoded inputs: pbar = J_pe(p)^T cinb[pe(p)], nbar = J_pe(n)^T cinb[pe(n)] (either may be
+// NULL).  p, n: the saved inputs [Mp,4]; cinb complete (the per-layer backward, or color_h2 with keep_pe).
+__global__ void color_input_bwd_kernel(const float* __restrict__ cinb, int Cinp, int F, int pev, int multires_view,
+                                       const float* __restrict__ p4, const float* __restrict__ n4, int64_t M,
+                                       float* __restrict__ pbar, float* __restrict__ nbar) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= M) return;
+  for (int which = 0; which < 2; ++which) {
+    float* out = which ? nbar : pbar;
+    if (out == nullptr) continue;
+    const float* g = cinb + row * Cinp + F + which * pev;
+    const float* v = (which ? n4 : p4) + row * 4;
+    float t[3] = {g[0], g[1], g[2]};
+    float f = 1.f;
+    int c = 3;
+    for (int k = 0; k < multires_view; ++k) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        float sn, co;
+        sincosf(v[d] * f, &sn, &co);
+        t[d] += f * (g[c + d] * co - g[c + 3 + d] * sn);
+      }
+      c += 6;
+      f *= 2.f;
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) out[row * 3 + d] = t[d];
+  }
+}
+
 // =====================================================================================================
 // GEMM epilogues.  apply4(row, col, v): 4 consecutive columns col..col+3 (col % 4 == 0) of one output row.
 // All activation matrices have a padded leading dimension (multiple of 32), so 16-byte accesses are
@@ -641,6 +703,19 @@ struct EpiStore {
   float* out;
   int ld;
   __device__ void apply4(int row, int col, vf4 v) const { st4(out + (size_t)row * ld + col, v); }
+};
+
+// skip layer's encoding columns of zb_skip W_skip -> ebar (the first product of x's adjoint; layer 0's EpiR0 accumulates)
+struct EpiSkipPE {
+  float* ebar;
+  int Ep, k_split, pe;
+  __device__ void apply4(int row, int col, vf4 v) const {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int cc = col + c;
+      if (cc >= k_split && cc < k_split + pe) ebar[(size_t)row * Ep + (cc - k_split)] = v[c];
+    }
+  }
 };
 
 // =====================================================================================================
@@ -1027,6 +1102,8 @@ static int launch_absmax(const float* x, int64_t n, unsigned* slot, hipStream_t 
   return RNB_OK;
 }
 
+int launch_absmax_rows(const float* x, int64_t n, unsigned* slot, hipStream_t s) { return launch_absmax(x, n, slot, s); }
+
 // out[k] = max over a list of word slots (float bits) — the finishing step of rnb_render_range
 __global__ void range_fold_kernel(const unsigned* __restrict__ words, int n, int k, float* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -1144,15 +1221,66 @@ int sweep_color(const Layout& L, const float* packed, PointBufs& pb, const float
   return RNB_OK;
 }
 
+// x's adjoint after an SDF backward (sweep_backward_parts has flushed: geb is free and becomes ebar).  Needs zb_0, zb_skip,
+// pb.x and, with_normal, pb.ge (R sweep) and pb.nbar.  Two products in the per-layer kernels' shape of the R sweep's last
+// steps (zb W against the row-major W: k-contiguous in the layer's output width) + one point-wise kernel.
+int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s) {
+  float* ebar = pb.geb;
+  if (L.skip >= 1) {
+    const Lin& ln = L.hid[L.skip];
+    EpiSkipPE epi{ebar, L.Ep, ln.K - L.pe, L.pe};
+    RNB_TRY((launch_rows<true, EpiSkipPE>(pb.zb[L.skip], L.Hp, packed + ln.w_off, ln.Kp, pb.Mp, ln.Kp, ln.Np, epi,
+                                          mm_flops(pb.M, ln), s, false, nullptr, nullptr, 0, "input_adjoint")));
+  }
+  {
+    const Lin& ln = L.hid[0];
+    EpiR0 epi{ebar, L.Ep, L.pe, L.skip >= 1 ? 1 : 0};
+    RNB_TRY((launch_rows<true, EpiR0>(pb.zb[0], L.Hp, packed + ln.w_off, ln.Kp, pb.Mp, ln.Kp, ln.Np, epi, mm_flops(pb.M, ln), s,
+                                      false, nullptr, nullptr, 0, "input_adjoint")));
+  }
+  hipLaunchKernelGGL(sdf_xbar_kernel, dim3(blocks_for(pb.M, 256)), dim3(256), 0, s, pb.x, ebar,
+                     with_normal ? (const float*)pb.ge : nullptr, pb.nbar, L.Ep, L.multires, L.sdf_scale, pb.M, xbar);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+int launch_color_input_bwd(const Layout& L, const PointBufs& pb, float* pts_bar, float* nrm_bar, hipStream_t s) {
+  if (pts_bar == nullptr && nrm_bar == nullptr) return RNB_OK;
+  hipLaunchKernelGGL(color_input_bwd_kernel, dim3(blocks_for(pb.M, 256)), dim3(256), 0, s, pb.cinb, L.Cinp, L.F, L.pev,
+                     L.multires_view, pb.x, pb.nrm, pb.M, pts_bar, nrm_bar);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
 // Backward of everything above given pb.sbar, pb.nbar, pb.albbar (from the composite backward).
 // packed_grad (same layout as `packed`) must be zero on entry; it receives dW_eff / db of every layer.
 int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad,
                    bool fused, hipStream_t s) {
+  BwdParts parts;
+  parts.albedo = with_color;
+  parts.sdf = true;
+  parts.feat = with_color;
+  parts.normal = true;
+  parts.color_inputs = false;
+  return sweep_backward_parts(L, packed, pb, parts, packed_grad, fused, s);
+}
+
+// The same backward in parts (point-wise autograd of the direct network calls, api.hip):
+//   albedo        C' from pb.albbar: the albedo net's weight gradients and cinb
+//   sdf           the SDF half: sdf-head row, FB, dW of every hidden layer (seeded by pb.sbar)
+//   feat          FB's feature-head seed is cinb's feature block (the albedo backward's, or a caller-supplied adjoint)
+//   normal        pb.nbar is live: nbar -> geb, the RA sweep and the gz/u weight-gradient pairs.  Without it RA is skipped,
+//                 zR_l is zero and the layers' weight gradients are the single zb/a pair
+//   color_inputs  (albedo without sdf) cinb is left complete, encoding columns included, for the input adjoints
+// The render path (sweep_backward) is {albedo = with_color, sdf, feat = with_color, normal}: the same launches as before.
+int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, const BwdParts& parts, float* packed_grad,
+                         bool fused, hipStream_t s) {
+  const bool with_color = parts.albedo;
   const int64_t M = pb.M, Mp = pb.Mp;
   const bool det = (L.variant & RNB_VARIANT_DETERMINISTIC) != 0;
   if (pb.dw_part == nullptr) RNB_FAIL(RNB_E_WORKSPACE, "no weight-gradient slab workspace was carved");
   // workspace = [ordered-reduction slabs of the atomic kernels (deterministic variant only) | slabs of the staged kernel]
-  const int64_t staged_floats = dw_staged_floats(L, M, with_color);
+  const int64_t staged_floats = dw_staged_floats(L, M, parts.albedo || parts.feat);
   const int64_t det_floats = pb.dw_part_floats - staged_floats;
   if (det && det_floats > 0) RNB_CHECK_HIP(hipMemsetAsync(pb.dw_part, 0, (size_t)det_floats * sizeof(float), s));
   DwBatch dw(M, s, (L.variant & RNB_VARIANT_DW_LDS) != 0, det ? pb.dw_part : nullptr, det ? det_floats : 0,
@@ -1170,7 +1298,7 @@ int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool wit
   if (color_bf16) {
     RNB_TRY(bf16_color_backward(L, packed, pb, packed_grad, s));
   } else if (color_h2) {
-    RNB_TRY(color_h2_backward(L, packed, pb, s));
+    RNB_TRY(color_h2_backward(L, packed, pb, s, parts.sdf, parts.color_inputs));
     for (int l = L.nc - 1; l >= 0; --l) {
       const Lin& ln = L.col[l];
       const float* in = l == 0 ? pb.cin : pb.ac[l - 1];
@@ -1212,8 +1340,9 @@ int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool wit
       }
     }
   }
+  if (!parts.sdf) return dw.flush_all();
   // ---- nbar (+ albedo-net contribution) -> geb = u_0 -----------------------------------------------
-  if (!color_h2) {
+  if (!color_h2 && parts.normal) {
     const int wt = (with_color && L.Cinp - L.F > L.Ep) ? L.Cinp - L.F : L.Ep;
     hipLaunchKernelGGL(nbar_geb_kernel, dim3(blocks_for(Mp, 64)), dim3(64), (size_t)64 * (wt + 1) * sizeof(float), s,
                        pb.x, pb.nrm, pb.nbar, pb.cinb, L.Cinp, L.F, L.F + L.pev, L.multires_view, with_color ? 1 : 0,
@@ -1228,7 +1357,9 @@ int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool wit
   }
   // ---- RA: adjoint of the reverse sweep, forward layer order -----------------------------------------
   int u_tiles = 0;
-  if (fused) {
+  if (!parts.normal) {   // nbar == 0: RA's outputs are zero; FB adds zR_l, the layers' weight gradients skip the u pairs
+    for (int l = 0; l < L.nh; ++l) RNB_CHECK_HIP(hipMemsetAsync(pb.zR[l], 0, (size_t)Mp * L.Hp * sizeof(float), s));
+  } else if (fused) {
     RNB_TRY(fused_ra(L, packed, pb, s, &u_tiles));
   } else {
     for (int l = 0; l < L.nh; ++l) {
@@ -1258,7 +1389,7 @@ int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool wit
     float* part_w = slab_out ? pb.sdfh_part : nullptr;
     float* part_b = slab_out ? pb.sdfh_part + (size_t)nslab * L.Hp : nullptr;
     hipLaunchKernelGGL(sdf_head_bwd_kernel, dim3(nslab, chunks), dim3(512), 0, s, pb.a[L.nh - 1],
-                       fused ? (const float*)nullptr : (const float*)pb.u[L.nh], (const float*)pb.u[L.nh], u_tiles, L.Hp,
+                       (fused || !parts.normal) ? (const float*)nullptr : (const float*)pb.u[L.nh], (const float*)pb.u[L.nh], u_tiles, L.Hp,
                        L.H, pb.sbar, 1.f / L.sdf_scale, M, rows_per_blk,
                        packed_grad + L.wsdf_off, packed_grad + L.bsdf_off, part_w, part_b);
     RNB_CHECK_LAUNCH();
@@ -1266,16 +1397,16 @@ int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool wit
       RNB_TRY(dw.add_reduce_only(packed_grad + L.wsdf_off, L.Hp, packed_grad + L.bsdf_off, part_w, part_b, 1, L.Hp, (int)nslab));
   }
   // ---- FB head: zb_{nh-1} = (fbar Wf + sbar/scale w_sdf) * D + zR ----------------------------------
-  if (fused) RNB_TRY(fused_fb(L, packed, pb, with_color, s));   // all zb_l in one launch
+  if (fused) RNB_TRY(fused_fb(L, packed, pb, parts.feat, s));   // all zb_l in one launch
   {
     if (!fused) {
       EpiFB epi{pb.D[L.nh - 1], pb.zR[L.nh - 1], pb.zb[L.nh - 1], L.Hp, L.hid[L.nh - 1].N, pb.sbar,
                 packed + L.wsdf_off, 1.f / L.sdf_scale};
-      const int K = with_color ? L.feat.Np : 0;   // no_albedo: fbar == 0, the GEMM degenerates to its epilogue
+      const int K = parts.feat ? L.feat.Np : 0;   // no_albedo: fbar == 0, the GEMM degenerates to its epilogue
       RNB_TRY((launch_rows<true, EpiFB>(pb.cinb, L.Cinp, packed + L.feat.w_off, L.feat.Kp, Mp, L.feat.Kp, K, epi,
-                                        with_color ? mm_flops(M, L.feat) : 0.0, s)));
+                                        parts.feat ? mm_flops(M, L.feat) : 0.0, s)));
     }
-    if (with_color) {
+    if (parts.feat) {
       DwPair p{pb.cinb, L.Cinp, pb.a[L.nh - 1], L.Hp, 0, h2 ? pb.amax + AMAX_CINB : nullptr, h2 ? pb.smax + SMAX_A + L.nh - 1 : nullptr};
       RNB_TRY(dw.add(p, p, 1, L.feat.Np, L.feat.Kp, packed_grad + L.feat.w_off, L.feat.Kp,
                      packed_grad + L.feat.b_off, 0, mm_flops(M, L.feat)));
@@ -1291,8 +1422,11 @@ int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool wit
     DwPair p1{pb.gz[l], L.Hp, uin, ldin, 1, h2 ? pb.amax + AMAX_U + l : nullptr, h2 ? pb.smax + SMAX_GZ + l : nullptr};
     DwPair p2{pb.zb[l], L.Hp, in, ldin, 0, h2 ? pb.amax + AMAX_ZB + l : nullptr,
               h2 ? pb.smax + (l == 0 ? SMAX_E : SMAX_A + l - 1) : nullptr};
-    RNB_TRY(dw.add(p1, p2, 2, ln.Np, ln.Kp, packed_grad + ln.w_off, ln.Kp, packed_grad + ln.b_off, 1,
-                   2.0 * mm_flops(M, ln)));
+    if (parts.normal)
+      RNB_TRY(dw.add(p1, p2, 2, ln.Np, ln.Kp, packed_grad + ln.w_off, ln.Kp, packed_grad + ln.b_off, 1,
+                     2.0 * mm_flops(M, ln)));
+    else
+      RNB_TRY(dw.add(p2, p2, 1, ln.Np, ln.Kp, packed_grad + ln.w_off, ln.Kp, packed_grad + ln.b_off, 0, mm_flops(M, ln)));
     if (l > 0 && !fused) {
       const Lin& lp = L.hid[l - 1];
       EpiFB epi{pb.D[l - 1], pb.zR[l - 1], pb.zb[l - 1], L.Hp, lp.N, nullptr, nullptr, 1.f};

@@ -181,7 +181,8 @@ enum { AMAX_ZB = 0, AMAX_U = RNB_MAX_LIN, AMAX_ZC = 2 * RNB_MAX_LIN + 1, AMAX_CI
 // slots of PointBufs::smax: a_l, gz_l (hidden layers), e (positional encoding), cin (albedo-net input), ac_l (its hidden layers)
 enum { SMAX_A = 0, SMAX_GZ = RNB_MAX_LIN, SMAX_E = 2 * RNB_MAX_LIN, SMAX_CIN = 2 * RNB_MAX_LIN + 1, SMAX_AC = 2 * RNB_MAX_LIN + 2,
        SMAX_SLOTS = 3 * RNB_MAX_LIN + 2 };
-enum PointMode { PM_SDF_ONLY = 0, PM_WITH_NORMAL = 1, PM_WITH_COLOR = 2, PM_WITH_BACKWARD = 4 };
+// PM_NO_REVERSE: a backward without the normal's adjoint (point-wise autograd of SDFNetwork.forward): no gz_l, no u_l
+enum PointMode { PM_SDF_ONLY = 0, PM_WITH_NORMAL = 1, PM_WITH_COLOR = 2, PM_WITH_BACKWARD = 4, PM_NO_REVERSE = 8 };
 void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb);
 
 // ---- device sweeps (mlp.hip) -------------------------------------------------------------------
@@ -199,7 +200,21 @@ int64_t dw_partial_floats(const Layout& L, int64_t M, bool with_color);
 int64_t dw_staged_floats(const Layout& L, int64_t M, bool with_color);
 int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad,
                    bool fused, hipStream_t s);
-int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s);
+// which parts of sweep_backward run (mlp.hip); the render path is {with_color, true, with_color, true, false}
+struct BwdParts {
+  bool albedo;         // the albedo net's backward from pb.albbar
+  bool sdf;            // the SDF network's backward from pb.sbar (+ the two below)
+  bool feat;           // cinb's feature columns seed FB (the feature head's adjoint)
+  bool normal;         // pb.nbar is live: geb, RA and the gz/u weight-gradient pairs
+  bool color_inputs;   // (albedo only) leave all of cinb, encoding columns included, for the input adjoints
+};
+int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, const BwdParts& parts, float* packed_grad,
+                         bool fused, hipStream_t s);
+// input adjoints of the point-wise autograd calls (mlp.hip)
+int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s);
+int launch_color_input_bwd(const Layout& L, const PointBufs& pb, float* pts_bar, float* nrm_bar, hipStream_t s);
+int launch_absmax_rows(const float* x, int64_t n, unsigned* slot, hipStream_t s);
+int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool store_ge = false);
 int fused_ra(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, int* u_tiles = nullptr);
 int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_color, hipStream_t s);
 
@@ -243,7 +258,8 @@ int x3_pack_weights(const Layout& L, float* packed, hipStream_t s);
 // ---- the albedo network as two fused sweeps in the x2h arithmetic (color_h2.hip) ----
 bool color_h2_supported(const Layout& L);
 int color_h2_forward(const Layout& L, const float* packed, PointBufs& pb, const float* pts, const float* nrm, hipStream_t s);
-int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s);
+// sdf == false: no geb (the albedo net alone); keep_pe: also store cinb's 64 encoding columns (input adjoints)
+int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool sdf = true, bool keep_pe = false);
 int64_t color_h2_part_floats(const Layout& L, int64_t M);
 constexpr int kSdfHeadSlabs = 64;   // row slabs of sdf_head_bwd_kernel's partial sums (summed in slab order: no atomics)
 

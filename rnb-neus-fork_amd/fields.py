@@ -56,7 +56,15 @@ def _forward_only_guard(module: nn.Module, what: str, *inputs):
         raise RuntimeError(
             f"{what} is forward-only in rnb_neus_fork_amd: it returns a tensor without grad_fn, so gradients would silently "
             "not flow.  Training gradients flow through NeuSRenderer.render / render_rnb / render_rnb_warmup (whose backward is "
-            "native); for evaluation wrap the call in torch.no_grad() (or freeze the parameters with requires_grad_(False)).")
+            "native); for evaluation wrap the call in torch.no_grad() (or freeze the parameters with requires_grad_(False)).  "
+            "For gradients through this call, opt in with set_autograd(True) on the module.")
+
+
+def _autograd_wanted(module: nn.Module, *inputs):
+    """set_autograd(True), grad mode, and a trainable parameter or an input that requires grad: the differentiable call."""
+    if not getattr(module, "_autograd", False) or not torch.is_grad_enabled():
+        return False
+    return any(p.requires_grad for p in module.parameters()) or any(torch.is_tensor(t) and t.requires_grad for t in inputs)
 
 
 def _mlp_struct(lins, weight_norm, grads=None):
@@ -142,15 +150,32 @@ class SDFNetwork(nn.Module):
         from .runtime import StandaloneSDF
         return StandaloneSDF(self)
 
-    # -- reference API (forward only, and loud about it; training gradients flow through NeuSRenderer.render*) -----------
+    def set_autograd(self, enabled=True):
+        """Opt-in autograd of the direct calls below (off by default).  On: under grad mode with a trainable parameter or
+        an input that requires grad, forward / sdf / sdf_hidden_appearance / gradient return tensors with a grad_fn whose
+        backward is native (rnb_sdf_backward: every SDF leaf and x; gradient's output is differentiable once, the
+        reference's create_graph=True).  The forward keeps the render path's per-point state until the backward (INTEGRATION.md:
+        about 5 GB per 100,000 points at the shipped shape).  A plain attribute: not in state_dict(), kept by .to().
+        Returns self."""
+        self._autograd = bool(enabled)
+        return self
+
+    # -- reference API (forward only by default, and loud about it; set_autograd(True) for native gradients) ------------
     def forward(self, inputs):
-        """[N,3] -> [N,d_out] = [sdf, feature]  (models/fields.py:82-104).  Forward only: raises under grad mode."""
+        """[N,3] -> [N,d_out] = [sdf, feature]  (models/fields.py:82-104).  Raises under grad mode unless set_autograd(True)."""
+        if _autograd_wanted(self, inputs):
+            from .runtime import sdf_autograd
+            sdf, feat = sdf_autograd(self, inputs, "feature")
+            return torch.cat([sdf, feat], dim=-1)
         _forward_only_guard(self, "SDFNetwork.forward", inputs)
         ctx = self._standalone()
         return ctx.sdf_forward(inputs, with_feature=True)
 
     def sdf(self, x):
-        """[N,3] -> [N,1]  (models/fields.py:106-108).  Forward only: raises under grad mode."""
+        """[N,3] -> [N,1]  (models/fields.py:106-108).  Raises under grad mode unless set_autograd(True)."""
+        if _autograd_wanted(self, x):
+            from .runtime import sdf_autograd
+            return sdf_autograd(self, x, "sdf")
         _forward_only_guard(self, "SDFNetwork.sdf", x)
         ctx = self._standalone()
         return ctx.sdf_forward(x, with_feature=False)
@@ -159,8 +184,13 @@ class SDFNetwork(nn.Module):
         return self.forward(x)
 
     def gradient(self, x):
-        """[N,3] -> [N,1,3] = d sdf / d x  (models/fields.py:114-127), analytic reverse sweep.  Forward only (the
-        reference returns a differentiable graph, create_graph=True): raises under grad mode."""
+        """[N,3] -> [N,1,3] = d sdf / d x  (models/fields.py:114-127), analytic reverse sweep.  Raises under grad mode unless
+        set_autograd(True); then the result is differentiable in the parameters and in x (the reference's create_graph=True).
+        Unlike the reference, x itself is not switched to requires_grad_(True): x.grad is filled only if the caller's x
+        requires grad."""
+        if _autograd_wanted(self, x):
+            from .runtime import sdf_autograd
+            return sdf_autograd(self, x, "normal").unsqueeze(1)
         _forward_only_guard(self, "SDFNetwork.gradient", x)
         ctx = self._standalone()
         return ctx.sdf_gradient(x).unsqueeze(1)
@@ -198,9 +228,19 @@ class RenderingNetwork(nn.Module):
             out += lin.leaves()
         return out
 
+    def set_autograd(self, enabled=True):
+        """Opt-in autograd of forward() (off by default; see SDFNetwork.set_autograd): differentiable in every leaf, points,
+        normals and feature_vectors (rnb_color_backward); view_dirs get no gradient (unused in mode no_view_dir).
+        Returns self."""
+        self._autograd = bool(enabled)
+        return self
+
     def forward(self, points, normals, view_dirs, feature_vectors):
-        """models/fields.py:177-215 (view_dirs are encoded and discarded by the reference in this mode).  Forward only:
-        raises under grad mode."""
+        """models/fields.py:177-215 (view_dirs are encoded and discarded by the reference in this mode).  Raises under grad
+        mode unless set_autograd(True)."""
+        if _autograd_wanted(self, points, normals, feature_vectors):
+            from .runtime import color_autograd
+            return color_autograd(self, points, normals, feature_vectors)
         _forward_only_guard(self, "RenderingNetwork.forward", points, normals, feature_vectors)
         from .runtime import standalone_color
         return standalone_color(self, points, normals, feature_vectors)

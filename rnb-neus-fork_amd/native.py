@@ -17,6 +17,11 @@ FLAG_NO_ALBEDO = 4
 FLAG_LIGHT_PER_RAY = 8
 FLAG_FORWARD_ONLY = 16
 
+# flags of the point-wise autograd calls (include/rnbneus.h)
+POINTS_FEATURE = 1
+POINTS_NORMAL = 2
+POINTS_COLOR = 4
+
 # rnb_model_desc.variant bits (include/rnbneus.h)
 VARIANT_BF16 = 1
 VARIANT_DETERMINISTIC = 2
@@ -96,6 +101,15 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnb_color_forward": (C.c_int, [_P(ModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnb_points_grad_workspace_bytes": (C.c_int, [_P(ModelDesc), C.c_int64, C.c_int32, _P(C.c_int64)]),
+    "rnb_sdf_forward_save": (C.c_int, [_P(ModelDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnb_sdf_backward": (C.c_int, [_P(ModelDesc), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnb_color_forward_save": (C.c_int, [_P(ModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnb_color_backward": (C.c_int, [_P(ModelDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnb_sdf_grid_workspace_bytes": (C.c_int, [_P(ModelDesc), _P(GridDesc), _P(C.c_int64)]),
     "rnb_sdf_grid": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(GridDesc), C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p]),

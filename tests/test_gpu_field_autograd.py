@@ -1,0 +1,314 @@
+"""Opt-in autograd of the direct network calls (SDFNetwork / RenderingNetwork.set_autograd) against the fp64 oracle.
+
+Losses on sdf_network(x), .gradient(x) (the eikonal term: the reference's create_graph=True double backward) and
+color_network(p, n, n, f) are differentiated natively (rnb_sdf_backward / rnb_color_backward + rnb_weightnorm_bwd) and
+compared with torch autograd through oracle/rnb_oracle.py in fp64, with the calibrated rule of test_gpu_parity.py: outputs
+within K_OUT x the fp32 oracle's own max error + FLOOR_OUT, gradients within _grad_bound(rel-L2 of fp32 vs fp64).  States
+are shape_matrix.live_params, so the encoding's columns carry weight."""
+import ctypes as C
+
+import pytest
+import torch
+
+from oracle import rnb_oracle as O
+from tests.shape_matrix import BY_NAME, live_params, points
+from tests.test_gpu_parity import FLOOR_OUT, K_OUT, _grad_bound
+
+pytestmark = pytest.mark.gpu
+
+SDF_SHAPES = ["default_64x64", "no_skip", "skip1", "skip7", "scale3", "multires0", "no_weight_norm", "feat128", "w100"]
+COLOR_SHAPES = ["default_64x64", "mview0", "albedo_nl1", "feat128"]
+SIZES = [1, 63, 4097]
+FUSED_CLASSES = {"R_sweep", "FB_sweep", "RA_sweep", "dW(x3: 256x256 + narrow jobs)"}
+ALBEDO_H2_CLASSES = {"albedo_fwd", "albedo_bwd"}
+
+
+@pytest.fixture(scope="module")
+def R():
+    assert torch.cuda.is_available(), "GPU tests need a device"
+    import rnb_neus_fork_amd as pkg
+    pkg.native.load()
+    return pkg
+
+
+def _dev():
+    return torch.device("cuda:0")
+
+
+def _build(R, name):
+    shape = BY_NAME[name]
+    p = live_params(shape.mc, shape.seed)
+    sdf, devn, col, ren = R.build_from_named_params(shape.mc, p, _dev())
+    sdf.set_autograd(True)
+    col.set_autograd(True)
+    return shape, p, sdf, col, ren
+
+
+def _rel(a, b):
+    return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-300))
+
+
+def _check_out(got, r64, r32, what):
+    bound = K_OUT * float((r32.double() - r64).abs().max()) + FLOOR_OUT * max(1.0, float(r64.abs().max()))
+    err = float((got.double() - r64).abs().max())
+    assert err <= bound, f"{what}: max err {err:.3g} > bound {bound:.3g}"
+
+
+def _check_grad(got, g64, g32, what):
+    if float(g64.abs().max()) == 0.0:
+        assert float(got.abs().max()) == 0.0, f"{what}: non-zero gradient where the oracle's is zero"
+        return
+    err, bound = _rel(got, g64), _grad_bound(_rel(g32, g64))
+    assert err <= bound, f"{what}: rel-L2 {err:.3g} > bound {bound:.3g}"
+
+
+def _oracle(p, prefix, inputs, fn, dt):
+    """(output, {leaf: grad}, [input grads]) of loss = fn(q, *xs)[1] by torch autograd in dtype dt on the device."""
+    q = {k: v.to(_dev(), dt).detach().requires_grad_(k.startswith(prefix)) for k, v in p.items()}
+    xs = [t.to(_dev(), dt).detach().requires_grad_(True) for t in inputs]
+    with torch.enable_grad():
+        out, loss = fn(q, *xs)
+        keys = [k for k in q if k.startswith(prefix)]
+        ins = [q[k] for k in keys] + xs
+        gs = torch.autograd.grad(loss, ins, allow_unused=True)
+    gs = [torch.zeros_like(t) if g is None else g for g, t in zip(gs, ins)]   # (e.g. the sdf bias in an eikonal loss)
+    return out.detach(), dict(zip(keys, gs[:len(keys)])), list(gs[len(keys):])
+
+
+def _oracle_normal(q, conf, x):
+    """d sdf / d x with a graph (models/fields.py:114-127, create_graph=True), differentiable in x as well."""
+    y = O.sdf_only(q, conf, x)
+    (g,) = torch.autograd.grad(y, x, torch.ones_like(y), create_graph=True)
+    return g
+
+
+def _native_leaf_grads(net, prefix):
+    return {f"{prefix}.{k}": v.grad for k, v in net.named_parameters()}
+
+
+def _zero(*nets):
+    for net in nets:
+        for q in net.parameters():
+            q.grad = None
+
+
+def _compare_leaves(mine, g64, g32, tag):
+    assert set(mine) == set(g64), f"{tag}: leaves {sorted(set(mine) ^ set(g64))}"
+    for k in g64:
+        assert mine[k] is not None, f"{tag} {k}: no gradient"
+        _check_grad(mine[k], g64[k], g32[k], f"{tag} {k}")
+
+
+def _weights(n, width, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(n, width, generator=g)
+
+
+# ------------------------------------------------------------------------------------------------------- cases 1 and 2
+@pytest.mark.parametrize("name", SDF_SHAPES)
+def test_sdf_feature_loss_and_eikonal_against_fp64(R, name):
+    shape, p, sdf, col, ren = _build(R, name)
+    conf = shape.mc.sdf
+    F = conf.d_out - 1
+    for n in SIZES + ([100_000] if name == "default_64x64" else []):
+        x0 = points(n, seed=n)
+        w, W = _weights(n, 1, 1), _weights(n, F, 2)
+        # case 1: (w sdf).sum() + (W o feat).sum()
+        loss1 = lambda q, x: (lambda o: (o, (w.to(o) * o[:, :1]).sum() + (W.to(o) * o[:, 1:]).sum()))(O.sdf_forward(q, conf, x))
+        o64, g64, (x64,) = _oracle(p, "sdf.", [x0], loss1, torch.float64)
+        o32, g32, (x32,) = _oracle(p, "sdf.", [x0], loss1, torch.float32)
+        _zero(sdf)
+        x = x0.to(_dev()).requires_grad_(True)
+        out = sdf(x)
+        assert out.grad_fn is not None and out.shape == (n, conf.d_out)
+        _check_out(out.detach(), o64, o32, f"{name} n={n} forward")
+        ((w.to(_dev()) * out[:, :1]).sum() + (W.to(_dev()) * out[:, 1:]).sum()).backward()
+        _compare_leaves(_native_leaf_grads(sdf, "sdf"), g64, g32, f"{name} n={n} case1")
+        _check_grad(x.grad, x64, x32, f"{name} n={n} case1 x.grad")
+        # case 2: the eikonal loss on gradient(x) (the Hessian term in x.grad)
+        loss2 = lambda q, x: (lambda g: (g, ((g.norm(dim=-1) - 1) ** 2).mean()))(_oracle_normal(q, conf, x))
+        n64, g64, (x64,) = _oracle(p, "sdf.", [x0], loss2, torch.float64)
+        n32, g32, (x32,) = _oracle(p, "sdf.", [x0], loss2, torch.float32)
+        _zero(sdf)
+        x = x0.to(_dev()).requires_grad_(True)
+        g = sdf.gradient(x)
+        assert g.shape == (n, 1, 3) and g.grad_fn is not None
+        _check_out(g.detach().reshape(n, 3), n64, n32, f"{name} n={n} gradient")
+        ((g.norm(dim=-1) - 1) ** 2).mean().backward()
+        _compare_leaves(_native_leaf_grads(sdf, "sdf"), g64, g32, f"{name} n={n} eikonal")
+        _check_grad(x.grad, x64, x32, f"{name} n={n} eikonal x.grad")
+        # sdf(): the sdf column alone, parameters only (x does not require grad: no x adjoint work)
+        _zero(sdf)
+        xs = x0.to(_dev())
+        s = sdf.sdf(xs)
+        (w.to(_dev()) * s).sum().backward()
+        assert xs.grad is None and sdf.lin0.bias.grad is not None
+
+
+# ------------------------------------------------------------------------------------------------------- case 3
+@pytest.mark.parametrize("name", COLOR_SHAPES)
+def test_color_loss_against_fp64(R, name):
+    shape, p, sdf, col, ren = _build(R, name)
+    cc = shape.mc.color
+    for n in SIZES:
+        p0 = points(n, seed=n + 7)
+        nr0 = torch.nn.functional.normalize(_weights(n, 3, 3), dim=-1)
+        f0 = 0.5 * _weights(n, cc.d_feature, 4)
+        Wc = _weights(n, cc.d_out, 5)
+        loss = lambda q, pp, nn_, ff: (lambda a: (a, (Wc.to(a) * a).sum()))(O.color_forward(q, cc, pp, nn_, nn_, ff))
+        a64, g64, i64 = _oracle(p, "color.", [p0, nr0, f0], loss, torch.float64)
+        a32, g32, i32 = _oracle(p, "color.", [p0, nr0, f0], loss, torch.float32)
+        _zero(col)
+        pp, nn_, ff = (t.to(_dev()).requires_grad_(True) for t in (p0, nr0, f0))
+        vd = nr0.to(_dev()).requires_grad_(True)
+        a = col(pp, nn_, vd, ff)
+        assert a.grad_fn is not None
+        _check_out(a.detach(), a64, a32, f"{name} n={n} albedo")
+        (Wc.to(_dev()) * a).sum().backward()
+        _compare_leaves(_native_leaf_grads(col, "color"), g64, g32, f"{name} n={n} color")
+        for t, r64, r32, what in zip((pp, nn_, ff), i64, i32, ("points", "normals", "feats")):
+            _check_grad(t.grad, r64, r32, f"{name} n={n} {what}.grad")
+        assert vd.grad is None
+
+
+# ------------------------------------------------------------------------------------------------------- case 4
+def _mesh_texture(sdf, col, v):
+    """Runner.validate_mesh_texture's three calls (exp_runner.py:584-615)."""
+    feats = sdf.sdf_hidden_appearance(v)[:, 1:]
+    normals = sdf.gradient(v).squeeze(1)
+    return col(v, normals, normals, feats)
+
+
+@pytest.mark.parametrize("name", ["default_64x64", "mview0"])
+def test_validate_mesh_texture_sequence(R, name):
+    shape, p, sdf, col, ren = _build(R, name)
+    sc, cc = shape.mc.sdf, shape.mc.color
+    lib = R.native.load()
+    for n in SIZES + ([4096, 100_000] if name == "default_64x64" else []):
+        v0 = points(n, seed=n + 11)
+        with torch.no_grad():
+            ref = _mesh_texture(sdf, col, v0.to(_dev()))
+        Wa = _weights(n, cc.d_out, 6)
+
+        def chain(q, v):
+            nrm = _oracle_normal(q, sc, v)
+            a = O.color_forward(q, cc, v, nrm, nrm, O.sdf_forward(q, sc, v)[:, 1:])
+            return a, (Wa.to(a) * a).sum()
+        a64, g64, _ = _oracle(p, "", [v0], chain, torch.float64)
+        a32, g32, _ = _oracle(p, "", [v0], chain, torch.float32)
+        _zero(sdf, col)
+        profile = name == "default_64x64" and n == 4096   # (a multiple of 32 points: the staged x3 weight-gradient jobs)
+        if profile:
+            lib.rnb_profile_enable(1)
+        try:
+            alb = _mesh_texture(sdf, col, v0.to(_dev()))
+            assert alb.grad_fn is not None
+            _check_out(alb.detach(), a64, a32, f"{name} n={n} texture")
+            _check_out(ref, a64, a32, f"{name} n={n} texture (no_grad)")
+            (Wa.to(_dev()) * alb).sum().backward()
+            if profile:
+                torch.cuda.synchronize()
+                classes = _profile_classes(R)
+                assert FUSED_CLASSES <= classes, f"fused sweeps missing: {sorted(FUSED_CLASSES - classes)}"
+                assert ALBEDO_H2_CLASSES <= classes, "the fused albedo sweeps did not run"
+        finally:
+            lib.rnb_profile_enable(0)
+        mine = _native_leaf_grads(sdf, "sdf")
+        mine.update(_native_leaf_grads(col, "color"))
+        g64 = {k: v for k, v in g64.items() if k.startswith(("sdf.", "color."))}
+        _compare_leaves(mine, g64, g32, f"{name} n={n} texture")
+        # the SDF leaves get gradient through the feature AND the normal: the feature head's rows and lin0 both move
+        assert float(sdf.lin0.bias.grad.abs().max()) > 0
+
+
+def _profile_classes(R):
+    lib = R.native.load()
+    ms, cnt, fl = C.c_double(), C.c_int64(), C.c_double()
+    R.native.check(lib.rnb_profile_collect(C.byref(ms), C.byref(cnt), C.byref(fl)))
+    need = lib.rnb_profile_report(None, 0)
+    buf = C.create_string_buffer(int(need) + 16)
+    lib.rnb_profile_report(buf, len(buf))
+    return {ln.rsplit(" ", 3)[0] for ln in buf.value.decode().splitlines()}
+
+
+# ------------------------------------------------------------------------------------------------------- case 5
+def test_render_loss_and_eikonal_accumulate(R):
+    shape, p, sdf, col, ren = _build(R, "default_64x64")
+    b = {k: v.to(_dev()) for k, v in O.synthetic_batch(64, seed=3, step=1).items()}
+    x0 = points(4097, seed=5).to(_dev())
+
+    def render_loss():
+        out = ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0,
+                             t_rand=b["t_rand"])
+        loss, _ = R.rnb_loss(out, b["true_rgb"], b["mask"])
+        return loss
+
+    def eik():
+        return ((sdf.gradient(x0).norm(dim=-1) - 1) ** 2).mean()
+
+    nets = (sdf, col, ren.deviation_network)
+    grads = []
+    for fn in (render_loss, eik, lambda: render_loss() + eik()):
+        _zero(*nets)
+        fn().backward()
+        grads.append({k: v.grad.clone() for k, v in sdf.named_parameters()})
+    for k in grads[0]:
+        want = grads[0][k] + grads[1][k]
+        assert _rel(grads[2][k], want) <= 1e-5, f"{k}: render + eikonal in one backward != the sum of the two"
+    assert float(grads[1]["lin0.bias"].abs().max()) > 0 and float(grads[0]["lin0.bias"].abs().max()) > 0
+
+
+# ------------------------------------------------------------------------------------------------------- cases 6, 7, 8
+def test_adjoint_scale_determinism_and_lifetime(R):
+    shape, p, sdf, col, ren = _build(R, "default_64x64")
+    n = 4096   # (a multiple of the weight-gradient chunk: every reduction of the default arithmetic is ordered, no atomics)
+    x0 = points(n, seed=9).to(_dev())
+    f0 = 0.5 * _weights(n, 256, 4).to(_dev())
+    nr0 = torch.nn.functional.normalize(_weights(n, 3, 3), dim=-1).to(_dev())
+    W, Wn, Wc = _weights(n, 257, 2).to(_dev()), _weights(n, 3, 8).to(_dev()), _weights(n, 3, 5).to(_dev())
+
+    def run(scale):
+        _zero(sdf, col)
+        x = x0.clone().requires_grad_(True)
+        ((W * sdf(x)).sum() * scale + (Wn * sdf.gradient(x).squeeze(1)).sum() * scale
+         + (Wc * col(x, nr0, nr0, f0)).sum() * scale).backward()
+        gs = [q.grad.clone() for q in list(sdf.parameters()) + list(col.parameters())]
+        return gs + [x.grad.clone()]
+
+    base = run(1.0)
+    again = run(1.0)
+    for a, b in zip(base, again):   # case 7: bit-identical
+        assert torch.equal(a, b)
+    for k in (40, -40):              # case 6: a loss times 2^k gives gradients times 2^k, bit for bit
+        s = 2.0 ** k
+        for a, b in zip(base, run(s)):
+            assert torch.equal(a * s, b), f"2^{k}: gradients not scaled bit for bit"
+    # case 8: the second backward and create_graph=True raise; the saved state is released by the backward
+    _zero(sdf, col)
+    x = x0.clone().requires_grad_(True)
+    torch.cuda.synchronize()
+    baseline = torch.cuda.memory_allocated()
+    out = sdf(x)
+    loss = (W * out).sum()
+    loss.backward(retain_graph=True)
+    with pytest.raises(RuntimeError, match="second time"):
+        loss.backward()
+    del out, loss
+    a = col(x0, nr0, nr0, f0)
+    with pytest.raises(RuntimeError, match="differentiable once"):
+        torch.autograd.grad((Wc * a).sum(), list(col.parameters()), create_graph=True)
+    del a
+    g = sdf.gradient(x0)
+    with pytest.raises(RuntimeError, match="differentiable once"):
+        torch.autograd.grad(g.sum(), list(sdf.parameters()), create_graph=True)
+    del g
+    x.grad = None
+    _zero(sdf, col)
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == baseline
+    # the default path stays forward-only and loud, whatever the other module's flag
+    sdf.set_autograd(False)
+    with pytest.raises(RuntimeError, match="forward-only"):
+        sdf(x0)
+    with torch.no_grad():
+        assert sdf(x0).grad_fn is None
