@@ -1559,6 +1559,54 @@ int bf16_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_
   return RNB_OK;
 }
 
+// The weight-gradient jobs of one bf16 backward, in launch order: the hidden layers 0 .. nh-1 (pairs gz_l / u_l and
+// zb_l / in_l), the feature head (with_color), and with color_bf16 the albedo net's layers nc-1 .. 1 and its layer 0
+// as two jobs (the 256 feature columns, the encoding columns).  f(job, flops) gets every field but the slabs.  Sizing
+// lists a PointBufs without buffers and no packed gradient: the operands and targets are then null.
+template <class F>
+static void bf16_dw_list(const Layout& L, const PointBufs& pb, bool with_color, bool color_bf16, float* packed_grad, F f) {
+  const int64_t M = pb.M;
+  auto bf = [](const void* p) { return reinterpret_cast<const bfraw*>(p); };
+  auto add = [&](const void* X1, const void* Y1, int Cy1, const void* X2, const void* Y2, int Cy2, int npairs, int K,
+                 const Lin& ln, int bias_pair, double fl, int ycol0 = 0, bool with_bias = true) {
+    BfDwJob J;
+    memset(&J, 0, sizeof(J));
+    J.X[0] = bf(X1); J.Y[0] = bf(Y1); J.Cy[0] = Cy1; J.ycol0[0] = ycol0;
+    J.X[1] = bf(X2); J.Y[1] = bf(Y2); J.Cy[1] = Cy2; J.ycol0[1] = ycol0;
+    J.npairs = npairs; J.K = K; J.lddw = ln.Kp; J.bias_pair = bias_pair;
+    if (packed_grad != nullptr) {
+      J.dW = packed_grad + ln.w_off + ycol0;      // a column range [ycol0, ycol0 + K) of the layer's [256 x Kp] gradient
+      J.db = with_bias ? packed_grad + ln.b_off : nullptr;
+    }
+    f(J, fl);
+  };
+  for (int l = 0; l < L.nh; ++l) {
+    const Lin& ln = L.hid[l];
+    const void* in = l == 0 ? (const void*)pb.e : (const void*)pb.a[l - 1];
+    const void* uin = l == 0 ? (const void*)pb.u0_k8 : (const void*)pb.u[l];
+    const int Cy = l == 0 ? L.Ep : FH;
+    add(pb.gz[l], uin, Cy, pb.zb[l], in, Cy, 2, ln.Kp, ln, 1, 4.0 * (double)M * ln.N * ln.K);
+  }
+  if (!with_color) return;
+  add(pb.fbar_k8, pb.a[L.nh - 1], FH, nullptr, nullptr, 0, 1, L.feat.Kp, L.feat, 0, 2.0 * (double)M * L.feat.N * L.feat.K);
+  if (!color_bf16) return;
+  // the albedo net's hidden layers: dW_l = zc_l^T in_l
+  for (int l = L.nc - 1; l >= 1; --l)
+    add(pb.zc8[l], pb.ac8[l - 1], FH, nullptr, nullptr, 0, 1, L.col[l].Kp, L.col[l], 0, 2.0 * (double)M * L.col[l].N * L.col[l].K);
+  // layer 0 reads the Cinp-wide input: its 256 feature columns and its 64 pe columns are two jobs
+  add(pb.zc8[0], pb.cin8, L.Cinp, nullptr, nullptr, 0, 1, FH, L.col[0], 0, 2.0 * (double)M * L.col[0].N * L.col[0].K);
+  add(pb.zc8[0], pb.cin8, L.Cinp, nullptr, nullptr, 0, 1, L.Cinp - FH, L.col[0], 0, 0.0, FH, false);
+}
+
+// points per workgroup: enough workgroups to fill the chip (njobs x splits >= ~2 per CU), ranges a multiple of 64
+static void bf16_dw_split(int64_t M, int njobs, int* splits_out, int64_t* rows_out) {
+  int splits = (int)((512 + njobs - 1) / njobs);
+  int64_t rows = (M + splits - 1) / splits;
+  rows = (rows + 63) / 64 * 64;
+  *splits_out = (int)((M + rows - 1) / rows);
+  *rows_out = rows;
+}
+
 // RA, sdf-head row gradient, FB and every dW job of the SDF network (+ the feature head's) for one backward
 int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, bool color_bf16, float* packed_grad,
                   hipStream_t s) {
@@ -1596,58 +1644,26 @@ int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with
   BfDwGroup grp;
   memset(&grp, 0, sizeof(grp));
   grp.M = M;
-  // points per workgroup: enough workgroups to fill the chip (njobs x splits >= ~2 per CU), ranges a multiple of 16
-  const int njobs_est = L.nh + (with_color ? 1 : 0) + ((with_color && color_bf16) ? L.nc + 1 : 0);
-  int splits = (int)((512 + njobs_est - 1) / njobs_est);
-  int64_t rows = (M + splits - 1) / splits;
-  rows = (rows + 63) / 64 * 64;
-  splits = (int)((M + rows - 1) / rows);
-  grp.splits = splits;
-  grp.rows_per_split = rows;
-  // (the staged fp32 kernel's slabs at the tail of the workspace are free again: its reduction was enqueued earlier)
-  float* part = det ? pb.dw_part : nullptr;
-  int64_t part_left = det ? pb.dw_part_floats : 0;
   double fl = 0;
-  auto add = [&](const bfraw* X1, const bfraw* Y1, int Cy1, const bfraw* X2, const bfraw* Y2, int Cy2, int npairs, int K,
-                 const Lin& ln, int bias_pair, double f, int ycol0 = 0, bool with_bias = true) -> int {
-    if (grp.njobs == kMaxBfDwJobs) RNB_FAIL(RNB_E_INVALID, "too many weight-gradient jobs for one bf16 launch");
-    BfDwJob& J = grp.job[grp.njobs++];
-    J.X[0] = X1; J.Y[0] = Y1; J.Cy[0] = Cy1; J.ycol0[0] = ycol0;
-    J.X[1] = X2; J.Y[1] = Y2; J.Cy[1] = Cy2; J.ycol0[1] = ycol0;
-    J.npairs = npairs; J.K = K; J.lddw = ln.Kp; J.bias_pair = bias_pair;
-    J.dW = packed_grad + ln.w_off + ycol0;      // a column range [ycol0, ycol0 + K) of the layer's [256 x Kp] gradient
-    J.db = with_bias ? packed_grad + ln.b_off : nullptr;
-    J.part = nullptr; J.partb = nullptr;
-    if (det) {
-      const int64_t need = (int64_t)splits * FH * ln.Kp + (int64_t)splits * FH;
-      if (need > part_left) RNB_FAIL(RNB_E_WORKSPACE, "deterministic bf16 dW: partial-slab workspace exhausted");
-      J.part = part; J.partb = part + (int64_t)splits * FH * ln.Kp;
-      part += need; part_left -= need;
-    }
+  bf16_dw_list(L, pb, with_color, color_bf16, packed_grad, [&](const BfDwJob& J, double f) {
+    if (grp.njobs < kMaxBfDwJobs) grp.job[grp.njobs] = J;
+    ++grp.njobs;
     fl += f;
-    return RNB_OK;
-  };
-  if (det) RNB_CHECK_HIP(hipMemsetAsync(pb.dw_part, 0, (size_t)pb.dw_part_floats * sizeof(float), s));
-  for (int l = 0; l < L.nh; ++l) {
-    const Lin& ln = L.hid[l];
-    const bfraw* in = l == 0 ? reinterpret_cast<const bfraw*>(pb.e) : reinterpret_cast<const bfraw*>(pb.a[l - 1]);
-    const bfraw* uin = l == 0 ? reinterpret_cast<const bfraw*>(pb.u0_k8) : reinterpret_cast<const bfraw*>(pb.u[l]);
-    const int Cy = l == 0 ? L.Ep : FH;
-    RNB_TRY(add(reinterpret_cast<const bfraw*>(pb.gz[l]), uin, Cy, reinterpret_cast<const bfraw*>(pb.zb[l]), in, Cy, 2, ln.Kp,
-                ln, 1, 4.0 * (double)M * ln.N * ln.K));
-  }
-  if (with_color) {
-    RNB_TRY(add(reinterpret_cast<const bfraw*>(pb.fbar_k8), reinterpret_cast<const bfraw*>(pb.a[L.nh - 1]), FH, nullptr,
-                nullptr, 0, 1, L.feat.Kp, L.feat, 0, 2.0 * (double)M * L.feat.N * L.feat.K));
-    if (color_bf16) {   // the albedo net's hidden layers: dW_l = zc_l^T in_l
-      for (int l = L.nc - 1; l >= 1; --l)
-        RNB_TRY(add(reinterpret_cast<const bfraw*>(pb.zc8[l]), reinterpret_cast<const bfraw*>(pb.ac8[l - 1]), FH, nullptr, nullptr,
-                    0, 1, L.col[l].Kp, L.col[l], 0, 2.0 * (double)M * L.col[l].N * L.col[l].K));
-      // layer 0 reads the Cinp-wide input: its 256 feature columns and its 64 pe columns are two jobs
-      RNB_TRY(add(reinterpret_cast<const bfraw*>(pb.zc8[0]), reinterpret_cast<const bfraw*>(pb.cin8), L.Cinp, nullptr, nullptr, 0, 1,
-                  FH, L.col[0], 0, 2.0 * (double)M * L.col[0].N * L.col[0].K));
-      RNB_TRY(add(reinterpret_cast<const bfraw*>(pb.zc8[0]), reinterpret_cast<const bfraw*>(pb.cin8), L.Cinp, nullptr, nullptr, 0, 1,
-                  L.Cinp - FH, L.col[0], 0, 0.0, FH, false));
+  });
+  if (grp.njobs > kMaxBfDwJobs) RNB_FAIL(RNB_E_INVALID, "too many weight-gradient jobs for one bf16 launch");
+  bf16_dw_split(M, grp.njobs, &grp.splits, &grp.rows_per_split);
+  const int splits = grp.splits;
+  // (the staged fp32 kernel's slabs at the tail of the workspace are free again: its reduction was enqueued earlier)
+  if (det) {
+    RNB_CHECK_HIP(hipMemsetAsync(pb.dw_part, 0, (size_t)pb.dw_part_floats * sizeof(float), s));
+    float* part = pb.dw_part;
+    int64_t part_left = pb.dw_part_floats;
+    for (int q = 0; q < grp.njobs; ++q) {
+      BfDwJob& J = grp.job[q];
+      const int64_t need = (int64_t)splits * FH * J.lddw + (int64_t)splits * FH;
+      if (need > part_left) RNB_FAIL(RNB_E_WORKSPACE, "deterministic bf16 dW: partial-slab workspace exhausted");
+      J.part = part; J.partb = part + (int64_t)splits * FH * J.lddw;
+      part += need; part_left -= need;
     }
   }
   {
@@ -1662,22 +1678,18 @@ int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with
   return RNB_OK;
 }
 
-// floats of deterministic partial-slab workspace for bf16_backward over M points
-int64_t bf16_dw_partial_floats(const Layout& L, int64_t M, bool with_color) {
-  const bool cbf = with_color && bf16_color_supported(L);
-  const int njobs_est = L.nh + (with_color ? 1 : 0) + (cbf ? L.nc + 1 : 0);
-  int splits = (int)((512 + njobs_est - 1) / njobs_est);
-  int64_t rows = (M + splits - 1) / splits;
-  rows = (rows + 63) / 64 * 64;
-  splits = (int)((M + rows - 1) / rows);
-  int64_t total = 0;
-  for (int l = 0; l < L.nh; ++l) total += (int64_t)splits * FH * L.hid[l].Kp + (int64_t)splits * FH;
-  if (with_color) total += (int64_t)splits * FH * L.feat.Kp + (int64_t)splits * FH;
-  if (cbf) {
-    for (int l = 1; l < L.nc; ++l) total += (int64_t)splits * FH * L.col[l].Kp + (int64_t)splits * FH;
-    total += 2 * ((int64_t)splits * FH * L.col[0].Kp + (int64_t)splits * FH);
-  }
-  return total;
+int64_t bf16_dw_floats(const Layout& L, int64_t M, bool with_color) {
+  PointBufs pb{};
+  int njobs = 0;
+  int64_t kp = 0;   // (each job: [splits][256][lddw] + [splits][256])
+  bf16_dw_list(L, pb, with_color, with_color && bf16_color_supported(L), nullptr, [&](const BfDwJob& J, double) {
+    ++njobs;
+    kp += J.lddw;
+  });
+  int splits;
+  int64_t rows;
+  bf16_dw_split(M, njobs, &splits, &rows);
+  return (int64_t)splits * FH * (kp + njobs);
 }
 
 }  // namespace rnb

@@ -721,8 +721,6 @@ struct EpiSkipPE {
 // =====================================================================================================
 // launch helpers
 // =====================================================================================================
-// algorithmic FLOPs of one layer-shaped GEMM over M points: real (unpadded) layer shape
-static inline double mm_flops(int64_t M, const Lin& ln) { return 2.0 * (double)M * ln.N * ln.K; }
 
 // x3: the product as six bf16 MFMA terms (RNB_VARIANT_X3; k-contiguous weights, N >= 256, K % 16 == 0)
 template <bool B_KMAJOR, class Epi>
@@ -764,307 +762,6 @@ static int launch_rows(const float* A, int lda, const float* W, int ldw, int64_t
   }
   RNB_CHECK_LAUNCH();
   return RNB_OK;
-}
-
-// Collects the dW jobs of one backward pass and launches them as (at most) three grouped GEMMs, one per kernel
-// variant (K-tile 128 exact / K-tile 64 exact / K-tile 64 guarded).  Every job reads buffers that stay untouched until the end of sweep_backward, so deferring the
-// launch is safe.
-// split-K plan of one dW job: kernel variant v ([0] K % 128 == 0, [1] K % 64 == 0, [2] anything: guarded), number of
-// point splits and points per split.  Shared by DwBatch::add and by the sizing of the deterministic partial slabs.
-static void dw_plan(int64_t M, int N, int K, int* v_out, int* splits_out, int* rows_out) {
-  const bool exact = N % 128 == 0 && M % BK == 0;
-  const int v = (exact && K % 128 == 0) ? 0 : (exact && K % 64 == 0) ? 1 : 2;
-  const int kt = v == 0 ? 128 : 64;                  // tile width along K of the variant (see kernel)
-  const int min_rows = v == 0 ? 1024 : 512;          // points per block (half-size tiles: half the rows)
-  const int tiles = ((N + 127) / 128) * ((K + kt - 1) / kt);
-  int splits = (int)((M + min_rows - 1) / min_rows);
-  const int max_splits = (1024 + tiles - 1) / tiles;  // ~1024 blocks per job
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  if (splits >= 8) splits = splits / 8 * 8;   // multiple of 8: enables the XCD-aware placement in the kernel
-  int rows = (int)((M + splits - 1) / splits);
-  rows = (rows + BK - 1) / BK * BK;
-  // (the kernel tolerates empty splits, so the job keeps the multiple-of-8 split count)
-  if ((int64_t)rows * splits < M) splits = (int)((M + rows - 1) / rows);
-  *v_out = v;
-  *splits_out = splits;
-  *rows_out = rows;
-}
-
-// Point split of the staged 256 x 256 kernel: one workgroup per (job, split) and ONE round of workgroups (<= 256, one per
-// CU), each job's share of them proportional to its work (operand pairs), so every CU multiplies for the whole launch.
-// Partial gradients leave through plain stores into slabs that dw_reduce_kernel sums in split order: an fp32 atomic tail
-// of 256 KB per workgroup would cost ~50 us per round at the chip's ~1.3 TB/s atomic rate, with nothing to hide under.
-static void dw_staged_plan(int64_t M, int npairs, int total_pairs, int* splits_out, int* rows_out) {
-  int splits = total_pairs > 0 ? (256 * npairs) / total_pairs : 1;
-  if (splits < 1) splits = 1;
-  int64_t rows = (M + splits - 1) / splits;
-  rows = (rows + kStChunk - 1) / kStChunk * kStChunk;
-  if (rows < 2 * kStChunk) rows = 2 * kStChunk;
-  splits = (int)((M + rows - 1) / rows);     // every split is non-empty: the reduction reads every slab
-  *splits_out = splits;
-  *rows_out = (int)rows;
-}
-
-// Jobs of the one-workgroup-per-gradient kernels.  The LDS-DMA staged kernel takes 256 x 256 matrices only; the x3
-// kernel also takes 256 x K with K a multiple of 64 as COLUMN RANGES of the Y operand: 256-column ranges run as whole
-// jobs, what is left as narrow (64-column) jobs — the PE-input layer (K = 64) and the albedo net's first layer
-// (K = 320 = 256 + 64) then ride in the same launch instead of a separate fp32-MFMA one.  Work units for the split
-// plan: a 256-column pair costs about twice a narrow pair (a quarter of the MFMAs, the same staging of X).
-static bool x3_job_shape(bool x3, int N, int K) { return N == 256 && (K == 256 || (x3 && K % 64 == 0 && K >= 64 && K <= 1024)); }
-static int x3_job_units(int npairs, int width) { return npairs * (width >= 256 ? 2 : 1); }
-template <class F>
-static void x3_for_each_range(int K, F f) {   // f(first column, width): 256-wide ranges, then 64-wide ones
-  int c = 0;
-  for (; c + 256 <= K; c += 256) f(c, 256);
-  for (; c + 64 <= K; c += 64) f(c, 64);
-}
-
-struct DwBatch {
-  DwGroup grp[4];     // [0] K % 128 == 0, [1] K % 64 == 0, [2] anything (guarded), [3] 256 x 256 (LDS-DMA staged)
-  double flops[4];
-  int64_t M;
-  hipStream_t s;
-  bool lds_path;      // RNB_VARIANT_DW_LDS: staged-through-LDS kernels (A/B switch)
-  bool no_staged = true;    // RNB_VARIANT_DW_STAGED clears it: 256 x 256 jobs through the LDS-DMA staged kernel
-  bool x3 = false;          // RNB_VARIANT_X3: 256 x 256 jobs through gemm_dw_x3_kernel (same split plan and slabs)
-  bool h2 = false;          // RNB_VARIANT_X2H: ... as three fp16 terms, the adjoint operands scaled by their recorded maxima
-  float* part;        // RNB_VARIANT_DETERMINISTIC: bump allocator over the zeroed partial-slab workspace (or nullptr)
-  int64_t part_left;
-  float* slab;        // slabs of the staged 256 x 256 kernel (always; the tail of the same workspace)
-  int64_t slab_left;
-  float* const slab_base;         // the slab workspace as handed in: every flushed group starts from it again
-  const int64_t slab_floats;
-  // reduce-only jobs: slabs that OTHER kernels wrote (per-tile column sums of the fused albedo backward, per-slab sums of the
-  // sdf-head row): summed by the reduction launch that follows the last group of weight-gradient jobs, no launch of their own
-  DwJob extra[kMaxDwExtra];
-  int nextra = 0;
-  int add_reduce_only(float* dW, int lddw, float* db, float* part, float* partb, int N, int K, int splits) {
-    if (nextra == kMaxDwExtra) RNB_FAIL(RNB_E_INVALID, "too many reduce-only jobs");
-    DwJob& j = extra[nextra++];
-    memset(&j, 0, sizeof(j));
-    j.dW = dW; j.db = db; j.part = part; j.partb = partb;
-    j.N = N; j.K = K; j.lddw = lddw; j.splits = splits;
-    return RNB_OK;
-  }
-  DwBatch(int64_t M_, hipStream_t s_, bool lds_path_, float* part_, int64_t part_floats, float* slab_, int64_t slab_floats_)
-      : M(M_), s(s_), lds_path(lds_path_), part(part_), part_left(part_floats), slab(slab_), slab_left(slab_floats_),
-        slab_base(slab_), slab_floats(slab_floats_) {
-    for (int v = 0; v < 4; ++v) { grp[v].njobs = 0; grp[v].M = (int)M_; flops[v] = 0.0; }
-  }
-  // the staged kernel: every job of the group is split the same way, decided when the group is complete
-  int flush_staged(bool final = false) {
-    DwGroup& g = grp[3];
-    if (g.njobs == 0 && !(final && nextra > 0)) return RNB_OK;
-    int total_pairs = 0;   // (work units: x3_job_units)
-    for (int q = 0; q < g.njobs; ++q) total_pairs += x3_job_units(g.job[q].npairs, g.job[q].K);
-    for (int a = 0, b = g.njobs - 1; a < b; ++a, --b) {   // most recently produced operands first (see flush)
-      const DwJob t = g.job[a];
-      g.job[a] = g.job[b];
-      g.job[b] = t;
-    }
-    int end = 0;
-    for (int q = 0; q < g.njobs; ++q) {
-      DwJob& j = g.job[q];
-      int splits, rows;
-      dw_staged_plan(M, x3_job_units(j.npairs, j.K), total_pairs, &splits, &rows);
-      {   // never more slabs than the workspace holds (a group smaller than the one the workspace was sized for)
-        const int64_t per_split = (int64_t)j.N * j.K + j.N;
-        const int64_t room = slab != nullptr ? slab_left / per_split / (g.njobs - q) : 0;
-        if (room < 1) RNB_FAIL(RNB_E_WORKSPACE, "weight-gradient slab workspace exhausted");
-        if (splits > room) {
-          splits = (int)room;
-          int64_t r = (M + splits - 1) / splits;
-          r = (r + kStChunk - 1) / kStChunk * kStChunk;
-          rows = (int)r;
-          splits = (int)((M + rows - 1) / rows);
-        }
-      }
-      j.splits = splits;
-      j.rows_per_split = rows;
-      end += splits;
-      j.block_end = end;
-      const int64_t need = (int64_t)splits * j.N * j.K + (int64_t)splits * j.N;
-      if (slab == nullptr || need > slab_left) RNB_FAIL(RNB_E_WORKSPACE, "weight-gradient slab workspace exhausted");
-      j.part = slab;
-      j.partb = slab + (int64_t)splits * j.N * j.K;
-      slab += need;
-      slab_left -= need;
-    }
-    if (end > 0) {   // (two scopes: the class time of the weight-gradient kernel is then its own launch duration, as a kernel trace shows it)
-      ProfScope prof(flops[3], s, "dW(x3: 256x256 + narrow jobs)");
-      if (x3 && h2) hipLaunchKernelGGL((gemm_dw_x3_kernel<0, 2>), dim3((unsigned)end), dim3(512), 0, s, g);
-      else if (x3) hipLaunchKernelGGL((gemm_dw_x3_kernel<0, 3>), dim3((unsigned)end), dim3(512), 0, s, g);
-      else hipLaunchKernelGGL(gemm_dw_staged_kernel<0>, dim3((unsigned)end), dim3(1024), 0, s, g);
-    }
-    RNB_CHECK_LAUNCH();
-    int nred = g.njobs;
-    if (final) {   // the reduce-only jobs ride behind the real ones (no blocks of the kernel above: block_end stays `end`)
-      for (int q = 0; q < nextra; ++q) {
-        g.job[nred] = extra[q];
-        g.job[nred].block_end = end;
-        ++nred;
-      }
-      nextra = 0;
-    }
-    {
-      ProfScope prof(0.0, s, "dW(slab reduce)");
-      hipLaunchKernelGGL(dw_reduce_kernel<0>, dim3(256, nred), dim3(256), 0, s, g);
-    }
-    g.njobs = 0;
-    flops[3] = 0.0;
-    // the reduction above has read every slab of this group and the next group's kernels follow it on the same
-    // stream: the workspace (sized for ONE group of kMaxDwJobs, dw_slab_floats) is free again.  Without this a model
-    // with more 256-wide gradient jobs than one group holds ran out of slabs on its second group.
-    slab = slab_base;
-    slab_left = slab_floats;
-    RNB_CHECK_LAUNCH();
-    return RNB_OK;
-  }
-  int flush(int v) {
-    DwGroup& g = grp[v];
-    if (g.njobs == 0) return RNB_OK;
-    // Jobs are added in the order the backward produces their operands (layer nh-1 first); launch them
-    // most-recent-first so that the operands written last (zb_0, zb_1, ...) are still in the memory-side
-    // cache when their job runs.
-    for (int a = 0, b = g.njobs - 1; a < b; ++a, --b) {
-      const DwJob t = g.job[a];
-      g.job[a] = g.job[b];
-      g.job[b] = t;
-    }
-    {
-      int end = 0;   // recompute the prefix sums of the block counts for the new order
-      for (int q = 0; q < g.njobs; ++q) {
-        DwJob& j = g.job[q];
-        const int kt = v == 0 ? 128 : 64;
-        const int tiles = ((j.N + 127) / 128) * ((j.K + kt - 1) / kt);
-        end += (tiles * j.splits + 7) / 8 * 8;
-        j.block_end = end;
-      }
-    }
-    const dim3 grid((unsigned)g.job[g.njobs - 1].block_end);
-    {
-      ProfScope prof(flops[v], s, "dW(other)");
-      if (v == 0 && !lds_path) hipLaunchKernelGGL((gemm_dw_direct_kernel<128, 3>), grid, dim3(256), 0, s, g);
-      else if (v == 1 && !lds_path) hipLaunchKernelGGL((gemm_dw_direct_kernel<64, 3>), grid, dim3(256), 0, s, g);
-      else if (v == 0) hipLaunchKernelGGL((gemm_dw_kernel<false, 128>), grid, dim3(256), 0, s, g);
-      else if (v == 1) hipLaunchKernelGGL((gemm_dw_kernel<false, 64>), grid, dim3(256), 0, s, g);
-      else hipLaunchKernelGGL((gemm_dw_kernel<true, 64>), grid, dim3(256), 0, s, g);
-      if (part != nullptr) {   // ordered reduction of the partial slabs
-        RNB_CHECK_LAUNCH();
-        hipLaunchKernelGGL(dw_reduce_kernel<0>, dim3(256, g.njobs), dim3(256), 0, s, g);
-      }
-    }
-    g.njobs = 0;
-    flops[v] = 0.0;
-    RNB_CHECK_LAUNCH();
-    return RNB_OK;
-  }
-  int add(DwPair p1, DwPair p2, int npairs, int N, int K, float* dW, int lddw, float* db, int bias_pair, double fl) {
-    int v, splits, rows;
-    dw_plan(M, N, K, &v, &splits, &rows);
-    if (x3_job_shape(x3, N, K) && M % kStChunk == 0 && !lds_path && !no_staged) {   // -> the one-workgroup-per-gradient kernel
-      int rc = RNB_OK;
-      x3_for_each_range(K, [&](int c0, int width) {
-        if (rc != RNB_OK) return;
-        if (grp[3].njobs == kMaxDwJobs) rc = flush_staged();
-        if (rc != RNB_OK) return;
-        DwJob& j = grp[3].job[grp[3].njobs++];
-        j.p1 = p1; j.p2 = p2;
-        j.p1.Y += c0; j.p2.Y += c0;              // column range of the Y operands (their leading dimension stays)
-        j.dW = dW + c0;
-        j.db = c0 == 0 ? db : nullptr;            // the bias sums (columns of X) belong to the first range
-        j.part = nullptr; j.partb = nullptr;
-        j.npairs = npairs; j.N = N; j.K = width; j.lddw = lddw; j.bias_pair = bias_pair;
-        j.splits = 0; j.rows_per_split = 0; j.block_end = 0;
-      });
-      RNB_TRY(rc);
-      flops[3] += fl;
-      return RNB_OK;
-    }
-    if (grp[v].njobs == kMaxDwJobs) RNB_TRY(flush(v));
-    const int kt = v == 0 ? 128 : 64;
-    const int tiles = ((N + 127) / 128) * ((K + kt - 1) / kt);
-    DwGroup& g = grp[v];
-    DwJob& j = g.job[g.njobs];
-    j.p1 = p1; j.p2 = p2; j.dW = dW; j.db = db;
-    j.part = nullptr;
-    j.partb = nullptr;
-    if (part != nullptr) {
-      const int64_t need = (int64_t)splits * N * lddw + (int64_t)splits * N;
-      if (need > part_left) RNB_FAIL(RNB_E_WORKSPACE, "deterministic dW: partial-slab workspace exhausted");
-      j.part = part;
-      j.partb = part + (int64_t)splits * N * lddw;
-      part += need;
-      part_left -= need;
-    }
-    j.npairs = npairs; j.N = N; j.K = K; j.lddw = lddw; j.bias_pair = bias_pair;
-    j.splits = splits; j.rows_per_split = rows;
-    // jobs start on a multiple of 8 blocks so that (block & 7) is the XCD inside every job
-    const int begin = g.njobs ? g.job[g.njobs - 1].block_end : 0;
-    j.block_end = begin + (tiles * splits + 7) / 8 * 8;
-    ++g.njobs;
-    flops[v] += fl;
-    return RNB_OK;
-  }
-  int flush_all() {
-    RNB_TRY(flush(1));   // holds the first layer's job: its operands are the most recent
-    RNB_TRY(flush_staged(true));
-    RNB_TRY(flush(0));
-    return flush(2);
-  }
-};
-
-// floats of partial-slab workspace the deterministic variant needs for one backward over M points: the same job list
-// as sweep_backward
-// floats of slab workspace of the staged kernel for one backward over M points (the 256 x 256 jobs of sweep_backward)
-int64_t dw_staged_floats(const Layout& L, int64_t M, bool with_color) {
-  const bool x3 = is_x3(L);
-  int total_units = 0;
-  auto units = [&](const Lin& ln, int npairs) {
-    if (!x3_job_shape(x3, ln.Np, ln.Kp)) return;
-    x3_for_each_range(ln.Kp, [&](int, int width) { total_units += x3_job_units(npairs, width); });
-  };
-  for (int l = 0; l < L.nh; ++l) units(L.hid[l], 2);
-  if (with_color) {
-    units(L.feat, 1);
-    for (int l = 0; l < L.nc; ++l) units(L.col[l], 1);
-  }
-  int64_t total = 0;
-  auto job = [&](const Lin& ln, int npairs) {
-    if (!x3_job_shape(x3, ln.Np, ln.Kp)) return;
-    x3_for_each_range(ln.Kp, [&](int, int width) {
-      int splits, rows;
-      dw_staged_plan(M, x3_job_units(npairs, width), total_units, &splits, &rows);
-      total += (int64_t)splits * 256 * width + (int64_t)splits * 256;
-    });
-  };
-  for (int l = 0; l < L.nh; ++l) job(L.hid[l], 2);
-  if (with_color) {
-    job(L.feat, 1);
-    for (int l = 0; l < L.nc; ++l) job(L.col[l], 1);
-  }
-  return total;
-}
-
-// floats of ordered-reduction workspace of the atomic kernels (RNB_VARIANT_DETERMINISTIC), same job list as sweep_backward
-int64_t dw_partial_floats(const Layout& L, int64_t M, bool with_color) {
-  int64_t total = 0;
-  // (jobs that DwBatch::add hands to the one-workgroup-per-gradient kernels leave through that kernel's own slabs, whatever
-  // the variant: no ordered-reduction slabs — and no 200 MB memset per step — for them)
-  const bool staged_path = (is_x3(L) || (L.variant & RNB_VARIANT_DW_STAGED) != 0) && !(L.variant & RNB_VARIANT_DW_LDS);
-  auto job = [&](int N, int K) {
-    if (staged_path && x3_job_shape(is_x3(L), N, K) && M % kStChunk == 0) return;
-    int v, splits, rows;
-    dw_plan(M, N, K, &v, &splits, &rows);
-    total += (int64_t)splits * N * K + (int64_t)splits * N;
-  };
-  if (with_color) {
-    for (int l = 0; l < L.nc; ++l) job(L.col[l].Np, L.col[l].Kp);
-    job(L.feat.Np, L.feat.Kp);
-  }
-  for (int l = 0; l < L.nh; ++l) job(L.hid[l].Np, L.hid[l].Kp);
-  return total;
 }
 
 // the split mirror of the matrix at float offset `off` of the packed buffer (x3_pack_weights), or nullptr
@@ -1278,38 +975,21 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
   const bool with_color = parts.albedo;
   const int64_t M = pb.M, Mp = pb.Mp;
   const bool det = (L.variant & RNB_VARIANT_DETERMINISTIC) != 0;
-  if (pb.dw_part == nullptr) RNB_FAIL(RNB_E_WORKSPACE, "no weight-gradient slab workspace was carved");
-  // workspace = [ordered-reduction slabs of the atomic kernels (deterministic variant only) | slabs of the staged kernel]
-  const int64_t staged_floats = dw_staged_floats(L, M, parts.albedo || parts.feat);
-  const int64_t det_floats = pb.dw_part_floats - staged_floats;
-  if (det && det_floats > 0) RNB_CHECK_HIP(hipMemsetAsync(pb.dw_part, 0, (size_t)det_floats * sizeof(float), s));
-  DwBatch dw(M, s, (L.variant & RNB_VARIANT_DW_LDS) != 0, det ? pb.dw_part : nullptr, det ? det_floats : 0,
-             pb.dw_part + det_floats, staged_floats);
-  dw.x3 = is_x3(L);
-  dw.no_staged = (L.variant & RNB_VARIANT_DW_STAGED) == 0 && !dw.x3;
+  RNB_TRY(dw_zero_partials(L, pb, parts, s));
   // x2h weight gradients: every adjoint tensor's producer (fused sweeps, albedo backward) records its maximum
   const bool h2 = is_x2h(L) && fused && !is_bf16(L) && pb.amax != nullptr;
-  dw.h2 = h2;
   // (pb.amax was zeroed by the composite backward, the first kernel of rnb_render_bwd)
   const bool color_bf16 = is_bf16(L) && with_color && bf16_color_supported(L) && pb.cin8 != nullptr;
   // the albedo network's backward as ONE fused sweep (color_h2.hip), which also forms geb = J_pe(x) nbar_total
   const bool color_h2 = with_color && h2 && color_h2_supported(L) && pb.col_part != nullptr;
+  // the weight-gradient jobs (dw.hip) follow every other launch of the backward; bf16_color_backward's are bf16_backward's
+  BwdParts dw_parts = parts;
+  dw_parts.albedo = with_color && !color_bf16;
   // ---- C': albedo network backward ---------------------------------------------------------------
   if (color_bf16) {
     RNB_TRY(bf16_color_backward(L, packed, pb, packed_grad, s));
   } else if (color_h2) {
     RNB_TRY(color_h2_backward(L, packed, pb, s, parts.sdf, parts.color_inputs));
-    for (int l = L.nc - 1; l >= 0; --l) {
-      const Lin& ln = L.col[l];
-      const float* in = l == 0 ? pb.cin : pb.ac[l - 1];
-      const int ldin = l == 0 ? L.Cinp : L.Hcp;
-      DwPair p{pb.zc[l], L.Hcp, in, ldin, 0, pb.amax + AMAX_ZC + l, pb.smax + (l == 0 ? SMAX_CIN : SMAX_AC + l - 1)};
-      RNB_TRY(dw.add(p, p, 1, ln.Np, ln.Kp, packed_grad + ln.w_off, ln.Kp, packed_grad + ln.b_off, 0, mm_flops(M, ln)));
-    }
-    // the output layer's gradient: per-tile column sums, summed in tile order by the reduction launch of the weight gradients
-    const int64_t tiles = Mp / 64;
-    RNB_TRY(dw.add_reduce_only(packed_grad + L.colo.w_off, L.colo.Kp, packed_grad + L.colo.b_off, pb.col_part,
-                               pb.col_part + tiles * L.Co * L.Hcp, L.Co, L.Hcp, (int)tiles));
   } else if (with_color) {
     const int chunks = L.Hcp / 32;   // 32-column chunks x row slabs, ~256 workgroups, slabs a multiple of 64 rows
     int64_t slabs = det ? 1 : (256 + chunks - 1) / chunks;   // deterministic: ONE slab, i.e. one add per address onto zero
@@ -1318,29 +998,24 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
     hipLaunchKernelGGL(color_out_bwd_kernel, dim3(blocks_for(M, rows_per_blk), chunks), dim3(512), 0, s, pb.albbar, pb.alb,
                        pb.ac[L.nc - 1], L.Hcp, L.Hc, packed + L.colo.w_off, L.colo.Kp, L.Co, L.squeeze, M,
                        rows_per_blk, pb.zc[L.nc - 1], packed_grad + L.colo.w_off, packed_grad + L.colo.b_off,
-                       h2 ? pb.amax + AMAX_ZC + (L.nc - 1) : (unsigned*)nullptr);
+                       h2_slot(h2, pb.amax, AMAX_ZC + L.nc - 1));
     RNB_CHECK_LAUNCH();
     for (int l = L.nc - 1; l >= 0; --l) {
       const Lin& ln = L.col[l];
-      const float* in = l == 0 ? pb.cin : pb.ac[l - 1];
-      const int ldin = l == 0 ? L.Cinp : L.Hcp;
-      DwPair p{pb.zc[l], L.Hcp, in, ldin, 0, h2 ? pb.amax + AMAX_ZC + l : nullptr,
-               h2 ? pb.smax + (l == 0 ? SMAX_CIN : SMAX_AC + l - 1) : nullptr};
-      RNB_TRY(dw.add(p, p, 1, ln.Np, ln.Kp, packed_grad + ln.w_off, ln.Kp, packed_grad + ln.b_off, 0, mm_flops(M, ln)));
       if (l > 0) {
         EpiReluMask epi{pb.ac[l - 1], pb.zc[l - 1], L.Hcp, L.col[l - 1].N};
         // zc_{l-1} = (zc_l W_l) * relu': k-contiguous product against the transposed copy W_l^T [Kp x Np]
         // (per-layer path: six bf16 terms; the kernel leaves max |acc| for the x2h weight-gradient job of zc_{l-1})
         RNB_TRY((launch_rows<false, EpiReluMask>(pb.zc[l], L.Hcp, packed + ln.wT_off, ln.Np, Mp, ln.Kp, ln.Np, epi, mm_flops(M, ln), s, is_x3(L),
-                                                 x3_mirror(L, packed, ln.wT_off), h2 ? pb.amax + AMAX_ZC + (l - 1) : nullptr, M)));
+                                                 x3_mirror(L, packed, ln.wT_off), h2_slot(h2, pb.amax, AMAX_ZC + l - 1), M)));
       } else {
         EpiStore epi{pb.cinb, L.Cinp};
         RNB_TRY((launch_rows<false, EpiStore>(pb.zc[0], L.Hcp, packed + ln.wT_off, ln.Np, Mp, ln.Kp, ln.Np, epi, mm_flops(M, ln), s, is_x3(L),
-                                              x3_mirror(L, packed, ln.wT_off), h2 ? pb.amax + AMAX_CINB : nullptr, M)));
+                                              x3_mirror(L, packed, ln.wT_off), h2_slot(h2, pb.amax, AMAX_CINB), M)));
       }
     }
   }
-  if (!parts.sdf) return dw.flush_all();
+  if (!parts.sdf) return dw_backward(L, pb, dw_parts, h2, color_h2, 0, packed_grad, s);
   // ---- nbar (+ albedo-net contribution) -> geb = u_0 -----------------------------------------------
   if (!color_h2 && parts.normal) {
     const int wt = (with_color && L.Cinp - L.F > L.Ep) ? L.Cinp - L.F : L.Ep;
@@ -1351,8 +1026,9 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
   RNB_CHECK_LAUNCH();
   if (is_bf16(L)) {
     // RNB_VARIANT_BF16: RA, the sdf-head row, FB and every weight gradient of the SDF network (+ feature head) run as
-    // bf16 sweeps on the bf16 saved state; the albedo net's own (fp32) weight-gradient jobs were queued above
-    RNB_TRY(dw.flush_all());
+    // bf16 sweeps on the bf16 saved state; the albedo net's own (fp32) weight-gradient jobs go first
+    dw_parts.sdf = false;
+    RNB_TRY(dw_backward(L, pb, dw_parts, h2, color_h2, 0, packed_grad, s));
     return bf16_backward(L, packed, pb, with_color, color_bf16, packed_grad, s);
   }
   // ---- RA: adjoint of the reverse sweep, forward layer order -----------------------------------------
@@ -1371,69 +1047,39 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
     }
   }
   // ---- sdf-head row gradient ---------------------------------------------------------------------
-  {
-    // Hp / 32 column chunks x row slabs, ~256 workgroups in total, slabs a multiple of the 64 row phases
-    const int chunks = L.Hp / 32;
-    int64_t slabs = det ? 1 : (256 + chunks - 1) / chunks;
-    int rows_per_blk = (int)((M + slabs - 1) / slabs);
-    rows_per_blk = (rows_per_blk + 63) / 64 * 64;
-    // with the one-workgroup-per-gradient kernels (x3 / staged) there is a slab reduction at the end of the backward: the row
-    // slabs' sums ride in it (no atomics: bit-reproducible); otherwise fp32 atomics (one slab in the deterministic variant)
-    const bool slab_out = !dw.no_staged && !dw.lds_path && pb.sdfh_part != nullptr && M % kStChunk == 0;
-    if (slab_out) {
-      slabs = kSdfHeadSlabs;
-      rows_per_blk = (int)((M + slabs - 1) / slabs);
-      rows_per_blk = (rows_per_blk + 63) / 64 * 64;
-    }
-    const unsigned nslab = blocks_for(M, rows_per_blk);
-    float* part_w = slab_out ? pb.sdfh_part : nullptr;
-    float* part_b = slab_out ? pb.sdfh_part + (size_t)nslab * L.Hp : nullptr;
-    hipLaunchKernelGGL(sdf_head_bwd_kernel, dim3(nslab, chunks), dim3(512), 0, s, pb.a[L.nh - 1],
-                       (fused || !parts.normal) ? (const float*)nullptr : (const float*)pb.u[L.nh], (const float*)pb.u[L.nh], u_tiles, L.Hp,
-                       L.H, pb.sbar, 1.f / L.sdf_scale, M, rows_per_blk,
-                       packed_grad + L.wsdf_off, packed_grad + L.bsdf_off, part_w, part_b);
-    RNB_CHECK_LAUNCH();
-    if (slab_out)
-      RNB_TRY(dw.add_reduce_only(packed_grad + L.wsdf_off, L.Hp, packed_grad + L.bsdf_off, part_w, part_b, 1, L.Hp, (int)nslab));
-  }
+  // Hp / 32 column chunks x row slabs, ~256 workgroups in total, slabs a multiple of the 64 row phases
+  const int chunks = L.Hp / 32;
+  int64_t slabs = det ? 1 : (256 + chunks - 1) / chunks;
+  // with the one-workgroup-per-gradient kernel there is a slab reduction at the end of the backward: the row slabs'
+  // sums ride in it (no atomics: bit-reproducible); otherwise fp32 atomics (one slab in the deterministic variant)
+  const bool slab_out = dw_one_wg_runs(L, M) && pb.sdfh_part != nullptr;
+  if (slab_out) slabs = kSdfHeadSlabs;
+  int rows_per_blk = (int)((M + slabs - 1) / slabs);
+  rows_per_blk = (rows_per_blk + 63) / 64 * 64;
+  const unsigned nslab = blocks_for(M, rows_per_blk);
+  hipLaunchKernelGGL(sdf_head_bwd_kernel, dim3(nslab, chunks), dim3(512), 0, s, pb.a[L.nh - 1],
+                     (fused || !parts.normal) ? (const float*)nullptr : (const float*)pb.u[L.nh], (const float*)pb.u[L.nh], u_tiles, L.Hp,
+                     L.H, pb.sbar, 1.f / L.sdf_scale, M, rows_per_blk, packed_grad + L.wsdf_off, packed_grad + L.bsdf_off,
+                     slab_out ? pb.sdfh_part : nullptr, slab_out ? pb.sdfh_part + (size_t)nslab * L.Hp : nullptr);
+  RNB_CHECK_LAUNCH();
   // ---- FB head: zb_{nh-1} = (fbar Wf + sbar/scale w_sdf) * D + zR ----------------------------------
-  if (fused) RNB_TRY(fused_fb(L, packed, pb, parts.feat, s));   // all zb_l in one launch
-  {
-    if (!fused) {
-      EpiFB epi{pb.D[L.nh - 1], pb.zR[L.nh - 1], pb.zb[L.nh - 1], L.Hp, L.hid[L.nh - 1].N, pb.sbar,
-                packed + L.wsdf_off, 1.f / L.sdf_scale};
-      const int K = parts.feat ? L.feat.Np : 0;   // no_albedo: fbar == 0, the GEMM degenerates to its epilogue
-      RNB_TRY((launch_rows<true, EpiFB>(pb.cinb, L.Cinp, packed + L.feat.w_off, L.feat.Kp, Mp, L.feat.Kp, K, epi,
-                                        parts.feat ? mm_flops(M, L.feat) : 0.0, s)));
-    }
-    if (parts.feat) {
-      DwPair p{pb.cinb, L.Cinp, pb.a[L.nh - 1], L.Hp, 0, h2 ? pb.amax + AMAX_CINB : nullptr, h2 ? pb.smax + SMAX_A + L.nh - 1 : nullptr};
-      RNB_TRY(dw.add(p, p, 1, L.feat.Np, L.feat.Kp, packed_grad + L.feat.w_off, L.feat.Kp,
-                     packed_grad + L.feat.b_off, 0, mm_flops(M, L.feat)));
-    }
-  }
-  // ---- FB + dW, layers nh-1 .. 0 -------------------------------------------------------------------
-  for (int l = L.nh - 1; l >= 0; --l) {
-    const Lin& ln = L.hid[l];
-    const float* in = l == 0 ? pb.e : pb.a[l - 1];
-    const int ldin = l == 0 ? L.Ep : L.Hp;
-    const float* uin = l == 0 ? pb.geb : pb.u[l];
-    // (x2h: adjoint operand, its recorded maximum; the state operand's recorded maximum)
-    DwPair p1{pb.gz[l], L.Hp, uin, ldin, 1, h2 ? pb.amax + AMAX_U + l : nullptr, h2 ? pb.smax + SMAX_GZ + l : nullptr};
-    DwPair p2{pb.zb[l], L.Hp, in, ldin, 0, h2 ? pb.amax + AMAX_ZB + l : nullptr,
-              h2 ? pb.smax + (l == 0 ? SMAX_E : SMAX_A + l - 1) : nullptr};
-    if (parts.normal)
-      RNB_TRY(dw.add(p1, p2, 2, ln.Np, ln.Kp, packed_grad + ln.w_off, ln.Kp, packed_grad + ln.b_off, 1,
-                     2.0 * mm_flops(M, ln)));
-    else
-      RNB_TRY(dw.add(p2, p2, 1, ln.Np, ln.Kp, packed_grad + ln.w_off, ln.Kp, packed_grad + ln.b_off, 0, mm_flops(M, ln)));
-    if (l > 0 && !fused) {
+  if (fused) {
+    RNB_TRY(fused_fb(L, packed, pb, parts.feat, s));   // all zb_l in one launch
+  } else {
+    EpiFB epi{pb.D[L.nh - 1], pb.zR[L.nh - 1], pb.zb[L.nh - 1], L.Hp, L.hid[L.nh - 1].N, pb.sbar,
+              packed + L.wsdf_off, 1.f / L.sdf_scale};
+    const int K = parts.feat ? L.feat.Np : 0;   // no_albedo: fbar == 0, the GEMM degenerates to its epilogue
+    RNB_TRY((launch_rows<true, EpiFB>(pb.cinb, L.Cinp, packed + L.feat.w_off, L.feat.Kp, Mp, L.feat.Kp, K, epi,
+                                      parts.feat ? mm_flops(M, L.feat) : 0.0, s)));
+    // ---- FB, layers nh-1 .. 1 ------------------------------------------------------------------------
+    for (int l = L.nh - 1; l >= 1; --l) {
+      const Lin& ln = L.hid[l];
       const Lin& lp = L.hid[l - 1];
       EpiFB epi{pb.D[l - 1], pb.zR[l - 1], pb.zb[l - 1], L.Hp, lp.N, nullptr, nullptr, 1.f};
       RNB_TRY((launch_rows<true, EpiFB>(pb.zb[l], L.Hp, packed + ln.w_off, ln.Kp, Mp, ln.Kp, ln.Np, epi, mm_flops(M, ln), s)));
     }
   }
-  return dw.flush_all();
+  return dw_backward(L, pb, dw_parts, h2, color_h2, slab_out ? (int)nslab : 0, packed_grad, s);
 }
 
 }  // namespace rnb

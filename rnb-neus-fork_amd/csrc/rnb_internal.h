@@ -41,6 +41,8 @@ struct Lin {
   int64_t b_off;   // float offset of b
   float scale;     // factor folded into W (1/sqrt2 for the skip layer)
 };
+// algorithmic FLOPs of one layer-shaped GEMM over M points: real (unpadded) layer shape
+inline double mm_flops(int64_t M, const Lin& ln) { return 2.0 * (double)M * ln.N * ln.K; }
 
 // Packed layout of both networks (see weightnorm.hip for how leaves map onto it).
 struct Layout {
@@ -181,6 +183,9 @@ enum { AMAX_ZB = 0, AMAX_U = RNB_MAX_LIN, AMAX_ZC = 2 * RNB_MAX_LIN + 1, AMAX_CI
 // slots of PointBufs::smax: a_l, gz_l (hidden layers), e (positional encoding), cin (albedo-net input), ac_l (its hidden layers)
 enum { SMAX_A = 0, SMAX_GZ = RNB_MAX_LIN, SMAX_E = 2 * RNB_MAX_LIN, SMAX_CIN = 2 * RNB_MAX_LIN + 1, SMAX_AC = 2 * RNB_MAX_LIN + 2,
        SMAX_SLOTS = 3 * RNB_MAX_LIN + 2 };
+// slot i of an x2h maxima array (PointBufs::amax / ::smax), or nullptr when x2h is off or the array is absent: a weight-
+// gradient job then scales by the fixed 2^6, a GEMM records no maximum
+inline unsigned* h2_slot(bool h2, unsigned* slots, int i) { return h2 && slots != nullptr ? slots + i : nullptr; }
 // PM_NO_REVERSE: a backward without the normal's adjoint (point-wise autograd of SDFNetwork.forward): no gz_l, no u_l
 enum PointMode { PM_SDF_ONLY = 0, PM_WITH_NORMAL = 1, PM_WITH_COLOR = 2, PM_WITH_BACKWARD = 4, PM_NO_REVERSE = 8 };
 void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb);
@@ -196,8 +201,6 @@ int launch_copy_cols(const float* src, int ld, int ncols, int64_t M, float* out,
 int launch_range_report(const Layout& L, const float* packed, const PointBufs& pb, bool with_color, bool with_backward, float* out,
                         hipStream_t s);
 int launch_fill_cols(const float* src, int ncols, int64_t M, int64_t Mp, int ld, float* dst, hipStream_t s);
-int64_t dw_partial_floats(const Layout& L, int64_t M, bool with_color);
-int64_t dw_staged_floats(const Layout& L, int64_t M, bool with_color);
 int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad,
                    bool fused, hipStream_t s);
 // which parts of sweep_backward run (mlp.hip); the render path is {with_color, true, with_color, true, false}
@@ -210,6 +213,16 @@ struct BwdParts {
 };
 int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, const BwdParts& parts, float* packed_grad,
                          bool fused, hipStream_t s);
+// ---- weight-gradient jobs of a backward (dw.hip) ----
+// floats of PointBufs::dw_part (carve_points) for a backward over M points
+int64_t dw_workspace_floats(const Layout& L, int64_t M, bool with_color);
+// the one-workgroup-per-gradient kernel runs for this variant over M points (its slab reduction then sums the sdf-head row)
+bool dw_one_wg_runs(const Layout& L, int64_t M);
+// zeroes the deterministic variant's ordered-reduction slabs (before the backward's first launch)
+int dw_zero_partials(const Layout& L, const PointBufs& pb, const BwdParts& parts, hipStream_t s);
+// queues and launches every weight-gradient job of a backward of these parts (its other launches are enqueued)
+int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, bool h2, bool color_h2, int sdfh_slabs,
+                float* packed_grad, hipStream_t s);
 // input adjoints of the point-wise autograd calls (mlp.hip)
 int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s);
 int launch_color_input_bwd(const Layout& L, const PointBufs& pb, float* pts_bar, float* nrm_bar, hipStream_t s);
@@ -274,7 +287,8 @@ int bf16_color_forward(const Layout& L, const float* packed, PointBufs& pb, cons
 int bf16_color_backward(const Layout& L, const float* packed, PointBufs& pb, float* packed_grad, hipStream_t s);
 int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, bool color_bf16, float* packed_grad,
                   hipStream_t s);
-int64_t bf16_dw_partial_floats(const Layout& L, int64_t M, bool with_color);
+// floats of bf16_backward's ordered-reduction slabs over M points (deterministic variant)
+int64_t bf16_dw_floats(const Layout& L, int64_t M, bool with_color);
 
 // ---- sampling / composite ------------------------------------------------------------------------
 int launch_up_sample_step(const float* rays_o, const float* rays_d, const float* z_in, const float* sdf_old,

@@ -10,7 +10,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../rnb-neus-fork_amd/csrc/gemm.hip.h"
+#include "../rnb-neus-fork_amd/csrc/dw.hip.h"
 
 using namespace rnb;
 

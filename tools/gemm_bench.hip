@@ -7,7 +7,7 @@
 
 #include <vector>
 
-#include "../rnb-neus-fork_amd/csrc/gemm.hip.h"
+#include "../rnb-neus-fork_amd/csrc/dw.hip.h"
 
 using namespace rnb;
 
