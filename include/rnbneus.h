@@ -274,7 +274,8 @@ enum {
   RNB_FLAG_RELU_SHADING = 2,    /* warm-up: relu on n.l (renderer.py:913)           */
   RNB_FLAG_NO_ALBEDO = 4,       /* albedo := 1 (renderer.py:905-906, :1009-1010)    */
   RNB_FLAG_LIGHT_PER_RAY = 8,   /* lights_dir is [L,B,3] instead of [L,3]           */
-  RNB_FLAG_FORWARD_ONLY = 16    /* no backward will follow                          */
+  RNB_FLAG_FORWARD_ONLY = 16,   /* no backward will follow                          */
+  RNB_FLAG_INPUT_GRADS = 32     /* keep what rnb_render_bwd_inputs needs (below)    */
 };
 
 typedef struct rnb_render_args {
@@ -328,6 +329,35 @@ int rnb_render_fwd(const rnb_model_desc* desc, const float* packed, const rnb_re
 int rnb_render_bwd(const rnb_model_desc* desc, const float* packed, const rnb_render_args* args,
                    const rnb_render_grads* gout, float* packed_grad, float* variance_grad, void* ws,
                    size_t ws_bytes, rnb_stream_t stream);
+
+/* Gradients with respect to the render's floating-point INPUTS (the reference's autograd reaches every input that requires
+ * grad, models/renderer.py:209-272, :478-540, :905-914, :1009-1017):
+ *   rays_o [B,3], rays_d [B,3]   through pts = o + d * mid_z into sdf(pts), the normal (its Hessian-vector term included,
+ *                                models/fields.py:114-127) and the albedo net's encoded points and normals; rays_d also
+ *                                through true_cos = d . n
+ *   lights_dir [L,3] | [L,B,3]   through the shading n . l (with the warm-up's ReLU mask); MVPS only
+ *   background_rgb [3]           through colour += bg * (1 - sum w); CORE only
+ *   z_vals [B,S]                 through dists (the last one is the constant sample_dist) and mid_z
+ * A NULL field is "not wanted"; every other field is OVERWRITTEN (not accumulated).  Shared lights and the background are
+ * sums over the rays in a fixed order (no floating-point atomics: bit-reproducible). */
+typedef struct rnb_render_input_grads {
+  float* rays_o;
+  float* rays_d;
+  float* lights_dir;
+  float* background_rgb;
+  float* z_vals;
+} rnb_render_input_grads;
+
+/* Everything rnb_render_bwd does (same packed_grad and variance_grad), plus the input gradients `igrads` asks for.  The
+ * forward must have been made with RNB_FLAG_INPUT_GRADS in args->flags: it then keeps d sdf / d e of the normal's sweep
+ * (the Hessian term) and the workspace holds the per-ray partial sums (rnb_render_workspace_bytes with the flag is never
+ * smaller than without it).  Lights or background alone do not run the point-wise input adjoint.  Returns RNB_E_INVALID
+ * for RNB_VARIANT_BF16 (the flag is refused by the workspace query and the forward too), for a request on a forward made
+ * without the flag, for lights in RNB_MODE_CORE and for the background in RNB_MODE_MVPS or without a background.
+ * igrads == NULL or all fields NULL: exactly rnb_render_bwd. */
+int rnb_render_bwd_inputs(const rnb_model_desc* desc, const float* packed, const rnb_render_args* args,
+                          const rnb_render_grads* gout, const rnb_render_input_grads* igrads, float* packed_grad,
+                          float* variance_grad, void* ws, size_t ws_bytes, rnb_stream_t stream);
 
 /* Name/duration of the heaviest kernel family, for bench.py's roofline line: fills `flops` with the
  * algorithmic MLP FLOPs of one rnb_render_fwd+bwd (+ sampling) at the given shape. */

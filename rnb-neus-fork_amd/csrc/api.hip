@@ -542,6 +542,11 @@ struct RenderBufs {
   float* gerr_den;
   float* invs_part;
   PointBufs pb;
+  // RNB_FLAG_INPUT_GRADS: the composite backward's per-ray / per-sample parts of the input adjoints (else nullptr)
+  float* ig_cos_d;    // [B,3]
+  float* ig_light;    // [kMaxRenderLights,B,3]
+  float* ig_bg;       // [B,3]
+  float* ig_dists;    // [B,S]
 };
 
 static int render_mode_of(int flags, const Layout& L) {
@@ -561,6 +566,19 @@ static void carve_render(const Layout& L, Carver& c, int64_t B, int S, int flags
   rb->invs_part = c.take<float>(B);
   carve_points(L, c, B * S, render_mode_of(flags, L), &rb->pb);
   if (!(render_mode_of(flags, L) & PM_WITH_COLOR)) rb->pb.alb = c.take<float>(rb->pb.Mp * 4);
+  rb->ig_cos_d = rb->ig_light = rb->ig_bg = rb->ig_dists = nullptr;
+  if (flags & RNB_FLAG_INPUT_GRADS) {   // behind everything else: the rest of the layout is the one without the flag
+    rb->ig_cos_d = c.take<float>(B * 3);
+    rb->ig_light = c.take<float>((int64_t)kMaxRenderLights * B * 3);
+    rb->ig_bg = c.take<float>(B * 3);
+    rb->ig_dists = c.take<float>(B * S);
+  }
+}
+
+static int check_input_grads_flag(const Layout& L, int flags) {
+  if ((flags & RNB_FLAG_INPUT_GRADS) && is_bf16(L))
+    RNB_FAIL(RNB_E_INVALID, "RNB_FLAG_INPUT_GRADS: RNB_VARIANT_BF16 has no input adjoints (the fp32 variants only)");
+  return RNB_OK;
 }
 
 RNB_API int rnb_render_workspace_bytes(const rnb_model_desc* desc, int64_t B, int32_t S, int32_t flags,
@@ -569,6 +587,7 @@ RNB_API int rnb_render_workspace_bytes(const rnb_model_desc* desc, int64_t B, in
   Layout L;
   RNB_TRY(make_layout(desc, &L));
   if (B < 0 || S < 1) RNB_FAIL(RNB_E_INVALID, "bad B/S");
+  RNB_TRY(check_input_grads_flag(L, flags));
   Carver c(nullptr, 0);
   RenderBufs rb;
   carve_render(L, c, B, S, flags, &rb);
@@ -589,6 +608,7 @@ static int render_setup(const rnb_model_desc* desc, const rnb_render_args* a, vo
   RNB_REQUIRE(a->rays_d, "rays_d");
   RNB_REQUIRE(a->z_vals, "z_vals");
   RNB_REQUIRE(a->variance, "variance");
+  RNB_TRY(check_input_grads_flag(*L, a->flags));
   Carver c(ws, ws_bytes);
   carve_render(*L, c, a->B, a->S, a->flags, rb);
   if (!c.ok) RNB_FAIL(RNB_E_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
@@ -653,7 +673,10 @@ RNB_API int rnb_render_fwd(const rnb_model_desc* desc, const float* packed, cons
   } else {
     RNB_TRY(forward_points(L, packed, rb.pts, a->B * a->S, rb.pb, true, use_color, !use_fused(L) && !is_bf16(L), nullptr, s));
   }
-  RNB_TRY(reverse_points(L, packed, rb.pb, s));
+  // RNB_FLAG_INPUT_GRADS: the fused R sweep also keeps d sdf / d e (the Hessian term of the point adjoint; the per-layer
+  // chain always leaves it in pb.ge)
+  if ((a->flags & RNB_FLAG_INPUT_GRADS) && use_fused(L)) RNB_TRY(fused_reverse(L, packed, rb.pb, s, true));
+  else RNB_TRY(reverse_points(L, packed, rb.pb, s));
   if (color_bf16) RNB_TRY(bf16_color_forward(L, packed, rb.pb, rb.pts, s));
   else if (use_color && use_fused(L) && color_h2_supported(L)) RNB_TRY(color_h2_forward(L, packed, rb.pb, rb.pts, rb.pb.nrm, s));
   else if (use_color) RNB_TRY(sweep_color(L, packed, rb.pb, rb.pts, rb.pb.nrm, 4, s));
@@ -665,20 +688,35 @@ RNB_API int rnb_render_fwd(const rnb_model_desc* desc, const float* packed, cons
   return RNB_OK;
 }
 
-RNB_API int rnb_render_bwd(const rnb_model_desc* desc, const float* packed, const rnb_render_args* a,
-                           const rnb_render_grads* gout, float* packed_grad, float* variance_grad, void* ws,
-                           size_t ws_bytes, rnb_stream_t stream) {
+// rnb_render_bwd (ig == nullptr) and rnb_render_bwd_inputs
+static int render_bwd_body(const rnb_model_desc* desc, const float* packed, const rnb_render_args* a,
+                           const rnb_render_grads* gout, const rnb_render_input_grads* ig, float* packed_grad,
+                           float* variance_grad, void* ws, size_t ws_bytes, hipStream_t s) {
   RNB_REQUIRE(packed, "packed");
   RNB_REQUIRE(gout, "gout");
   RNB_REQUIRE(packed_grad, "packed_grad");
   RNB_REQUIRE(variance_grad, "variance_grad");
-  hipStream_t s = (hipStream_t)stream;
   Layout L;
+  RNB_TRY(make_layout(desc, &L));
+  if (ig != nullptr && !(ig->rays_o || ig->rays_d || ig->lights_dir || ig->background_rgb || ig->z_vals)) ig = nullptr;
+  if (ig != nullptr) {
+    RNB_REQUIRE(a, "args");
+    const bool mvps = (a->flags & RNB_MODE_MVPS) != 0;
+    if (is_bf16(L)) RNB_FAIL(RNB_E_INVALID, "input gradients: RNB_VARIANT_BF16 has no input adjoints (the fp32 variants only)");
+    if (!(a->flags & RNB_FLAG_INPUT_GRADS))
+      RNB_FAIL(RNB_E_INVALID, "input gradients need a forward made with RNB_FLAG_INPUT_GRADS (it keeps their state)");
+    if (ig->lights_dir && !mvps) RNB_FAIL(RNB_E_INVALID, "input gradients: lights_dir in RNB_MODE_CORE (no lights)");
+    if (ig->background_rgb && (mvps || !a->background_rgb))
+      RNB_FAIL(RNB_E_INVALID, "input gradients: background_rgb needs RNB_MODE_CORE with a background");
+  }
   RenderBufs rb;
   RNB_TRY(render_setup(desc, a, ws, ws_bytes, &L, &rb));
   if (a->flags & RNB_FLAG_FORWARD_ONLY) RNB_FAIL(RNB_E_INVALID, "forward-only render has no backward state");
   const int mode = render_mode_of(a->flags, L);
   const bool use_color = (mode & PM_WITH_COLOR) != 0;
+  // the point adjoint pbar feeds rays_o, rays_d and z; lights and background come from the composite alone
+  const bool need_pbar = ig != nullptr && (ig->rays_o || ig->rays_d || ig->z_vals);
+  const bool shared_lights = !(a->flags & RNB_FLAG_LIGHT_PER_RAY);
   CompBwdArgs g;
   memset(&g, 0, sizeof(g));
   g.f = comp_args_of(L, a, rb);
@@ -699,10 +737,66 @@ RNB_API int rnb_render_bwd(const rnb_model_desc* desc, const float* packed, cons
   g.invs_part = rb.invs_part;
   g.dvar = variance_grad;
   g.amax_to_zero = rb.pb.amax;
+  if (ig != nullptr) {
+    g.ig_cos_d = ig->rays_d ? rb.ig_cos_d : nullptr;
+    g.ig_light = ig->lights_dir ? (shared_lights ? rb.ig_light : ig->lights_dir) : nullptr;
+    g.ig_bg = ig->background_rgb ? rb.ig_bg : nullptr;
+    g.ig_dists = ig->z_vals ? rb.ig_dists : nullptr;
+  }
   RNB_TRY(launch_composite_bwd(g, s));
+  if (ig != nullptr && ig->lights_dir && shared_lights) RNB_TRY(launch_sum_over_rays(rb.ig_light, a->B, a->n_lights, ig->lights_dir, s));
+  if (ig != nullptr && ig->background_rgb) RNB_TRY(launch_sum_over_rays(rb.ig_bg, a->B, 1, ig->background_rgb, s));
   RNB_CHECK_HIP(hipMemsetAsync(packed_grad, 0, (size_t)L.total * sizeof(float), s));
-  RNB_TRY(sweep_backward(L, packed, rb.pb, use_color, packed_grad, use_fused(L), s));
-  return RNB_OK;
+  if (!need_pbar) return sweep_backward(L, packed, rb.pb, use_color, packed_grad, use_fused(L), s);
+  // the render path's backward with the albedo net's encoding columns of cinb kept (color_inputs)
+  BwdParts parts;
+  parts.albedo = use_color;
+  parts.sdf = true;
+  parts.feat = use_color;
+  parts.normal = true;
+  parts.color_inputs = use_color;
+  RNB_TRY(sweep_backward_parts(L, packed, rb.pb, parts, packed_grad, use_fused(L), s));
+  float* ebar = nullptr;
+  RNB_TRY(launch_sdf_ebar(L, packed, rb.pb, &ebar, s));
+  RayAdjArgs r;
+  memset(&r, 0, sizeof(r));
+  r.ebar = ebar;
+  r.B = a->B;
+  r.S = a->S;
+  r.pts = rb.pts;
+  r.dists = rb.dists;
+  r.z = a->z_vals;
+  r.rays_d = a->rays_d;
+  r.x4 = rb.pb.x;
+  r.ge = rb.pb.ge;
+  r.nbar = rb.pb.nbar;
+  r.nrm = rb.pb.nrm;
+  r.cinb = use_color ? rb.pb.cinb : nullptr;
+  r.Ep = L.Ep;
+  r.multires = L.multires;
+  r.Cinp = L.Cinp;
+  r.F = L.F;
+  r.pev = L.pev;
+  r.multires_view = L.multires_view;
+  r.scale = L.sdf_scale;
+  r.cos_d = ig->rays_d ? rb.ig_cos_d : nullptr;
+  r.dists_bar = ig->z_vals ? rb.ig_dists : nullptr;
+  r.o_bar = ig->rays_o;
+  r.d_bar = ig->rays_d;
+  r.z_bar = ig->z_vals;
+  return launch_ray_input_adjoint(r, s);
+}
+
+RNB_API int rnb_render_bwd(const rnb_model_desc* desc, const float* packed, const rnb_render_args* a,
+                           const rnb_render_grads* gout, float* packed_grad, float* variance_grad, void* ws,
+                           size_t ws_bytes, rnb_stream_t stream) {
+  return render_bwd_body(desc, packed, a, gout, nullptr, packed_grad, variance_grad, ws, ws_bytes, (hipStream_t)stream);
+}
+
+RNB_API int rnb_render_bwd_inputs(const rnb_model_desc* desc, const float* packed, const rnb_render_args* a,
+                                  const rnb_render_grads* gout, const rnb_render_input_grads* igrads, float* packed_grad,
+                                  float* variance_grad, void* ws, size_t ws_bytes, rnb_stream_t stream) {
+  return render_bwd_body(desc, packed, a, gout, igrads, packed_grad, variance_grad, ws, ws_bytes, (hipStream_t)stream);
 }
 
 RNB_API int rnb_render_range(const rnb_model_desc* desc, const float* packed, const void* ws, size_t ws_bytes, int64_t B, int32_t S,

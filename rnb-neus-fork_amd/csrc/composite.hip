@@ -10,7 +10,7 @@
 namespace rnb {
 
 constexpr int kMaxS = 512;
-constexpr int kMaxL = 8;
+constexpr int kMaxL = kMaxRenderLights;
 
 __device__ inline float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -201,7 +201,10 @@ __global__ __launch_bounds__(256) void gerr_finalize_kernel(const float* __restr
 }
 
 
-__global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) {
+// IG: also the input adjoints of rnb_render_bwd_inputs (CompBwdArgs::ig_*, each may be nullptr).  The render backward
+// without them is the IG = false instance, composite_bwd_kernel, compiled from exactly the code it had before they existed.
+template <bool IG>
+__device__ __forceinline__ void composite_bwd_body(const CompBwdArgs& g) {
   __shared__ float sAlpha[kMaxS], sT[kMaxS], sWbar[kMaxS], sSuf[kMaxS];
   // first kernel of a backward: the maxima of the adjoint tensors (PointBufs::amax) start from zero (was a memset launch)
   if (g.amax_to_zero != nullptr && blockIdx.x == 0) {
@@ -240,6 +243,13 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) {
   float carry = 1.0f;
   float wmax = -1.f;
   int wmax_j = 0;
+  // input adjoints (rnb_render_bwd_inputs): lbar[l] = sum_s shb n, the weight sum for the background
+  float lbar[kMaxL][3];
+  float wsum_ig = 0.f;
+  if constexpr (IG) {
+#pragma unroll
+    for (int l = 0; l < kMaxL; ++l) lbar[l][0] = lbar[l][1] = lbar[l][2] = 0.f;
+  }
   for (int j0 = 0; j0 < S; j0 += 64) {
     const int j = j0 + lane;
     const bool on = j < S;
@@ -274,6 +284,7 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) {
           float shb = ca * w;
           if (relu_sh && !(sh_raw > 0.f)) shb = 0.f;
           nb0 = fmaf(shb, Lv[l][0], nb0); nb1 = fmaf(shb, Lv[l][1], nb1); nb2 = fmaf(shb, Lv[l][2], nb2);
+          if constexpr (IG) if (g.ig_light) { lbar[l][0] = fmaf(shb, n0, lbar[l][0]); lbar[l][1] = fmaf(shb, n1, lbar[l][1]); lbar[l][2] = fmaf(shb, n2, lbar[l][2]); }
         }
         if (no_alb) { ab[0] = ab[1] = ab[2] = ab[3] = 0.f; }
       } else {
@@ -288,6 +299,22 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) g.albbar[p * 4 + c] = ab[c];
       if (w > wmax) { wmax = w; wmax_j = j; }
+      if constexpr (IG) wsum_ig += w;
+    }
+  }
+  if constexpr (IG) {
+    if (g.ig_light) {
+      for (int l = 0; l < a.L; ++l)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const float v = wave_sum(lbar[l][d]);
+          if (lane == 0) g.ig_light[((int64_t)l * a.B + b) * 3 + d] = v;
+        }
+    }
+    if (g.ig_bg) {   // colour += bg (1 - sum w): the forward's sum, in the forward's order
+      const float ws = wave_sum(wsum_ig);
+      if (lane == 0)
+        for (int c = 0; c < 3; ++c) g.ig_bg[b * 3 + c] = Cb[0][c] * (1.0f - ws);
     }
   }
   // weight_max cotangent goes to the (first) arg-max sample
@@ -312,6 +339,7 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) {
   // pass 2: back through alpha -> cdfs -> sdf / cos -> normal ; eikonal ; inv_s
   const float gerr_coef = g.g_gerr ? g.g_gerr[0] / (g.gerr_den_global ? g.gerr_den_global[0] : g.gerr_den[0]) : 0.f;
   float invs_bar = 0.f;
+  float cosd0 = 0.f, cosd1 = 0.f, cosd2 = 0.f;   // rays_d's part through true_cos (input adjoints)
   for (int j0 = 0; j0 < S; j0 += 64) {
     const int j = j0 + lane;
     if (j >= S) continue;
@@ -334,6 +362,11 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) {
     const float icbar = (enb - epb) * delta * 0.5f;
     const float tcbar = icbar * (((-st.tc * 0.5f + 0.5f) > 0.f ? 0.5f * (1.0f - c_an) : 0.f) +
                                  ((-st.tc) > 0.f ? c_an : 0.f));
+    if constexpr (IG) if (g.ig_cos_d) { cosd0 = fmaf(tcbar, n0, cosd0); cosd1 = fmaf(tcbar, n1, cosd1); cosd2 = fmaf(tcbar, n2, cosd2); }
+    if constexpr (IG) if (g.ig_dists) {   // e_next / e_prev = s +- ic delta / 2
+      const float ic = -(relu_nan(-st.tc * 0.5f + 0.5f) * (1.0f - c_an) + relu_nan(-st.tc) * c_an);
+      g.ig_dists[p] = (enb - epb) * ic * 0.5f;
+    }
     float nb0 = g.nbar[p * 4] + tcbar * d0, nb1 = g.nbar[p * 4 + 1] + tcbar * d1, nb2 = g.nbar[p * 4 + 2] + tcbar * d2;
     if (g.g_gerr) {
       const float px = a.pts[p * 3], py = a.pts[p * 3 + 1], pz = a.pts[p * 3 + 2];
@@ -355,6 +388,122 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) {
     if (g.g_s_val) invs_bar -= g.g_s_val[b] / (inv_s * inv_s);
     g.invs_part[b] = invs_bar;
   }
+  if constexpr (IG) if (g.ig_cos_d) {
+    cosd0 = wave_sum(cosd0);
+    cosd1 = wave_sum(cosd1);
+    cosd2 = wave_sum(cosd2);
+    if (lane == 0) { g.ig_cos_d[b * 3] = cosd0; g.ig_cos_d[b * 3 + 1] = cosd1; g.ig_cos_d[b * 3 + 2] = cosd2; }
+  }
+}
+
+__global__ __launch_bounds__(64) void composite_bwd_kernel(CompBwdArgs g) { composite_bwd_body<false>(g); }
+__global__ __launch_bounds__(64) void composite_bwd_ig_kernel(CompBwdArgs g) { composite_bwd_body<true>(g); }
+
+// ---- input adjoints of a render (rnb_render_bwd_inputs) ---------------------------------------------------------------
+// One wave64 per ray, one sample per lane.  Per sample the point adjoint pbar = d loss / d pts is formed where it is
+// consumed (it never goes to HBM):
+//   nbar_tot = nbar + J_pe(n)^T cinb[pe(n)]                         (the normal's total adjoint: composite + albedo input)
+//   pbar     = scale ( J_pe(xs)^T ebar - sum_k ge_k d^2 pe_k / d xs^2 . nbar_tot ) + J_pe(p)^T cinb[pe(p)]
+// (sdf_xbar_kernel / color_input_bwd_kernel of the point-wise calls, mlp.hip).  pts = o + d mid, mid = z + dists / 2,
+// dists_s = z_{s+1} - z_s (the last one a constant), so with mbar_s = pbar_s . d and Dbar_s = dists_bar_s + mbar_s / 2:
+//   o_bar = sum_s pbar_s ;  d_bar = sum_s mid_s pbar_s + cos_d ;  z_bar_s = mbar_s - [s < S-1] Dbar_s + [s > 0] Dbar_{s-1}.
+// Sums are lane-local over the 64-sample chunks, then a shuffle butterfly: a fixed order.
+__global__ __launch_bounds__(64) void ray_input_adjoint_kernel(RayAdjArgs r) {
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int S = r.S;
+  const float d0 = r.rays_d[b * 3], d1 = r.rays_d[b * 3 + 1], d2 = r.rays_d[b * 3 + 2];
+  float ob[3] = {0.f, 0.f, 0.f}, db[3] = {0.f, 0.f, 0.f};
+  float carry_D = 0.f;   // Dbar of the previous chunk's last sample
+  for (int j0 = 0; j0 < S; j0 += 64) {
+    const int j = j0 + lane;
+    const bool on = j < S;
+    const int64_t p = b * S + (on ? j : S - 1);
+    float nt[3], pb[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) nt[d] = r.nbar[p * 4 + d];
+    if (r.cinb != nullptr) {
+      const float* gn = r.cinb + p * r.Cinp + r.F + r.pev;
+      const float* gp = r.cinb + p * r.Cinp + r.F;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) { nt[d] += gn[d]; pb[d] = gp[d]; }
+      float f = 1.f;
+      int c = 3;
+      for (int k = 0; k < r.multires_view; ++k) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          float sn, co;
+          sincosf(r.nrm[p * 4 + d] * f, &sn, &co);
+          nt[d] += f * (gn[c + d] * co - gn[c + 3 + d] * sn);
+          sincosf(r.pts[p * 3 + d] * f, &sn, &co);
+          pb[d] += f * (gp[c + d] * co - gp[c + 3 + d] * sn);
+        }
+        c += 6;
+        f *= 2.f;
+      }
+    } else {
+      pb[0] = pb[1] = pb[2] = 0.f;
+    }
+    {
+      const float* eb = r.ebar + p * r.Ep;
+      const float* ge = r.ge + p * r.Ep;
+      float acc[3] = {eb[0], eb[1], eb[2]};
+      float f = 1.f;
+      int c = 3;
+      for (int k = 0; k < r.multires; ++k) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          float sn, co;
+          sincosf(r.x4[p * 4 + d] * f, &sn, &co);
+          acc[d] += f * (eb[c + d] * co - eb[c + 3 + d] * sn);
+          acc[d] -= f * f * (ge[c + d] * sn + ge[c + 3 + d] * co) * nt[d];
+        }
+        c += 6;
+        f *= 2.f;
+      }
+#pragma unroll
+      for (int d = 0; d < 3; ++d) pb[d] = on ? fmaf(r.scale, acc[d], pb[d]) : 0.f;
+    }
+    const float dd = r.dists[p];
+    const float mid = r.z[p] + dd * 0.5f;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      ob[d] += pb[d];
+      db[d] = fmaf(mid, pb[d], db[d]);
+    }
+    if (r.z_bar != nullptr) {
+      const float mb = pb[0] * d0 + pb[1] * d1 + pb[2] * d2;
+      const float Db = on ? r.dists_bar[p] + 0.5f * mb : 0.f;
+      float prev = __shfl_up(Db, 1, 64);
+      if (lane == 0) prev = carry_D;
+      carry_D = __shfl(Db, 63, 64);
+      if (on) r.z_bar[p] = mb - (j + 1 < S ? Db : 0.f) + (j > 0 ? prev : 0.f);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    ob[d] = wave_sum(ob[d]);
+    db[d] = wave_sum(db[d]);
+  }
+  if (lane == 0) {
+    if (r.o_bar != nullptr)
+      for (int d = 0; d < 3; ++d) r.o_bar[b * 3 + d] = ob[d];
+    if (r.d_bar != nullptr)
+      for (int d = 0; d < 3; ++d) r.d_bar[b * 3 + d] = db[d] + (r.cos_d != nullptr ? r.cos_d[b * 3 + d] : 0.f);
+  }
+}
+
+// out[v*3 + c] = sum_b part[(v*B + b)*3 + c]: one workgroup per output, strided lanes, butterfly, four waves in order
+__global__ __launch_bounds__(256) void sum_over_rays_kernel(const float* __restrict__ part, int64_t B, float* __restrict__ out) {
+  __shared__ float red[4];
+  const int v = blockIdx.x / 3, c = blockIdx.x - v * 3;
+  const float* q = part + (int64_t)v * B * 3 + c;
+  float t = 0.f;
+  for (int64_t i = threadIdx.x; i < B; i += 256) t += q[i * 3];
+  t = wave_sum(t);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // d loss / d variance = (sum_b invs_part) * 10 * inv_s * [raw inv_s inside the clip range]
@@ -395,9 +544,24 @@ int launch_composite_fwd(const CompArgs& a, hipStream_t s) {
   return RNB_OK;
 }
 
+int launch_ray_input_adjoint(const RayAdjArgs& r, hipStream_t s) {
+  if (r.z_bar != nullptr && r.dists_bar == nullptr) RNB_FAIL(RNB_E_NULL, "ray input adjoint: z_bar needs dists_bar");
+  hipLaunchKernelGGL(ray_input_adjoint_kernel, dim3((unsigned)r.B), dim3(64), 0, s, r);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+int launch_sum_over_rays(const float* part, int64_t B, int nvec, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(sum_over_rays_kernel, dim3((unsigned)(nvec * 3)), dim3(256), 0, s, part, B, out);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
 int launch_composite_bwd(const CompBwdArgs& g, hipStream_t s) {
   if (g.dvar == nullptr) RNB_FAIL(RNB_E_NULL, "composite backward: missing reduction buffers");
-  hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)g.f.B), dim3(64), 0, s, g);
+  const bool ig = g.ig_cos_d || g.ig_light || g.ig_bg || g.ig_dists;
+  if (ig) hipLaunchKernelGGL(composite_bwd_ig_kernel, dim3((unsigned)g.f.B), dim3(64), 0, s, g);
+  else hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)g.f.B), dim3(64), 0, s, g);
   RNB_CHECK_LAUNCH();
   hipLaunchKernelGGL(variance_grad_kernel, dim3(1), dim3(256), 0, s, g.invs_part, g.f.B, g.f.variance, g.dvar);
   RNB_CHECK_LAUNCH();

@@ -922,6 +922,15 @@ int sweep_color(const Layout& L, const float* packed, PointBufs& pb, const float
 // pb.x and, with_normal, pb.ge (R sweep) and pb.nbar.  Two products in the per-layer kernels' shape of the R sweep's last
 // steps (zb W against the row-major W: k-contiguous in the layer's output width) + one point-wise kernel.
 int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s) {
+  float* ebar = nullptr;
+  RNB_TRY(launch_sdf_ebar(L, packed, pb, &ebar, s));
+  hipLaunchKernelGGL(sdf_xbar_kernel, dim3(blocks_for(pb.M, 256)), dim3(256), 0, s, pb.x, ebar,
+                     with_normal ? (const float*)pb.ge : nullptr, pb.nbar, L.Ep, L.multires, L.sdf_scale, pb.M, xbar);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+int launch_sdf_ebar(const Layout& L, const float* packed, PointBufs& pb, float** ebar_out, hipStream_t s) {
   float* ebar = pb.geb;
   if (L.skip >= 1) {
     const Lin& ln = L.hid[L.skip];
@@ -935,9 +944,7 @@ int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool wi
     RNB_TRY((launch_rows<true, EpiR0>(pb.zb[0], L.Hp, packed + ln.w_off, ln.Kp, pb.Mp, ln.Kp, ln.Np, epi, mm_flops(pb.M, ln), s,
                                       false, nullptr, nullptr, 0, "input_adjoint")));
   }
-  hipLaunchKernelGGL(sdf_xbar_kernel, dim3(blocks_for(pb.M, 256)), dim3(256), 0, s, pb.x, ebar,
-                     with_normal ? (const float*)pb.ge : nullptr, pb.nbar, L.Ep, L.multires, L.sdf_scale, pb.M, xbar);
-  RNB_CHECK_LAUNCH();
+  *ebar_out = ebar;
   return RNB_OK;
 }
 

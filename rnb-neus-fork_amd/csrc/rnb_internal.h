@@ -225,6 +225,8 @@ int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, boo
                 float* packed_grad, hipStream_t s);
 // input adjoints of the point-wise autograd calls (mlp.hip)
 int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s);
+// its first half: ebar = d loss / d e (into pb.geb, free after the backward); returns pb.geb
+int launch_sdf_ebar(const Layout& L, const float* packed, PointBufs& pb, float** ebar, hipStream_t s);
 int launch_color_input_bwd(const Layout& L, const PointBufs& pb, float* pts_bar, float* nrm_bar, hipStream_t s);
 int launch_absmax_rows(const float* x, int64_t n, unsigned* slot, hipStream_t s);
 int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool store_ge = false);
@@ -348,12 +350,45 @@ struct CompBwdArgs {
   float* invs_part;          // [B] partial d loss / d inv_s
   float* dvar;               // [1] d loss / d variance
   unsigned* amax_to_zero;    // PointBufs::amax (AMAX_SLOTS words) zeroed by the first workgroup, or nullptr
+  // input adjoints (rnb_render_bwd_inputs), each nullptr = not wanted
+  float* ig_cos_d;           // [B,3]   sum_s cosbar_s n_s: rays_d's part through true_cos
+  float* ig_light;           // [L,B,3] sum_s shbar_s n_s per light and ray
+  float* ig_bg;              // [B,3]   colour cotangent * (1 - sum w)
+  float* ig_dists;           // [B,S]   d loss / d dists through the alpha estimate
 };
 
 int launch_fine_points(const float* rays_o, const float* rays_d, const float* z, int64_t B, int S, float sample_dist,
                        float* pts, float* dists, unsigned* smax_to_zero, hipStream_t s);
 int launch_composite_fwd(const CompArgs& a, hipStream_t s);
 int launch_composite_bwd(const CompBwdArgs& g, hipStream_t s);
+constexpr int kMaxRenderLights = 8;
+// per-ray reduction of the point adjoints pbar = d loss / d pts (rnb_render_bwd_inputs): pbar is formed per sample from
+// the SDF network's encoding adjoint ebar, the Hessian term (d sdf / d e with the total normal adjoint) and the albedo
+// net's encoded point / normal columns of cinb, and reduced into o_bar, d_bar (+ cos_d) and z_bar (with dists_bar)
+struct RayAdjArgs {
+  int64_t B;
+  int S;
+  const float* pts;        // [B*S,3] sample points (the albedo net's input)
+  const float* dists;      // [B*S]
+  const float* z;          // [B,S]
+  const float* rays_d;     // [B,3]
+  const float* x4;         // [Mp,4] scaled points
+  const float* ebar;       // [Mp,Ep] d loss / d e
+  const float* ge;         // [Mp,Ep] d sdf / d e
+  const float* nbar;       // [Mp,4] the composite's normal adjoint
+  const float* nrm;        // [Mp,4]
+  const float* cinb;       // [Mp,Cinp] albedo-net input adjoint (encoding columns complete), or nullptr (no albedo net)
+  int Ep, multires, Cinp, F, pev, multires_view;
+  float scale;
+  const float* cos_d;      // [B,3] or nullptr
+  const float* dists_bar;  // [B,S] or nullptr (needed with z_bar)
+  float* o_bar;            // [B,3] or nullptr
+  float* d_bar;            // [B,3] or nullptr
+  float* z_bar;            // [B,S] or nullptr
+};
+int launch_ray_input_adjoint(const RayAdjArgs& r, hipStream_t s);
+// out[v*3 + c] = sum_b part[(v*B + b)*3 + c] for v < nvec, in a fixed order
+int launch_sum_over_rays(const float* part, int64_t B, int nvec, float* out, hipStream_t s);
 
 // ---- sampling (sampling.hip) ---------------------------------------------------------------------
 int launch_z_init(const float* rays_o, const float* rays_d, const float* near, const float* far,

@@ -16,6 +16,7 @@ FLAG_RELU_SHADING = 2
 FLAG_NO_ALBEDO = 4
 FLAG_LIGHT_PER_RAY = 8
 FLAG_FORWARD_ONLY = 16
+FLAG_INPUT_GRADS = 32
 
 # flags of the point-wise autograd calls (include/rnbneus.h)
 POINTS_FEATURE = 1
@@ -85,6 +86,11 @@ class RenderGrads(C.Structure):
                 ("s_val", C.c_void_p), ("gradient_error", C.c_void_p)]
 
 
+class RenderInputGrads(C.Structure):
+    _fields_ = [("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("lights_dir", C.c_void_p),
+                ("background_rgb", C.c_void_p), ("z_vals", C.c_void_p)]
+
+
 _P = C.POINTER
 _SIGNATURES = {
     "rnb_abi_version": (C.c_int, []),
@@ -130,6 +136,9 @@ _SIGNATURES = {
     "rnb_render_fwd": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(RenderArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnb_render_bwd": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(RenderArgs), _P(RenderGrads), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnb_render_bwd_inputs": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(RenderArgs), _P(RenderGrads),
+                                        _P(RenderInputGrads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
     "rnb_render_range": (C.c_int, [_P(ModelDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_void_p, C.c_void_p]),
     "rnb_algorithmic_flops": (C.c_int, [_P(ModelDesc), C.c_int64, C.c_int32, _P(C.c_double), _P(C.c_double)]),

@@ -38,6 +38,10 @@ from .parallel import allreduce_mean_, allreduce_sum_
 _MESH_BACKEND_LOGGED = False
 
 
+def _requires_grad(t):
+    return isinstance(t, torch.Tensor) and t.requires_grad
+
+
 class ExactDPToken:
     """Travels on `out["gradient_error"]` of a render made under grad in exact data-parallel mode.  Carries this
     shard's eikonal (numerator, count) to `rnb_loss(..., group=)`, which all-reduces them with the mask counts, writes
@@ -51,12 +55,37 @@ _OUT_KEYS = ("color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gra
              "gradient_error", "inside_sphere")
 
 
-class _FinePass(torch.autograd.Function):
-    """forward: rnb_weightnorm_fwd (done by the caller) + rnb_render_fwd; backward: rnb_render_bwd +
-    rnb_weightnorm_bwd (+ optional RCCL all-reduce of the flat gradient buffer)."""
+_N_INPUTS = 5   # rays_o, rays_d, lights, background_rgb, z_vals: the differentiable inputs of _FinePass, before the leaves
+
+
+class _ZFromNearFar(torch.autograd.Function):
+    """n_importance == 0: z = near + (far - near) t_s (+ the perturbation) as the native sampler computed it (models/renderer.py
+    :560-572).  The forward returns those z unchanged (no recomputation in torch: their bits stay the sampler's); the
+    backward is near_bar = sum_s z_bar (1 - t_s), far_bar = sum_s z_bar t_s."""
 
     @staticmethod
-    def forward(ctx, renderer, call, *leaves):
+    def forward(ctx, near, far, z):
+        ctx.shapes = (getattr(near, "shape", None), getattr(far, "shape", None))
+        return z.clone()
+
+    @staticmethod
+    def backward(ctx, zbar):
+        if zbar is None:
+            return None, None, None
+        t = torch.linspace(0.0, 1.0, zbar.shape[1], device=zbar.device, dtype=torch.float32)
+        near_bar = (zbar * (1.0 - t)).sum(-1).reshape(ctx.shapes[0]) if ctx.needs_input_grad[0] else None
+        far_bar = (zbar * t).sum(-1).reshape(ctx.shapes[1]) if ctx.needs_input_grad[1] else None
+        return near_bar, far_bar, None
+
+
+class _FinePass(torch.autograd.Function):
+    """forward: rnb_weightnorm_fwd (done by the caller) + rnb_render_fwd; backward: rnb_render_bwd +
+    rnb_weightnorm_bwd (+ optional RCCL all-reduce of the flat gradient buffer).  With an input that requires grad
+    (rays_o, rays_d, lights, background_rgb, z_vals; RNB_FLAG_INPUT_GRADS in the forward) the backward is
+    rnb_render_bwd_inputs, which also writes those inputs' gradients (shard-local: never all-reduced)."""
+
+    @staticmethod
+    def forward(ctx, renderer, call, rays_o, rays_d, lights, bg, z, *leaves):
         lib = native.load()
         desc = renderer.desc
         dev = call["rays_o"].device
@@ -162,10 +191,29 @@ class _FinePass(torch.autograd.Function):
         packed_grad = torch.empty_like(call["packed"])
         flat, views, order = renderer._alloc_flat_grads(call["train_color"], dev)
         dvar = views[id(renderer.deviation_network.variance)]
+        # input gradients (float32, the shapes handed to the forward; autograd maps them back to the caller's through the
+        # differentiable .to() / reshape of _run)
+        want = ctx.needs_input_grad[2:2 + _N_INPUTS]
+        in_grads = [None] * _N_INPUTS
+        ig = None
+        if any(want):
+            ig = native.RenderInputGrads()
+            for i, (name, src) in enumerate((("rays_o", call["rays_o"]), ("rays_d", call["rays_d"]),
+                                             ("lights_dir", call["lights"]), ("background_rgb", call["background_rgb"]),
+                                             ("z_vals", call["z_vals"]))):
+                if want[i]:
+                    in_grads[i] = torch.empty(src.shape, dtype=torch.float32, device=dev)
+                    setattr(ig, name, in_grads[i].data_ptr())
         with native.on_device(dev) as stream:
-            native.check(lib.rnb_render_bwd(C.byref(desc), native.ptr(call["packed"]), C.byref(ctx.args), C.byref(rg),
-                                            native.ptr(packed_grad), C.c_void_p(dvar.data_ptr()), native.ptr(ctx.ws),
-                                            ctx.ws.numel(), stream))
+            if ig is None:
+                native.check(lib.rnb_render_bwd(C.byref(desc), native.ptr(call["packed"]), C.byref(ctx.args),
+                                                C.byref(rg), native.ptr(packed_grad), C.c_void_p(dvar.data_ptr()),
+                                                native.ptr(ctx.ws), ctx.ws.numel(), stream))
+            else:
+                native.check(lib.rnb_render_bwd_inputs(C.byref(desc), native.ptr(call["packed"]), C.byref(ctx.args),
+                                                       C.byref(rg), C.byref(ig), native.ptr(packed_grad),
+                                                       C.c_void_p(dvar.data_ptr()), native.ptr(ctx.ws), ctx.ws.numel(),
+                                                       stream))
         if renderer.track_range:
             renderer._collect_range(desc, call["packed"], ctx.ws, ctx.args.B, ctx.args.S, ctx.args.flags)
         sdf_net, col_net = renderer.sdf_network, renderer.color_network
@@ -187,10 +235,10 @@ class _FinePass(torch.autograd.Function):
                 allreduce_mean_(flat, dp_group)
         ctx.ws = None
         grads = []
-        for leaf in call["leaves"]:
+        for i, leaf in enumerate(call["leaves"]):
             v = views.get(id(leaf))
-            grads.append(v.view_as(leaf) if v is not None else None)
-        return (None, None) + tuple(grads)
+            grads.append(v.view_as(leaf) if v is not None and ctx.needs_input_grad[2 + _N_INPUTS + i] else None)
+        return (None, None) + tuple(in_grads) + tuple(grads)
 
 
 class NeuSRenderer:
@@ -230,7 +278,10 @@ class NeuSRenderer:
         exact=True (default): large-batch semantics, see the module docstring; the loss MUST then be
         `rnb_loss(..., group=group)` — the pairing is checked both ways (the backward raises otherwise, and so does
         `rnb_loss(group=)` on a render that was not made in exact mode).  exact=False: DDP mean of per-rank
-        gradients, per-rank normalisers, any loss (`rnb_loss` without a group, or the reference's torch ops)."""
+        gradients, per-rank normalisers, any loss (`rnb_loss` without a group, or the reference's torch ops).
+        Gradients of the render's inputs (rays, lights, background, z) are shard-local and never all-reduced, as DDP treats
+        non-parameter tensors: in exact mode a rank's per-ray rows equal the single-process rows, and the single-process
+        gradient of a replicated input (shared lights, the background) is the sum over the ranks."""
         self.dp_group = (group if group is not None else dist.group.WORLD) if enabled else None
         self.dp_exact = bool(exact)
 
@@ -295,23 +346,37 @@ class NeuSRenderer:
             raise RuntimeError(f"NeuSRenderer: rays live on {dev} but the networks on "
                                f"{self.sdf_network.lin0.bias.device}")
         B = rays_o.shape[0]
-        rays_o = rays_o.detach().to(torch.float32).contiguous()
-        rays_d = rays_d.detach().to(torch.float32).contiguous()
         mvps = bool(flags & native.MODE_MVPS)
         no_albedo = bool(flags & native.FLAG_NO_ALBEDO)
         use_color = not (mvps and no_albedo)
+        # inputs the caller's graph differentiates (the reference's autograd reaches each of them): rays, lights (render_rnb*),
+        # the background (render) and z (given, or near / far with n_importance == 0: models/renderer.py:560, :590)
+        grad_enabled = torch.is_grad_enabled()
+        z_req = _requires_grad(z_vals) if z_vals is not None else (
+            self.n_importance == 0 and (_requires_grad(near) or _requires_grad(far)))
+        in_req = grad_enabled and (_requires_grad(rays_o) or _requires_grad(rays_d) or z_req or
+                                   (mvps and _requires_grad(lights_dir)) or (not mvps and _requires_grad(background_rgb)))
+        if in_req and (self.desc.variant & native.VARIANT_BF16):
+            raise RuntimeError("NeuSRenderer: gradients with respect to rays, lights, background or z are not available "
+                               "with set_variant(bf16=True) (the bf16 sweeps have no input adjoints); use the default "
+                               "variant, or detach those inputs")
+        # (differentiable: a float32 contiguous input is passed through as is, with its bits)
+        rays_o = rays_o.to(torch.float32).contiguous()
+        rays_d = rays_d.to(torch.float32).contiguous()
         packed = self._pack(use_color)
         perturb = self.perturb if perturb_overwrite < 0 else perturb_overwrite
         if z_vals is None:
             with torch.no_grad():
-                z_vals = self.sample_z_vals(rays_o, rays_d, near, far, packed, perturb, t_rand)
+                z_vals = self.sample_z_vals(rays_o.detach(), rays_d.detach(), near, far, packed, perturb, t_rand)
+            if z_req and grad_enabled:
+                z_vals = _ZFromNearFar.apply(near, far, z_vals)
         else:
-            z_vals = z_vals.detach().to(torch.float32).contiguous()
-        self.last_z_vals = z_vals
+            z_vals = z_vals.to(torch.float32).contiguous()
+        self.last_z_vals = z_vals.detach()
         lights = None
         if mvps:
             L = lights_dir.shape[0]
-            lt = lights_dir.detach().to(torch.float32)
+            lt = lights_dir.to(torch.float32)
             if lt.numel() == L * 3:
                 lights = lt.reshape(L, 3).contiguous()
             else:
@@ -319,17 +384,19 @@ class NeuSRenderer:
                 flags |= native.FLAG_LIGHT_PER_RAY
         bg = None
         if background_rgb is not None and not mvps:
-            bg = background_rgb.detach().to(torch.float32).reshape(3).contiguous()
+            bg = background_rgb.to(torch.float32).reshape(3).contiguous()
         # leaves that receive gradients: as in exp_runner.py:105-112 the albedo net is trained unless no_albedo
         train_color = use_color
         leaves = self._leaves(train_color)
-        grad_on = torch.is_grad_enabled() and any(p.requires_grad for p in leaves)
+        grad_on = grad_enabled and (in_req or any(p.requires_grad for p in leaves))
         if not grad_on:
             flags |= native.FLAG_FORWARD_ONLY
+        if in_req:
+            flags |= native.FLAG_INPUT_GRADS
         call = dict(rays_o=rays_o, rays_d=rays_d, z_vals=z_vals, lights=lights, background_rgb=bg,
                     cos_anneal_ratio=cos_anneal_ratio, flags=flags, packed=packed, leaves=leaves,
                     train_color=train_color, want_extras=self.want_extras)
-        outs = _FinePass.apply(self, call, *leaves)
+        outs = _FinePass.apply(self, call, rays_o, rays_d, lights, bg, z_vals, *leaves)
         out = dict(zip(_OUT_KEYS, outs))
         token = getattr(self, "_last_dp_token", None)
         self._last_dp_token = None
