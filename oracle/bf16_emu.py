@@ -33,7 +33,7 @@ Not rounded, as on the device: the sdf-head row and the albedo output layer (fp3
 :386-:402, :855-:882), every epilogue (softplus, its derivative, sigmoid, ReLU masks, the composite and its backward),
 g_e and the normal (:530, :553, :558-:574), the skip connection's g_e share, the fp32 accumulators, every dW / db sum
 and the weight-norm backward.  The albedo network runs in bf16 only where `bf16_color_supported` (bf16.hip:1364)
-holds; otherwise it is the fp32 path (mlp.hip), as on the device.
+holds; otherwise it is the fp32 path (layers.hip), as on the device.
 
 Weights: `weights_from_packed` reads the device's own fp32 effective weights (the fp32 part of `packed`, after
 rnb_weightnorm_fwd: the skip layer's 1/sqrt(2) folded in, the albedo layer-0 columns permuted to [feature | pe(p) |
@@ -346,7 +346,7 @@ class Bf16FinePass(FinePass):
             if self.color_bf16:
                 fbar, pen_bar = self._color_backward(albbar, grads)
             else:
-                # fp32 albedo path (mlp.hip): FinePass's C'; FB rounds the feature adjoint as it loads it (:700)
+                # fp32 albedo path (layers.hip): FinePass's C'; FB rounds the feature adjoint as it loads it (:700)
                 zb = albbar * self.albedo * (1 - self.albedo) if cc.squeeze_out else albbar
                 nl = cc.n_layers + 1
                 for l in range(nl - 1, -1, -1):

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
-HIP_SOURCES = ["api.hip", "layout.hip", "mlp.hip", "dw.hip", "weightnorm.hip", "sampling.hip", "composite.hip", "prof.hip", "fused.hip",
+HIP_SOURCES = ["api.hip", "layout.hip", "layers.hip", "backward.hip", "util.hip", "dw.hip", "weightnorm.hip", "sampling.hip", "composite.hip", "prof.hip", "fused.hip",
                "sweep_mv.hip", "fused_bwd.hip", "color_h2.hip", "bf16.hip", "train.hip", "raygen.hip", "mcubes.hip"]
 COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 EXTRA_FLAGS = {

@@ -76,30 +76,47 @@ static int points_setup(const rnb_model_desc* desc, int64_t n, void* ws, size_t 
   return RNB_OK;
 }
 
-// positional encoding + forward sweep: fused single-launch kernel for the 256-wide network, generic
-// per-layer GEMM chain otherwise.  RNB_VARIANT_GENERIC in the descriptor forces the generic path (A/B testing).
-static bool use_fused(const Layout& L) { return !(L.variant & RNB_VARIANT_GENERIC) && fused_supported(L); }
+// The three sweeps of a point batch, each on the model's kernel route (Layout::route).
+// positional encoding + forward sweep.  reverse_follows: the caller runs reverse_points next (the per-layer chain's
+// forward then leaves the reverse sweep's seed; the fused sweeps seed themselves from D_last).
 static int forward_points(const Layout& L, const float* packed, const float* pts, int64_t n, PointBufs& pb,
-                          bool save, bool need_feat, bool need_gz_last, float* feat_dense, hipStream_t s) {
-  if (is_bf16(L)) {
-    RNB_TRY(bf16_forward(L, packed, pts, n, pb, save, need_feat, s));
-    if (need_feat && feat_dense) RNB_TRY(launch_copy_cols(pb.cin, L.Cinp, L.F, n, feat_dense, s));
-    return RNB_OK;
+                          bool save, bool need_feat, bool reverse_follows, float* feat_dense, hipStream_t s) {
+  switch (L.route.sdf) {
+    case SDF_BF16:
+      // (a saved forward whose albedo net is bf16 too: the feature head writes bf16 K8 straight into that net's input)
+      RNB_TRY(bf16_forward(L, packed, pts, n, pb, save, need_feat, s, nullptr, save && need_feat && L.route.color == COLOR_BF16));
+      break;
+    case SDF_FUSED:
+      RNB_TRY(fused_forward(L, packed, pts, n, pb, save, need_feat, false, s));
+      break;
+    case SDF_LAYERS:
+      RNB_TRY(launch_pe_points(L, pts, n, pb, s));
+      return sweep_forward(L, packed, pb, need_feat, reverse_follows, feat_dense, s);
   }
-  if (use_fused(L)) {
-    RNB_TRY(fused_forward(L, packed, pts, n, pb, save, need_feat, need_gz_last, s));
-    if (need_feat && feat_dense) RNB_TRY(launch_copy_cols(pb.cin, L.Cinp, L.F, n, feat_dense, s));
-    return RNB_OK;
-  }
-  RNB_TRY(launch_pe_points(L, pts, n, pb, s));
-  return sweep_forward(L, packed, pb, need_feat, need_gz_last, feat_dense, s);
+  if (need_feat && feat_dense) RNB_TRY(launch_copy_cols(pb.cin, L.Cinp, L.F, n, feat_dense, s));
+  return RNB_OK;
 }
 
-// reverse-mode normal: fused sweep (seeds itself from D_last) or the generic chain (seeded by the forward)
-static int reverse_points(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s) {
-  if (is_bf16(L)) return bf16_reverse(L, packed, pb, s);
-  if (use_fused(L)) return fused_reverse(L, packed, pb, s);
+// reverse-mode normal.  store_ge: also keep d sdf / d e in pb.ge (the Hessian term of the point adjoint; the per-layer
+// chain always leaves it, the bf16 route has no input adjoints)
+static int reverse_points(const Layout& L, const float* packed, PointBufs& pb, bool store_ge, hipStream_t s) {
+  switch (L.route.sdf) {
+    case SDF_BF16: return bf16_reverse(L, packed, pb, s);
+    case SDF_FUSED: return fused_reverse(L, packed, pb, s, store_ge);
+    case SDF_LAYERS: break;
+  }
   return sweep_reverse(L, packed, pb, s);
+}
+
+// albedo network on the state the two sweeps above left (features in pb.cin / cin8, normals in pb.nrm [Mp,4])
+static int color_points(const Layout& L, const float* packed, PointBufs& pb, const float* pts, hipStream_t s) {
+  switch (L.route.color) {
+    case COLOR_BF16: return bf16_color_forward(L, packed, pb, pts, s);
+    case COLOR_H2: return color_h2_forward(L, packed, pb, pts, pb.nrm, s);
+    case COLOR_LAYERS: return sweep_color(L, packed, pb, pts, pb.nrm, 4, s);
+    case COLOR_NONE: break;
+  }
+  RNB_FAIL(RNB_E_INVALID, "model has no albedo network");
 }
 
 RNB_API int rnb_sdf_forward(const rnb_model_desc* desc, const float* packed, const float* pts, int64_t n,
@@ -127,8 +144,8 @@ RNB_API int rnb_sdf_gradient(const rnb_model_desc* desc, const float* packed, co
   Layout L;
   PointBufs pb;
   RNB_TRY(points_setup(desc, n, ws, ws_bytes, &L, &pb));
-  RNB_TRY(forward_points(L, packed, pts, n, pb, true, false, !use_fused(L) && !is_bf16(L), nullptr, s));
-  RNB_TRY(reverse_points(L, packed, pb, s));
+  RNB_TRY(forward_points(L, packed, pts, n, pb, true, false, true, nullptr, s));
+  RNB_TRY(reverse_points(L, packed, pb, false, s));
   RNB_TRY(launch_copy_cols(pb.nrm, 4, 3, n, grad_out, s));
   if (sdf_out) RNB_CHECK_HIP(hipMemcpyAsync(sdf_out, pb.sdf, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
   return RNB_OK;
@@ -149,6 +166,7 @@ RNB_API int rnb_color_forward(const rnb_model_desc* desc, const float* packed, c
   RNB_TRY(points_setup(desc, n, ws, ws_bytes, &L, &pb));
   if (L.F <= 0) RNB_FAIL(RNB_E_INVALID, "model has no feature head");
   RNB_TRY(launch_fill_cols(feats, L.F, n, pb.Mp, L.Cinp, pb.cin, s));
+  // (always the per-layer chain, whatever the route: it alone reads the caller's dense [n,3] normals and fp32 features)
   RNB_TRY(sweep_color(L, packed, pb, pts, normals, 3, s));
   RNB_TRY(launch_copy_cols(pb.alb, 4, L.Co, n, out, s));
   return RNB_OK;
@@ -214,13 +232,11 @@ RNB_API int rnb_sdf_forward_save(const rnb_model_desc* desc, const float* packed
   Layout L;
   PointBufs pb;
   RNB_TRY(grad_setup(desc, n, flags, ws, ws_bytes, &L, &pb));
-  const bool fused = use_fused(L);
   // state maxima of the x2h weight-gradient jobs: zeroed here (a render's first kernel does it there), grown by the sweeps
   RNB_CHECK_HIP(hipMemsetAsync(pb.smax, 0, SMAX_SLOTS * sizeof(unsigned), s));
-  RNB_TRY(forward_points(L, packed, pts, n, pb, true, feat, normal && !fused, feat ? feat_out : nullptr, s));
+  RNB_TRY(forward_points(L, packed, pts, n, pb, true, feat, normal, feat ? feat_out : nullptr, s));
   if (normal) {
-    if (fused) RNB_TRY(fused_reverse(L, packed, pb, s, true));   // (+ d sdf / d e for the Hessian term of x's adjoint)
-    else RNB_TRY(sweep_reverse(L, packed, pb, s));
+    RNB_TRY(reverse_points(L, packed, pb, true, s));   // (+ d sdf / d e for the Hessian term of x's adjoint)
     RNB_TRY(launch_copy_cols(pb.nrm, 4, 3, n, nrm_out, s));
   }
   RNB_CHECK_HIP(hipMemcpyAsync(sdf_out, pb.sdf, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -256,16 +272,10 @@ RNB_API int rnb_sdf_backward(const rnb_model_desc* desc, const float* packed, in
   if (feat_bar) {
     RNB_CHECK_HIP(hipMemsetAsync(pb.cinb, 0, (size_t)Mp * L.Cinp * sizeof(float), s));
     RNB_TRY(launch_fill_cols(feat_bar, L.F, n, Mp, L.Cinp, pb.cinb, s));
-    if (is_x2h(L)) RNB_TRY(launch_absmax_rows(pb.cinb, Mp * L.Cinp, pb.amax + AMAX_CINB, s));
+    if (L.route.h2) RNB_TRY(launch_absmax_rows(pb.cinb, Mp * L.Cinp, pb.amax + AMAX_CINB, s));
   }
-  BwdParts parts;
-  parts.albedo = false;
-  parts.sdf = true;
-  parts.feat = feat_bar != nullptr;
-  parts.normal = nrm_bar != nullptr;
-  parts.color_inputs = false;
-  RNB_TRY(sweep_backward_parts(L, packed, pb, parts, packed_grad, use_fused(L), s));
-  if (x_bar) RNB_TRY(launch_sdf_xbar(L, packed, pb, parts.normal, x_bar, s));
+  RNB_TRY(sweep_backward_parts(L, packed, pb, BwdParts::sdf_points(feat_bar != nullptr, nrm_bar != nullptr), packed_grad, s));
+  if (x_bar) RNB_TRY(launch_sdf_xbar(L, packed, pb, nrm_bar != nullptr, x_bar, s));
   return RNB_OK;
 }
 
@@ -290,8 +300,7 @@ RNB_API int rnb_color_forward_save(const rnb_model_desc* desc, const float* pack
   RNB_TRY(launch_fill_cols(pts, 3, n, Mp, 4, pb.x, s));
   RNB_TRY(launch_fill_cols(normals, 3, n, Mp, 4, pb.nrm, s));
   RNB_TRY(launch_fill_cols(feats, L.F, n, Mp, L.Cinp, pb.cin, s));
-  if (use_fused(L) && color_h2_supported(L)) RNB_TRY(color_h2_forward(L, packed, pb, pts, pb.nrm, s));
-  else RNB_TRY(sweep_color(L, packed, pb, pts, pb.nrm, 4, s));
+  RNB_TRY(color_points(L, packed, pb, pts, s));
   RNB_TRY(launch_copy_cols(pb.alb, 4, L.Co, n, out, s));
   return RNB_OK;
 }
@@ -314,13 +323,7 @@ RNB_API int rnb_color_backward(const rnb_model_desc* desc, const float* packed, 
   RNB_CHECK_HIP(hipMemsetAsync(pb.amax, 0, AMAX_SLOTS * sizeof(unsigned), s));
   RNB_CHECK_HIP(hipMemsetAsync(pb.albbar, 0, (size_t)Mp * 4 * sizeof(float), s));
   RNB_TRY(launch_fill_cols(alb_bar, L.Co, n, Mp, 4, pb.albbar, s));
-  BwdParts parts;
-  parts.albedo = true;
-  parts.sdf = false;
-  parts.feat = false;
-  parts.normal = false;
-  parts.color_inputs = pts_bar != nullptr || nrm_bar != nullptr;
-  RNB_TRY(sweep_backward_parts(L, packed, pb, parts, packed_grad, use_fused(L), s));
+  RNB_TRY(sweep_backward_parts(L, packed, pb, BwdParts::color_points(pts_bar != nullptr || nrm_bar != nullptr), packed_grad, s));
   if (feat_bar) RNB_TRY(launch_copy_cols(pb.cinb, L.Cinp, L.F, n, feat_bar, s));
   RNB_TRY(launch_color_input_bwd(L, pb, pts_bar, nrm_bar, s));
   return RNB_OK;
@@ -356,7 +359,7 @@ RNB_API int rnb_sdf_grid_workspace_bytes(const rnb_model_desc* desc, const rnb_g
   RNB_TRY(make_layout(desc, &L));
   int64_t n;
   RNB_TRY(check_grid(grid, &n));
-  if (use_fused(L) || is_bf16(L)) { *bytes = 256; return RNB_OK; }   // the fused sweep keeps everything in LDS
+  if (L.route.sdf != SDF_LAYERS) { *bytes = 256; return RNB_OK; }   // the fused sweeps keep everything in LDS
   Carver c(nullptr, 0);
   PointBufs pb;
   c.take<float>(kGridChunk * 3);
@@ -376,13 +379,13 @@ RNB_API int rnb_sdf_grid(const rnb_model_desc* desc, const float* packed, const 
   RNB_TRY(check_grid(grid, &n));
   if (n == 0) return RNB_OK;
   const GridGen gg = grid_gen_of(grid);
-  if (use_fused(L) || is_bf16(L)) {
+  if (L.route.sdf != SDF_LAYERS) {   // the grid points are generated inside the forward kernel
     PointBufs pb;
     memset(&pb, 0, sizeof(pb));
     pb.M = n;
     pb.Mp = pad_rows(n);
     pb.sdf = volume;   // grid mode writes rows < M only
-    if (is_bf16(L)) return bf16_forward(L, packed, nullptr, n, pb, false, false, s, &gg);
+    if (L.route.sdf == SDF_BF16) return bf16_forward(L, packed, nullptr, n, pb, false, false, s, &gg);
     return fused_forward(L, packed, nullptr, n, pb, false, false, false, s, &gg);
   }
   RNB_REQUIRE(ws, "workspace");
@@ -667,19 +670,9 @@ RNB_API int rnb_render_fwd(const rnb_model_desc* desc, const float* packed, cons
   const bool use_color = (mode & PM_WITH_COLOR) != 0;
   RNB_TRY(launch_fine_points(a->rays_o, a->rays_d, a->z_vals, a->B, a->S, 2.0f / (float)desc->n_samples, rb.pts,
                              rb.dists, rb.pb.smax, s));
-  const bool color_bf16 = is_bf16(L) && use_color && bf16_color_supported(L);
-  if (color_bf16) {   // the feature head writes bf16 K8 straight into the albedo net's input
-    RNB_TRY(bf16_forward(L, packed, rb.pts, a->B * a->S, rb.pb, true, true, s, nullptr, true));
-  } else {
-    RNB_TRY(forward_points(L, packed, rb.pts, a->B * a->S, rb.pb, true, use_color, !use_fused(L) && !is_bf16(L), nullptr, s));
-  }
-  // RNB_FLAG_INPUT_GRADS: the fused R sweep also keeps d sdf / d e (the Hessian term of the point adjoint; the per-layer
-  // chain always leaves it in pb.ge)
-  if ((a->flags & RNB_FLAG_INPUT_GRADS) && use_fused(L)) RNB_TRY(fused_reverse(L, packed, rb.pb, s, true));
-  else RNB_TRY(reverse_points(L, packed, rb.pb, s));
-  if (color_bf16) RNB_TRY(bf16_color_forward(L, packed, rb.pb, rb.pts, s));
-  else if (use_color && use_fused(L) && color_h2_supported(L)) RNB_TRY(color_h2_forward(L, packed, rb.pb, rb.pts, rb.pb.nrm, s));
-  else if (use_color) RNB_TRY(sweep_color(L, packed, rb.pb, rb.pts, rb.pb.nrm, 4, s));
+  RNB_TRY(forward_points(L, packed, rb.pts, a->B * a->S, rb.pb, true, use_color, true, nullptr, s));
+  RNB_TRY(reverse_points(L, packed, rb.pb, (a->flags & RNB_FLAG_INPUT_GRADS) != 0, s));
+  if (use_color) RNB_TRY(color_points(L, packed, rb.pb, rb.pts, s));
   CompArgs c = comp_args_of(L, a, rb);
   c.gerr = a->gradient_error;
   c.gerr_den = rb.gerr_den;
@@ -747,15 +740,9 @@ static int render_bwd_body(const rnb_model_desc* desc, const float* packed, cons
   if (ig != nullptr && ig->lights_dir && shared_lights) RNB_TRY(launch_sum_over_rays(rb.ig_light, a->B, a->n_lights, ig->lights_dir, s));
   if (ig != nullptr && ig->background_rgb) RNB_TRY(launch_sum_over_rays(rb.ig_bg, a->B, 1, ig->background_rgb, s));
   RNB_CHECK_HIP(hipMemsetAsync(packed_grad, 0, (size_t)L.total * sizeof(float), s));
-  if (!need_pbar) return sweep_backward(L, packed, rb.pb, use_color, packed_grad, use_fused(L), s);
+  if (!need_pbar) return sweep_backward(L, packed, rb.pb, use_color, packed_grad, s);
   // the render path's backward with the albedo net's encoding columns of cinb kept (color_inputs)
-  BwdParts parts;
-  parts.albedo = use_color;
-  parts.sdf = true;
-  parts.feat = use_color;
-  parts.normal = true;
-  parts.color_inputs = use_color;
-  RNB_TRY(sweep_backward_parts(L, packed, rb.pb, parts, packed_grad, use_fused(L), s));
+  RNB_TRY(sweep_backward_parts(L, packed, rb.pb, BwdParts::render(use_color, use_color), packed_grad, s));
   float* ebar = nullptr;
   RNB_TRY(launch_sdf_ebar(L, packed, rb.pb, &ebar, s));
   RayAdjArgs r;
@@ -836,7 +823,7 @@ RNB_API int rnb_algorithmic_bytes(const rnb_model_desc* desc, int64_t B, int32_t
     // albedo network: cin (1 write, 2 reads), ac_l (1 write; read by the next layer, the relu mask and a dW), zc_l
     // (1 write, 2 reads), cinb (1 write; read by FB and by the normal's adjoint).  bf16 too when the bf16 albedo
     // kernels apply (RNB_VARIANT_BF16 with the shipped shape), else fp32.
-    const double ec = (is_bf16(L) && bf16_color_supported(L)) ? 2.0 : 4.0;
+    const double ec = L.route.color == COLOR_BF16 ? 2.0 : 4.0;
     per_pt += ec * (3.0 * L.Cinp + 4.0 * L.Hcp + 3.0 * L.Hcp * (L.nc - 1) + 3.0 * L.Hcp * L.nc + 2.0 * L.Cinp);
     per_pt += e * 2.0 * L.Hp;         // feature head's weight gradient: fbar and a_last
   }

@@ -1360,7 +1360,7 @@ __global__ void bf_pack_kernel(const float* __restrict__ src, BfPackTable t, bfr
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-// the albedo network runs in bf16 too when it has the shipped shape; otherwise its fp32 kernels (mlp.hip) are used
+// the albedo network runs in bf16 too when it has the shipped shape; otherwise its fp32 kernels (layers.hip) are used
 bool bf16_color_supported(const Layout& L) {
   if (L.F != FH || L.Hc != FH || L.Hcp != FH) return false;
   if (L.Cinp > CMAX || L.Cinp % 64 != 0 || L.Cinp - L.F > 64) return false;
@@ -1560,11 +1560,11 @@ int bf16_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_
 }
 
 // The weight-gradient jobs of one bf16 backward, in launch order: the hidden layers 0 .. nh-1 (pairs gz_l / u_l and
-// zb_l / in_l), the feature head (with_color), and with color_bf16 the albedo net's layers nc-1 .. 1 and its layer 0
+// zb_l / in_l), the feature head (with_color), and on the bf16 albedo route the albedo net's layers nc-1 .. 1 and its layer 0
 // as two jobs (the 256 feature columns, the encoding columns).  f(job, flops) gets every field but the slabs.  Sizing
 // lists a PointBufs without buffers and no packed gradient: the operands and targets are then null.
 template <class F>
-static void bf16_dw_list(const Layout& L, const PointBufs& pb, bool with_color, bool color_bf16, float* packed_grad, F f) {
+static void bf16_dw_list(const Layout& L, const PointBufs& pb, bool with_color, float* packed_grad, F f) {
   const int64_t M = pb.M;
   auto bf = [](const void* p) { return reinterpret_cast<const bfraw*>(p); };
   auto add = [&](const void* X1, const void* Y1, int Cy1, const void* X2, const void* Y2, int Cy2, int npairs, int K,
@@ -1589,7 +1589,7 @@ static void bf16_dw_list(const Layout& L, const PointBufs& pb, bool with_color, 
   }
   if (!with_color) return;
   add(pb.fbar_k8, pb.a[L.nh - 1], FH, nullptr, nullptr, 0, 1, L.feat.Kp, L.feat, 0, 2.0 * (double)M * L.feat.N * L.feat.K);
-  if (!color_bf16) return;
+  if (L.route.color != COLOR_BF16) return;
   // the albedo net's hidden layers: dW_l = zc_l^T in_l
   for (int l = L.nc - 1; l >= 1; --l)
     add(pb.zc8[l], pb.ac8[l - 1], FH, nullptr, nullptr, 0, 1, L.col[l].Kp, L.col[l], 0, 2.0 * (double)M * L.col[l].N * L.col[l].K);
@@ -1608,9 +1608,9 @@ static void bf16_dw_split(int64_t M, int njobs, int* splits_out, int64_t* rows_o
 }
 
 // RA, sdf-head row gradient, FB and every dW job of the SDF network (+ the feature head's) for one backward
-int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, bool color_bf16, float* packed_grad,
-                  hipStream_t s) {
+int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad, hipStream_t s) {
   const int64_t M = pb.M;
+  const bool color_bf16 = with_color && L.route.color == COLOR_BF16;
   const bool det = (L.variant & RNB_VARIANT_DETERMINISTIC) != 0;
   BfBwdArgs g;
   fill_bwd(L, packed, pb, g);
@@ -1645,7 +1645,7 @@ int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with
   memset(&grp, 0, sizeof(grp));
   grp.M = M;
   double fl = 0;
-  bf16_dw_list(L, pb, with_color, color_bf16, packed_grad, [&](const BfDwJob& J, double f) {
+  bf16_dw_list(L, pb, with_color, packed_grad, [&](const BfDwJob& J, double f) {
     if (grp.njobs < kMaxBfDwJobs) grp.job[grp.njobs] = J;
     ++grp.njobs;
     fl += f;
@@ -1682,7 +1682,7 @@ int64_t bf16_dw_floats(const Layout& L, int64_t M, bool with_color) {
   PointBufs pb{};
   int njobs = 0;
   int64_t kp = 0;   // (each job: [splits][256][lddw] + [splits][256])
-  bf16_dw_list(L, pb, with_color, with_color && bf16_color_supported(L), nullptr, [&](const BfDwJob& J, double) {
+  bf16_dw_list(L, pb, with_color, nullptr, [&](const BfDwJob& J, double) {
     ++njobs;
     kp += J.lddw;
   });

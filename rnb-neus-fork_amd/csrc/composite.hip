@@ -404,7 +404,7 @@ __global__ __launch_bounds__(64) void composite_bwd_ig_kernel(CompBwdArgs g) { c
 // consumed (it never goes to HBM):
 //   nbar_tot = nbar + J_pe(n)^T cinb[pe(n)]                         (the normal's total adjoint: composite + albedo input)
 //   pbar     = scale ( J_pe(xs)^T ebar - sum_k ge_k d^2 pe_k / d xs^2 . nbar_tot ) + J_pe(p)^T cinb[pe(p)]
-// (sdf_xbar_kernel / color_input_bwd_kernel of the point-wise calls, mlp.hip).  pts = o + d mid, mid = z + dists / 2,
+// (sdf_xbar_kernel / color_input_bwd_kernel of the point-wise calls, backward.hip).  pts = o + d mid, mid = z + dists / 2,
 // dists_s = z_{s+1} - z_s (the last one a constant), so with mbar_s = pbar_s . d and Dbar_s = dists_bar_s + mbar_s / 2:
 //   o_bar = sum_s pbar_s ;  d_bar = sum_s mid_s pbar_s + cos_d ;  z_bar_s = mbar_s - [s < S-1] Dbar_s + [s > 0] Dbar_{s-1}.
 // Sums are lane-local over the 64-sample chunks, then a shuffle butterfly: a fixed order.

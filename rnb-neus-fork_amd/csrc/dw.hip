@@ -80,11 +80,11 @@ struct DwListed {
 
 // The weight-gradient jobs of one backward, in the order DwBatch takes them: the albedo layers nc-1 .. 0, the reduce-only
 // slabs (the fused albedo output layer, the sdf-head row), the feature head, the hidden layers nh-1 .. 0 (with the
-// normal two operand pairs: gz_l / u_l and zb_l / in_l; without it the second alone).  h2: the pairs carry their x2h
-// maxima slots.  sdfh_slabs > 0: the sdf-head row's gradient waits in pb.sdfh_part as that many slabs.  Sizing lists a
-// PointBufs without buffers: the operands are then null.
+// normal two operand pairs: gz_l / u_l and zb_l / in_l; without it the second alone).  On an x2h route the pairs carry
+// their maxima slots (h2_slot).  sdfh_slabs > 0: the sdf-head row's gradient waits in pb.sdfh_part as that many slabs.
+// Sizing lists a PointBufs without buffers: the operands are then null.
 template <class F>
-static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts, bool h2, bool color_h2, int sdfh_slabs, F f) {
+static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts, int sdfh_slabs, F f) {
   const int64_t M = pb.M;
   auto job = [&](const DwPair& p1, const DwPair& p2, int npairs, const Lin& ln, int bias_pair, double fl) {
     f(DwListed{p1, p2, npairs, ln.Np, ln.Kp, bias_pair, ln.w_off, ln.b_off, fl, nullptr, nullptr, 0});
@@ -93,11 +93,11 @@ static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts,
     for (int l = L.nc - 1; l >= 0; --l) {
       const float* in = l == 0 ? pb.cin : pb.ac[l - 1];
       const int ldin = l == 0 ? L.Cinp : L.Hcp;
-      const DwPair p{pb.zc[l], L.Hcp, in, ldin, 0, h2_slot(h2, pb.amax, AMAX_ZC + l),
-                     h2_slot(h2, pb.smax, l == 0 ? SMAX_CIN : SMAX_AC + l - 1)};
+      const DwPair p{pb.zc[l], L.Hcp, in, ldin, 0, h2_slot(L, pb.amax, AMAX_ZC + l),
+                     h2_slot(L, pb.smax, l == 0 ? SMAX_CIN : SMAX_AC + l - 1)};
       job(p, p, 1, L.col[l], 0, mm_flops(M, L.col[l]));
     }
-    if (color_h2) {   // the output layer's gradient: per-tile column sums (color_h2_backward)
+    if (L.route.color == COLOR_H2) {   // the output layer's gradient: per-tile column sums (color_h2_backward)
       const int tiles = (int)(pb.Mp / 64);
       f(DwListed{{}, {}, 0, L.Co, L.Hcp, 0, L.colo.w_off, L.colo.b_off, 0.0, pb.col_part,
                  pb.col_part + (int64_t)tiles * L.Co * L.Hcp, tiles});
@@ -108,7 +108,7 @@ static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts,
     f(DwListed{{}, {}, 0, 1, L.Hp, 0, L.wsdf_off, L.bsdf_off, 0.0, pb.sdfh_part, pb.sdfh_part + (int64_t)sdfh_slabs * L.Hp,
                sdfh_slabs});
   if (parts.feat) {
-    const DwPair p{pb.cinb, L.Cinp, pb.a[L.nh - 1], L.Hp, 0, h2_slot(h2, pb.amax, AMAX_CINB), h2_slot(h2, pb.smax, SMAX_A + L.nh - 1)};
+    const DwPair p{pb.cinb, L.Cinp, pb.a[L.nh - 1], L.Hp, 0, h2_slot(L, pb.amax, AMAX_CINB), h2_slot(L, pb.smax, SMAX_A + L.nh - 1)};
     job(p, p, 1, L.feat, 0, mm_flops(M, L.feat));
   }
   for (int l = L.nh - 1; l >= 0; --l) {
@@ -117,9 +117,9 @@ static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts,
     const int ldin = l == 0 ? L.Ep : L.Hp;
     const float* uin = l == 0 ? pb.geb : pb.u[l];
     // (x2h: adjoint operand, its recorded maximum; the state operand's recorded maximum)
-    const DwPair p1{pb.gz[l], L.Hp, uin, ldin, 1, h2_slot(h2, pb.amax, AMAX_U + l), h2_slot(h2, pb.smax, SMAX_GZ + l)};
-    const DwPair p2{pb.zb[l], L.Hp, in, ldin, 0, h2_slot(h2, pb.amax, AMAX_ZB + l),
-                    h2_slot(h2, pb.smax, l == 0 ? SMAX_E : SMAX_A + l - 1)};
+    const DwPair p1{pb.gz[l], L.Hp, uin, ldin, 1, h2_slot(L, pb.amax, AMAX_U + l), h2_slot(L, pb.smax, SMAX_GZ + l)};
+    const DwPair p2{pb.zb[l], L.Hp, in, ldin, 0, h2_slot(L, pb.amax, AMAX_ZB + l),
+                    h2_slot(L, pb.smax, l == 0 ? SMAX_E : SMAX_A + l - 1)};
     if (parts.normal) job(p1, p2, 2, ln, 1, 2.0 * mm_flops(M, ln));
     else job(p2, p2, 1, ln, 0, mm_flops(M, ln));
   }
@@ -132,14 +132,17 @@ static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts,
 static void dw_sizes(const Layout& L, int64_t M, bool with_color, int64_t* det_floats, int64_t* staged_floats) {
   PointBufs pb{};
   pb.M = M;
-  const BwdParts render{with_color, true, with_color, true, false};
   const bool x3 = is_x3(L);
+  // (reduce-only jobs are other kernels' slabs, carved with their producers: no room of their own here)
+  auto each_job = [&](auto f) {
+    dw_list(L, pb, BwdParts::render(with_color, false), 0, [&](const DwListed& j) { if (j.npairs > 0) f(j); });
+  };
   int total_units = 0;
-  dw_list(L, pb, render, false, false, 0, [&](const DwListed& j) {
+  each_job([&](const DwListed& j) {
     if (x3_job_shape(x3, j.N, j.K)) x3_for_each_range(j.K, [&](int, int width) { total_units += x3_job_units(j.npairs, width); });
   });
   *det_floats = *staged_floats = 0;
-  dw_list(L, pb, render, false, false, 0, [&](const DwListed& j) {
+  each_job([&](const DwListed& j) {
     int splits, rows;
     if (x3_job_shape(x3, j.N, j.K))
       x3_for_each_range(j.K, [&](int, int width) {
@@ -207,9 +210,9 @@ struct DwBatch {
     j.N = N; j.K = K; j.lddw = lddw; j.splits = splits;
     return RNB_OK;
   }
-  DwBatch(const Layout& L_, int64_t M_, bool h2_, float* part_, int64_t part_floats, float* slab_, int64_t slab_floats_,
+  DwBatch(const Layout& L_, int64_t M_, float* part_, int64_t part_floats, float* slab_, int64_t slab_floats_,
           hipStream_t s_)
-      : L(L_), M(M_), s(s_), lds_path((L_.variant & RNB_VARIANT_DW_LDS) != 0), x3(is_x3(L_)), h2(h2_), part(part_),
+      : L(L_), M(M_), s(s_), lds_path((L_.variant & RNB_VARIANT_DW_LDS) != 0), x3(is_x3(L_)), h2(L_.route.h2), part(part_),
         part_left(part_floats), slab(slab_), slab_left(slab_floats_), slab_base(slab_), slab_floats(slab_floats_) {
     for (int v = 0; v < 4; ++v) { grp[v].njobs = 0; grp[v].M = (int)M_; flops[v] = 0.0; }
   }
@@ -377,14 +380,13 @@ struct DwBatch {
 };
 
 // Called after every other launch of the backward: no job reads a buffer that a later launch writes.
-int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, bool h2, bool color_h2, int sdfh_slabs,
-                float* packed_grad, hipStream_t s) {
+int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, int sdfh_slabs, float* packed_grad, hipStream_t s) {
   const bool det = (L.variant & RNB_VARIANT_DETERMINISTIC) != 0;
   const int64_t det_floats = dw_det_floats(L, pb, parts);
-  DwBatch dw(L, pb.M, h2, det ? pb.dw_part : nullptr, det ? det_floats : 0, pb.dw_part + det_floats,
+  DwBatch dw(L, pb.M, det ? pb.dw_part : nullptr, det ? det_floats : 0, pb.dw_part + det_floats,
              pb.dw_part_floats - det_floats, s);
   int rc = RNB_OK;
-  dw_list(L, pb, parts, h2, color_h2, sdfh_slabs, [&](const DwListed& j) {
+  dw_list(L, pb, parts, sdfh_slabs, [&](const DwListed& j) {
     if (rc != RNB_OK) return;
     float* dW = packed_grad + j.w_off;
     float* db = packed_grad + j.b_off;

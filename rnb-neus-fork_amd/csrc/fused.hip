@@ -3,7 +3,7 @@
 // straight into MFMA B-fragments (each 128-byte weight line is fetched once per workgroup and consumed by
 // four back-to-back 16-byte loads), and what the backward pass needs is written to HBM with fire-and-forget
 // stores that overlap the next layer's matrix work.  Replaces, per sweep, the chain of per-layer GEMM
-// launches of mlp.hip (which remain the generic path for other widths).
+// launches of layers.hip (which remain the generic path for other widths).
 //
 //   fused_forward_kernel   positional encoding + F sweep (+ sdf head, + feature head)
 //                          models/embedder.py:40-46, models/fields.py:82-104

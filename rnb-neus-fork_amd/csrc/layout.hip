@@ -141,6 +141,14 @@ int make_layout(const rnb_model_desc* d, Layout* L) {
     L->total_all += 256;
     if (L->nh + 1 + L->nc > kH2TabSlots) RNB_FAIL(RNB_E_INVALID, "too many layers for the x2h scale table");
   }
+  // the route: fused single-launch sweeps for the 256-wide network, the per-layer GEMM chain otherwise;
+  // RNB_VARIANT_GENERIC forces the per-layer chain (A/B testing)
+  Route& r = L->route;
+  r.sdf = is_bf16(*L) ? SDF_BF16 : (!(L->variant & RNB_VARIANT_GENERIC) && fused_supported(*L)) ? SDF_FUSED : SDF_LAYERS;
+  r.color = (is_bf16(*L) && bf16_color_supported(*L)) ? COLOR_BF16
+            : (r.sdf == SDF_FUSED && color_h2_supported(*L)) ? COLOR_H2
+            : L->F > 0 ? COLOR_LAYERS : COLOR_NONE;
+  r.h2 = is_x2h(*L) && r.sdf == SDF_FUSED;
   return RNB_OK;
 }
 
@@ -149,7 +157,7 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
   pb->M = M;
   pb->Mp = pad_rows(M);
   const int64_t Mp = pb->Mp;
-  const bool bf = (L.variant & RNB_VARIANT_BF16) != 0;
+  const bool bf = L.route.sdf == SDF_BF16;
   // RNB_VARIANT_BF16: the per-point state of the SDF sweeps is bf16 (K8 layout, bf16.hip): half the bytes
   auto take_state = [&](int64_t n) { return bf ? reinterpret_cast<float*>(c.take<uint16_t>(n)) : c.take<float>(n); };
   pb->x = c.take<float>(Mp * 4);
@@ -168,8 +176,8 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
     pb->cin = c.take<float>(Mp * L.Cinp);
     for (int l = 0; l < L.nc; ++l) pb->ac[l] = c.take<float>(Mp * L.Hcp);
     pb->alb = c.take<float>(Mp * 4);
-    if (color_h2_supported(L)) pb->ac0_mask = c.take<unsigned>(Mp / 64 * 256 * 2);
-    if (bf && bf16_color_supported(L)) {
+    if (L.route.color == COLOR_H2) pb->ac0_mask = c.take<unsigned>(Mp / 64 * 256 * 2);
+    if (L.route.color == COLOR_BF16) {
       pb->cin8 = c.take<uint16_t>(Mp * L.Cinp);
       for (int l = 0; l < L.nc; ++l) pb->ac8[l] = c.take<uint16_t>(Mp * L.Hcp);
     }
@@ -191,14 +199,14 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
     if (mode & PM_WITH_COLOR) {
       for (int l = 0; l < L.nc; ++l) pb->zc[l] = c.take<float>(Mp * L.Hcp);
       pb->cinb = c.take<float>(Mp * L.Cinp);
-      if (bf && bf16_color_supported(L))
+      if (L.route.color == COLOR_BF16)
         for (int l = 0; l < L.nc; ++l) pb->zc8[l] = c.take<uint16_t>(Mp * L.Hcp);
     }
     {
       const bool wc = (mode & PM_WITH_COLOR) != 0;
       pb->dw_part_floats = dw_workspace_floats(L, M, wc);
       pb->dw_part = c.take<float>(pb->dw_part_floats > 0 ? pb->dw_part_floats : 64);
-      if (wc && color_h2_supported(L)) pb->col_part = c.take<float>(color_h2_part_floats(L, M));
+      if (wc && L.route.color == COLOR_H2) pb->col_part = c.take<float>(color_h2_part_floats(L, M));
       pb->sdfh_part = c.take<float>((int64_t)kSdfHeadSlabs * (L.Hp + 1));
     }
   }

@@ -13,6 +13,7 @@ constexpr int kPad = 32;          // every feature width is padded to the MFMA t
 constexpr int kRowPad = 128;      // point counts are padded to the GEMM block height
 inline int pad32(int x) { return (x + kPad - 1) / kPad * kPad; }
 inline int64_t pad_rows(int64_t m) { return (m + kRowPad - 1) / kRowPad * kRowPad; }
+inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 void set_error(const char* fmt, ...);
 #define RNB_FAIL(code, ...)        \
@@ -44,6 +45,16 @@ struct Lin {
 // algorithmic FLOPs of one layer-shaped GEMM over M points: real (unpadded) layer shape
 inline double mm_flops(int64_t M, const Lin& ln) { return 2.0 * (double)M * ln.N * ln.K; }
 
+// The kernel route of each network: a function of the descriptor alone, decided once by make_layout.  Forward, backward
+// and carve_points all read it, so the buffers carved, the sweeps that fill them and the backward that reads them agree.
+enum SdfRoute { SDF_LAYERS, SDF_FUSED, SDF_BF16 };   // per-layer chain (layers.hip) | fused.hip / fused_bwd.hip | bf16.hip
+enum ColorRoute { COLOR_NONE, COLOR_LAYERS, COLOR_H2, COLOR_BF16 };   // no albedo net | layers.hip | color_h2.hip | bf16.hip
+struct Route {
+  SdfRoute sdf;
+  ColorRoute color;
+  bool h2;   // x2h weight gradients: every producer records the maximum of its tensor, the dW jobs scale by them
+};
+
 // Packed layout of both networks (see weightnorm.hip for how leaves map onto it).
 struct Layout {
   // SDF network: nh hidden layers (softplus) + output layer split into sdf row and feature rows
@@ -74,6 +85,7 @@ struct Layout {
   int64_t h2tab_off;      // RNB_VARIANT_X2H: float offset of the scale table of the fp16 mirror (H2Tab), else -1
   int variant;            // rnb_model_desc.variant (RNB_VARIANT_* bits)
   int knob(int shift) const { return (variant >> shift) & 3; }
+  Route route;            // which kernels run the two networks (make_layout's last step)
 };
 
 int make_layout(const rnb_model_desc* d, Layout* L);
@@ -183,36 +195,55 @@ enum { AMAX_ZB = 0, AMAX_U = RNB_MAX_LIN, AMAX_ZC = 2 * RNB_MAX_LIN + 1, AMAX_CI
 // slots of PointBufs::smax: a_l, gz_l (hidden layers), e (positional encoding), cin (albedo-net input), ac_l (its hidden layers)
 enum { SMAX_A = 0, SMAX_GZ = RNB_MAX_LIN, SMAX_E = 2 * RNB_MAX_LIN, SMAX_CIN = 2 * RNB_MAX_LIN + 1, SMAX_AC = 2 * RNB_MAX_LIN + 2,
        SMAX_SLOTS = 3 * RNB_MAX_LIN + 2 };
-// slot i of an x2h maxima array (PointBufs::amax / ::smax), or nullptr when x2h is off or the array is absent: a weight-
-// gradient job then scales by the fixed 2^6, a GEMM records no maximum
-inline unsigned* h2_slot(bool h2, unsigned* slots, int i) { return h2 && slots != nullptr ? slots + i : nullptr; }
+// slot i of an x2h maxima array (PointBufs::amax / ::smax) when the route records them, else nullptr (also for the
+// buffer-less PointBufs of a sizing query): a weight-gradient job then scales by the fixed 2^6, a GEMM records no maximum
+inline unsigned* h2_slot(const Layout& L, unsigned* slots, int i) { return L.route.h2 && slots != nullptr ? slots + i : nullptr; }
 // PM_NO_REVERSE: a backward without the normal's adjoint (point-wise autograd of SDFNetwork.forward): no gz_l, no u_l
 enum PointMode { PM_SDF_ONLY = 0, PM_WITH_NORMAL = 1, PM_WITH_COLOR = 2, PM_WITH_BACKWARD = 4, PM_NO_REVERSE = 8 };
 void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb);
 
-// ---- device sweeps (mlp.hip) -------------------------------------------------------------------
+// ---- the per-layer route (layers.hip): one GEMM launch per layer, any shape ---------------------
 int launch_pe_points(const Layout& L, const float* pts, int64_t M, PointBufs& pb, hipStream_t s);
 int sweep_forward(const Layout& L, const float* packed, PointBufs& pb, bool need_feat, bool need_gz_last,
                   float* feat_dense, hipStream_t s);
 int sweep_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s);
 int sweep_color(const Layout& L, const float* packed, PointBufs& pb, const float* pts, const float* nrm, int nrm_ld,
                 hipStream_t s);
+// its backward stages, in the shape of their fused counterparts (color_h2_backward, fused_ra, fused_fb)
+int layers_color_backward(const Layout& L, const float* packed, PointBufs& pb, float* packed_grad, hipStream_t s);
+int layers_ra(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s);
+int layers_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_feat, hipStream_t s);
+// ebar = d loss / d e after an SDF backward of any fp32 route (into pb.geb, free after the backward); returns pb.geb
+int launch_sdf_ebar(const Layout& L, const float* packed, PointBufs& pb, float** ebar, hipStream_t s);
+
+// ---- small utility launches (util.hip) --------------------------------------------------------------
 int launch_copy_cols(const float* src, int ld, int ncols, int64_t M, float* out, hipStream_t s);
+int launch_fill_cols(const float* src, int ncols, int64_t M, int64_t Mp, int ld, float* dst, hipStream_t s);
+int launch_grid_points(const GridGen& g, int64_t first, int64_t n, float* pts, hipStream_t s);
+int launch_scale_copy(const float* src, float scale, int64_t n, float* dst, hipStream_t s);
+int launch_absmax_rows(const float* x, int64_t n, unsigned* slot, hipStream_t s);
 int launch_range_report(const Layout& L, const float* packed, const PointBufs& pb, bool with_color, bool with_backward, float* out,
                         hipStream_t s);
-int launch_fill_cols(const float* src, int ncols, int64_t M, int64_t Mp, int ld, float* dst, hipStream_t s);
-int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad,
-                   bool fused, hipStream_t s);
-// which parts of sweep_backward run (mlp.hip); the render path is {with_color, true, with_color, true, false}
+
+// ---- the backward of every route (backward.hip) -----------------------------------------------------
+// which parts of the backward run
 struct BwdParts {
   bool albedo;         // the albedo net's backward from pb.albbar
   bool sdf;            // the SDF network's backward from pb.sbar (+ the two below)
   bool feat;           // cinb's feature columns seed FB (the feature head's adjoint)
   bool normal;         // pb.nbar is live: geb, RA and the gz/u weight-gradient pairs
-  bool color_inputs;   // (albedo only) leave all of cinb, encoding columns included, for the input adjoints
+  bool color_inputs;   // leave all of cinb, encoding columns included, for the input adjoints
+  // a render's backward; the SDF network alone (SDFNetwork.forward / .gradient); the albedo net alone (RenderingNetwork)
+  static BwdParts render(bool with_color, bool keep_color_inputs) { return {with_color, true, with_color, true, keep_color_inputs}; }
+  static BwdParts sdf_points(bool feat, bool normal) { return {false, true, feat, normal, false}; }
+  static BwdParts color_points(bool inputs) { return {true, false, false, false, inputs}; }
 };
+int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad, hipStream_t s);
 int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, const BwdParts& parts, float* packed_grad,
-                         bool fused, hipStream_t s);
+                         hipStream_t s);
+// input adjoints of the point-wise autograd calls
+int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s);
+int launch_color_input_bwd(const Layout& L, const PointBufs& pb, float* pts_bar, float* nrm_bar, hipStream_t s);
 // ---- weight-gradient jobs of a backward (dw.hip) ----
 // floats of PointBufs::dw_part (carve_points) for a backward over M points
 int64_t dw_workspace_floats(const Layout& L, int64_t M, bool with_color);
@@ -221,14 +252,7 @@ bool dw_one_wg_runs(const Layout& L, int64_t M);
 // zeroes the deterministic variant's ordered-reduction slabs (before the backward's first launch)
 int dw_zero_partials(const Layout& L, const PointBufs& pb, const BwdParts& parts, hipStream_t s);
 // queues and launches every weight-gradient job of a backward of these parts (its other launches are enqueued)
-int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, bool h2, bool color_h2, int sdfh_slabs,
-                float* packed_grad, hipStream_t s);
-// input adjoints of the point-wise autograd calls (mlp.hip)
-int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s);
-// its first half: ebar = d loss / d e (into pb.geb, free after the backward); returns pb.geb
-int launch_sdf_ebar(const Layout& L, const float* packed, PointBufs& pb, float** ebar, hipStream_t s);
-int launch_color_input_bwd(const Layout& L, const PointBufs& pb, float* pts_bar, float* nrm_bar, hipStream_t s);
-int launch_absmax_rows(const float* x, int64_t n, unsigned* slot, hipStream_t s);
+int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, int sdfh_slabs, float* packed_grad, hipStream_t s);
 int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool store_ge = false);
 int fused_ra(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, int* u_tiles = nullptr);
 int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_color, hipStream_t s);
@@ -249,8 +273,6 @@ inline bool use_reg_tile(const Layout& L, int64_t Mp) {
   if (L.variant & RNB_VARIANT_REG_TILE) return true;
   return kRegTileDefault && Mp >= 128 * 200;
 }
-int launch_grid_points(const GridGen& g, int64_t first, int64_t n, float* pts, hipStream_t s);
-int launch_scale_copy(const float* src, float scale, int64_t n, float* dst, hipStream_t s);
 
 // ---- RNB_VARIANT_X3: fp32 products as six bf16 MFMA terms (fused_common.hip.h); the split weight mirror ----
 inline bool is_x3(const Layout& L) { return (L.variant & RNB_VARIANT_X3) != 0; }
@@ -287,8 +309,7 @@ int bf16_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_
 bool bf16_color_supported(const Layout& L);
 int bf16_color_forward(const Layout& L, const float* packed, PointBufs& pb, const float* pts, hipStream_t s);
 int bf16_color_backward(const Layout& L, const float* packed, PointBufs& pb, float* packed_grad, hipStream_t s);
-int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, bool color_bf16, float* packed_grad,
-                  hipStream_t s);
+int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad, hipStream_t s);
 // floats of bf16_backward's ordered-reduction slabs over M points (deterministic variant)
 int64_t bf16_dw_floats(const Layout& L, int64_t M, bool with_color);
 

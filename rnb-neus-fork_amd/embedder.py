@@ -1,7 +1,7 @@
 """Positional encoding with the reference's interface (models/embedder.py:58-74):
 `embed_fn, out_dim = get_embedder(multires, input_dims)`.
 
-Inside the renderer the encoding is computed by the HIP kernels (csrc/mlp.hip: pe_points_kernel,
+Inside the renderer the encoding is computed by the HIP kernels (csrc/layers.hip: pe_points_kernel,
 color_input_kernel); this torch version exists for API compatibility of code that calls the closure
 directly and defines the column order gamma(x) = [x, sin(2^0 x), cos(2^0 x), ..., cos(2^{L-1} x)]."""
 import torch

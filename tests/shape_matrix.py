@@ -6,7 +6,7 @@ cannot end up testing a generic path under a fused label.
 
 Per entry:
   path      "x2h": the fused 256-wide sweeps (fused.hip, fused_bwd.hip, the x3 weight gradients) in the default
-            arithmetic; "generic": the per-layer GEMMs (mlp.hip, gemm.hip.h, dw.hip).  fused.hip fused_supported decides: hidden
+            arithmetic; "generic": the per-layer GEMMs (layers.hip, gemm.hip.h, dw.hip).  fused.hip fused_supported decides: hidden
             width 256, pe <= FEP = 40, feature width 225..256 (a 256-row feature head, or none).
   bf16      RNB_VARIANT_BF16 accepts the shape: a fused shape with Ep = 64 and no skip connection at layer 1
             (make_layout rejects it otherwise).
