@@ -249,7 +249,11 @@ int rnb_sdf_grid(const rnb_model_desc* desc, const float* packed, const rnb_grid
  *   (models/renderer.py:557-608 == :829-880 == :933-984): z = near + (far-near)*linspace(0,1,n_samples)
  *   (+ (t_rand-0.5)*2/n_samples when t_rand != NULL), coarse SDF, up_sample_steps x (up_sample,
  *   cat_z_vals incl. SDF evaluation of the new points).  z_vals_out [B, n_samples+n_importance].
- *   `t_rand` [B] is the torch.rand([B,1]) draw of renderer.py:572, made by the caller. */
+ *   `t_rand` [B] is the torch.rand([B,1]) draw of renderer.py:572, made by the caller.
+ * Limits (one wave64 per ray, the ray's depths in LDS): n >= 2, 1 <= n_new <= 64, n + n_new <= 512 per step; for a
+ *   descriptor: n_samples >= 2 and, with n_importance > 0, n_importance a multiple of up_sample_steps,
+ *   n_importance / up_sample_steps <= min(n_samples, 64) and n_samples + n_importance <= 512.  A descriptor outside
+ *   them is refused with RNB_E_INVALID by rnb_sample_workspace_bytes, and by rnb_sample_rays before its first launch. */
 int rnb_up_sample_step(const float* rays_o, const float* rays_d, const float* z_in, const float* sdf_in,
                        int64_t B, int32_t n, int32_t n_new, float inv_s, float* new_z, int32_t* inds,
                        float* z_out, int32_t* sort_index, rnb_stream_t stream);
@@ -322,6 +326,9 @@ typedef struct rnb_render_grads { /* d loss / d <output>; NULL = zero */
   const float* gradient_error;
 } rnb_render_grads;
 
+/* Limits: 1 <= S <= 512 samples per ray, n_lights <= 8 (RNB_MODE_MVPS).  rnb_render_workspace_bytes refuses a larger S,
+ * rnb_render_fwd / rnb_render_bwd / rnb_render_bwd_inputs refuse a larger S or light count (RNB_E_INVALID) before they
+ * launch anything. */
 int rnb_render_workspace_bytes(const rnb_model_desc* desc, int64_t B, int32_t S, int32_t flags,
                                int64_t* bytes);
 int rnb_render_fwd(const rnb_model_desc* desc, const float* packed, const rnb_render_args* args,

@@ -517,6 +517,22 @@ def flags_case():
              weights_from="full_main_sharp", grad_stride=7)
 
 
+def odd_case():
+    """Odd sample counts: the tiny networks in the state of tiny_main_sharp (read back from its .npz) at 17 + 15 / 3 —
+    torch.linspace over 17 depths (its two halves differ), three up-sampling steps of n_new = 5 on n = 17, 22, 27
+    (linspace over 5 quantiles, searchsorted and sort at odd sizes), S = 32.  `render_rnb`, 8 rays.  Written on its own
+    (`python oracle/gen_golden.py odd`): no other fixture is regenerated."""
+    import dataclasses
+    mc = tiny_conf()
+    mc = dataclasses.replace(mc, render=dataclasses.replace(mc.render, n_samples=17, n_importance=15, up_sample_steps=3))
+    sdf, dev, col, ren = build_reference(mc, seed=0)
+    load_fixture_state("tiny_main_sharp", sdf, dev, col)
+    b = O.synthetic_batch(8, seed=8, step=7, warmup=False)
+    out = run_case("tiny_main_odd_17x15", mc, sdf, dev, col, ren, b, api="render_rnb", cos_anneal_ratio=0.3,
+                   weights_from="tiny_main_sharp")
+    print(f"  tiny_main_odd_17x15: weight_sum mean {float(out['weight_sum'].detach().mean()):.3f}")
+
+
 def grid_case():
     """The SDF grid of validate_mesh from the REFERENCE's own `extract_fields` (models/renderer.py:10-25, called with
     query_func = -sdf_network.sdf as at :1219-1224): tiny networks (seed 0 state of tiny_warmup_geo), asymmetric bounds,
@@ -662,13 +678,15 @@ def main():
     b512_case()
     # ---- (iv) the non-default flags on the full-size networks ----------------------------------------
     flags_case()
+    # ---- (v) odd sample counts on the tiny networks ---------------------------------------------------
+    odd_case()
 
 
-if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] in ("raygen", "checkpoint", "convergence", "b512", "grid", "flags"):
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] in ("raygen", "checkpoint", "convergence", "b512", "grid", "flags", "odd"):
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     {"raygen": raygen_case, "checkpoint": checkpoint_case, "convergence": convergence_case,
-     "b512": b512_case, "grid": grid_case, "flags": flags_case}[sys.argv[1]]()
+     "b512": b512_case, "grid": grid_case, "flags": flags_case, "odd": odd_case}[sys.argv[1]]()
     sys.exit(0)
 
 if __name__ == "__main__":

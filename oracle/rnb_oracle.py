@@ -223,6 +223,7 @@ def sample_pdf_det(bins, weights, n_new, trace: Optional[dict] = None):
     t = (u - cdf_lo) / denom
     if trace is not None:
         trace["inds"] = inds
+        trace["cdf"] = cdf
     return bin_lo + t * (bin_hi - bin_lo)
 
 
@@ -310,7 +311,10 @@ def sample_rays(p: Params, mc: ModelConf, rays_o, rays_d, near, far, t_rand, per
 def _core_common(p: Params, mc: ModelConf, rays_o, rays_d, z_vals, sample_dist, cos_anneal_ratio):
     B, S = z_vals.shape
     dists = z_vals[..., 1:] - z_vals[..., :-1]
-    dists = torch.cat([dists, torch.full_like(dists[..., :1], sample_dist)], -1)
+    # (shaped like z_vals[..., :1], not dists[..., :1] as renderer.py:210 writes it: the same tensor for S >= 2, and S = 1 —
+    # where the reference's expand gives an empty column and then fails — is one sample of width sample_dist, as the
+    # device's fine_points_kernel defines it)
+    dists = torch.cat([dists, torch.full_like(z_vals[..., :1], sample_dist)], -1)
     mid_z = z_vals + dists * 0.5
     pts = (rays_o[:, None, :] + rays_d[:, None, :] * mid_z[..., :, None]).reshape(-1, 3)
     dirs = rays_d[:, None, :].expand(B, S, 3).reshape(-1, 3)

@@ -459,6 +459,14 @@ static int check_sampling_desc(const rnb_model_desc* d) {
                d->n_importance, d->up_sample_steps);
     if (d->n_importance / d->up_sample_steps > d->n_samples)
       RNB_FAIL(RNB_E_INVALID, "n_importance/up_sample_steps must not exceed n_samples");
+    // the limits of up_sample_kernel (launch_up_sample_step checks them again per step): refused here, before the
+    // workspace query answers and before rnb_sample_rays launches the coarse forward
+    if (d->n_importance / d->up_sample_steps > kMaxNew)
+      RNB_FAIL(RNB_E_INVALID, "n_importance/up_sample_steps = %d new depths per step > %d (kMaxNew)",
+               d->n_importance / d->up_sample_steps, kMaxNew);
+    if (d->n_samples + d->n_importance > kMaxZ)
+      RNB_FAIL(RNB_E_INVALID, "n_samples + n_importance = %d depths per ray > %d (kMaxZ)",
+               d->n_samples + d->n_importance, kMaxZ);
   }
   return RNB_OK;
 }
@@ -590,6 +598,7 @@ RNB_API int rnb_render_workspace_bytes(const rnb_model_desc* desc, int64_t B, in
   Layout L;
   RNB_TRY(make_layout(desc, &L));
   if (B < 0 || S < 1) RNB_FAIL(RNB_E_INVALID, "bad B/S");
+  if (S > kMaxS) RNB_FAIL(RNB_E_INVALID, "samples per ray %d > %d (kMaxS)", S, kMaxS);
   RNB_TRY(check_input_grads_flag(L, flags));
   Carver c(nullptr, 0);
   RenderBufs rb;
@@ -604,8 +613,12 @@ static int render_setup(const rnb_model_desc* desc, const rnb_render_args* a, vo
   RNB_REQUIRE(a, "args");
   RNB_REQUIRE(ws, "workspace");
   if (a->B <= 0 || a->S < 1) RNB_FAIL(RNB_E_INVALID, "bad B/S");
+  // the composite kernels' limits (launch_composite_fwd checks them again): refused before carve_render and any launch
+  if (a->S > kMaxS) RNB_FAIL(RNB_E_INVALID, "samples per ray %d > %d (kMaxS)", a->S, kMaxS);
   const bool mvps = (a->flags & RNB_MODE_MVPS) != 0;
   if (mvps && (a->n_lights < 1 || !a->lights_dir)) RNB_FAIL(RNB_E_INVALID, "MVPS mode needs lights");
+  if (mvps && a->n_lights > kMaxRenderLights)
+    RNB_FAIL(RNB_E_INVALID, "n_lights %d > %d (kMaxRenderLights)", a->n_lights, kMaxRenderLights);
   if (L->F <= 0) RNB_FAIL(RNB_E_INVALID, "model has no feature head");
   RNB_REQUIRE(a->rays_o, "rays_o");
   RNB_REQUIRE(a->rays_d, "rays_d");

@@ -9,7 +9,6 @@
 
 namespace rnb {
 
-constexpr int kMaxS = 512;
 constexpr int kMaxL = kMaxRenderLights;
 
 __device__ inline float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }

@@ -228,13 +228,21 @@ struct DwBatch {
       g.job[b] = t;
     }
     int end = 0;
+    int64_t one_each = 0;   // floats of ONE split of every job not yet placed
+    for (int q = 0; q < g.njobs; ++q) one_each += (int64_t)g.job[q].N * g.job[q].K + g.job[q].N;
     for (int q = 0; q < g.njobs; ++q) {
       DwJob& j = g.job[q];
       int splits, rows;
       dw_staged_plan(M, x3_job_units(j.npairs, j.K), total_pairs, &splits, &rows);
       {   // never more slabs than the workspace holds (a group smaller than the one the workspace was sized for)
         const int64_t per_split = (int64_t)j.N * j.K + j.N;
-        const int64_t room = slab != nullptr ? slab_left / per_split / (g.njobs - q) : 0;
+        one_each -= per_split;
+        int64_t room = slab != nullptr ? slab_left / per_split / (g.njobs - q) : 0;
+        // The equal share above counts every remaining job at THIS job's slab size.  With 32 or 64 points every job has one
+        // split and the workspace (dw_sizes) holds exactly one slab of each: a 256-column job followed by 64-column ones
+        // then computed a share of zero and the backward was refused.  What is left after one split of every later job
+        // is this job's to take.
+        if (room < 1 && slab != nullptr) room = (slab_left - one_each) / per_split;
         if (room < 1) RNB_FAIL(RNB_E_WORKSPACE, "weight-gradient slab workspace exhausted");
         if (splits > room) {
           splits = (int)room;

@@ -382,6 +382,9 @@ int launch_fine_points(const float* rays_o, const float* rays_d, const float* z,
                        float* pts, float* dists, unsigned* smax_to_zero, hipStream_t s);
 int launch_composite_fwd(const CompArgs& a, hipStream_t s);
 int launch_composite_bwd(const CompBwdArgs& g, hipStream_t s);
+// limits of the per-ray kernels, defined once: composite.hip sizes its LDS rows and light registers by them, and api.hip
+// refuses a larger S or light count in the workspace query and in render_setup, before anything is launched
+constexpr int kMaxS = 512;               // samples per ray of the fine pass
 constexpr int kMaxRenderLights = 8;
 // per-ray reduction of the point adjoints pbar = d loss / d pts (rnb_render_bwd_inputs): pbar is formed per sample from
 // the SDF network's encoding adjoint ebar, the Hessian term (d sdf / d e with the total normal adjoint) and the albedo
@@ -412,6 +415,9 @@ int launch_ray_input_adjoint(const RayAdjArgs& r, hipStream_t s);
 int launch_sum_over_rays(const float* part, int64_t B, int nvec, float* out, hipStream_t s);
 
 // ---- sampling (sampling.hip) ---------------------------------------------------------------------
+// limits of up_sample_kernel (its LDS rows; one lane per new depth), also checked up front by api.hip check_sampling_desc
+constexpr int kMaxZ = 512;    // n + n_new upper bound
+constexpr int kMaxNew = 64;
 int launch_z_init(const float* rays_o, const float* rays_d, const float* near, const float* far,
                   const float* t_rand, int64_t B, int n, float* z, float* pts, hipStream_t s);
 int launch_gather_sdf(const float* sdf_old, const float* sdf_new, const int32_t* index, int64_t B, int n, int n_new,

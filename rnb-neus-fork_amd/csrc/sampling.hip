@@ -14,9 +14,6 @@
 
 namespace rnb {
 
-constexpr int kMaxZ = 512;    // n + n_new upper bound
-constexpr int kMaxNew = 64;
-
 
 __device__ inline float sigmoidf_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
 

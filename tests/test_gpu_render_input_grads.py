@@ -15,6 +15,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import rnb_oracle as O
+from tests.ray_matrix import Z_GRAD_S
 from tests.shape_matrix import BY_NAME, live_params, step_batch
 from tests.test_gpu_parity import _grad_bound
 
@@ -90,28 +91,34 @@ def _native(ren, case, b, want, variant=None):
     for q in list(ren.color_network.parameters()) + list(ren.deviation_network.parameters()):
         q.grad = None
     x = {k: v.to(_dev()).detach().requires_grad_(k in want) for k, v in b.items()}
+    zv = x.get("z_vals")     # explicit depths (an input like the others: it may require grad), else the device samples
     if case == "render":
         out = ren.render(x["rays_o"], x["rays_d"], x["near"], x["far"], background_rgb=x["bg"], cos_anneal_ratio=0.5,
-                         t_rand=x["t_rand"])
+                         t_rand=x["t_rand"], z_vals=zv)
     else:
         fn = ren.render_rnb_warmup if case == "warmup" else ren.render_rnb
-        out = fn(x["rays_o"], x["rays_d"], x["near"], x["far"], x["lights_dir"], cos_anneal_ratio=0.5, t_rand=x["t_rand"])
+        out = fn(x["rays_o"], x["rays_d"], x["near"], x["far"], x["lights_dir"], cos_anneal_ratio=0.5, t_rand=x["t_rand"],
+                 z_vals=zv)
     _loss(out, x, case != "render").backward()
     torch.cuda.synchronize()
     return out, {k: x[k].grad for k in want}
 
 
-def _oracle(p, mc, case, b, want, z, dt):
+def _oracle(p, mc, case, b, want, z, dt, outs=None):
+    """`z`: the depths the device sampled, or None with explicit depths in b["z_vals"]; `outs`: receives the outputs"""
     q = {k: v.to(dt).detach().requires_grad_(True) for k, v in p.items()}
     x = {k: v.to(dt).detach().requires_grad_(k in want) for k, v in b.items()}
+    zv = x["z_vals"] if "z_vals" in x else (None if z is None else z.to(dt))
     with torch.enable_grad():
         if case == "render":
             out = O.render(q, mc, x["rays_o"], x["rays_d"], x["near"], x["far"], background_rgb=x["bg"],
-                           cos_anneal_ratio=0.5, z_vals=None if z is None else z.to(dt), t_rand=x["t_rand"])
+                           cos_anneal_ratio=0.5, z_vals=zv, t_rand=x["t_rand"])
         else:
             out = O.render_rnb(q, mc, x["rays_o"], x["rays_d"], x["near"], x["far"], x["lights_dir"], cos_anneal_ratio=0.5,
-                               warmup=case == "warmup", z_vals=None if z is None else z.to(dt), t_rand=x["t_rand"])
+                               warmup=case == "warmup", z_vals=zv, t_rand=x["t_rand"])
         _loss(out, x, case != "render").backward()
+    if outs is not None:
+        outs.update({k: v.detach() for k, v in out.items()})
     return {k: x[k].grad for k in want}
 
 
@@ -178,6 +185,79 @@ def test_near_far_with_no_importance_samples(R, graph_normal):
     torch.set_num_threads(16)
     _check(mine, oracle(torch.float64), oracle(torch.float32), "n_importance0")
     assert set(mine) == set(want)
+
+
+# ------------------------------------------------------------------------------------------------------------ case 2b
+# Explicit depths that require grad (renderer.py: "z_vals given"): ray_input_adjoint_kernel's z_bar stencil,
+#   z_bar_s = mbar_s - [s < S-1] Dbar_s + [s > 0] Dbar_{s-1},
+# walks the ray in 64-sample chunks and hands Dbar of a chunk's last sample to the next chunk in carry_D.  S = 2 and 63 stay
+# inside one chunk; 65, 129 and 190 carry once or twice into a ragged last chunk (tests/ray_matrix.py Z_GRAD_S).
+BZ = 32
+
+
+def _explicit_depths(batch, S, seed=0):
+    """sorted non-uniform depths [B, S] between near and far"""
+    gen = torch.Generator().manual_seed(7919 * S + seed)
+    u = torch.sort(torch.rand(batch["near"].shape[0], S, generator=gen), dim=-1).values
+    return (batch["near"] + (batch["far"] - batch["near"]) * u).contiguous()
+
+
+def _check_chunk_boundaries(mine, g64, g32, S, tag):
+    """the samples on either side of every 64-sample chunk boundary, as a tensor of their own: what carry_D feeds"""
+    cols = [c for j0 in range(64, S, 64) for c in (j0 - 1, j0)]
+    if cols:
+        _check({"z_vals": mine["z_vals"][:, cols]}, {"z_vals": g64["z_vals"][:, cols]}, {"z_vals": g32["z_vals"][:, cols]},
+               f"{tag} columns {cols}")
+
+
+@pytest.mark.parametrize("case", ["render", "rnb"])
+@pytest.mark.parametrize("S", Z_GRAD_S)
+def test_explicit_depth_gradients_against_fp64(R, graph_normal, S, case):
+    mc, p, sdf, devn, col, ren = _build(R, "default_64x64")
+    b, want = _case_inputs(case, step_batch(BZ))
+    b["z_vals"] = _explicit_depths(b, S)
+    want = want + ("z_vals",)
+    out, mine = _native(ren, case, b, want)
+    assert tuple(mine["z_vals"].shape) == (BZ, S)
+    assert torch.equal(ren.last_z_vals.cpu(), b["z_vals"]), "the render must run at the depths it was given"
+    torch.set_num_threads(16)
+    g64 = _oracle(p, mc, case, b, want, None, torch.float64)
+    g32 = _oracle(p, mc, case, b, want, None, torch.float32)
+    _check(mine, g64, g32, f"z_vals S={S}/{case}")
+    _check_chunk_boundaries(mine, g64, g32, S, f"z_vals S={S}/{case}")
+
+
+@pytest.mark.parametrize("per_ray", [False, True], ids=["shared", "per_ray"])
+@pytest.mark.parametrize("L", [1, 2, 5, 8])
+def test_light_counts_at_a_carry_and_a_ragged_chunk(R, graph_normal, L, per_ray):
+    """1, 2, 5 and kMaxRenderLights = 8 lights at S = 129 explicit depths, shared [L,1,1,3] and per ray [L,B,1,3]:
+    lights_dir.grad (with rays and z_vals) by _grad_bound, color_fine per light by the output rule of test_gpu_parity.py"""
+    from tests.test_gpu_parity import FLOOR_OUT, K_OUT
+    S = 129
+    mc, p, sdf, devn, col, ren = _build(R, "default_64x64")
+    b = dict(O.synthetic_batch(BZ, n_lights=L, seed=11, step=1, warmup=False))
+    if not per_ray:
+        gen = torch.Generator().manual_seed(40 + L)
+        lt = torch.randn(L, 1, 1, 3, generator=gen)
+        b["lights_dir"] = (lt / lt.norm(dim=-1, keepdim=True)).contiguous()
+    b["z_vals"] = _explicit_depths(b, S)
+    want = ("rays_o", "rays_d", "lights_dir", "z_vals")
+    out, mine = _native(ren, "rnb", b, want)
+    assert tuple(out["color_fine"].shape) == (L, BZ, 3) and tuple(mine["lights_dir"].shape) == tuple(b["lights_dir"].shape)
+    torch.set_num_threads(16)
+    o64, o32 = {}, {}
+    g64 = _oracle(p, mc, "rnb", b, want, None, torch.float64, o64)
+    g32 = _oracle(p, mc, "rnb", b, want, None, torch.float32, o32)
+    tag = f"{L} lights {'per ray' if per_ray else 'shared'} S={S}"
+    _check(mine, g64, g32, tag)
+    _check_chunk_boundaries(mine, g64, g32, S, tag)
+    for l in range(L):
+        r64 = o64["color_fine"][l]
+        e_hip = float((out["color_fine"][l].detach().cpu().double() - r64).abs().max())
+        e_ref = float((o32["color_fine"][l].double() - r64).abs().max())
+        bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(r64.abs().max()))
+        assert float(r64.abs().max()) > 1e-3, f"{tag}: light {l} renders nothing"
+        assert e_hip <= bound, f"{tag}: color_fine[{l}]: |hip - fp64| {e_hip:.3e} > {bound:.3e} (fp32 oracle: {e_ref:.3e})"
 
 
 # ------------------------------------------------------------------------------------------------------------ cases 3-5
