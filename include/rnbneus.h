@@ -238,6 +238,55 @@ int rnb_sdf_grid_workspace_bytes(const rnb_model_desc* desc, const rnb_grid_desc
 int rnb_sdf_grid(const rnb_model_desc* desc, const float* packed, const rnb_grid_desc* grid, float* volume,
                  void* ws, size_t ws_bytes, rnb_stream_t stream);
 
+/* ---- sparse SDF grid: only the bricks the iso-surface may pass through are evaluated ------------------
+ * The grid is rnb_sdf_grid's (same samples, same index arithmetic, the whole grid: x_begin = 0, x_end = resolution);
+ * "inside" is marching cubes' notion, value <= threshold, NaN = outside.
+ *   brick   : a cube of `brick`^3 cells, i.e. the (brick+1)^3 samples [b*brick, min((b+1)*brick, res-1)] per axis;
+ *             neighbours share their face samples, the last brick per axis may be short; nb = ceil((res-1)/brick) per axis.
+ *   lattice : the brick corners, the grid samples min(k*brick, res-1), k = 0..nb — evaluated by the same kernel as the
+ *             dense grid, so a lattice value is the very number rnb_sdf_grid writes there.
+ *   seeds   : bricks whose 8 corners are not all inside / all outside, or have a non-finite corner, or have a corner with
+ *             |value - threshold| < margin * |out_scale| * (half the brick's diagonal in world units).  `margin` is the
+ *             Lipschitz constant of the SDF the caller assumes (1 = exact for a true distance field: every point of a cube
+ *             is within half a diagonal of a corner; 0 = sign changes only).
+ *   growth  : every face of an evaluated brick whose samples are not all inside / all outside lists the brick behind it;
+ *             rounds repeat until one lists nothing (at most 3*nb rounds).
+ *   volume  : [res,res,res] fp32, dense.  Samples of listed bricks hold the evaluated values, BIT-EQUAL to rnb_sdf_grid's
+ *             (same coordinates, same kernel family, rows independent of their tile mates; a tile of the default arithmetic
+ *             whose activations outgrow the fixed fp16 scale is rescaled as a whole, which is the one case where tile mates
+ *             matter).  Every other sample holds the trilinear interpolant of its brick's 8 lattice values clamped to their
+ *             min / max: not an SDF value, but on the corners' side of the threshold and continuous across unlisted faces,
+ *             so marching cubes on the volume creates no crossing outside the listed bricks.
+ * Guarantee: every iso-surface component that passes through at least one seed brick is reproduced exactly as the dense
+ * grid gives it.  A component lying wholly inside bricks whose corners have one sign and are farther than the margin from
+ * the threshold is MISSED: raise `margin`, or use rnb_sdf_grid.
+ *
+ * Calling sequence (no allocation, no synchronisation, the given stream only; the host reads the 8-byte device counter
+ * n_listed between calls and sizes the next call from it):
+ *   _seed   evaluates the lattice into the workspace, lists the seeds, writes their number to *n_listed;
+ *   _round  evaluates the listed bricks [first, first+count) into `volume` (count <= the value read), then grows:
+ *           *n_listed becomes the new length of the list; repeat with the new tail until nothing was added;
+ *   _finish fills every sample outside the listed bricks; brick_mask (device uint8 [nb,nb,nb], or NULL) gets 1 for listed.
+ * The workspace holds the lattice, one state byte per brick and the list (O(nb^3)), plus the per-point buffers of one
+ * 2^20-point chunk for shapes on the per-layer route; the same buffer must be passed to all calls of one extraction.
+ * RNB_E_INVALID before any launch: an x-slab, brick not in {4, 8, 16, 32}, margin < 0 or NaN, resolution < 2, more than
+ * 2^31 - 1 bricks.  RNB_E_WORKSPACE before any launch: ws_bytes below the query's answer. */
+typedef struct rnb_sparse_grid_desc {
+  int32_t brick;
+  float threshold;
+  float margin;
+} rnb_sparse_grid_desc;
+int rnb_sdf_grid_sparse_workspace_bytes(const rnb_model_desc* desc, const rnb_grid_desc* grid,
+                                        const rnb_sparse_grid_desc* sparse, int64_t* bytes);
+int rnb_sdf_grid_sparse_seed(const rnb_model_desc* desc, const float* packed, const rnb_grid_desc* grid,
+                             const rnb_sparse_grid_desc* sparse, void* ws, size_t ws_bytes, int64_t* n_listed,
+                             rnb_stream_t stream);
+int rnb_sdf_grid_sparse_round(const rnb_model_desc* desc, const float* packed, const rnb_grid_desc* grid,
+                              const rnb_sparse_grid_desc* sparse, float* volume, void* ws, size_t ws_bytes, int64_t first,
+                              int64_t count, int64_t* n_listed, rnb_stream_t stream);
+int rnb_sdf_grid_sparse_finish(const rnb_model_desc* desc, const rnb_grid_desc* grid, const rnb_sparse_grid_desc* sparse,
+                               float* volume, void* ws, size_t ws_bytes, uint8_t* brick_mask, rnb_stream_t stream);
+
 /* ---- hierarchical sampling ---------------------------------------------------------------------
  * rnb_up_sample_step: one iteration of the loop at models/renderer.py:970-982 WITHOUT the network
  *   call: NeuSRenderer.up_sample (:132-176) + sample_pdf(det=True) (:39-69) + the concat/sort half of

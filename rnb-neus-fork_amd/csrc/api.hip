@@ -1,4 +1,5 @@
 // C-ABI entry points of librnbneus_hip.so (declared in include/rnbneus.h).
+#include <math.h>
 #include <stdlib.h>
 
 #include "rnb_internal.h"
@@ -345,7 +346,8 @@ static int check_grid(const rnb_grid_desc* gd, int64_t* n_points) {
 
 static GridGen grid_gen_of(const rnb_grid_desc* gd) {
   GridGen g;
-  g.on = 1;
+  memset(&g, 0, sizeof(g));
+  g.on = GRID_DENSE;
   g.res = gd->resolution;
   g.x_begin = gd->x_begin;
   for (int d = 0; d < 3; ++d) { g.bmin[d] = gd->bound_min[d]; g.bmax[d] = gd->bound_max[d]; }
@@ -402,6 +404,161 @@ RNB_API int rnb_sdf_grid(const rnb_model_desc* desc, const float* packed, const 
     RNB_TRY(forward_points(L, packed, pts, m, pb, false, false, false, nullptr, s));
     RNB_TRY(launch_scale_copy(pb.sdf, gg.out_scale, m, volume + first, s));
   }
+  return RNB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// sparse SDF grid: the bricks near the surface only (kernels: sparse_grid.hip + the brick mode of the forward sweeps)
+// ---------------------------------------------------------------------------------------------------
+constexpr int64_t kSparseRowsPerLaunch = (int64_t)1 << 28;   // rows of one brick-mode sweep (its block count fits 32 bits)
+
+struct SparseSetup {
+  Layout L;
+  GridGen gg;          // the dense grid's generator + brick geometry (on is set per sweep)
+  SparseGeom sg;
+  float* lattice;      // [nl^3] values at the brick corners
+  uint32_t* state;     // [ceil(nb^3 / 4)] one byte per brick
+  int32_t* list;       // [nb^3] listed bricks
+  float* pts;          // per-layer route: points of one chunk, and the chunk's buffers
+  PointBufs pb;
+};
+
+// checks + workspace carving shared by the four entry points (ws == nullptr: sizing only)
+static int sparse_setup(const rnb_model_desc* desc, const rnb_grid_desc* grid, const rnb_sparse_grid_desc* sp, void* ws,
+                        size_t ws_bytes, SparseSetup* S, size_t* need) {
+  RNB_REQUIRE(sp, "sparse");
+  RNB_TRY(make_layout(desc, &S->L));
+  int64_t n;
+  RNB_TRY(check_grid(grid, &n));
+  const int res = grid->resolution, bs = sp->brick;
+  if (res < 2) RNB_FAIL(RNB_E_INVALID, "sparse grid: resolution %d has no cells", res);
+  if (grid->x_begin != 0 || grid->x_end != res)
+    RNB_FAIL(RNB_E_INVALID, "sparse grid: x-slab [%d, %d) is not the whole %d grid (use rnb_sdf_grid for slabs)", grid->x_begin,
+             grid->x_end, res);
+  if (bs != 4 && bs != 8 && bs != 16 && bs != 32) RNB_FAIL(RNB_E_INVALID, "sparse grid: brick must be 4, 8, 16 or 32 (%d)", bs);
+  if (!(sp->margin >= 0.f)) RNB_FAIL(RNB_E_INVALID, "sparse grid: margin must be >= 0 (%g)", (double)sp->margin);
+  if (sp->threshold != sp->threshold) RNB_FAIL(RNB_E_INVALID, "sparse grid: threshold is NaN");
+  const int nb = (res - 1 + bs - 1) / bs, nl = nb + 1;
+  const int64_t nbr = (int64_t)nb * nb * nb;
+  if (nbr > INT32_MAX) RNB_FAIL(RNB_E_INVALID, "sparse grid: %lld bricks do not fit a 32-bit id", (long long)nbr);
+  S->gg = grid_gen_of(grid);
+  S->gg.bs = bs;
+  S->gg.nb = nb;
+  S->gg.rows_per_brick = ((bs + 1) * (bs + 1) * (bs + 1) + 63) / 64 * 64;
+  S->gg.family_rows = pad_rows(n);
+  double diag2 = 0;
+  for (int d = 0; d < 3; ++d) {
+    const double edge = ((double)grid->bound_max[d] - (double)grid->bound_min[d]) / (res - 1) * bs;
+    diag2 += edge * edge;
+  }
+  S->sg.res = res; S->sg.bs = bs; S->sg.nb = nb; S->sg.nl = nl;
+  S->sg.thr = sp->threshold;
+  // (the volume holds out_scale * sdf: a Lipschitz constant `margin` of the SDF is margin * |out_scale| of the values)
+  S->sg.seed_dist = (float)((double)sp->margin * fabs((double)grid->out_scale) * 0.5 * sqrt(diag2));
+  Carver c(ws, ws_bytes);
+  S->lattice = c.take<float>((int64_t)nl * nl * nl);
+  S->state = c.take<uint32_t>((nbr + 3) / 4);
+  S->list = c.take<int32_t>(nbr);
+  S->pts = nullptr;
+  if (S->L.route.sdf == SDF_LAYERS) {   // the fused sweeps keep everything in LDS
+    S->pts = c.take<float>(kGridChunk * 3);
+    carve_points(S->L, c, kGridChunk, PM_SDF_ONLY, &S->pb);
+  }
+  *need = c.off;
+  if (ws == nullptr) return RNB_OK;
+  if (!c.ok) RNB_FAIL(RNB_E_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
+  return RNB_OK;
+}
+
+// rows [0, M) of the grid generator g (brick list or lattice) through the model's forward route, values to `out`
+static int sparse_eval(SparseSetup& S, const float* packed, const GridGen& g, int64_t M, float* out, hipStream_t s) {
+  if (S.L.route.sdf != SDF_LAYERS) {
+    PointBufs pb;
+    memset(&pb, 0, sizeof(pb));
+    pb.M = M;
+    pb.Mp = pad_rows(M);
+    pb.sdf = out;
+    if (S.L.route.sdf == SDF_BF16) return bf16_forward(S.L, packed, nullptr, M, pb, false, false, s, &g);
+    return fused_forward(S.L, packed, nullptr, M, pb, false, false, false, s, &g);
+  }
+  for (int64_t first = 0; first < M; first += kGridChunk) {
+    const int64_t m = M - first < kGridChunk ? M - first : kGridChunk;
+    PointBufs pb = S.pb;
+    pb.M = m;
+    pb.Mp = pad_rows(m);
+    RNB_TRY(launch_grid_points(g, first, m, S.pts, s));
+    RNB_TRY(forward_points(S.L, packed, S.pts, m, pb, false, false, false, nullptr, s));
+    RNB_TRY(launch_grid_scatter(g, pb.sdf, first, m, out, s));
+  }
+  return RNB_OK;
+}
+
+RNB_API int rnb_sdf_grid_sparse_workspace_bytes(const rnb_model_desc* desc, const rnb_grid_desc* grid,
+                                                const rnb_sparse_grid_desc* sparse, int64_t* bytes) {
+  RNB_REQUIRE(bytes, "bytes");
+  SparseSetup S;
+  size_t need = 0;
+  RNB_TRY(sparse_setup(desc, grid, sparse, nullptr, 0, &S, &need));
+  *bytes = (int64_t)need;
+  return RNB_OK;
+}
+
+RNB_API int rnb_sdf_grid_sparse_seed(const rnb_model_desc* desc, const float* packed, const rnb_grid_desc* grid,
+                                     const rnb_sparse_grid_desc* sparse, void* ws, size_t ws_bytes, int64_t* n_listed,
+                                     rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(ws, "workspace");
+  RNB_REQUIRE(n_listed, "n_listed");
+  hipStream_t s = (hipStream_t)stream;
+  SparseSetup S;
+  size_t need = 0;
+  RNB_TRY(sparse_setup(desc, grid, sparse, ws, ws_bytes, &S, &need));
+  RNB_CHECK_HIP(hipMemsetAsync(n_listed, 0, sizeof(int64_t), s));
+  GridGen g = S.gg;
+  g.on = GRID_LATTICE;
+  RNB_TRY(sparse_eval(S, packed, g, (int64_t)S.sg.nl * S.sg.nl * S.sg.nl, S.lattice, s));
+  return launch_sparse_classify(S.sg, S.lattice, S.state, S.list, n_listed, s);
+}
+
+RNB_API int rnb_sdf_grid_sparse_round(const rnb_model_desc* desc, const float* packed, const rnb_grid_desc* grid,
+                                      const rnb_sparse_grid_desc* sparse, float* volume, void* ws, size_t ws_bytes,
+                                      int64_t first, int64_t count, int64_t* n_listed, rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(volume, "volume");
+  RNB_REQUIRE(ws, "workspace");
+  RNB_REQUIRE(n_listed, "n_listed");
+  hipStream_t s = (hipStream_t)stream;
+  SparseSetup S;
+  size_t need = 0;
+  RNB_TRY(sparse_setup(desc, grid, sparse, ws, ws_bytes, &S, &need));
+  const int64_t nbr = (int64_t)S.sg.nb * S.sg.nb * S.sg.nb;
+  if (first < 0 || count < 0 || first + count > nbr)
+    RNB_FAIL(RNB_E_INVALID, "sparse grid: bricks [%lld, %lld) of a list of at most %lld", (long long)first,
+             (long long)(first + count), (long long)nbr);
+  if (count == 0) return RNB_OK;
+  GridGen g = S.gg;
+  g.on = GRID_BRICKS;
+  const int64_t per = kSparseRowsPerLaunch / g.rows_per_brick;   // bricks per sweep
+  for (int64_t at = 0; at < count; at += per) {
+    const int64_t nbk = count - at < per ? count - at : per;
+    g.bricks = S.list + first + at;
+    RNB_TRY(sparse_eval(S, packed, g, nbk * g.rows_per_brick, volume, s));
+  }
+  return launch_sparse_grow(S.sg, volume, first, count, S.state, S.list, n_listed, s);
+}
+
+RNB_API int rnb_sdf_grid_sparse_finish(const rnb_model_desc* desc, const rnb_grid_desc* grid,
+                                       const rnb_sparse_grid_desc* sparse, float* volume, void* ws, size_t ws_bytes,
+                                       uint8_t* brick_mask, rnb_stream_t stream) {
+  RNB_REQUIRE(volume, "volume");
+  RNB_REQUIRE(ws, "workspace");
+  hipStream_t s = (hipStream_t)stream;
+  SparseSetup S;
+  size_t need = 0;
+  RNB_TRY(sparse_setup(desc, grid, sparse, ws, ws_bytes, &S, &need));
+  RNB_TRY(launch_sparse_fill(S.sg, S.lattice, S.state, volume, s));
+  if (brick_mask)
+    RNB_CHECK_HIP(hipMemcpyAsync(brick_mask, S.state, (size_t)S.sg.nb * S.sg.nb * S.sg.nb, hipMemcpyDeviceToDevice, s));
   return RNB_OK;
 }
 

@@ -280,16 +280,14 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_forward_ker
     const int64_t row = row0 + p;
     float x[3] = {0.f, 0.f, 0.f};
     if (row < g.M) {
-      if (g.grid.on) {
+      if (g.grid.on) {   // (dense slab, brick list or brick-corner lattice: grid_locate)
         const int res = g.grid.res;
-        int64_t r = row;
-        const int iz = (int)(r % res);
-        r /= res;
-        const int iy = (int)(r % res);
-        const int ix = (int)(r / res) + g.grid.x_begin;
-        x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
-        x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
-        x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
+        int ix, iy, iz;
+        if (grid_locate(g.grid, row, g.M, ix, iy, iz) >= 0) {
+          x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
+          x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
+          x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
+        }
       } else {
         x[0] = g.pts[row * 3] * g.scale;
         x[1] = g.pts[row * 3 + 1] * g.scale;
@@ -398,7 +396,10 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_forward_ker
       if (lane == 0) {
         const float v = (s + bs) / g.scale;
         if (!g.grid.on) g.sdf[row0 + row] = v;
-        else if (row0 + row < g.M) g.sdf[row0 + row] = v * g.grid.out_scale;
+        else {   // (brick mode scatters; shared face samples get the same bits from both bricks, see fused.hip)
+          const int64_t o = grid_out_index(g.grid, row0 + row, g.M);
+          if (o >= 0) g.sdf[o] = v * g.grid.out_scale;
+        }
       }
     }
   }

@@ -74,16 +74,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     const int64_t row = row0 + p;
     float x[3] = {0.f, 0.f, 0.f};
     if (row < g.M) {
-      if (g.grid.on) {   // row = ((ix - x_begin) * res + iy) * res + iz of the slab
+      if (g.grid.on) {   // the grid sample of this row (dense slab, brick list or brick-corner lattice: grid_locate)
         const int res = g.grid.res;
-        int64_t r = row;
-        const int iz = (int)(r % res);
-        r /= res;
-        const int iy = (int)(r % res);
-        const int ix = (int)(r / res) + g.grid.x_begin;
-        x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
-        x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
-        x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
+        int ix, iy, iz;
+        if (grid_locate(g.grid, row, g.M, ix, iy, iz) >= 0) {
+          x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
+          x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
+          x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
+        }
       } else {
         x[0] = g.pts[row * 3] * g.scale;
         x[1] = g.pts[row * 3 + 1] * g.scale;
@@ -291,7 +289,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
       if (lane == 0) {
         const float v = (H2 ? __builtin_fmaf(s, isa, bs) : s + bs) / g.scale;
         if (!g.grid.on) g.sdf[row0 + row] = v;
-        else if (row0 + row < g.M) g.sdf[row0 + row] = v * g.grid.out_scale;   // the volume has exactly M entries
+        else {   // the volume has exactly M entries; brick mode scatters (a face sample shared by two listed bricks is
+          // written by both with the same bits: same coordinates, same kernel family, rows independent of their tile mates)
+          const int64_t o = grid_out_index(g.grid, row0 + row, g.M);
+          if (o >= 0) g.sdf[o] = v * g.grid.out_scale;
+        }
       }
     }
   }
@@ -461,7 +463,8 @@ bool fused_supported(const Layout& L) {
 // Fused replacement of launch_pe_points + sweep_forward (same outputs; pb.a / pb.D only when `save`).
 int fused_forward(const Layout& L, const float* packed, const float* pts, int64_t M, PointBufs& pb, bool save,
                   bool need_feat, bool need_gz_last, hipStream_t s, const GridGen* grid) {
-  if (!save && use_reg_tile(L, pb.Mp)) return sweep_mv_forward(L, packed, pts, M, pb, save, need_feat, need_gz_last, s, grid);
+  const int64_t fam_rows = family_rows_of(grid, pb.Mp);   // (a sparse sweep runs the dense grid's kernel family)
+  if (!save && use_reg_tile(L, fam_rows)) return sweep_mv_forward(L, packed, pts, M, pb, save, need_feat, need_gz_last, s, grid);
   FusedFwdArgs g;
   memset(&g, 0, sizeof(g));
   if (grid) g.grid = *grid;
@@ -508,7 +511,7 @@ int fused_forward(const Layout& L, const float* packed, const float* pts, int64_
   ProfScope prof(fl, s, save ? "F_sweep(save)" : "F_sweep(forward_only)");
   // 64-point tiles when that still gives every CU >= 2 workgroups, 32-point tiles for small batches
   const int force_ti = L.knob(RNB_VARIANT_FWD_TI_SHIFT);   // tuning knob: 1 or 2 forces the tile height
-  const bool small = force_ti ? (force_ti == 1) : (pb.Mp / 64 < 512);
+  const bool small = force_ti ? (force_ti == 1) : (fam_rows / 64 < 512);
   const int force_nw = L.knob(RNB_VARIANT_FWD_NW_SHIFT);   // tuning knob: 1 = 4 waves, 2 = 8 waves (small batches)
   const bool x3 = is_x3(L);
   // (Measured and not kept: the 32-point form of the pre-split kernel for the sampling passes, and weight fragments four
@@ -516,7 +519,7 @@ int fused_forward(const Layout& L, const float* packed, const float* pts, int64_
   // whole 3.5 MB of weight planes from L2, 0.9 GB per pass at the ~16 TB/s the L2s deliver for shared rows.)
   if (small) {
     const unsigned blocks = (unsigned)(pb.Mp / 32);
-    const bool wide = force_nw ? (force_nw == 2) : (blocks <= 256);   // at most one workgroup per CU
+    const bool wide = force_nw ? (force_nw == 2) : (fam_rows / 32 <= 256);   // at most one workgroup per CU
     if (h2) {
       if (save && wide) hipLaunchKernelGGL((fused_forward_kernel<1, true, 8, true, true>), dim3(blocks), dim3(512), 0, s, g);
       else if (save) hipLaunchKernelGGL((fused_forward_kernel<1, true, 4, true, true>), dim3(blocks), dim3(256), 0, s, g);

@@ -110,12 +110,67 @@ __device__ inline float linspace_at(float start, float end, int steps, int i) {
 #endif
 
 // regular grid of extract_fields, generated inside the forward kernel (rnb_sdf_grid)
+// on == GRID_BRICKS / GRID_LATTICE (rnb_sdf_grid_sparse_*, sparse_grid.hip): the rows are samples of the SAME grid, picked
+// by index, so a value is the very number the dense sweep computes there.
+//   GRID_BRICKS : row r -> brick bricks[r / rows_per_brick] (linear id (bx * nb + by) * nb + bz), local sample
+//                 r % rows_per_brick -> (lx, ly, lz) in a (bs + 1)^3 cube, i = b * bs + l; rows past (bs + 1)^3 and samples
+//                 past res - 1 (a short last brick) are masked; the value is SCATTERED to volume[(ix * res + iy) * res + iz]
+//   GRID_LATTICE: row r -> brick corner (kx, ky, kz) of the (nb + 1)^3 lattice, i = min(k * bs, res - 1); value -> out[r]
+enum { GRID_OFF = 0, GRID_DENSE = 1, GRID_BRICKS = 2, GRID_LATTICE = 3 };
 struct GridGen {
   int on;
   int res, x_begin;
   float bmin[3], bmax[3];
   float out_scale;
+  const int32_t* bricks;   // GRID_BRICKS: the brick list (device)
+  int bs, nb;              // cells per brick edge, bricks per axis
+  int rows_per_brick;      // (bs + 1)^3 rounded up to the 64-point tile
+  int64_t family_rows;     // != 0: the launcher picks the kernel family of a sweep over this many rows (the dense grid's), so
+                           // that a sparse sample carries the dense sample's bits
 };
+inline int64_t family_rows_of(const GridGen* g, int64_t Mp) { return g != nullptr && g->family_rows != 0 ? g->family_rows : Mp; }
+
+#if defined(__HIPCC__)
+// Grid sample of row `row` of a sweep over M rows: its indices, and where its value goes (-1: a masked row — it computes on
+// the origin like a padding row and stores nothing).  GRID_DENSE is rnb_sdf_grid's arithmetic unchanged.
+__device__ inline int64_t grid_locate(const GridGen& g, int64_t row, int64_t M, int& ix, int& iy, int& iz) {
+  if (row >= M) return -1;
+  if (g.on == GRID_DENSE) {   // row = ((ix - x_begin) * res + iy) * res + iz of the slab
+    int64_t r = row;
+    iz = (int)(r % g.res);
+    r /= g.res;
+    iy = (int)(r % g.res);
+    ix = (int)(r / g.res) + g.x_begin;
+    return row;
+  }
+  if (g.on == GRID_BRICKS) {
+    const int n1 = g.bs + 1;
+    const int l = (int)(row % g.rows_per_brick);
+    if (l >= n1 * n1 * n1) return -1;
+    int b = g.bricks[row / g.rows_per_brick];
+    const int bz = b % g.nb;
+    b /= g.nb;
+    ix = (b / g.nb) * g.bs + l / (n1 * n1);
+    iy = (b % g.nb) * g.bs + (l / n1) % n1;
+    iz = bz * g.bs + l % n1;
+    if (ix >= g.res || iy >= g.res || iz >= g.res) return -1;
+    return ((int64_t)ix * g.res + iy) * g.res + iz;
+  }
+  const int nl = g.nb + 1;   // GRID_LATTICE
+  int64_t r = row;
+  iz = min((int)(r % nl) * g.bs, g.res - 1);
+  r /= nl;
+  iy = min((int)(r % nl) * g.bs, g.res - 1);
+  ix = min((int)(r / nl) * g.bs, g.res - 1);
+  return row;
+}
+// the store side of the same mapping
+__device__ inline int64_t grid_out_index(const GridGen& g, int64_t row, int64_t M) {
+  if (g.on == GRID_DENSE) return row < M ? row : -1;
+  int ix, iy, iz;
+  return grid_locate(g, row, M, ix, iy, iz);
+}
+#endif
 
 // ---- workspace carving ------------------------------------------------------------------------
 struct Carver {
@@ -221,6 +276,21 @@ int launch_copy_cols(const float* src, int ld, int ncols, int64_t M, float* out,
 int launch_fill_cols(const float* src, int ncols, int64_t M, int64_t Mp, int ld, float* dst, hipStream_t s);
 int launch_grid_points(const GridGen& g, int64_t first, int64_t n, float* pts, hipStream_t s);
 int launch_scale_copy(const float* src, float scale, int64_t n, float* dst, hipStream_t s);
+int launch_grid_scatter(const GridGen& g, const float* src, int64_t first, int64_t n, float* dst, hipStream_t s);
+
+// ---- sparse SDF grid (sparse_grid.hip): brick bookkeeping around the forward sweeps' brick mode --------
+struct SparseGeom {
+  int res, bs, nb, nl;   // grid samples, cells per brick edge, bricks and lattice points (nb + 1) per axis
+  float thr;             // "inside" = value <= thr, as marching cubes has it
+  float seed_dist;       // a corner closer to thr than this makes its bricks seeds (margin x half a brick diagonal)
+};
+// state: one byte per brick (0 = not listed, 1 = listed) in whole 32-bit words; list: brick ids in listing order;
+// n_listed: device counter (the list's length), read by the host between rounds
+int launch_sparse_classify(const SparseGeom& sg, const float* lattice, uint32_t* state, int32_t* list, int64_t* n_listed,
+                           hipStream_t s);
+int launch_sparse_grow(const SparseGeom& sg, const float* volume, int64_t first, int64_t count, uint32_t* state, int32_t* list,
+                       int64_t* n_listed, hipStream_t s);
+int launch_sparse_fill(const SparseGeom& sg, const float* lattice, const uint32_t* state, float* volume, hipStream_t s);
 int launch_absmax_rows(const float* x, int64_t n, unsigned* slot, hipStream_t s);
 int launch_range_report(const Layout& L, const float* packed, const PointBufs& pb, bool with_color, bool with_backward, float* out,
                         hipStream_t s);

@@ -501,16 +501,14 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
     const int64_t row = row0 + pp;
     float x[3] = {0.f, 0.f, 0.f};
     if (row < g.M) {
-      if (g.grid.on) {   // row = ((ix - x_begin) * res + iy) * res + iz of the slab
+      if (g.grid.on) {   // the grid sample of this row (dense slab, brick list or brick-corner lattice: grid_locate)
         const int res = g.grid.res;
-        int64_t r = row;
-        const int iz = (int)(r % res);
-        r /= res;
-        const int iy = (int)(r % res);
-        const int ix = (int)(r / res) + g.grid.x_begin;
-        x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
-        x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
-        x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
+        int ix, iy, iz;
+        if (grid_locate(g.grid, row, g.M, ix, iy, iz) >= 0) {
+          x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
+          x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
+          x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
+        }
       } else {
         x[0] = g.pts[row * 3] * g.scale;
         x[1] = g.pts[row * 3 + 1] * g.scale;
@@ -692,7 +690,10 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
       // failing loudly without a device synchronisation (the host cannot see the error word before the caller syncs)
       if (*(LDSP(volatile int))(pr.sync + 3) != 0) val = __builtin_nanf("");
       if (!g.grid.on) g.sdf[v.row[i]] = val;
-      else if (v.row[i] < g.M) g.sdf[v.row[i]] = val * g.grid.out_scale;   // the volume has exactly M entries
+      else {   // the volume has exactly M entries; brick mode scatters (shared face samples: same bits, see fused.hip)
+        const int64_t o = grid_out_index(g.grid, v.row[i], g.M);
+        if (o >= 0) g.sdf[o] = val * g.grid.out_scale;
+      }
     }
   }
 }

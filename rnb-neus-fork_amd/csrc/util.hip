@@ -9,11 +9,8 @@ namespace rnb {
 __global__ void grid_points_kernel(GridGen g, int64_t first, int64_t n, float* __restrict__ pts) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int64_t r = first + i;
-  const int iz = (int)(r % g.res);
-  r /= g.res;
-  const int iy = (int)(r % g.res);
-  const int ix = (int)(r / g.res) + g.x_begin;
+  int ix = 0, iy = 0, iz = 0;   // (a masked row of a brick list computes on the grid's first sample and stores nothing)
+  grid_locate(g, first + i, first + n, ix, iy, iz);
   pts[i * 3] = linspace_at(g.bmin[0], g.bmax[0], g.res, ix);
   pts[i * 3 + 1] = linspace_at(g.bmin[1], g.bmax[1], g.res, iy);
   pts[i * 3 + 2] = linspace_at(g.bmin[2], g.bmax[2], g.res, iz);
@@ -54,6 +51,18 @@ __global__ void fill_cols_kernel(const float* __restrict__ src, int ncols, int64
 
 int launch_grid_points(const GridGen& g, int64_t first, int64_t n, float* pts, hipStream_t s) {
   hipLaunchKernelGGL(grid_points_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, g, first, n, pts);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+// dst[grid_out_index(first + i)] = src[i] * scale: the scatter of a brick list / the lattice on the per-layer route
+__global__ void grid_scatter_kernel(GridGen g, const float* __restrict__ src, int64_t first, int64_t n, float* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t o = grid_out_index(g, first + i, first + n);
+  if (o >= 0) dst[o] = src[i] * g.out_scale;   // (shared face samples: both bricks write the same bits, see fused.hip)
+}
+int launch_grid_scatter(const GridGen& g, const float* src, int64_t first, int64_t n, float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(grid_scatter_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, g, src, first, n, dst);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

@@ -80,6 +80,29 @@ class GridDesc(C.Structure):
                 ("x_begin", C.c_int32), ("x_end", C.c_int32), ("out_scale", C.c_float)]
 
 
+class SparseGridDesc(C.Structure):
+    _fields_ = [("brick", C.c_int32), ("threshold", C.c_float), ("margin", C.c_float)]
+
+
+SPARSE_BRICKS = (4, 8, 16, 32)
+
+
+def brick_geometry(res: int, brick: int) -> dict:
+    """Brick layout of a sparse SDF grid (include/rnbneus.h, rnb_sdf_grid_sparse_*), as the library lays it out:
+    `nb` bricks per axis, `lattice` = the grid indices of the nb + 1 brick corners per axis, `samples` = grid samples per
+    brick edge (brick + 1), `rows` = rows one brick occupies in a forward sweep ((brick + 1)^3 rounded up to the 64-point
+    tile), `bricks_total` = nb^3."""
+    res, brick = int(res), int(brick)
+    if res < 2:
+        raise ValueError(f"a grid of resolution {res} has no cells")
+    if brick not in SPARSE_BRICKS:
+        raise ValueError(f"brick must be one of {SPARSE_BRICKS}, not {brick}")
+    nb = (res - 1 + brick - 1) // brick
+    n1 = brick + 1
+    return {"nb": nb, "lattice": [min(k * brick, res - 1) for k in range(nb + 1)], "samples": n1,
+            "rows": (n1 ** 3 + 63) // 64 * 64, "bricks_total": nb ** 3}
+
+
 class RenderGrads(C.Structure):
     _fields_ = [("color_fine", C.c_void_p), ("weights", C.c_void_p), ("cdf_fine", C.c_void_p),
                 ("gradients", C.c_void_p), ("weight_sum", C.c_void_p), ("weight_max", C.c_void_p),
@@ -119,6 +142,13 @@ _SIGNATURES = {
     "rnb_sdf_grid_workspace_bytes": (C.c_int, [_P(ModelDesc), _P(GridDesc), _P(C.c_int64)]),
     "rnb_sdf_grid": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(GridDesc), C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p]),
+    "rnb_sdf_grid_sparse_workspace_bytes": (C.c_int, [_P(ModelDesc), _P(GridDesc), _P(SparseGridDesc), _P(C.c_int64)]),
+    "rnb_sdf_grid_sparse_seed": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(GridDesc), _P(SparseGridDesc), C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rnb_sdf_grid_sparse_round": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(GridDesc), _P(SparseGridDesc), C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rnb_sdf_grid_sparse_finish": (C.c_int, [_P(ModelDesc), _P(GridDesc), _P(SparseGridDesc), C.c_void_p, C.c_void_p,
+                                             C.c_size_t, C.c_void_p, C.c_void_p]),
     "rnb_marching_cubes_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64)]),
     "rnb_marching_cubes_count": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                            C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -36,6 +36,8 @@ from .fields import _mlp_struct, model_desc
 from .parallel import allreduce_mean_, allreduce_sum_
 
 _MESH_BACKEND_LOGGED = False
+# cells per brick edge of extract_fields_sparse(brick=None): chosen from profiles/sparse_grid.txt
+DEFAULT_SPARSE_BRICK = 8
 
 
 def _requires_grad(t):
@@ -269,6 +271,7 @@ class NeuSRenderer:
         # more pass over the saved state per step — off by default); range_report() returns the last ones
         self.track_range = False
         self._range = None
+        self.last_sparse_grid = None   # `info` of the last extract_geometry(sparse=True)
 
     # ------------------------------------------------------------------ data parallel
     def set_data_parallel(self, group=None, enabled=True, exact=True):
@@ -468,6 +471,68 @@ class NeuSRenderer:
                 u = slab[:res]
         return u.cpu().numpy() if to_host else u
 
+    def extract_fields_sparse(self, bound_min, bound_max, resolution, threshold=0.0, brick=None, margin=1.0, to_host=False):
+        """The volume of `extract_fields` with only the bricks near the iso-surface evaluated (`rnb_sdf_grid_sparse_*`,
+        include/rnbneus.h has the contract).  Returns `(u, info)`: `u` [res,res,res] — samples of the evaluated bricks are
+        bit-equal to `extract_fields`', every other sample holds the clamped trilinear interpolant of its brick's corner
+        values, which lies on the corners' side of `threshold` — so marching cubes at `threshold` gives the dense volume's
+        mesh for every surface component that passes through a seed brick.  `brick`: cells per brick edge (4, 8, 16, 32;
+        None = `DEFAULT_SPARSE_BRICK`); `margin`: the Lipschitz constant of the SDF to assume when seeding (1.0 is exact
+        for a true distance field; 0 seeds from sign changes between brick corners only; a component lying wholly inside
+        bricks whose corners are farther than margin x half a brick diagonal from the threshold is missed).
+        `info`: `brick`, `bricks_total`, `bricks_seeded`, `bricks_active`, `rounds` (growth rounds that listed new
+        bricks), `points_evaluated` (brick-corner lattice + (brick+1)^3 per evaluated brick) and `mask` (bool [nb,nb,nb]
+        device tensor of the evaluated bricks).  The host reads one 8-byte counter per round.  Data-parallel sparse grids
+        do not exist: with `set_data_parallel` enabled this raises rather than run replicated."""
+        res = int(resolution)
+        brick = DEFAULT_SPARSE_BRICK if brick is None else int(brick)
+        geo = native.brick_geometry(res, brick)   # (ValueError for a resolution below 2 or an unknown brick size)
+        margin, threshold = float(margin), float(threshold)
+        if not margin >= 0.0:
+            raise ValueError(f"extract_fields_sparse: margin must be >= 0, not {margin}")
+        if threshold != threshold:
+            raise ValueError("extract_fields_sparse: threshold is NaN")
+        if geo["bricks_total"] > 2 ** 31 - 1:
+            raise ValueError(f"extract_fields_sparse: {geo['bricks_total']} bricks do not fit a 32-bit id")
+        if self.dp_group is not None:
+            raise ValueError("extract_fields_sparse: data-parallel sparse grids are not supported "
+                             "(extract_fields serves set_data_parallel)")
+        dev = self.sdf_network.lin0.bias.device
+        if dev.type != "cuda":
+            raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+        lib = native.load()
+        gd = native.GridDesc()
+        for d in range(3):
+            gd.bound_min[d] = float(bound_min[d])
+            gd.bound_max[d] = float(bound_max[d])
+        gd.resolution, gd.x_begin, gd.x_end, gd.out_scale = res, 0, res, -1.0
+        sd = native.SparseGridDesc(brick, threshold, margin)
+        nb = geo["nb"]
+        with torch.no_grad():
+            packed = self._pack(False)
+            nbytes = C.c_int64()
+            native.check(lib.rnb_sdf_grid_sparse_workspace_bytes(C.byref(self.desc), C.byref(gd), C.byref(sd), C.byref(nbytes)))
+            ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=dev)
+            u = torch.empty(res, res, res, dtype=torch.float32, device=dev)
+            mask = torch.empty(nb, nb, nb, dtype=torch.uint8, device=dev)
+            n_listed = torch.zeros(1, dtype=torch.int64, device=dev)
+            with native.on_device(dev) as stream:
+                native.check(lib.rnb_sdf_grid_sparse_seed(C.byref(self.desc), native.ptr(packed), C.byref(gd), C.byref(sd),
+                                                          native.ptr(ws), ws.numel(), native.ptr(n_listed), stream))
+                seeded = n = int(n_listed.item())
+                first, rounds = 0, 0
+                while first < n:   # evaluate the list's tail, grow from it; every launch is sized from a count read here
+                    native.check(lib.rnb_sdf_grid_sparse_round(C.byref(self.desc), native.ptr(packed), C.byref(gd),
+                                                               C.byref(sd), native.ptr(u), native.ptr(ws), ws.numel(), first,
+                                                               n - first, native.ptr(n_listed), stream))
+                    first, n = n, int(n_listed.item())
+                    rounds += 1 if n > first else 0
+                native.check(lib.rnb_sdf_grid_sparse_finish(C.byref(self.desc), C.byref(gd), C.byref(sd), native.ptr(u),
+                                                            native.ptr(ws), ws.numel(), native.ptr(mask), stream))
+        info = {"brick": brick, "bricks_total": geo["bricks_total"], "bricks_seeded": seeded, "bricks_active": n,
+                "rounds": rounds, "points_evaluated": (nb + 1) ** 3 + n * geo["samples"] ** 3, "mask": mask.bool()}
+        return (u.cpu().numpy() if to_host else u), info
+
     def _collect_range(self, desc, packed, ws, B, S, flags):
         if self._range is None or self._range.device != ws.device:
             self._range = torch.zeros(8, dtype=torch.float32, device=ws.device)
@@ -506,7 +571,8 @@ class NeuSRenderer:
                         worst, where = m, f"{prefix}.lin{i}"
         return {"max_abs_weight": worst, "layer": where, "limit": 255.0, "ok": bool(worst < 255.0)}
 
-    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, backend=None):
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, backend=None, sparse=False, margin=1.0,
+                         brick=None):
         """models/renderer.py:1219-1224 / :27-36: SDF grid + marching cubes + rescaling to the bounding box; returns
         numpy `(vertices [V,3] float64, triangles [T,3])` as the reference does.
         `backend`: "native" — the library's own marching cubes on the volume still resident in HBM
@@ -515,7 +581,12 @@ class NeuSRenderer:
         else "native".  The choice made for None is logged once per process (logger `rnb_neus_fork_amd`, INFO) and kept in
         `self.last_mesh_backend`, so the same script cannot silently produce different triangulations on two machines.
         The native mesh has the same vertices (one per crossed grid edge, same interpolation); its triangulation of
-        ambiguous cells / quad diagonals may differ from PyMCubes' table (parity unpinned: DESIGN)."""
+        ambiguous cells / quad diagonals may differ from PyMCubes' table (parity unpinned: DESIGN).
+        `sparse=True`: the volume comes from `extract_fields_sparse(threshold=threshold, margin=margin, brick=brick)` —
+        only the bricks near the surface are evaluated, the mesh is the dense one for every component that passes through
+        a seed brick (see there for what `margin` can miss) — and its `info` is kept in `self.last_sparse_grid`.  Marching
+        cubes itself is unchanged and runs over the dense array; its limit of 2^32 grid points caps `resolution` at 1625
+        either way."""
         if backend is None:
             try:
                 import mcubes  # noqa: F401
@@ -535,11 +606,19 @@ class NeuSRenderer:
         b_min = bound_min.detach().cpu().numpy()
         if backend == "mcubes":
             import mcubes
-            u = self.extract_fields(bound_min, bound_max, resolution)
+            if sparse:
+                u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, resolution, threshold, brick,
+                                                                      margin, to_host=True)
+            else:
+                u = self.extract_fields(bound_min, bound_max, resolution)
             vertices, triangles = mcubes.marching_cubes(u, threshold)
         else:
             from .mcubes import marching_cubes
-            u = self.extract_fields(bound_min, bound_max, resolution, to_host=False)
+            if sparse:
+                u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, resolution, threshold, brick,
+                                                                      margin, to_host=False)
+            else:
+                u = self.extract_fields(bound_min, bound_max, resolution, to_host=False)
             v, t = marching_cubes(u, threshold)
             vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
