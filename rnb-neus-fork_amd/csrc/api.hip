@@ -88,7 +88,7 @@ static int forward_points(const Layout& L, const float* packed, const float* pts
       RNB_TRY(bf16_forward(L, packed, pts, n, pb, save, need_feat, s, nullptr, save && need_feat && L.route.color == COLOR_BF16));
       break;
     case SDF_FUSED:
-      RNB_TRY(fused_forward(L, packed, pts, n, pb, save, need_feat, false, s));
+      RNB_TRY(fused_forward(L, packed, pts, n, pb, save, need_feat, s));
       break;
     case SDF_LAYERS:
       RNB_TRY(launch_pe_points(L, pts, n, pb, s));
@@ -388,7 +388,7 @@ RNB_API int rnb_sdf_grid(const rnb_model_desc* desc, const float* packed, const 
     pb.Mp = pad_rows(n);
     pb.sdf = volume;   // grid mode writes rows < M only
     if (L.route.sdf == SDF_BF16) return bf16_forward(L, packed, nullptr, n, pb, false, false, s, &gg);
-    return fused_forward(L, packed, nullptr, n, pb, false, false, false, s, &gg);
+    return fused_forward(L, packed, nullptr, n, pb, false, false, s, &gg);
   }
   RNB_REQUIRE(ws, "workspace");
   for (int64_t first = 0; first < n; first += kGridChunk) {
@@ -479,7 +479,7 @@ static int sparse_eval(SparseSetup& S, const float* packed, const GridGen& g, in
     pb.Mp = pad_rows(M);
     pb.sdf = out;
     if (S.L.route.sdf == SDF_BF16) return bf16_forward(S.L, packed, nullptr, M, pb, false, false, s, &g);
-    return fused_forward(S.L, packed, nullptr, M, pb, false, false, false, s, &g);
+    return fused_forward(S.L, packed, nullptr, M, pb, false, false, s, &g);
   }
   for (int64_t first = 0; first < M; first += kGridChunk) {
     const int64_t m = M - first < kGridChunk ? M - first : kGridChunk;

@@ -241,14 +241,8 @@ struct BfFwdArgs {
   int64_t M;
   const float* packed;     // fp32 packed weights (biases, sdf head row)
   const bfraw* wbf;        // bf16 mirror of the packed buffer (same offsets)
-  int nh, skip, pe, multires, Ep;
-  float scale;
-  int n_real[RNB_MAX_LIN];
-  int Kp[RNB_MAX_LIN];
-  long long w_off[RNB_MAX_LIN], b_off[RNB_MAX_LIN];
-  long long wsdf_off, bsdf_off;
-  int with_feat, F, Cinp;
-  long long wf_off, bf_off;
+  SdfNetArgs net;
+  int with_feat;
   float* cin;              // [Mp,Cinp] fp32 feature block destination (with_feat, cin8 == nullptr)
   bfraw* cin8;             // [Mp,Cinp] K8 bf16 feature block destination (bf16 albedo path) or nullptr
   float* sdf;              // [Mp]
@@ -278,80 +272,51 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_forward_ker
     constexpr int PARTS = NT / BT;   // 4 or 8 threads per point
     const int p = tid % BT, part = tid / BT;
     const int64_t row = row0 + p;
-    float x[3] = {0.f, 0.f, 0.f};
-    if (row < g.M) {
-      if (g.grid.on) {   // (dense slab, brick list or brick-corner lattice: grid_locate)
-        const int res = g.grid.res;
-        int ix, iy, iz;
-        if (grid_locate(g.grid, row, g.M, ix, iy, iz) >= 0) {
-          x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
-          x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
-          x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
-        }
-      } else {
-        x[0] = g.pts[row * 3] * g.scale;
-        x[1] = g.pts[row * 3 + 1] * g.scale;
-        x[2] = g.pts[row * 3 + 2] * g.scale;
-      }
-    }
+    float x[3];
+    sweep_point(g.grid, g.pts, row, g.M, g.net.scale, x);
     bfraw* xr = X + p * BP;
     float* er = E + p * FEP;
     if (part == 0) {
 #pragma unroll
       for (int d = 0; d < 3; ++d) { xr[d] = to_bf(x[d]); er[d] = x[d]; }
-      for (int c = g.pe; c < g.Ep; ++c) xr[c] = 0;
+      for (int c = g.net.pe; c < g.net.Ep; ++c) xr[c] = 0;
       if (SAVE) {
         g.x4[row * 4] = x[0]; g.x4[row * 4 + 1] = x[1]; g.x4[row * 4 + 2] = x[2]; g.x4[row * 4 + 3] = 0.f;
       }
     }
-    for (int k = part; k < g.multires; k += PARTS) {
-      const float f = (float)(1 << k);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float s, co;
-        sincosf(x[d] * f, &s, &co);
-        const int c = 3 + 6 * k + d;
-        xr[c] = to_bf(s); xr[c + 3] = to_bf(co);
-        er[c] = s; er[c + 3] = co;
-      }
-    }
+    pe_sincos(x, g.net.multires, part, PARTS, [&](int c, float s, float co) {
+      xr[c] = to_bf(s); xr[c + 3] = to_bf(co);
+      er[c] = s; er[c + 3] = co;
+    });
   }
   __syncthreads();
   if (SAVE) {   // e (bf16, K8, 64 columns): the Y operand of layer 0's weight gradient
-    for (int u = tid; u < (BT / 8) * g.Ep; u += NT) {
-      const int blk = u / g.Ep, c = u - blk * g.Ep;
-      bfraw v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = X[(blk * 8 + j) * BP + c];
-      vu4 o = {(unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16),
-               (unsigned)v[4] | ((unsigned)v[5] << 16), (unsigned)v[6] | ((unsigned)v[7] << 16)};
-      *reinterpret_cast<vu4*>(g.e + (((size_t)(row0 >> 3) + blk) * g.Ep + c) * 8) = o;
+    for (int u = tid; u < (BT / 8) * g.net.Ep; u += NT) {
+      const int blk = u / g.net.Ep, c = u - blk * g.net.Ep;
+      *reinterpret_cast<vu4*>(g.e + (((size_t)(row0 >> 3) + blk) * g.net.Ep + c) * 8) = lds_gather8<BP>(X, blk, c);
     }
   }
 
   v16f acc[TI][2];
-  // cross-layer weight prefetch (the next layer's block 0 in flight during the epilogue) only where the registers are
-  // free: with SAVE the epilogue also holds the D values and the packed stores (29 spilled registers otherwise)
-  constexpr bool XL = true;
+  // cross-layer weight prefetch: the next product's block 0 is in flight during a layer's epilogue
   BfMma<TI> mm;
-  if (XL) mm.request(g.wbf + g.w_off[0], g.Kp[0], n0, lane);
-  for (int l = 0; l < g.nh; ++l) {
-    const bfraw* wn = !XL ? nullptr : (l + 1 < g.nh ? g.wbf + g.w_off[l + 1] : (g.with_feat ? g.wbf + g.wf_off : nullptr));
-    if (!XL) mm.request(g.wbf + g.w_off[l], g.Kp[l], n0, lane);
-    if (l == 0) mm.template run<64>(Xw, g.wbf + g.w_off[0], n0, lane, acc, wn, FH, n0);   // (fused_supported: Ep = 64, hidden 256)
-    else mm.template run<256>(Xw, g.wbf + g.w_off[l], n0, lane, acc, wn, FH, n0);
+  mm.request(g.wbf + g.net.w_off[0], g.net.Kp[0], n0, lane);
+  for (int l = 0; l < g.net.nh; ++l) {
+    const bfraw* wn = l + 1 < g.net.nh ? g.wbf + g.net.w_off[l + 1] : (g.with_feat ? g.wbf + g.net.wf_off : nullptr);
+    if (l == 0) mm.template run<64>(Xw, g.wbf + g.net.w_off[0], n0, lane, acc, wn, FH, n0);   // (fused_supported: Ep = 64, hidden 256)
+    else mm.template run<256>(Xw, g.wbf + g.net.w_off[l], n0, lane, acc, wn, FH, n0);
     lds_barrier();   // every wave has finished reading the input activations (the tile is updated in place)
     const int lo = opaque(lane), h = lo >> 5, cl = lo & 31;
-    const float* bias = g.packed + g.b_off[l];
-    const int n_real = g.n_real[l];
-    const bool pe_tail = (l + 1 == g.skip);
+    const float* bias = g.packed + g.net.b_off[l];
+    const int n_real = g.net.n_real[l];
+    const bool pe_tail = (l + 1 == g.net.skip);
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
       const int col = n0 + tj * 32 + cl;
       const float bc = bias[col];
       const bool tile_full = n0 + tj * 32 + 32 <= n_real;   // wave-uniform: no per-element column tests
       const bool real = col < n_real;
-      const bool pe_col = pe_tail && !real && col < n_real + g.pe;
+      const bool pe_col = pe_tail && !real && col < n_real + g.net.pe;
 #pragma unroll
       for (int ti = 0; ti < TI; ++ti) {
 #pragma unroll
@@ -381,11 +346,11 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_forward_ker
 
   // ---- sdf head: row 0 of the output layer, fp32 weights on the bf16 activations ---------------------------------
   {
-    const float* ws = g.packed + g.wsdf_off;
+    const float* ws = g.packed + g.net.wsdf_off;
     float w[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) w[u] = ws[lane + 64 * u];
-    const float bs = g.packed[g.bsdf_off];
+    const float bs = g.packed[g.net.bsdf_off];
     for (int rr = 0; rr < BT / NW; ++rr) {
       const int row = wave * (BT / NW) + rr;
       float s = 0.f;
@@ -394,24 +359,19 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_forward_ker
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
       if (lane == 0) {
-        const float v = (s + bs) / g.scale;
-        if (!g.grid.on) g.sdf[row0 + row] = v;
-        else {   // (brick mode scatters; shared face samples get the same bits from both bricks, see fused.hip)
-          const int64_t o = grid_out_index(g.grid, row0 + row, g.M);
-          if (o >= 0) g.sdf[o] = v * g.grid.out_scale;
-        }
+        const float v = (s + bs) / g.net.scale;
+        sweep_store_sdf(g.grid, g.sdf, row0, row, g.M, v);
       }
     }
   }
   // ---- feature head: rows 1.. of the output layer, written (fp32) into the albedo network's input -------------------
   if (g.with_feat) {
-    if (!XL) mm.request(g.wbf + g.wf_off, FH, n0, lane);
-    mm.template run<256>(Xw, g.wbf + g.wf_off, n0, lane, acc, nullptr, 0, 0);   // (XL: block 0 was requested by the last hidden layer)
-    const float* bias = g.packed + g.bf_off;
+    mm.template run<256>(Xw, g.wbf + g.net.wf_off, n0, lane, acc, nullptr, 0, 0);   // (block 0 was requested by the last hidden layer)
+    const float* bias = g.packed + g.net.bf_off;
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
       const int col = n0 + tj * 32 + cl;
-      if (col < g.F) {
+      if (col < g.net.F) {
         const float bc = bias[col];
         if (g.cin8 != nullptr) {
 #pragma unroll
@@ -419,14 +379,14 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_forward_ker
 #pragma unroll
             for (int q = 0; q < 4; ++q)
               k8_store_quad(g.cin8, rowW, ti, q, col, h, acc[ti][tj][4 * q] + bc, acc[ti][tj][4 * q + 1] + bc,
-                            acc[ti][tj][4 * q + 2] + bc, acc[ti][tj][4 * q + 3] + bc, g.Cinp);
+                            acc[ti][tj][4 * q + 2] + bc, acc[ti][tj][4 * q + 3] + bc, g.net.Cinp);
         } else {
 #pragma unroll
           for (int ti = 0; ti < TI; ++ti)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int row = rb + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-              g.cin[(size_t)(row0 + row) * g.Cinp + col] = acc[ti][tj][r] + bc;
+              g.cin[(size_t)(row0 + row) * g.net.Cinp + col] = acc[ti][tj][r] + bc;
             }
         }
       }
@@ -441,12 +401,7 @@ struct BfBwdArgs {
   const float* packed;
   const bfraw* wbf;
   int64_t M;
-  int nh, skip, pe, multires, Ep;
-  float inv_scale;
-  int n_real[RNB_MAX_LIN];
-  int Kp[RNB_MAX_LIN];
-  long long w_off[RNB_MAX_LIN], wT_off[RNB_MAX_LIN];
-  long long wsdf_off, wfT_off;
+  SdfNetArgs net;
   bfraw* D[RNB_MAX_LIN];
   bfraw* gz[RNB_MAX_LIN];
   bfraw* u[RNB_MAX_LIN + 1];   // u[0]: [Mp,64] K8 (written by RA from geb); u[l >= 1]: [Mp,256] K8
@@ -479,9 +434,9 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_reverse_ker
 
   // seed: gz_{nh-1} = w_sdf * D_{nh-1}; one K8 unit (8 points of one column) per thread and step
   {
-    const bfraw* Dl = g.D[g.nh - 1] + (size_t)(row0 >> 3) * FH * 8;
-    bfraw* gzl = g.gz[g.nh - 1] + (size_t)(row0 >> 3) * FH * 8;
-    const float* ws = g.packed + g.wsdf_off;
+    const bfraw* Dl = g.D[g.net.nh - 1] + (size_t)(row0 >> 3) * FH * 8;
+    bfraw* gzl = g.gz[g.net.nh - 1] + (size_t)(row0 >> 3) * FH * 8;
+    const float* ws = g.packed + g.net.wsdf_off;
     for (int u = tid; u < (BT / 8) * FH; u += NT) {
       const int blk = u / FH, c = u - blk * FH;
       const vu4 d = *reinterpret_cast<const vu4*>(Dl + (size_t)u * 8);
@@ -500,15 +455,15 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_reverse_ker
   v16f acc[TI][2];
   AuxBf<TI> aD;
   BfMma<TI> mm;
-  mm.request(g.wbf + g.wT_off[g.nh - 1], FH, n0, lane);
-  for (int l = g.nh - 1; l >= 1; --l) {
+  mm.request(g.wbf + g.net.wT_off[g.net.nh - 1], FH, n0, lane);
+  for (int l = g.net.nh - 1; l >= 1; --l) {
     k8_prefetch<TI>(g.D[l - 1], rowW, n0, opaque(lane), aD);
-    const bfraw* wn = (l > 1 || n0 < 64) ? g.wbf + g.wT_off[l - 1] : nullptr;   // layer 0's product: wave(s) of columns 0..63
-    mm.template run<256>(Xw, g.wbf + g.wT_off[l], n0, lane, acc, wn, FH, n0);   // g = gz_l W_l  (columns = inputs of layer l)
+    const bfraw* wn = (l > 1 || n0 < 64) ? g.wbf + g.net.wT_off[l - 1] : nullptr;   // layer 0's product: wave(s) of columns 0..63
+    mm.template run<256>(Xw, g.wbf + g.net.wT_off[l], n0, lane, acc, wn, FH, n0);   // g = gz_l W_l  (columns = inputs of layer l)
     lds_barrier();
     const int lo = opaque(lane), h = lo >> 5, cl = lo & 31;
-    const bool is_skip = (l == g.skip);
-    const int ksplit = is_skip ? FH - g.pe : FH;   // columns that belong to layer l-1's output
+    const bool is_skip = (l == g.net.skip);
+    const int ksplit = is_skip ? FH - g.net.pe : FH;   // columns that belong to layer l-1's output
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
       const int col = n0 + tj * 32 + cl;
@@ -528,7 +483,7 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_reverse_ker
               const float v = acc[ti][tj][r];
               if (col < ksplit) o[j] = v * aux_at(aD, ti, tj, r);
               else {
-                if (col < ksplit + g.pe) GE[(rb + 4 * h) * FEP + (col - ksplit) + (ti * 32 + 8 * q + j) * FEP] = v;   // skip connection: straight to g_e
+                if (col < ksplit + g.net.pe) GE[(rb + 4 * h) * FEP + (col - ksplit) + (ti * 32 + 8 * q + j) * FEP] = v;   // skip connection: straight to g_e
                 o[j] = 0.f;
               }
             }
@@ -542,12 +497,12 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_reverse_ker
   }
   // layer 0: g_e += gz_0 W_0 (Ep = 64 columns: wave 0)
   if (n0 < 64) {
-    if (g.nh == 1) mm.request(g.wbf + g.wT_off[0], FH, n0, lane);
-    mm.template run<256>(Xw, g.wbf + g.wT_off[0], n0, lane, acc, nullptr, 0, 0);
+    if (g.net.nh == 1) mm.request(g.wbf + g.net.wT_off[0], FH, n0, lane);
+    mm.template run<256>(Xw, g.wbf + g.net.wT_off[0], n0, lane, acc, nullptr, 0, 0);
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
       const int col = n0 + tj * 32 + cl;
-      if (col < g.pe) {
+      if (col < g.net.pe) {
 #pragma unroll
         for (int ti = 0; ti < TI; ++ti)
 #pragma unroll
@@ -562,7 +517,7 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_reverse_ker
     float n[3] = {ge[0], ge[1], ge[2]};
     float f = 1.f;
     int c = 3;
-    for (int k = 0; k < g.multires; ++k) {
+    for (int k = 0; k < g.net.multires; ++k) {
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
         float s, co;
@@ -590,40 +545,35 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_ra_kernel(B
   const int64_t rowW = row0 + rb;
   const bfraw* Xw = X + rb * BP;
 
-  for (int idx = tid; idx < BT * g.Ep; idx += NT) {
-    const int r = idx / g.Ep, c = idx - r * g.Ep;
-    const float v = g.geb[(row0 + r) * g.Ep + c];
+  for (int idx = tid; idx < BT * g.net.Ep; idx += NT) {
+    const int r = idx / g.net.Ep, c = idx - r * g.net.Ep;
+    const float v = g.geb[(row0 + r) * g.net.Ep + c];
     X[r * BP + c] = to_bf(v);
     if (c < FEP) E[r * FEP + c] = v;
   }
   __syncthreads();
   // u_0 in K8 (the Y operand of layer 0's weight gradient)
-  for (int u = tid; u < (BT / 8) * g.Ep; u += NT) {
-    const int blk = u / g.Ep, c = u - blk * g.Ep;
-    bfraw v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = X[(blk * 8 + j) * BP + c];
-    vu4 o = {(unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16),
-             (unsigned)v[4] | ((unsigned)v[5] << 16), (unsigned)v[6] | ((unsigned)v[7] << 16)};
-    *reinterpret_cast<vu4*>(g.u[0] + (((size_t)(row0 >> 3) + blk) * g.Ep + c) * 8) = o;
+  for (int u = tid; u < (BT / 8) * g.net.Ep; u += NT) {
+    const int blk = u / g.net.Ep, c = u - blk * g.net.Ep;
+    *reinterpret_cast<vu4*>(g.u[0] + (((size_t)(row0 >> 3) + blk) * g.net.Ep + c) * 8) = lds_gather8<BP>(X, blk, c);
   }
 
   v16f acc[TI][2];
   AuxBf<TI> aD, aG;
   // no cross-layer weight prefetch and 32-k weight blocks here: the two epilogue operand tiles already fill the registers
   BfMma<TI> mm;
-  mm.request(g.wbf + g.w_off[0], g.Kp[0], n0, lane);
-  for (int l = 0; l < g.nh; ++l) {
+  mm.request(g.wbf + g.net.w_off[0], g.net.Kp[0], n0, lane);
+  for (int l = 0; l < g.net.nh; ++l) {
     const int lp = opaque(lane);
     k8_prefetch<TI>(g.D[l], rowW, n0, lp, aD);
     k8_prefetch<TI>(g.gz[l], rowW, n0, lp, aG);
-    const bfraw* wn = l + 1 < g.nh ? g.wbf + g.w_off[l + 1] : nullptr;
-    if (l == 0) mm.template run<64>(Xw, g.wbf + g.w_off[0], n0, lane, acc, wn, FH, n0);   // gzb = u_l W_l^T
-    else mm.template run<256>(Xw, g.wbf + g.w_off[l], n0, lane, acc, wn, FH, n0);
+    const bfraw* wn = l + 1 < g.net.nh ? g.wbf + g.net.w_off[l + 1] : nullptr;
+    if (l == 0) mm.template run<64>(Xw, g.wbf + g.net.w_off[0], n0, lane, acc, wn, FH, n0);   // gzb = u_l W_l^T
+    else mm.template run<256>(Xw, g.wbf + g.net.w_off[l], n0, lane, acc, wn, FH, n0);
     lds_barrier();
     const int lo = opaque(lane), h = lo >> 5, cl = lo & 31;
-    const int n_real = g.n_real[l];
-    const bool pe_tail = (l + 1 == g.skip);
+    const int n_real = g.net.n_real[l];
+    const bool pe_tail = (l + 1 == g.net.skip);
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
       const int col = n0 + tj * 32 + cl;
@@ -651,7 +601,7 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_ra_kernel(B
                 zr[j] = ((v - un[j]) * aux_at(aG, ti, tj, r)) * 100.f;
               } else {
                 zr[j] = 0.f;
-                un[j] = (pe_tail && col < n_real + g.pe) ? E[(rb + 4 * h) * FEP + (col - n_real) + (ti * 32 + 8 * q + j) * FEP] : 0.f;
+                un[j] = (pe_tail && col < n_real + g.net.pe) ? E[(rb + 4 * h) * FEP + (col - n_real) + (ti * 32 + 8 * q + j) * FEP] : 0.f;
               }
             }
           }
@@ -682,16 +632,16 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_fb_kernel(B
   AuxBf<TI> aD, aZ;
   BfMma<TI> mm;
   const bool has_head = g.fbar_in_k8 || g.fbar != nullptr;
-  if (has_head) mm.request(g.wbf + g.wfT_off, FH, n0, lane);
-  else if (g.nh > 1) mm.request(g.wbf + g.wT_off[g.nh - 1], FH, n0, lane);
-  const bfraw* w_first = g.nh > 1 ? g.wbf + g.wT_off[g.nh - 1] : nullptr;
+  if (has_head) mm.request(g.wbf + g.net.wfT_off, FH, n0, lane);
+  else if (g.net.nh > 1) mm.request(g.wbf + g.net.wT_off[g.net.nh - 1], FH, n0, lane);
+  const bfraw* w_first = g.net.nh > 1 ? g.wbf + g.net.wT_off[g.net.nh - 1] : nullptr;
   bf_zero<TI>(acc);
   if (g.fbar_in_k8) {
     const bfraw* fb = g.fbar8 + (size_t)(row0 >> 3) * FH * 8;
     for (int u = tid; u < (BT / 8) * FH; u += NT)
       lds_scatter8<BP>(X, u / FH, u % FH, *reinterpret_cast<const vu4*>(fb + (size_t)u * 8));
     __syncthreads();
-    mm.template run<256>(Xw, g.wbf + g.wfT_off, n0, lane, acc, w_first, FH, n0);
+    mm.template run<256>(Xw, g.wbf + g.net.wfT_off, n0, lane, acc, w_first, FH, n0);
     lds_barrier();
   } else if (g.fbar != nullptr) {
     // fbar (fp32 row-major, from the albedo net's backward) -> LDS bf16, and K8 for the feature head's dW
@@ -704,26 +654,21 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_fb_kernel(B
     __syncthreads();
     for (int u = tid; u < (BT / 8) * FH; u += NT) {
       const int blk = u / FH, c = u - blk * FH;
-      bfraw v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = X[(blk * 8 + j) * BP + c];
-      vu4 o = {(unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16),
-               (unsigned)v[4] | ((unsigned)v[5] << 16), (unsigned)v[6] | ((unsigned)v[7] << 16)};
-      *reinterpret_cast<vu4*>(g.fbar8 + (((size_t)(row0 >> 3) + blk) * FH + c) * 8) = o;
+      *reinterpret_cast<vu4*>(g.fbar8 + (((size_t)(row0 >> 3) + blk) * FH + c) * 8) = lds_gather8<BP>(X, blk, c);
     }
-    mm.template run<256>(Xw, g.wbf + g.wfT_off, n0, lane, acc, w_first, FH, n0);
+    mm.template run<256>(Xw, g.wbf + g.net.wfT_off, n0, lane, acc, w_first, FH, n0);
     lds_barrier();
   }
-  for (int l = g.nh - 1; l >= 0; --l) {
+  for (int l = g.net.nh - 1; l >= 0; --l) {
     const int lo = opaque(lane), h = lo >> 5, cl = lo & 31;
     k8_prefetch<TI>(g.D[l], rowW, n0, lo, aD);
     k8_prefetch<TI>(g.zR[l], rowW, n0, lo, aZ);
-    const int n_real = g.n_real[l];
-    const bool head = (l == g.nh - 1);
+    const int n_real = g.net.n_real[l];
+    const bool head = (l == g.net.nh - 1);
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
       const int col = n0 + tj * 32 + cl;
-      const float ws = head ? g.packed[g.wsdf_off + col] : 0.f;
+      const float ws = head ? g.packed[g.net.wsdf_off + col] : 0.f;
 #pragma unroll
       for (int ti = 0; ti < TI; ++ti)
 #pragma unroll
@@ -733,7 +678,7 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_fb_kernel(B
           for (int j = 0; j < 4; ++j) {
             const int r = 4 * q + j;
             float v = acc[ti][tj][r];
-            if (head) v = fmaf(g.sbar[row0 + rb + 4 * h + (ti * 32 + 8 * q + j)] * g.inv_scale, ws, v);   // the sdf head's contribution
+            if (head) v = fmaf(g.sbar[row0 + rb + 4 * h + (ti * 32 + 8 * q + j)] * g.net.inv_scale, ws, v);   // the sdf head's contribution
             zb[j] = col < n_real ? fmaf(v, aux_at(aD, ti, tj, r), aux_at(aZ, ti, tj, r)) : 0.f;
             X[(rb + 4 * h) * BP + col + (ti * 32 + 8 * q + j) * BP] = to_bf(zb[j]);
           }
@@ -742,7 +687,7 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_fb_kernel(B
     }
     if (l == 0) break;
     lds_barrier();
-    mm.template run<256>(Xw, g.wbf + g.wT_off[l], n0, lane, acc, l > 1 ? g.wbf + g.wT_off[l - 1] : nullptr, FH, n0);   // ab_{l-1} = zb_l W_l
+    mm.template run<256>(Xw, g.wbf + g.net.wT_off[l], n0, lane, acc, l > 1 ? g.wbf + g.net.wT_off[l - 1] : nullptr, FH, n0);   // ab_{l-1} = zb_l W_l
     lds_barrier();   // every wave has finished reading the tile
   }
 }
@@ -1472,68 +1417,48 @@ static int bf_ti(const Layout& L, int shift) {
 
 static const bfraw* wbf_of(const Layout& L, const float* packed) { return reinterpret_cast<const bfraw*>(packed + L.total); }
 
-static double hidden_flops_bf(const Layout& L, int64_t M, int first) {
-  double fl = 0;
-  for (int l = first; l < L.nh; ++l) fl += 2.0 * (double)M * L.hid[l].N * L.hid[l].K;
-  return fl;
+// the tile height of a sweep -> f(TI as a constant, grid, block): the kernel's own workgroup shape
+template <class F>
+static void pick_bf_tile(int ti, const PointBufs& pb, F&& f) {
+  pick_c<1, 2>(ti, [&](auto ti_c) { f(ti_c, dim3((unsigned)(pb.Mp / BT)), dim3(BfCfg<decltype(ti_c)::value>::NT)); });
 }
 
 int bf16_forward(const Layout& L, const float* packed, const float* pts, int64_t M, PointBufs& pb, bool save, bool need_feat,
                  hipStream_t s, const GridGen* grid, bool feat_k8) {
   BfFwdArgs g;
   memset(&g, 0, sizeof(g));
+  g.net = sdf_net_args(L);
   if (grid) g.grid = *grid;
   g.pts = pts;
   g.M = M;
   g.packed = packed;
   g.wbf = wbf_of(L, packed);
-  g.nh = L.nh; g.skip = L.skip; g.pe = L.pe; g.multires = L.multires; g.Ep = L.Ep;
-  g.scale = L.sdf_scale;
   for (int l = 0; l < L.nh; ++l) {
-    g.n_real[l] = L.hid[l].N;
-    g.Kp[l] = L.hid[l].Kp;
-    g.w_off[l] = L.hid[l].w_off;
-    g.b_off[l] = L.hid[l].b_off;
     g.a[l] = reinterpret_cast<bfraw*>(pb.a[l]);
     g.D[l] = reinterpret_cast<bfraw*>(pb.D[l]);
   }
-  g.wsdf_off = L.wsdf_off;
-  g.bsdf_off = L.bsdf_off;
   g.with_feat = need_feat ? 1 : 0;
-  g.F = L.F;
-  g.Cinp = L.Cinp;
-  g.wf_off = L.feat.w_off;
-  g.bf_off = L.feat.b_off;
   g.cin = pb.cin;
   g.cin8 = feat_k8 ? reinterpret_cast<bfraw*>(pb.cin8) : nullptr;
   g.sdf = pb.sdf;
   g.x4 = pb.x;
   g.e = reinterpret_cast<bfraw*>(pb.e);
-  double fl = hidden_flops_bf(L, M, 0) + 2.0 * (double)M * L.H;
-  if (need_feat) fl += 2.0 * (double)M * L.F * L.H;
-  ProfScope prof(fl, s, save ? "F_sweep(save)" : "F_sweep(forward_only)");
-  const unsigned blocks = (unsigned)(pb.Mp / BT);
-  const int ti = bf_ti(L, RNB_VARIANT_FWD_TI_SHIFT);
-  if (save && ti == 1) hipLaunchKernelGGL((bf_forward_kernel<true, 1>), dim3(blocks), dim3(512), 0, s, g);
-  else if (save) hipLaunchKernelGGL((bf_forward_kernel<true, 2>), dim3(blocks), dim3(256), 0, s, g);
-  else if (ti == 1) hipLaunchKernelGGL((bf_forward_kernel<false, 1>), dim3(blocks), dim3(512), 0, s, g);
-  else hipLaunchKernelGGL((bf_forward_kernel<false, 2>), dim3(blocks), dim3(256), 0, s, g);
+  ProfScope prof(sdf_sweep_flops(L, M, 0, true, need_feat), s, save ? "F_sweep(save)" : "F_sweep(forward_only)");
+  pick_bf_tile(bf_ti(L, RNB_VARIANT_FWD_TI_SHIFT), pb, [&](auto ti_c, dim3 grid, dim3 block) {
+    if (save) hipLaunchKernelGGL((bf_forward_kernel<true, decltype(ti_c)::value>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((bf_forward_kernel<false, decltype(ti_c)::value>), grid, block, 0, s, g);
+  });
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
 
 static void fill_bwd(const Layout& L, const float* packed, PointBufs& pb, BfBwdArgs& g) {
   memset(&g, 0, sizeof(g));
+  g.net = sdf_net_args(L);
   g.packed = packed;
   g.wbf = wbf_of(L, packed);
   g.M = pb.M;
-  g.nh = L.nh; g.skip = L.skip; g.pe = L.pe; g.multires = L.multires; g.Ep = L.Ep;
-  g.inv_scale = 1.f / L.sdf_scale;
   for (int l = 0; l < L.nh; ++l) {
-    g.n_real[l] = L.hid[l].N;
-    g.Kp[l] = L.hid[l].Kp;
-    g.w_off[l] = L.hid[l].w_off;
-    g.wT_off[l] = L.hid[l].wT_off;
     g.D[l] = reinterpret_cast<bfraw*>(pb.D[l]);
     g.gz[l] = reinterpret_cast<bfraw*>(pb.gz[l]);
     g.zR[l] = reinterpret_cast<bfraw*>(pb.zR[l]);
@@ -1542,8 +1467,6 @@ static void fill_bwd(const Layout& L, const float* packed, PointBufs& pb, BfBwdA
   g.u[0] = reinterpret_cast<bfraw*>(pb.u0_k8);
   for (int l = 1; l <= L.nh; ++l) g.u[l] = reinterpret_cast<bfraw*>(pb.u[l]);
   g.fbar8 = reinterpret_cast<bfraw*>(pb.fbar_k8);
-  g.wsdf_off = L.wsdf_off;
-  g.wfT_off = L.feat.wT_off;
   g.x4 = pb.x;
   g.nrm = pb.nrm;
   g.geb = pb.geb;
@@ -1553,9 +1476,10 @@ static void fill_bwd(const Layout& L, const float* packed, PointBufs& pb, BfBwdA
 int bf16_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s) {
   BfBwdArgs g;
   fill_bwd(L, packed, pb, g);
-  ProfScope prof(hidden_flops_bf(L, pb.M, 0), s, "R_sweep");
-  if (bf_ti(L, RNB_VARIANT_BWD_TI_SHIFT) == 1) hipLaunchKernelGGL(bf_reverse_kernel<1>, dim3((unsigned)(pb.Mp / BT)), dim3(512), 0, s, g);
-  else hipLaunchKernelGGL(bf_reverse_kernel<2>, dim3((unsigned)(pb.Mp / BT)), dim3(256), 0, s, g);
+  ProfScope prof(sdf_sweep_flops(L, pb.M, 0, false, false), s, "R_sweep");
+  pick_bf_tile(bf_ti(L, RNB_VARIANT_BWD_TI_SHIFT), pb, [&](auto ti_c, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(bf_reverse_kernel<decltype(ti_c)::value>, grid, block, 0, s, g);
+  });
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -1615,12 +1539,12 @@ int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with
   const bool det = (L.variant & RNB_VARIANT_DETERMINISTIC) != 0;
   BfBwdArgs g;
   fill_bwd(L, packed, pb, g);
-  const unsigned blocks = (unsigned)(pb.Mp / BT);
   const int bti = bf_ti(L, RNB_VARIANT_BWD_TI_SHIFT);
   {
-    ProfScope prof(hidden_flops_bf(L, M, 0), s, "RA_sweep");
-    if (bti == 1) hipLaunchKernelGGL(bf_ra_kernel<1>, dim3(blocks), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL(bf_ra_kernel<2>, dim3(blocks), dim3(256), 0, s, g);
+    ProfScope prof(sdf_sweep_flops(L, M, 0, false, false), s, "RA_sweep");
+    pick_bf_tile(bti, pb, [&](auto ti_c, dim3 grid, dim3 block) {
+      hipLaunchKernelGGL(bf_ra_kernel<decltype(ti_c)::value>, grid, block, 0, s, g);
+    });
     RNB_CHECK_LAUNCH();
   }
   {
@@ -1636,9 +1560,10 @@ int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with
     g.fbar = (with_color && !color_bf16) ? pb.cinb : nullptr;
     g.ld_fbar = L.Cinp;
     g.fbar_in_k8 = (with_color && color_bf16) ? 1 : 0;
-    ProfScope prof(hidden_flops_bf(L, M, 1) + (with_color ? 2.0 * (double)M * L.F * L.H : 0.0), s, "FB_sweep");
-    if (bti == 1) hipLaunchKernelGGL(bf_fb_kernel<1>, dim3(blocks), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL(bf_fb_kernel<2>, dim3(blocks), dim3(256), 0, s, g);
+    ProfScope prof(sdf_sweep_flops(L, M, 1, false, with_color), s, "FB_sweep");
+    pick_bf_tile(bti, pb, [&](auto ti_c, dim3 grid, dim3 block) {
+      hipLaunchKernelGGL(bf_fb_kernel<decltype(ti_c)::value>, grid, block, 0, s, g);
+    });
     RNB_CHECK_LAUNCH();
   }
   // ---- dW jobs ----------------------------------------------------------------------------------------------

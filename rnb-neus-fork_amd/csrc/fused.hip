@@ -72,43 +72,22 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     constexpr int PARTS = NT / FT;
     const int p = tid % FT, part = tid / FT;
     const int64_t row = row0 + p;
-    float x[3] = {0.f, 0.f, 0.f};
-    if (row < g.M) {
-      if (g.grid.on) {   // the grid sample of this row (dense slab, brick list or brick-corner lattice: grid_locate)
-        const int res = g.grid.res;
-        int ix, iy, iz;
-        if (grid_locate(g.grid, row, g.M, ix, iy, iz) >= 0) {
-          x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
-          x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
-          x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
-        }
-      } else {
-        x[0] = g.pts[row * 3] * g.scale;
-        x[1] = g.pts[row * 3 + 1] * g.scale;
-        x[2] = g.pts[row * 3 + 2] * g.scale;
-      }
-    }
+    float x[3];
+    sweep_point(g.grid, g.pts, row, g.M, g.net.scale, x);
     float* xr = X + p * FP;
     float* er = E + p * FEP;
     if (part == 0) {
       xr[0] = x[0] * SA; xr[1] = x[1] * SA; xr[2] = x[2] * SA;
       er[0] = x[0]; er[1] = x[1]; er[2] = x[2];
-      for (int c = g.pe; c < g.Ep; ++c) xr[c] = 0.f;
+      for (int c = g.net.pe; c < g.net.Ep; ++c) xr[c] = 0.f;
       if (SAVE) {
         g.x4[row * 4] = x[0]; g.x4[row * 4 + 1] = x[1]; g.x4[row * 4 + 2] = x[2]; g.x4[row * 4 + 3] = 0.f;
       }
     }
-    for (int k = part; k < g.multires; k += PARTS) {
-      const float f = (float)(1 << k);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float s, co;
-        sincosf(x[d] * f, &s, &co);
-        const int c = 3 + 6 * k + d;
-        xr[c] = s * SA; xr[c + 3] = co * SA;
-        er[c] = s; er[c + 3] = co;
-      }
-    }
+    pe_sincos(x, g.net.multires, part, PARTS, [&](int c, float s, float co) {
+      xr[c] = s * SA; xr[c + 3] = co * SA;
+      er[c] = s; er[c + 3] = co;
+    });
     if constexpr (H2) {   // the only unbounded entries of the encoding are the coordinates themselves
       xm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fabsf(x[2]));
       // (every wave leaves its own word: nothing to initialise; the layers' flags start from zero behind the same barrier)
@@ -129,24 +108,24 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
       if (SAVE && g.smax != nullptr && tid == 0) amax_tile_commit(g.smax + SMAX_E, tm);
       x2h_dyn_scale(__builtin_bit_cast(unsigned, tm), sa, isa);
       const float f = sa * (1.f / SA);
-      for (int idx = tid; idx < FT * g.Ep; idx += NT) {
-        const int r = idx / g.Ep, c = idx - r * g.Ep;
+      for (int idx = tid; idx < FT * g.net.Ep; idx += NT) {
+        const int r = idx / g.net.Ep, c = idx - r * g.net.Ep;
         X[r * FP + c] *= f;
       }
       __syncthreads();
     }
   }
   if (SAVE) {   // e is an operand of the backward (dW of layer 0) and of the R sweep: FT x Ep floats
-    for (int idx = tid; idx < FT * g.Ep; idx += NT) {
-      const int r = idx / g.Ep, c = idx - r * g.Ep;
-      g.e[(row0 + r) * g.Ep + c] = X[r * FP + c] * isa;
+    for (int idx = tid; idx < FT * g.net.Ep; idx += NT) {
+      const int r = idx / g.net.Ep, c = idx - r * g.net.Ep;
+      g.e[(row0 + r) * g.net.Ep + c] = X[r * FP + c] * isa;
     }
   }
 
   const int h = lane >> 5, cl = lane & 31;
   v16f acc[TI][TJ];
   [[maybe_unused]] X3Mma<TI, TJ, WP> mm;
-  if constexpr (X3) mm.request(g.w3 + WP * g.w_off[0], g.Kp[0], n0, lane);
+  if constexpr (X3) mm.request(g.w3 + WP * g.net.w_off[0], g.net.Kp[0], n0, lane);
   // x2h, rare path: the tile at X (written by layer l_written, times SA) holds a value beyond the fixed scale — the waves
   // exchange their maxima, every thread rescales the elements it wrote, the tile's maximum goes to PointBufs::smax
   [[maybe_unused]] auto rescale_input = [&](float am_thread, int l_written) {
@@ -167,7 +146,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     lds_barrier();
   };
   [[maybe_unused]] float am_prev = 0.f;   // x2h: this thread's maximum of what it wrote to the tile in the previous layer
-  for (int l = 0; l < g.nh; ++l) {
+  for (int l = 0; l < g.net.nh; ++l) {
     // x2h: the flag of the tile this layer reads is REQUESTED here and looked at after the matrix loop (its LDS round trip
     // hides under the loop; read right behind the previous layer's barrier it cost F(save) 7 us): the product runs
     // speculatively on the fixed scale and is redone on the rare tile that needed another one
@@ -182,8 +161,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     [[maybe_unused]] float inv = H2 ? isa * h2_iws_at(iwsv, l) : 1.f;
 #endif
     if constexpr (X3) {   // the next product's first weight steps are requested before this layer's epilogue
-      const x3raw* wn = l + 1 < g.nh ? g.w3 + WP * g.w_off[l + 1] : (g.with_feat ? g.w3 + WP * g.wf_off : nullptr);
-      mm.run(X, g.w3 + WP * g.w_off[l], g.Kp[l], n0, lane, acc, wn, FH, n0);
+      const x3raw* wn = l + 1 < g.net.nh ? g.w3 + WP * g.net.w_off[l + 1] : (g.with_feat ? g.w3 + WP * g.net.wf_off : nullptr);
+      mm.run(X, g.w3 + WP * g.net.w_off[l], g.net.Kp[l], n0, lane, acc, wn, FH, n0);
       if constexpr (H2 && (RNB_H2_GUARD_AB == 0 || RNB_H2_GUARD_AB == 3)) {
         if (__builtin_expect(__builtin_amdgcn_readfirstlane(pend) != 0, 0)) {   // (workgroup-uniform)
           lds_barrier();   // every wave has finished its (void) pass over the tile
@@ -191,20 +170,20 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
 #if RNB_H2_GUARD_AB != 3
           inv = isa * h2_iws_at(iwsv, l);
 #endif
-          mm.request(g.w3 + WP * g.w_off[l], g.Kp[l], n0, lane);
-          mm.run(X, g.w3 + WP * g.w_off[l], g.Kp[l], n0, lane, acc, wn, FH, n0);
+          mm.request(g.w3 + WP * g.net.w_off[l], g.net.Kp[l], n0, lane);
+          mm.run(X, g.w3 + WP * g.net.w_off[l], g.net.Kp[l], n0, lane, acc, wn, FH, n0);
         }
       }
-    } else layer_mma_nt<TI, NoHook, TJ>(X, g.packed + g.w_off[l], g.Kp[l], n0, lane, acc);
+    } else layer_mma_nt<TI, NoHook, TJ>(X, g.packed + g.net.w_off[l], g.net.Kp[l], n0, lane, acc);
     if constexpr (NBUF == 1) lds_barrier();   // every wave has finished reading the input activations
-    const float* bias = g.packed + g.b_off[l];
+    const float* bias = g.packed + g.net.b_off[l];
     // saved state goes out through buffer stores: one 32-bit lane offset per column tile plus a
     // compile-time row offset in the scalar operand (plain pointer stores cost a 64-bit VGPR address
     // pair per element, i.e. 128 extra registers and spills)
     const BufRsrc ra = tile_rsrc(SAVE ? g.a[l] + (size_t)row0 * FH : nullptr, FT * FH * 4);
     const BufRsrc rD = tile_rsrc(SAVE ? g.D[l] + (size_t)row0 * FH : nullptr, FT * FH * 4);
-    const int n_real = g.n_real[l];
-    const bool pe_tail = (l + 1 == g.skip);
+    const int n_real = g.net.n_real[l];
+    const bool pe_tail = (l + 1 == g.net.skip);
     // x2h: max |.| of what this thread writes to the tile.  Softplus outputs are >= +0: ONE v_max3_i32 per pair of values
     // (h2_track2), no branch; the signed encoding columns of the one tile that carries the skip connection are tracked where
     // they are written (a per-pair choice between the two forms cost a scalar branch per pair: +5 % on this kernel).
@@ -233,7 +212,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
           else a = softplus_a_sel<SCALAR_EPI>(z);
           if constexpr (!FULL) {
             if (col >= n_real) {   // only the tile straddling the skip connection's PE columns
-              const bool pe_col = pe_tail && col < n_real + g.pe;
+              const bool pe_col = pe_tail && col < n_real + g.net.pe;
               a = vf2{pe_col ? E[row * FEP + (col - n_real)] : 0.f, pe_col ? E[(row + 1) * FEP + (col - n_real)] : 0.f};
               D = vf2{0.f, 0.f};
               if constexpr (H2) am = fmaxf(am, fmaxf(fabsf(a.x), fabsf(a.y)));
@@ -269,16 +248,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     if constexpr (NBUF == 2) { float* t = X; X = Y; Y = t; }
   }
   if constexpr (H2 && RNB_H2_GUARD_AB == 0) {   // the last hidden layer's tile, read by the two heads below
-    if (h2_flag_up(&ovf[(g.nh - 1) & 1])) rescale_input(am_prev, g.nh - 1);
+    if (h2_flag_up(&ovf[(g.net.nh - 1) & 1])) rescale_input(am_prev, g.net.nh - 1);
   }
 
   // ---- sdf head: row 0 of the output layer (models/fields.py:104, :106-108) -----------------------------
   {
-    const float* ws = g.packed + g.wsdf_off;
+    const float* ws = g.packed + g.net.wsdf_off;
     float w[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) w[u] = ws[lane + 64 * u];
-    const float bs = g.packed[g.bsdf_off];
+    const float bs = g.packed[g.net.bsdf_off];
     for (int rr = 0; rr < FT / NW; ++rr) {
       const int row = wave * (FT / NW) + rr;
       float s = 0.f;
@@ -287,28 +266,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
       if (lane == 0) {
-        const float v = (H2 ? __builtin_fmaf(s, isa, bs) : s + bs) / g.scale;
-        if (!g.grid.on) g.sdf[row0 + row] = v;
-        else {   // the volume has exactly M entries; brick mode scatters (a face sample shared by two listed bricks is
-          // written by both with the same bits: same coordinates, same kernel family, rows independent of their tile mates)
-          const int64_t o = grid_out_index(g.grid, row0 + row, g.M);
-          if (o >= 0) g.sdf[o] = v * g.grid.out_scale;
-        }
+        const float v = (H2 ? __builtin_fmaf(s, isa, bs) : s + bs) / g.net.scale;
+        sweep_store_sdf(g.grid, g.sdf, row0, row, g.M, v);
       }
     }
   }
   // ---- feature head: rows 1.. of the output layer, written into the albedo network's input ------------
   if (g.with_feat) {
-    [[maybe_unused]] const float inv = H2 ? isa * h2_iws_at(iwsv, g.nh) : 1.f;
-    if constexpr (X3) mm.run(X, g.w3 + WP * g.wf_off, FH, n0, lane, acc, nullptr, 0, 0);   // (requested by the last hidden layer)
-    else layer_mma_nt<TI, NoHook, TJ>(X, g.packed + g.wf_off, FH, n0, lane, acc);
-    const float* bias = g.packed + g.bf_off;
-    const BufRsrc rc = tile_rsrc(g.cin + (size_t)row0 * g.Cinp, FT * g.Cinp * 4);
-    const unsigned rowb = (unsigned)g.Cinp * 4u;   // bytes per row of the albedo-net input
+    [[maybe_unused]] const float inv = H2 ? isa * h2_iws_at(iwsv, g.net.nh) : 1.f;
+    if constexpr (X3) mm.run(X, g.w3 + WP * g.net.wf_off, FH, n0, lane, acc, nullptr, 0, 0);   // (requested by the last hidden layer)
+    else layer_mma_nt<TI, NoHook, TJ>(X, g.packed + g.net.wf_off, FH, n0, lane, acc);
+    const float* bias = g.packed + g.net.bf_off;
+    const BufRsrc rc = tile_rsrc(g.cin + (size_t)row0 * g.net.Cinp, FT * g.net.Cinp * 4);
+    const unsigned rowb = (unsigned)g.net.Cinp * 4u;   // bytes per row of the albedo-net input
 #pragma unroll
     for (int tj = 0; tj < TJ; ++tj) {
       const int col = n0 + tj * 32 + cl;
-      if (col < g.F) {
+      if (col < g.net.F) {
         const float bc = bias[col];
         const unsigned voff = (unsigned)(4 * h) * rowb + (unsigned)col * 4u;
 #pragma unroll
@@ -462,89 +436,50 @@ bool fused_supported(const Layout& L) {
 
 // Fused replacement of launch_pe_points + sweep_forward (same outputs; pb.a / pb.D only when `save`).
 int fused_forward(const Layout& L, const float* packed, const float* pts, int64_t M, PointBufs& pb, bool save,
-                  bool need_feat, bool need_gz_last, hipStream_t s, const GridGen* grid) {
+                  bool need_feat, hipStream_t s, const GridGen* grid) {
   const int64_t fam_rows = family_rows_of(grid, pb.Mp);   // (a sparse sweep runs the dense grid's kernel family)
-  if (!save && use_reg_tile(L, fam_rows)) return sweep_mv_forward(L, packed, pts, M, pb, save, need_feat, need_gz_last, s, grid);
+  if (!save && use_reg_tile(L, fam_rows)) return sweep_mv_forward(L, packed, pts, M, pb, save, need_feat, s, grid);
+  const bool h2 = is_x2h(L);
   FusedFwdArgs g;
   memset(&g, 0, sizeof(g));
+  g.net = sdf_net_args(L);
   if (grid) g.grid = *grid;
   g.pts = pts;
   g.M = M;
   g.packed = packed;
-  const bool h2 = is_x2h(L);
   g.w3 = h2 ? x2h_mirror(L, packed) : reinterpret_cast<const x3raw*>(packed + L.total);
-  g.nh = L.nh;
-  g.skip = L.skip;
-  g.pe = L.pe;
-  g.multires = L.multires;
-  g.Ep = L.Ep;
-  g.scale = L.sdf_scale;
   for (int l = 0; l < L.nh; ++l) {
-    g.n_real[l] = L.hid[l].N;
-    g.Kp[l] = L.hid[l].Kp;
-    g.w_off[l] = L.hid[l].w_off;
-    g.b_off[l] = L.hid[l].b_off;
     g.a[l] = pb.a[l];
     g.D[l] = pb.D[l];
   }
-  g.wsdf_off = L.wsdf_off;
-  g.bsdf_off = L.bsdf_off;
   g.with_feat = need_feat ? 1 : 0;
-  g.F = L.F;
-  g.Cinp = L.Cinp;
-  g.wf_off = L.feat.w_off;
-  g.bf_off = L.feat.b_off;
   g.cin = pb.cin;
   g.sdf = pb.sdf;
   g.x4 = pb.x;
   g.e = pb.e;
-  // (the fused reverse sweep seeds itself from D_last: nobody asks this kernel for the seed any more)
-  if (need_gz_last) RNB_FAIL(RNB_E_INVALID, "fused forward sweep: the reverse sweep's seed is formed by fused_reverse_kernel");
-  g.gz_last = nullptr;
   g.h2tab = h2 ? h2_tab(L, packed) : nullptr;
   g.smax = (save && h2) ? pb.smax : nullptr;
-  // algorithmic FLOPs of the sweep (real layer shapes), for the optional event instrumentation
-  double fl = 0;
-  for (int l = 0; l < L.nh; ++l) fl += 2.0 * (double)M * L.hid[l].N * L.hid[l].K;
-  fl += 2.0 * (double)M * L.H;
-  if (need_feat) fl += 2.0 * (double)M * L.F * L.H;
-  ProfScope prof(fl, s, save ? "F_sweep(save)" : "F_sweep(forward_only)");
+  ProfScope prof(sdf_sweep_flops(L, M, 0, true, need_feat), s, save ? "F_sweep(save)" : "F_sweep(forward_only)");
   // 64-point tiles when that still gives every CU >= 2 workgroups, 32-point tiles for small batches
   const int force_ti = L.knob(RNB_VARIANT_FWD_TI_SHIFT);   // tuning knob: 1 or 2 forces the tile height
   const bool small = force_ti ? (force_ti == 1) : (fam_rows / 64 < 512);
   const int force_nw = L.knob(RNB_VARIANT_FWD_NW_SHIFT);   // tuning knob: 1 = 4 waves, 2 = 8 waves (small batches)
-  const bool x3 = is_x3(L);
+  const bool wide = force_nw ? (force_nw == 2) : (fam_rows / 32 <= 256);   // at most one workgroup per CU
   // (Measured and not kept: the 32-point form of the pre-split kernel for the sampling passes, and weight fragments four
   // steps ahead in the small-batch kernel: both 60 us per 8,192-point pass like the default — 256 workgroups each stream the
   // whole 3.5 MB of weight planes from L2, 0.9 GB per pass at the ~16 TB/s the L2s deliver for shared rows.)
-  if (small) {
-    const unsigned blocks = (unsigned)(pb.Mp / 32);
-    const bool wide = force_nw ? (force_nw == 2) : (fam_rows / 32 <= 256);   // at most one workgroup per CU
-    if (h2) {
-      if (save && wide) hipLaunchKernelGGL((fused_forward_kernel<1, true, 8, true, true>), dim3(blocks), dim3(512), 0, s, g);
-      else if (save) hipLaunchKernelGGL((fused_forward_kernel<1, true, 4, true, true>), dim3(blocks), dim3(256), 0, s, g);
-      else if (wide) hipLaunchKernelGGL((fused_forward_kernel<1, false, 8, true, true>), dim3(blocks), dim3(512), 0, s, g);
-      else hipLaunchKernelGGL((fused_forward_kernel<1, false, 4, true, true>), dim3(blocks), dim3(256), 0, s, g);
-    } else if (x3) {
-      if (save && wide) hipLaunchKernelGGL((fused_forward_kernel<1, true, 8, true>), dim3(blocks), dim3(512), 0, s, g);
-      else if (save) hipLaunchKernelGGL((fused_forward_kernel<1, true, 4, true>), dim3(blocks), dim3(256), 0, s, g);
-      else if (wide) hipLaunchKernelGGL((fused_forward_kernel<1, false, 8, true>), dim3(blocks), dim3(512), 0, s, g);
-      else hipLaunchKernelGGL((fused_forward_kernel<1, false, 4, true>), dim3(blocks), dim3(256), 0, s, g);
-    } else if (save && wide) hipLaunchKernelGGL((fused_forward_kernel<1, true, 8>), dim3(blocks), dim3(512), 0, s, g);
-    else if (save) hipLaunchKernelGGL((fused_forward_kernel<1, true>), dim3(blocks), dim3(256), 0, s, g);
-    else if (wide) hipLaunchKernelGGL((fused_forward_kernel<1, false, 8>), dim3(blocks), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL((fused_forward_kernel<1, false>), dim3(blocks), dim3(256), 0, s, g);
-  } else {
-    const unsigned blocks = (unsigned)(pb.Mp / 64);
-    if (h2) {
-      if (save) hipLaunchKernelGGL((fused_forward_kernel<2, true, 4, true, true>), dim3(blocks), dim3(256), 0, s, g);
-      else hipLaunchKernelGGL((fused_forward_kernel<2, false, 4, true, true>), dim3(blocks), dim3(256), 0, s, g);
-    } else if (x3) {
-      if (save) hipLaunchKernelGGL((fused_forward_kernel<2, true, 4, true>), dim3(blocks), dim3(256), 0, s, g);
-      else hipLaunchKernelGGL((fused_forward_kernel<2, false, 4, true>), dim3(blocks), dim3(256), 0, s, g);
-    } else if (save) hipLaunchKernelGGL((fused_forward_kernel<2, true>), dim3(blocks), dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((fused_forward_kernel<2, false>), dim3(blocks), dim3(256), 0, s, g);
-  }
+  // arithmetic: 0 = fp32 MFMA, 1 = x3, 2 = x2h; 8 waves exist for 32-point tiles only
+  pick_c<1, 0>(save, [&](auto save_c) {
+    pick_c<2, 1, 0>(h2 ? 2 : is_x3(L) ? 1 : 0, [&](auto ar_c) {
+      auto launch = [&](auto ti_c, auto nw_c) {
+        constexpr int TI = decltype(ti_c)::value, NW = decltype(nw_c)::value, AR = decltype(ar_c)::value;
+        hipLaunchKernelGGL((fused_forward_kernel<TI, decltype(save_c)::value != 0, NW, AR >= 1, AR == 2>),
+                           dim3((unsigned)(pb.Mp / (32 * TI))), dim3(64 * NW), 0, s, g);
+      };
+      if (!small) launch(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
+      else pick_c<8, 4>(wide ? 8 : 4, [&](auto nw_c) { launch(std::integral_constant<int, 1>{}, nw_c); });
+    });
+  });
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

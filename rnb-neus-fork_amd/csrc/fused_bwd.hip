@@ -24,12 +24,7 @@ namespace rnb {
 struct FusedBwdArgs {
   const float* packed;
   const x3raw* w3;      // RNB_VARIANT_X3: split mirror of the weight matrices (matrix at 3 x its float offset)
-  int nh, skip, pe, multires, Ep;
-  float inv_scale;
-  int n_real[RNB_MAX_LIN];   // real output width of hidden layer l
-  int Kp[RNB_MAX_LIN];       // padded input width of hidden layer l
-  long long w_off[RNB_MAX_LIN], wT_off[RNB_MAX_LIN];
-  long long wsdf_off, wfT_off;
+  SdfNetArgs net;
   float* D[RNB_MAX_LIN];
   float* gz[RNB_MAX_LIN];
   float* u[RNB_MAX_LIN + 1];
@@ -103,9 +98,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
   // seed: gz_{nh-1} = w_sdf * D_{nh-1}  (row 0 of the output layer is d sdf / d a_last)
   [[maybe_unused]] float sm = 0.f;
   {
-    const float* Dl = g.D[g.nh - 1] + (size_t)row0 * FH;
-    float* gzl = g.gz[g.nh - 1] + (size_t)row0 * FH;
-    const float* ws = g.packed + g.wsdf_off;
+    const float* Dl = g.D[g.net.nh - 1] + (size_t)row0 * FH;
+    float* gzl = g.gz[g.net.nh - 1] + (size_t)row0 * FH;
+    const float* ws = g.packed + g.net.wsdf_off;
     float m = 0.f;
     for (int idx = tid; idx < BT * FH / 4; idx += NT) {
       const int r = idx >> 6, c4 = idx & 63;
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
       if (lane == 0) wmx[wave] = sm;
       __syncthreads();
       const float tm = tile_max<NW>(wmx);
-      if (g.smax != nullptr && tid == 0) amax_tile_commit(g.smax + SMAX_GZ + g.nh - 1, tm);
+      if (g.smax != nullptr && tid == 0) amax_tile_commit(g.smax + SMAX_GZ + g.net.nh - 1, tm);
       x2h_dyn_scale(__builtin_bit_cast(unsigned, tm), sg, isg);
       const float f = sg * (1.f / SG);
       for (int idx = tid; idx < BT * FH / 4; idx += NT) {
@@ -148,23 +143,23 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
   AuxTile<TI, TJ> aD;
   [[maybe_unused]] X3Mma<TI, TJ, WP> mm;
   if constexpr (X3 && !(TI == 2 && TJ == 2)) {
-    if (g.nh > 1 || n0 < 64) mm.request(g.w3 + WP * g.wT_off[g.nh - 1], FH, n0, lane);
+    if (g.net.nh > 1 || n0 < 64) mm.request(g.w3 + WP * g.net.wT_off[g.net.nh - 1], FH, n0, lane);
   }
-  for (int l = g.nh - 1; l >= 1; --l) {
+  for (int l = g.net.nh - 1; l >= 1; --l) {
     // x2h: accumulator -> g: 1 / (scale of the tile x scale of this layer's matrix in the mirror)
     [[maybe_unused]] const float INV = H2 ? isg * h2_iws_at(iwsv, l) : 1.f;
-    const long long nxt = (l > 1 || n0 < 64) ? g.wT_off[l - 1] : -1;   // layer 0's product: the waves of columns 0..63
+    const long long nxt = (l > 1 || n0 < 64) ? g.net.wT_off[l - 1] : -1;   // layer 0's product: the waves of columns 0..63
     // x3, 64 x 64-output waves: the operand tile is requested AFTER the matrix loop, into the registers the loop's
     // fragments leave behind; the other workgroup of the CU multiplies while it travels
     constexpr bool LATE = X3 && TI == 2 && TJ == 2;
-    layer_mma<TI, TJ, X3>(X, g, g.wT_off[l], FH, n0, lane, acc, mm, nxt,   // g = gz_l W_l  (columns = inputs of layer l)
+    layer_mma<TI, TJ, X3>(X, g, g.net.wT_off[l], FH, n0, lane, acc, mm, nxt,   // g = gz_l W_l  (columns = inputs of layer l)
                      [&]() { if constexpr (!LATE) prefetch_tile<TI, TJ>(g.D[l - 1], row0, n0, lane, aD); });
     const int lane_e = opaque_lane(lane);   // the epilogue's per-lane offsets are rebuilt here, not carried through the loop
     const int h = lane_e >> 5;
     if constexpr (LATE) prefetch_tile<TI, TJ>(g.D[l - 1], row0, n0, lane_e, aD);
     if constexpr (NBUF == 1) lds_barrier();   // every wave has finished reading the tile
-    const bool is_skip = (l == g.skip);
-    const int ksplit = is_skip ? FH - g.pe : FH;   // columns that belong to layer l-1's output
+    const bool is_skip = (l == g.net.skip);
+    const int ksplit = is_skip ? FH - g.net.pe : FH;   // columns that belong to layer l-1's output
     const BufRsrc rg = tile_rsrc(g.gz[l - 1] + (size_t)row0 * FH, BT * FH * 4);
     [[maybe_unused]] float gm[2] = {0.f, 0.f};   // x2h: max |gz_{l-1}| of this thread
     for_each_acc_split<TI, TJ>(
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
           if (col < ksplit) {
             gzv = v * aD.v[ti][tj][r];
           } else {
-            if (col < ksplit + g.pe) GE[row * FEP + (col - ksplit)] = v;   // skip connection: straight to g_e
+            if (col < ksplit + g.net.pe) GE[row * FEP + (col - ksplit)] = v;   // skip connection: straight to g_e
             gzv = 0.f;
           }
           Y[row * FP + col] = gzv * SG;
@@ -211,9 +206,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
   // layer 0: g_e += gz_0 W_0 (Ep = 64 columns: the waves that own columns 0..63)
   if (n0 < 64) {
     [[maybe_unused]] const float INV = H2 ? isg * h2_iws_at(iwsv, 0) : 1.f;
-    layer_mma<TI, TJ, X3>(X, g, g.wT_off[0], FH, n0, lane, acc, mm, -1);
+    layer_mma<TI, TJ, X3>(X, g, g.net.wT_off[0], FH, n0, lane, acc, mm, -1);
     for_each_acc<TI, TJ>(n0, lane, [&](int tj, int ti, int r, int col, int rowc, int row) {
-      if (col < g.pe) GE[row * FEP + col] += acc[ti][tj][r] * INV;
+      if (col < g.net.pe) GE[row * FEP + col] += acc[ti][tj][r] * INV;
     });
   }
   __syncthreads();
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
     float n[3] = {ge[0], ge[1], ge[2]};
     float f = 1.f;
     int c = 3;
-    for (int k = 0; k < g.multires; ++k) {
+    for (int k = 0; k < g.net.multires; ++k) {
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
         float s, co;
@@ -236,7 +231,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
     }
     g.nrm[row * 4] = n[0]; g.nrm[row * 4 + 1] = n[1]; g.nrm[row * 4 + 2] = n[2]; g.nrm[row * 4 + 3] = 0.f;
     if (g.ge_out != nullptr)
-      for (int c = 0; c < g.pe; ++c) g.ge_out[row * g.Ep + c] = ge[c];
+      for (int c = 0; c < g.net.pe; ++c) g.ge_out[row * g.net.Ep + c] = ge[c];
   }
 }
 
@@ -262,9 +257,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
   const int n0 = wave * 32 * TJ;
 
   float gm = 0.f;   // max |geb| of the tile (its padding rows are written as zeros by nbar_geb_kernel: no mask)
-  for (int idx = tid; idx < BT * g.Ep; idx += NT) {
-    const int r = idx / g.Ep, c = idx - r * g.Ep;
-    const float v = g.geb[(row0 + r) * g.Ep + c];
+  for (int idx = tid; idx < BT * g.net.Ep; idx += NT) {
+    const int r = idx / g.net.Ep, c = idx - r * g.net.Ep;
+    const float v = g.geb[(row0 + r) * g.net.Ep + c];
     X[r * FP + c] = v;
     if (c < FEP) E[r * FEP + c] = v;
     gm = fmaxf(gm, fabsf(v));
@@ -284,11 +279,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
   v16f acc[TI][TJ];
   AuxTile<TI, TJ> aD, aG;
   [[maybe_unused]] X3Mma<TI, TJ> mm;
-  if constexpr (X3 && !(TI == 2 && TJ == 2)) mm.request(g.w3 + 3 * g.w_off[0], g.Kp[0], n0, lane);
-  for (int l = 0; l < g.nh; ++l) {
+  if constexpr (X3 && !(TI == 2 && TJ == 2)) mm.request(g.w3 + 3 * g.net.w_off[0], g.net.Kp[0], n0, lane);
+  for (int l = 0; l < g.net.nh; ++l) {
     // TI == 2: only one operand tile fits next to the weight fragments during the matrix loop; the second
     // one is requested right after it, into the registers the weight fragments leave behind
-    layer_mma<TI, TJ, X3>(X, g, g.w_off[l], g.Kp[l], n0, lane, acc, mm, l + 1 < g.nh ? g.w_off[l + 1] : -1,   // gzb = u_l W_l^T
+    layer_mma<TI, TJ, X3>(X, g, g.net.w_off[l], g.net.Kp[l], n0, lane, acc, mm, l + 1 < g.net.nh ? g.net.w_off[l + 1] : -1,   // gzb = u_l W_l^T
                      [&]() {
                        if constexpr (!(X3 && !BOTH_IN_LOOP)) prefetch_tile<TI, TJ>(g.D[l], row0, n0, lane, aD);
                        if constexpr (BOTH_IN_LOOP) prefetch_tile<TI, TJ>(g.gz[l], row0, n0, lane, aG);
@@ -298,10 +293,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
     if constexpr (X3 && !BOTH_IN_LOOP) prefetch_tile<TI, TJ>(g.D[l], row0, n0, lane_e, aD);   // (x3: both after the loop)
     if constexpr (!BOTH_IN_LOOP) prefetch_tile<TI, TJ>(g.gz[l], row0, n0, lane_e, aG);
     if constexpr (NBUF == 1) lds_barrier();
-    const int n_real = g.n_real[l];
-    const bool pe_tail = (l + 1 == g.skip);
+    const int n_real = g.net.n_real[l];
+    const bool pe_tail = (l + 1 == g.net.skip);
     const BufRsrc rzR = tile_rsrc(g.zR[l] + (size_t)row0 * FH, BT * FH * 4);
-    if (l + 1 == g.nh && g.ucol != nullptr) {
+    if (l + 1 == g.net.nh && g.ucol != nullptr) {
       // last layer: u_nh feeds nothing but the column sums of the sdf-head row gradient.  Every wave owns its columns
       // for all rows of the tile: sum the lane's 16 TI values per column tile, fold the two lane halves, one store per
       // column — 64 MB less to write here and to read there.  (No tile is written to LDS: nothing follows.)
@@ -349,7 +344,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
             zr = ((v - un) * aG.v[ti][tj][r]) * 100.f;
           } else {
             zr = 0.f;
-            un = (pe_tail && col < n_real + g.pe) ? E[row * FEP + (col - n_real)] : 0.f;
+            un = (pe_tail && col < n_real + g.net.pe) ? E[row * FEP + (col - n_real)] : 0.f;
           }
           Y[row * FP + col] = un;
           bstore(rzR, voff, soff, zr);
@@ -396,13 +391,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_f
   AuxTile<TI, TJ> aD, aZ;
   [[maybe_unused]] X3Mma<TI, TJ> mm;
   if constexpr (X3 && !(TI == 2 && TJ == 2)) {
-    if (g.fbar != nullptr) mm.request(g.w3 + 3 * g.wfT_off, FH, n0, lane);
-    else if (g.nh > 1) mm.request(g.w3 + 3 * g.wT_off[g.nh - 1], FH, n0, lane);
+    if (g.fbar != nullptr) mm.request(g.w3 + 3 * g.net.wfT_off, FH, n0, lane);
+    else if (g.net.nh > 1) mm.request(g.w3 + 3 * g.net.wT_off[g.net.nh - 1], FH, n0, lane);
   }
   constexpr bool LATE = X3 && TI == 2 && TJ == 2;   // operand tiles requested after the matrix loop (see fused_reverse_kernel)
   if constexpr (!LATE) {
-    prefetch_tile<TI, TJ>(g.D[g.nh - 1], row0, n0, lane, aD);
-    prefetch_tile<TI, TJ>(g.zR[g.nh - 1], row0, n0, lane, aZ);
+    prefetch_tile<TI, TJ>(g.D[g.net.nh - 1], row0, n0, lane, aD);
+    prefetch_tile<TI, TJ>(g.zR[g.net.nh - 1], row0, n0, lane, aZ);
   }
   for (int ti_ = 0; ti_ < TI; ++ti_) for (int tj_ = 0; tj_ < TJ; ++tj_) for (int r_ = 0; r_ < 16; ++r_) acc[ti_][tj_][r_] = 0.f;
   if (g.fbar != nullptr) {   // ab_{nh-1} = fbar W_feat (+ the sdf-head term below)
@@ -412,23 +407,23 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_f
       *reinterpret_cast<vf4*>(X + r * FP + c4 * 4) = *reinterpret_cast<const vf4*>(fb + (size_t)r * g.ld_fbar + c4 * 4);
     }
     __syncthreads();
-    layer_mma<TI, TJ, X3>(X, g, g.wfT_off, FH, n0, lane, acc, mm, g.nh > 1 ? g.wT_off[g.nh - 1] : -1);
+    layer_mma<TI, TJ, X3>(X, g, g.net.wfT_off, FH, n0, lane, acc, mm, g.net.nh > 1 ? g.net.wT_off[g.net.nh - 1] : -1);
     if constexpr (NBUF == 1) lds_barrier();
   }
   if constexpr (LATE) {
-    prefetch_tile<TI, TJ>(g.D[g.nh - 1], row0, n0, lane, aD);
-    prefetch_tile<TI, TJ>(g.zR[g.nh - 1], row0, n0, lane, aZ);
+    prefetch_tile<TI, TJ>(g.D[g.net.nh - 1], row0, n0, lane, aD);
+    prefetch_tile<TI, TJ>(g.zR[g.net.nh - 1], row0, n0, lane, aZ);
   }
-  for (int l = g.nh - 1; l >= 0; --l) {
+  for (int l = g.net.nh - 1; l >= 0; --l) {
     // epilogue of the product that produced ab_l: zb_l = ab_l * D_l + zR_l
     const int lane_e = opaque_lane(lane);   // (see fused_reverse_kernel)
     const int h = lane_e >> 5;
-    const int n_real = g.n_real[l];
-    const bool head = (l == g.nh - 1);
+    const int n_real = g.net.n_real[l];
+    const bool head = (l == g.net.nh - 1);
     const BufRsrc rzb = tile_rsrc(g.zb[l] + (size_t)row0 * FH, BT * FH * 4);
     if (head) {   // + sbar / scale * w_sdf  (the sdf head's contribution to ab_{nh-1}); once per launch
       for_each_acc<TI, TJ>(n0, lane_e, [&](int tj, int ti, int r, int col, int rowc, int row) {
-        acc[ti][tj][r] = fmaf(g.sbar[row0 + row] * g.inv_scale, g.packed[g.wsdf_off + col], acc[ti][tj][r]);
+        acc[ti][tj][r] = fmaf(g.sbar[row0 + row] * g.net.inv_scale, g.packed[g.net.wsdf_off + col], acc[ti][tj][r]);
       });
     }
     for_each_acc_split<TI, TJ>(
@@ -452,7 +447,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_f
     if (l == 0) break;
     lds_barrier();
     if constexpr (NBUF == 2) { float* t = X; X = Y; Y = t; }
-    layer_mma<TI, TJ, X3>(X, g, g.wT_off[l], FH, n0, lane, acc, mm, l > 1 ? g.wT_off[l - 1] : -1,   // ab_{l-1} = zb_l W_l
+    layer_mma<TI, TJ, X3>(X, g, g.net.wT_off[l], FH, n0, lane, acc, mm, l > 1 ? g.net.wT_off[l - 1] : -1,   // ab_{l-1} = zb_l W_l
                      [&]() {
                        if constexpr (!(X3 && !BOTH_IN_LOOP)) prefetch_tile<TI, TJ>(g.D[l - 1], row0, n0, lane, aD);
                        if constexpr (BOTH_IN_LOOP) prefetch_tile<TI, TJ>(g.zR[l - 1], row0, n0, lane, aZ);
@@ -491,10 +486,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_fb_h2_kernel(F
   X3Mma<TI, TJ, 2> mm;
   constexpr bool LATE = TJ == 2;   // 64 x 64-output waves: operand tiles requested after the matrix loop
   if constexpr (!LATE) {
-    if (g.fbar != nullptr) mm.request(g.w3 + 2 * g.wfT_off, FH, n0, lane);
-    else if (g.nh > 1) mm.request(g.w3 + 2 * g.wT_off[g.nh - 1], FH, n0, lane);
-    prefetch_tile<TI, TJ>(g.D[g.nh - 1], row0, n0, lane, aD);
-    prefetch_tile<TI, TJ>(g.zR[g.nh - 1], row0, n0, lane, aZ);
+    if (g.fbar != nullptr) mm.request(g.w3 + 2 * g.net.wfT_off, FH, n0, lane);
+    else if (g.net.nh > 1) mm.request(g.w3 + 2 * g.net.wT_off[g.net.nh - 1], FH, n0, lane);
+    prefetch_tile<TI, TJ>(g.D[g.net.nh - 1], row0, n0, lane, aD);
+    prefetch_tile<TI, TJ>(g.zR[g.net.nh - 1], row0, n0, lane, aZ);
   }
   for (int ti_ = 0; ti_ < TI; ++ti_) for (int tj_ = 0; tj_ < TJ; ++tj_) for (int r_ = 0; r_ < 16; ++r_) acc[ti_][tj_][r_] = 0.f;
   float unscale = 1.f;   // accumulator -> ab (true units)
@@ -519,25 +514,25 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_fb_h2_kernel(F
       *q = *q * s;
     }
     __syncthreads();
-    if constexpr (LATE) mm.request(g.w3 + 2 * g.wfT_off, FH, n0, lane);
-    mm.run(X, g.w3 + 2 * g.wfT_off, FH, n0, lane, acc, (!LATE && g.nh > 1) ? g.w3 + 2 * g.wT_off[g.nh - 1] : nullptr, FH, n0);
-    unscale = inv * h2_iws_at(iwsv, g.nh);   // (tile scale x the feature head's scale in the mirror)
+    if constexpr (LATE) mm.request(g.w3 + 2 * g.net.wfT_off, FH, n0, lane);
+    mm.run(X, g.w3 + 2 * g.net.wfT_off, FH, n0, lane, acc, (!LATE && g.net.nh > 1) ? g.w3 + 2 * g.net.wT_off[g.net.nh - 1] : nullptr, FH, n0);
+    unscale = inv * h2_iws_at(iwsv, g.net.nh);   // (tile scale x the feature head's scale in the mirror)
   }
   if constexpr (LATE) {
-    prefetch_tile<TI, TJ>(g.D[g.nh - 1], row0, n0, lane, aD);
-    prefetch_tile<TI, TJ>(g.zR[g.nh - 1], row0, n0, lane, aZ);
+    prefetch_tile<TI, TJ>(g.D[g.net.nh - 1], row0, n0, lane, aD);
+    prefetch_tile<TI, TJ>(g.zR[g.net.nh - 1], row0, n0, lane, aZ);
   }
-  for (int l = g.nh - 1; l >= 0; --l) {
+  for (int l = g.net.nh - 1; l >= 0; --l) {
     // phase 1 (registers and HBM only): zb_l = ab_l * D_l + zR_l, its maxima
     const int lane_e = opaque_lane(lane);
     const int h = lane_e >> 5;
-    const int n_real = g.n_real[l];
-    const bool head = (l == g.nh - 1);
+    const int n_real = g.net.n_real[l];
+    const bool head = (l == g.net.nh - 1);
     const int par = l & 1;
     const BufRsrc rzb = tile_rsrc(g.zb[l] + (size_t)row0 * FH, BT * FH * 4);
     if (head) {   // + sbar / scale * w_sdf  (the sdf head's contribution to ab_{nh-1}); once per launch
       for_each_acc<TI, TJ>(n0, lane_e, [&](int tj, int ti, int r, int col, int rowc, int row) {
-        acc[ti][tj][r] = fmaf(g.sbar[row0 + row] * g.inv_scale, g.packed[g.wsdf_off + col], acc[ti][tj][r] * unscale);
+        acc[ti][tj][r] = fmaf(g.sbar[row0 + row] * g.net.inv_scale, g.packed[g.net.wsdf_off + col], acc[ti][tj][r] * unscale);
       });
       unscale = 1.f;
     }
@@ -568,12 +563,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_fb_h2_kernel(F
     });
     lds_barrier();
     if constexpr (LATE) {
-      mm.request(g.w3 + 2 * g.wT_off[l], FH, n0, lane);
-      mm.run(X, g.w3 + 2 * g.wT_off[l], FH, n0, lane, acc, nullptr, 0, 0);   // ab_{l-1} = zb_l W_l
+      mm.request(g.w3 + 2 * g.net.wT_off[l], FH, n0, lane);
+      mm.run(X, g.w3 + 2 * g.net.wT_off[l], FH, n0, lane, acc, nullptr, 0, 0);   // ab_{l-1} = zb_l W_l
       prefetch_tile<TI, TJ>(g.D[l - 1], row0, n0, opaque_lane(lane), aD);
       prefetch_tile<TI, TJ>(g.zR[l - 1], row0, n0, opaque_lane(lane), aZ);
     } else {
-      mm.run(X, g.w3 + 2 * g.wT_off[l], FH, n0, lane, acc, l > 1 ? g.w3 + 2 * g.wT_off[l - 1] : nullptr, FH, n0, [&]() {
+      mm.run(X, g.w3 + 2 * g.net.wT_off[l], FH, n0, lane, acc, l > 1 ? g.w3 + 2 * g.net.wT_off[l - 1] : nullptr, FH, n0, [&]() {
         prefetch_tile<TI, TJ>(g.D[l - 1], row0, n0, lane, aD);
         prefetch_tile<TI, TJ>(g.zR[l - 1], row0, n0, lane, aZ);
       });
@@ -585,36 +580,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_fb_h2_kernel(F
 // ---------------------------------------------------------------------------------------------------------
 static void fill_args(const Layout& L, const float* packed, PointBufs& pb, FusedBwdArgs& g) {
   memset(&g, 0, sizeof(g));
+  g.net = sdf_net_args(L);
   g.packed = packed;
   g.w3 = reinterpret_cast<const x3raw*>(packed + L.total);
-  g.nh = L.nh;
-  g.skip = L.skip;
-  g.pe = L.pe;
-  g.multires = L.multires;
-  g.Ep = L.Ep;
-  g.inv_scale = 1.f / L.sdf_scale;
   for (int l = 0; l < L.nh; ++l) {
-    g.n_real[l] = L.hid[l].N;
-    g.Kp[l] = L.hid[l].Kp;
-    g.w_off[l] = L.hid[l].w_off;
-    g.wT_off[l] = L.hid[l].wT_off;
     g.D[l] = pb.D[l];
     g.gz[l] = pb.gz[l];
     g.zR[l] = pb.zR[l];
     g.zb[l] = pb.zb[l];
   }
   for (int l = 1; l <= L.nh; ++l) g.u[l] = pb.u[l];
-  g.wsdf_off = L.wsdf_off;
-  g.wfT_off = L.feat.wT_off;
   g.M = pb.M;
-  g.ucol = nullptr;
   g.x4 = pb.x;
   g.nrm = pb.nrm;
   g.geb = pb.geb;
   g.sbar = pb.sbar;
   g.amax = is_x2h(L) ? pb.amax : nullptr;
   g.h2tab = is_x2h(L) ? h2_tab(L, packed) : nullptr;
-  g.smax = nullptr;
 }
 
 // Variant of the three sweeps: tile height TI (32 / 64 points) x waves per workgroup NW (4: 64 columns per wave;
@@ -630,45 +612,31 @@ static void fill_args(const Layout& L, const float* packed, PointBufs& pb, Fused
 // point (32-point tiles ran at the CU's 64 B/clk fill rate, the matrix pipe 28-34 % busy) and the split work per MFMA;
 // the operand tiles of the epilogue are requested after the matrix loop, into the registers it frees, and travel while
 // the CU's other workgroup multiplies.
-static int bwd_nw(const Layout& L, int dflt) {
-  const int v = L.knob(RNB_VARIANT_BWD_NW_SHIFT);
-  return v == 1 ? 4 : v == 2 ? 8 : dflt;
-}
-
-static int bwd_ti(const Layout& L, int dflt) {
-  const int v = L.knob(RNB_VARIANT_BWD_TI_SHIFT);
-  return v == 1 || v == 2 ? v : dflt;
-}
-
-static double hidden_flops(const Layout& L, int64_t M, int first) {
-  double fl = 0;
-  for (int l = first; l < L.nh; ++l) fl += 2.0 * (double)M * L.hid[l].N * L.hid[l].K;
-  return fl;
+// pick_tile: that choice (knobs, else the defaults above) as f(TI, NW, grid, block) with TI, NW as constants
+template <class F>
+static void pick_tile(const Layout& L, const PointBufs& pb, F&& f) {
+  const int kt = L.knob(RNB_VARIANT_BWD_TI_SHIFT), kw = L.knob(RNB_VARIANT_BWD_NW_SHIFT);
+  const int ti = kt == 1 || kt == 2 ? kt : (is_x3(L) ? 2 : 1), nw = kw == 1 ? 4 : kw == 2 ? 8 : (is_x3(L) ? 4 : 8);
+  pick_c<2, 1>(ti, [&](auto ti_c) {
+    pick_c<8, 4>(nw, [&](auto nw_c) { f(ti_c, nw_c, dim3((unsigned)(pb.Mp / (32 * ti_c))), dim3(64 * nw_c)); });
+  });
 }
 
 int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool store_ge) {
   FusedBwdArgs g;
   fill_args(L, packed, pb, g);
   g.ge_out = store_ge ? pb.ge : nullptr;
-  ProfScope prof(hidden_flops(L, pb.M, 0), s, "R_sweep");
-  const int ti = bwd_ti(L, is_x3(L) ? 2 : 1), nw = bwd_nw(L, is_x3(L) ? 4 : 8);
-  const dim3 grid((unsigned)(pb.Mp / (32 * ti))), block(64 * nw);
   if (is_x2h(L)) {
     g.w3 = x2h_mirror(L, packed);
     g.smax = pb.smax;   // (nullptr outside a render forward)
-    if (ti == 2 && nw == 8) hipLaunchKernelGGL((fused_reverse_kernel<2, 8, true, true>), grid, block, 0, s, g);
-    else if (ti == 2) hipLaunchKernelGGL((fused_reverse_kernel<2, 4, true, true>), grid, block, 0, s, g);
-    else if (nw == 8) hipLaunchKernelGGL((fused_reverse_kernel<1, 8, true, true>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((fused_reverse_kernel<1, 4, true, true>), grid, block, 0, s, g);
-  } else if (is_x3(L)) {
-    if (ti == 2 && nw == 8) hipLaunchKernelGGL((fused_reverse_kernel<2, 8, true>), grid, block, 0, s, g);
-    else if (ti == 2) hipLaunchKernelGGL((fused_reverse_kernel<2, 4, true>), grid, block, 0, s, g);
-    else if (nw == 8) hipLaunchKernelGGL((fused_reverse_kernel<1, 8, true>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((fused_reverse_kernel<1, 4, true>), grid, block, 0, s, g);
-  } else if (ti == 2 && nw == 8) hipLaunchKernelGGL((fused_reverse_kernel<2, 8>), grid, block, 0, s, g);
-  else if (ti == 2) hipLaunchKernelGGL(fused_reverse_kernel<2>, grid, block, 0, s, g);
-  else if (nw == 8) hipLaunchKernelGGL((fused_reverse_kernel<1, 8>), grid, block, 0, s, g);
-  else hipLaunchKernelGGL(fused_reverse_kernel<1>, grid, block, 0, s, g);
+  }
+  ProfScope prof(sdf_sweep_flops(L, pb.M, 0, false, false), s, "R_sweep");
+  pick_tile(L, pb, [&](auto ti_c, auto nw_c, dim3 grid, dim3 block) {
+    pick_c<2, 1, 0>(is_x2h(L) ? 2 : is_x3(L) ? 1 : 0, [&](auto ar_c) {   // fp32 MFMA, x3, x2h
+      constexpr int AR = decltype(ar_c)::value;
+      hipLaunchKernelGGL((fused_reverse_kernel<decltype(ti_c)::value, decltype(nw_c)::value, AR >= 1, AR == 2>), grid, block, 0, s, g);
+    });
+  });
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -678,25 +646,19 @@ int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream
 int fused_ra(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, int* u_tiles) {
   FusedBwdArgs g;
   fill_args(L, packed, pb, g);
-  ProfScope prof(hidden_flops(L, pb.M, 0), s, "RA_sweep");
-  const int ti = bwd_ti(L, is_x3(L) ? 2 : 1), nw = bwd_nw(L, is_x3(L) ? 4 : 8);
-  if (u_tiles != nullptr) {
-    g.ucol = pb.u[L.nh];
-    *u_tiles = (int)(pb.Mp / (32 * ti));
-  }
-  const dim3 grid((unsigned)(pb.Mp / (32 * ti))), block(64 * nw);
+  ProfScope prof(sdf_sweep_flops(L, pb.M, 0, false, false), s, "RA_sweep");
   // RA stays on the six bf16 terms: it reads D_l, gz_l and writes zR_l, u_{l+1} — 2.1 GB per 65,536 points, 0.42 ms at
   // 5 TB/s against 0.45 ms measured: the matrix time hides under the state traffic.  (An x2h form with FB's two-phase
   // epilogue was built and measured in round 4 — 0.505 / 0.545 ms against 0.475, profiles/r04_ab_experiments.txt — and removed.)
-  if (is_x3(L)) {
-    if (ti == 2 && nw == 8) hipLaunchKernelGGL((fused_ra_kernel<2, 8, true>), grid, block, 0, s, g);
-    else if (ti == 2) hipLaunchKernelGGL((fused_ra_kernel<2, 4, true>), grid, block, 0, s, g);
-    else if (nw == 8) hipLaunchKernelGGL((fused_ra_kernel<1, 8, true>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((fused_ra_kernel<1, 4, true>), grid, block, 0, s, g);
-  } else if (ti == 2 && nw == 8) hipLaunchKernelGGL((fused_ra_kernel<2, 8>), grid, block, 0, s, g);
-  else if (ti == 2) hipLaunchKernelGGL(fused_ra_kernel<2>, grid, block, 0, s, g);
-  else if (nw == 8) hipLaunchKernelGGL((fused_ra_kernel<1, 8>), grid, block, 0, s, g);
-  else hipLaunchKernelGGL(fused_ra_kernel<1>, grid, block, 0, s, g);
+  pick_tile(L, pb, [&](auto ti_c, auto nw_c, dim3 grid, dim3 block) {
+    if (u_tiles != nullptr) {
+      g.ucol = pb.u[L.nh];
+      *u_tiles = (int)grid.x;
+    }
+    pick_c<1, 0>(is_x3(L), [&](auto x3_c) {
+      hipLaunchKernelGGL((fused_ra_kernel<decltype(ti_c)::value, decltype(nw_c)::value, decltype(x3_c)::value != 0>), grid, block, 0, s, g);
+    });
+  });
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -706,22 +668,20 @@ int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_colo
   fill_args(L, packed, pb, g);
   g.fbar = with_color ? pb.cinb : nullptr;
   g.ld_fbar = L.Cinp;
-  ProfScope prof(hidden_flops(L, pb.M, 1) + (with_color ? 2.0 * (double)pb.M * L.F * L.H : 0.0), s, "FB_sweep");
-  const int ti = bwd_ti(L, is_x3(L) ? 2 : 1), nw = bwd_nw(L, is_x3(L) ? 4 : 8);
-  const dim3 grid((unsigned)(pb.Mp / (32 * ti))), block(64 * nw);
-  if (is_x2h(L) && ti == 2) {   // three fp16 terms, per-tile scales (64-point tiles only: the in-place form)
-    g.w3 = x2h_mirror(L, packed);
-    if (nw == 8) hipLaunchKernelGGL((fused_fb_h2_kernel<8>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((fused_fb_h2_kernel<4>), grid, block, 0, s, g);
-  } else if (is_x3(L)) {
-    if (ti == 2 && nw == 8) hipLaunchKernelGGL((fused_fb_kernel<2, 8, true>), grid, block, 0, s, g);
-    else if (ti == 2) hipLaunchKernelGGL((fused_fb_kernel<2, 4, true>), grid, block, 0, s, g);
-    else if (nw == 8) hipLaunchKernelGGL((fused_fb_kernel<1, 8, true>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((fused_fb_kernel<1, 4, true>), grid, block, 0, s, g);
-  } else if (ti == 2 && nw == 8) hipLaunchKernelGGL((fused_fb_kernel<2, 8>), grid, block, 0, s, g);
-  else if (ti == 2) hipLaunchKernelGGL(fused_fb_kernel<2>, grid, block, 0, s, g);
-  else if (nw == 8) hipLaunchKernelGGL((fused_fb_kernel<1, 8>), grid, block, 0, s, g);
-  else hipLaunchKernelGGL(fused_fb_kernel<1>, grid, block, 0, s, g);
+  ProfScope prof(sdf_sweep_flops(L, pb.M, 1, false, with_color), s, "FB_sweep");
+  pick_tile(L, pb, [&](auto ti_c, auto nw_c, dim3 grid, dim3 block) {
+    constexpr int TI = decltype(ti_c)::value, NW = decltype(nw_c)::value;
+    if constexpr (TI == 2) {
+      if (is_x2h(L)) {   // three fp16 terms, per-tile scales (64-point tiles only: the in-place form)
+        g.w3 = x2h_mirror(L, packed);
+        hipLaunchKernelGGL((fused_fb_h2_kernel<NW>), grid, block, 0, s, g);
+        return;
+      }
+    }
+    pick_c<1, 0>(is_x3(L), [&](auto x3_c) {
+      hipLaunchKernelGGL((fused_fb_kernel<TI, NW, decltype(x3_c)::value != 0>), grid, block, 0, s, g);
+    });
+  });
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

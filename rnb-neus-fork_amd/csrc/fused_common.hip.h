@@ -18,14 +18,8 @@ struct FusedFwdArgs {
   const float* packed;
   const x3raw* w3;      // RNB_VARIANT_X3: split mirror of the weight matrices (matrix at 3 x its float offset;
                         // the fp16 mirror of the x2h kernels: at 2 x)
-  int nh, skip, pe, multires, Ep;
-  float scale;
-  int n_real[RNB_MAX_LIN];
-  int Kp[RNB_MAX_LIN];
-  long long w_off[RNB_MAX_LIN], b_off[RNB_MAX_LIN];
-  long long wsdf_off, bsdf_off;
-  int with_feat, F, Cinp;
-  long long wf_off, bf_off;
+  SdfNetArgs net;
+  int with_feat;
   float* cin;           // [Mp,Cinp] feature block destination (with_feat)
   float* sdf;           // [Mp]
   // saved state (SAVE only)
@@ -33,7 +27,6 @@ struct FusedFwdArgs {
   float* e;             // [Mp,Ep]
   float* a[RNB_MAX_LIN];
   float* D[RNB_MAX_LIN];
-  float* gz_last;       // [Mp,256] seed of the reverse sweep: w_sdf * D_last (optional)
   GridGen grid;         // on: points come from the regular grid, sdf (scaled) goes to rows < M only
   const H2Tab* h2tab;   // RNB_VARIANT_X2H: scales of the fp16 mirror's matrices (hidden layer l: id l, feature head: id nh)
   unsigned* smax;       // SAVE (render forward only): PointBufs::smax, grown by the tile maxima of e, a_l and the features; or nullptr

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/rnbneus.h"
 
 namespace rnb {
@@ -90,6 +92,58 @@ struct Layout {
 
 int make_layout(const rnb_model_desc* d, Layout* L);
 
+// The SDF network as its sweep kernels read it (fused.hip / fused_bwd.hip, sweep_mv.hip, bf16.hip): the layer table of the
+// Layout, by value inside every sweep's argument struct.  Offsets are float offsets into the packed buffer.
+struct SdfNetArgs {
+  int nh, skip, pe, multires, Ep;
+  float scale, inv_scale;      // sdf_scale and its reciprocal
+  int n_real[RNB_MAX_LIN];     // real output width of hidden layer l
+  int Kp[RNB_MAX_LIN];         // padded input width of hidden layer l
+  long long w_off[RNB_MAX_LIN], b_off[RNB_MAX_LIN], wT_off[RNB_MAX_LIN];
+  long long wsdf_off, bsdf_off;
+  int F, Cinp;                 // feature head: real rows, padded width of the albedo-net input it is written into
+  long long wf_off, bf_off, wfT_off;
+};
+inline SdfNetArgs sdf_net_args(const Layout& L) {
+  SdfNetArgs n;
+  memset(&n, 0, sizeof(n));
+  n.nh = L.nh; n.skip = L.skip; n.pe = L.pe; n.multires = L.multires; n.Ep = L.Ep;
+  n.scale = L.sdf_scale;
+  n.inv_scale = 1.f / L.sdf_scale;
+  for (int l = 0; l < L.nh; ++l) {
+    n.n_real[l] = L.hid[l].N;
+    n.Kp[l] = L.hid[l].Kp;
+    n.w_off[l] = L.hid[l].w_off;
+    n.b_off[l] = L.hid[l].b_off;
+    n.wT_off[l] = L.hid[l].wT_off;
+  }
+  n.wsdf_off = L.wsdf_off;
+  n.bsdf_off = L.bsdf_off;
+  n.F = L.F;
+  n.Cinp = L.Cinp;
+  n.wf_off = L.feat.w_off; n.bf_off = L.feat.b_off; n.wfT_off = L.feat.wT_off;
+  return n;
+}
+// algorithmic FLOPs of an SDF-network sweep over M points: hidden layers first .. nh - 1, the sdf row, the feature head
+inline double sdf_sweep_flops(const Layout& L, int64_t M, int first, bool sdf_row, bool feat) {
+  double fl = 0;
+  for (int l = first; l < L.nh; ++l) fl += mm_flops(M, L.hid[l]);
+  if (sdf_row) fl += 2.0 * (double)M * L.H;
+  if (feat) fl += 2.0 * (double)M * L.F * L.H;
+  return fl;
+}
+
+// Run-time value -> template argument: pick_c<A, B, ...>(v, f) calls f(std::integral_constant<int, X>{}) for the listed X
+// that equals v (the last one listed takes every other v).  Nested, they map a launcher's run-time choices to ONE kernel
+// instantiation that is called directly: only the listed combinations are instantiated, and the launch takes its block size
+// from the same constants as the kernel's __launch_bounds__.
+template <int V0, int... Vs, class F>
+inline void pick_c(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+  else if (v == V0) f(std::integral_constant<int, V0>{});
+  else pick_c<Vs...>(v, f);
+}
+
 #if defined(__HIPCC__)
 // torch.clamp / torch.minimum / torch.max / F.relu PROPAGATE NaN; fmaxf / fminf (v_max_f32 / v_min_f32) return the
 // other operand.  A diverged model must come back as NaN exactly where the reference's does, so the element-wise
@@ -169,6 +223,53 @@ __device__ inline int64_t grid_out_index(const GridGen& g, int64_t row, int64_t 
   if (g.on == GRID_DENSE) return row < M ? row : -1;
   int ix, iy, iz;
   return grid_locate(g, row, M, ix, iy, iz);
+}
+
+// ---- the front and the tail the forward sweeps share (fused.hip, sweep_mv.hip, bf16.hip) ----
+// The scaled point of row `row` of a sweep over M rows: the grid sample of the row (grid.on: dense slab, brick list or
+// brick-corner lattice) or row `row` of pts, times scale; masked and padding rows compute on the origin.
+__device__ inline void sweep_point(const GridGen& grid, const float* pts, int64_t row, int64_t M, float scale, float (&x)[3]) {
+  x[0] = x[1] = x[2] = 0.f;
+  if (row < M) {
+    if (grid.on) {
+      const int res = grid.res;
+      int ix, iy, iz;
+      if (grid_locate(grid, row, M, ix, iy, iz) >= 0) {
+        x[0] = linspace_at(grid.bmin[0], grid.bmax[0], res, ix) * scale;
+        x[1] = linspace_at(grid.bmin[1], grid.bmax[1], res, iy) * scale;
+        x[2] = linspace_at(grid.bmin[2], grid.bmax[2], res, iz) * scale;
+      }
+    } else {
+      x[0] = pts[row * 3] * scale;
+      x[1] = pts[row * 3 + 1] * scale;
+      x[2] = pts[row * 3 + 2] * scale;
+    }
+  }
+}
+// The sdf of row row0 + r (r: the row inside the tile at row0) -> its place: sdf[row], or with a grid the sample's entry of
+// the volume times out_scale (the volume has exactly M entries; brick mode scatters — a face sample shared by two listed
+// bricks is written by both with the same bits: same coordinates, same kernel family, rows independent of their tile mates;
+// masked rows store nothing).
+__device__ inline void sweep_store_sdf(const GridGen& grid, float* sdf, int64_t row0, int r, int64_t M, float v) {
+  if (!grid.on) sdf[row0 + r] = v;
+  else {
+    const int64_t o = grid_out_index(grid, row0 + r, M);
+    if (o >= 0) sdf[o] = v * grid.out_scale;
+  }
+}
+// The sin / cos columns of the positional encoding [x, sin(2^k x), cos(2^k x)]_k of one point (models/embedder.py:40-46),
+// frequencies k = k0, k0 + kstep, ...: put(c, sin, cos) gets column c = 3 + 6 k + d of the sine; the cosine's is c + 3.
+template <class Put>
+__device__ inline void pe_sincos(const float (&x)[3], int multires, int k0, int kstep, Put put) {
+  for (int k = k0; k < multires; k += kstep) {
+    const float f = (float)(1 << k);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      float s, co;
+      sincosf(x[d] * f, &s, &co);
+      put(3 + 6 * k + d, s, co);
+    }
+  }
 }
 #endif
 
@@ -330,12 +431,12 @@ int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_colo
 // ---- fused sweeps for hidden width 256 (fused.hip) ---------------------------------------------------
 bool fused_supported(const Layout& L);
 int fused_forward(const Layout& L, const float* packed, const float* pts, int64_t M, PointBufs& pb, bool save,
-                  bool need_feat, bool need_gz_last, hipStream_t s, const GridGen* grid = nullptr);
+                  bool need_feat, hipStream_t s, const GridGen* grid = nullptr);
 // ---- M/V sweeps (sweep_mv.hip): x3 arithmetic, matrix waves (32 points each, transposed product, weights through an
 // LDS-DMA ring) + vector waves (epilogues, saved state, operand split) ----
 bool sweep_mv_supported(const Layout& L);
 int sweep_mv_forward(const Layout& L, const float* packed, const float* pts, int64_t M, PointBufs& pb, bool save,
-                     bool need_feat, bool need_gz_last, hipStream_t s, const GridGen* grid = nullptr);
+                     bool need_feat, hipStream_t s, const GridGen* grid = nullptr);
 // family of a sweep over Mp points: the M/V kernels need >= one 128-point workgroup per CU to fill the chip
 constexpr bool kRegTileDefault = false;
 inline bool use_reg_tile(const Layout& L, int64_t Mp) {

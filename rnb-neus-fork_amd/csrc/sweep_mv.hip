@@ -436,7 +436,7 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
   pr.pl = pr.acc + MV_ACC_BYTES;
   pr.sync = (LDSP(int))(lds3 + MV_NSLOT * MV_SLOT + MV_MW * MV_PAIR_BYTES) + m * MV_SYNC;
   LDSP(float) const Bsh = (LDSP(float))(lds3 + MV_NSLOT * MV_SLOT + MV_MW * MV_PAIR_BYTES + MV_MW * MV_SYNC * 4);   // [nh + 1][256]
-  const int nprod = g.nh + (g.with_feat ? 1 : 0);
+  const int nprod = g.net.nh + (g.with_feat ? 1 : 0);
   MV_STAMP(0);
   MV_STAMP_REAL(60);
 
@@ -490,8 +490,8 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
   // latency into a barrier-paced window)
   {
     const int t4 = tid - 64 * MV_MW;   // 0..255 over the four V waves
-    for (int l = 0; l < g.nh; ++l) Bsh[l * FH + t4] = g.packed[g.b_off[l] + t4];
-    Bsh[g.nh * FH + t4] = g.packed[g.wsdf_off + t4];
+    for (int l = 0; l < g.net.nh; ++l) Bsh[l * FH + t4] = g.packed[g.net.b_off[l] + t4];
+    Bsh[g.net.nh * FH + t4] = g.packed[g.net.wsdf_off + t4];
   }
 
   // ---- positional encoding of the pair's 32 points -> staging tile (aliases the planes ring) ----------------------
@@ -499,39 +499,19 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
   {
     const int pp = lane & 31, hh = lane >> 5;
     const int64_t row = row0 + pp;
-    float x[3] = {0.f, 0.f, 0.f};
-    if (row < g.M) {
-      if (g.grid.on) {   // the grid sample of this row (dense slab, brick list or brick-corner lattice: grid_locate)
-        const int res = g.grid.res;
-        int ix, iy, iz;
-        if (grid_locate(g.grid, row, g.M, ix, iy, iz) >= 0) {
-          x[0] = linspace_at(g.grid.bmin[0], g.grid.bmax[0], res, ix) * g.scale;
-          x[1] = linspace_at(g.grid.bmin[1], g.grid.bmax[1], res, iy) * g.scale;
-          x[2] = linspace_at(g.grid.bmin[2], g.grid.bmax[2], res, iz) * g.scale;
-        }
-      } else {
-        x[0] = g.pts[row * 3] * g.scale;
-        x[1] = g.pts[row * 3 + 1] * g.scale;
-        x[2] = g.pts[row * 3 + 2] * g.scale;
-      }
-    }
+    float x[3];
+    sweep_point(g.grid, g.pts, row, g.M, g.net.scale, x);
     LDSP(float) er = E + pp * MV_EP;
     if (hh == 0) {
       er[0] = x[0]; er[1] = x[1]; er[2] = x[2];
-      for (int cc = g.pe; cc < 64; ++cc) er[cc] = 0.f;
+      for (int cc = g.net.pe; cc < 64; ++cc) er[cc] = 0.f;
       if (SAVE) *reinterpret_cast<vf4*>(g.x4 + row * 4) = vf4{x[0], x[1], x[2], 0.f};
     }
-    for (int k = hh; k < g.multires; k += 2) {   // the two lanes of a point share the frequencies
-      const float f = (float)(1 << k);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float s, co;
-        sincosf(x[d] * f, &s, &co);
-        const int cc = 3 + 6 * k + d;
-        er[cc] = s;
-        er[cc + 3] = co;
-      }
-    }
+    // (the two lanes of a point share the frequencies)
+    pe_sincos(x, g.net.multires, hh, 2, [&](int cc, float s, float co) {
+      er[cc] = s;
+      er[cc + 3] = co;
+    });
   }
   // (one wave wrote the tile and reads it: LDS instructions of a wave execute in order)
   vf4 pe0[2][4];      // PE in the V layout: blocks 0, 1 (features 0..63) of the four points
@@ -542,7 +522,7 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
   // the PE columns of the skip connection as they will sit in blocks 6, 7 of the layer that feeds it
   vf4 sk[2][4];
   {
-    const int nr = g.skip >= 1 ? g.n_real[g.skip - 1] : FH;
+    const int nr = g.net.skip >= 1 ? g.net.n_real[g.net.skip - 1] : FH;
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
@@ -553,7 +533,7 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
           const int idx = 32 * (6 + jb) + 4 * v.c + x - nr;
           const int ic = idx < 0 ? 0 : (idx > 63 ? 63 : idx);
           const float pv = E[(8 * i + v.p8) * MV_EP + ic];
-          t[x] = (idx >= 0 && idx < g.pe) ? pv : 0.f;
+          t[x] = (idx >= 0 && idx < g.net.pe) ? pv : 0.f;
         }
         sk[jb][i] = vf4{t[0], t[1], t[2], t[3]};
       }
@@ -590,11 +570,11 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
   auto epi = [&](int l) __attribute__((always_inline)) {
     MvEpi e;
     e.bias = Bsh + l * FH + 4 * v.c;
-    e.ws = (l + 1 == g.nh) ? Bsh + g.nh * FH + 4 * v.c : nullptr;
+    e.ws = (l + 1 == g.net.nh) ? Bsh + g.net.nh * FH + 4 * v.c : nullptr;
     e.a = SAVE ? g.a[l] + 4 * v.c : nullptr;
     e.D = SAVE ? g.D[l] + 4 * v.c : nullptr;
-    e.n_real = g.n_real[l];
-    e.pe_tail = (l + 1 == g.skip);
+    e.n_real = g.net.n_real[l];
+    e.pe_tail = (l + 1 == g.net.skip);
     return e;
   };
   // the whole task of block j (both halves) + its planes into steps 2 j, 2 j + 1 of the NEXT product (first step slot nslot0)
@@ -618,7 +598,7 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
     // ---- window of product pi's last step: drain its 8 blocks; block 0's task is on the M wave's critical path -------
     const int nks = pi == 0 ? 4 : 16;
     const int nslot0 = (gs + nks) % MV_PLN;       // ring slot of the next product's step 0
-    const bool hidden = pi < g.nh;
+    const bool hidden = pi < g.net.nh;
     MvEpi e = epi(hidden ? pi : 0);
 #pragma unroll
     for (int b = 0; b < 8; ++b) mv_v_drain(v, pr, nblk, vacc[b], lane);   // (nothing else meanwhile: the M wave hands a block over every ~230 clocks)
@@ -644,14 +624,14 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
           mv_v_act<SAVE, 2>(v, e, j, 2, vacc[j], sk, act, sacc);
         }
       } else {        // feature head: rows 1.. of the output layer into the albedo network's input
-        const float* bf = g.packed + g.bf_off + 4 * v.c;
+        const float* bf = g.packed + g.net.bf_off + 4 * v.c;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const vf4 bv = *reinterpret_cast<const vf4*>(bf + 32 * j);
-          if (32 * j + 4 * v.c < g.F) {
+          if (32 * j + 4 * v.c < g.net.F) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              __builtin_nontemporal_store(vacc[j][i] + bv, reinterpret_cast<vf4*>(g.cin + v.row[i] * g.Cinp + 32 * j + 4 * v.c));
+              __builtin_nontemporal_store(vacc[j][i] + bv, reinterpret_cast<vf4*>(g.cin + v.row[i] * g.net.Cinp + 32 * j + 4 * v.c));
           }
         }
       }
@@ -685,12 +665,12 @@ __global__ __launch_bounds__(128 * MV_MW, 2) void sweep_mv_forward_kernel(MvFwdA
     s += __shfl_xor(s, 2, 64);
     s += __shfl_xor(s, 4, 64);
     if (v.c == 0) {
-      float val = (s + g.packed[g.bsdf_off]) / g.scale;
+      float val = (s + g.packed[g.net.bsdf_off]) / g.net.scale;
       // a bounded wait of this pair gave up (never expected): what was computed is wrong — return NaN, the library's way of
       // failing loudly without a device synchronisation (the host cannot see the error word before the caller syncs)
       if (*(LDSP(volatile int))(pr.sync + 3) != 0) val = __builtin_nanf("");
       if (!g.grid.on) g.sdf[v.row[i]] = val;
-      else {   // the volume has exactly M entries; brick mode scatters (shared face samples: same bits, see fused.hip)
+      else {   // the volume has exactly M entries; brick mode scatters (shared face samples: same bits, see sweep_store_sdf)
         const int64_t o = grid_out_index(g.grid, v.row[i], g.M);
         if (o >= 0) g.sdf[o] = val * g.grid.out_scale;
       }
@@ -709,59 +689,37 @@ bool sweep_mv_supported(const Layout& L) {
 }
 
 int sweep_mv_forward(const Layout& L, const float* packed, const float* pts, int64_t M, PointBufs& pb, bool save,
-                     bool need_feat, bool need_gz_last, hipStream_t s, const GridGen* grid) {
-  if (need_gz_last) RNB_FAIL(RNB_E_INVALID, "M/V forward: the fused reverse sweep seeds itself (no gz_last)");
+                     bool need_feat, hipStream_t s, const GridGen* grid) {
   // (the saved-state form exists and is correct, but its vector waves spill — round 4 state, DESIGN 4 — and it is not wired in)
   if (save) RNB_FAIL(RNB_E_INVALID, "M/V forward: forward-only sweeps only");
   MvFwdArgs ga;
   memset(&ga, 0, sizeof(ga));
   FusedFwdArgs& g = ga.f;
+  g.net = sdf_net_args(L);
   if (grid) g.grid = *grid;
   g.pts = pts;
   g.M = M;
   g.packed = packed;
   g.w3 = reinterpret_cast<const x3raw*>(packed + L.total);
-  g.nh = L.nh;
-  g.skip = L.skip;
-  g.pe = L.pe;
-  g.multires = L.multires;
-  g.Ep = L.Ep;
-  g.scale = L.sdf_scale;
+  ga.st.nmat = L.nh + (need_feat ? 1 : 0);
+  for (int i = 0; i < ga.st.nmat; ++i) {
+    const Lin& ln = i < L.nh ? L.hid[i] : L.feat;
+    ga.st.nks[i] = ln.Kp / 16;
+    ga.st.boff[i] = (unsigned)(6 * ln.w_off);
+  }
   for (int l = 0; l < L.nh; ++l) {
-    g.n_real[l] = L.hid[l].N;
-    g.Kp[l] = L.hid[l].Kp;
-    g.w_off[l] = L.hid[l].w_off;
-    g.b_off[l] = L.hid[l].b_off;
     g.a[l] = pb.a[l];
     g.D[l] = pb.D[l];
-    ga.st.nks[l] = L.hid[l].Kp / 16;
-    ga.st.boff[l] = (unsigned)(6 * L.hid[l].w_off);
   }
-  ga.st.nmat = L.nh;
-  if (need_feat) {
-    ga.st.nks[L.nh] = L.feat.Kp / 16;
-    ga.st.boff[L.nh] = (unsigned)(6 * L.feat.w_off);
-    ga.st.nmat = L.nh + 1;
-  }
-  g.wsdf_off = L.wsdf_off;
-  g.bsdf_off = L.bsdf_off;
   g.with_feat = need_feat ? 1 : 0;
-  g.F = L.F;
-  g.Cinp = L.Cinp;
-  g.wf_off = L.feat.w_off;
-  g.bf_off = L.feat.b_off;
   g.cin = pb.cin;
   g.sdf = pb.sdf;
   g.x4 = pb.x;
   g.e = pb.e;
-  double fl = 0;
-  for (int l = 0; l < L.nh; ++l) fl += 2.0 * (double)M * L.hid[l].N * L.hid[l].K;
-  fl += 2.0 * (double)M * L.H;
-  if (need_feat) fl += 2.0 * (double)M * L.F * L.H;
-  ProfScope prof(fl, s, save ? "F_sweep(save)" : "F_sweep(forward_only)");
-  const unsigned blocks = (unsigned)(pb.Mp / MV_PT);   // (Mp is a multiple of 128)
-  if (save) hipLaunchKernelGGL((sweep_mv_forward_kernel<true>), dim3(blocks), dim3(128 * MV_MW), 0, s, ga);
-  else hipLaunchKernelGGL((sweep_mv_forward_kernel<false>), dim3(blocks), dim3(128 * MV_MW), 0, s, ga);
+  ProfScope prof(sdf_sweep_flops(L, M, 0, true, need_feat), s, save ? "F_sweep(save)" : "F_sweep(forward_only)");
+  const dim3 blocks((unsigned)(pb.Mp / MV_PT)), threads(128 * MV_MW);   // (Mp is a multiple of 128)
+  if (save) hipLaunchKernelGGL((sweep_mv_forward_kernel<true>), blocks, threads, 0, s, ga);
+  else hipLaunchKernelGGL((sweep_mv_forward_kernel<false>), blocks, threads, 0, s, ga);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

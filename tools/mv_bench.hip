@@ -66,27 +66,33 @@ int main(int argc, char** argv) {
   unsigned long long* stamps;
   CK(hipMalloc(&stamps, (size_t)blocks * 64 * 8));
   CK(hipMemset(stamps, 0, (size_t)blocks * 64 * 8));
+  // the network as make_layout describes it, through the library's own filler
+  Layout L;
+  memset(&L, 0, sizeof(L));
+  L.nh = nh; L.skip = 4; L.pe = 39; L.multires = 6; L.Ep = 64; L.sdf_scale = 1.f;
+  for (int l = 0; l < nh; ++l) {
+    L.hid[l].N = (l + 1 == 4) ? 217 : 256;
+    L.hid[l].Kp = l == 0 ? 64 : 256;
+    L.hid[l].w_off = w_off[l]; L.hid[l].b_off = b_off[l];
+  }
+  L.wsdf_off = wsdf; L.bsdf_off = bsdf;
   MvFwdArgs ga;
   memset(&ga, 0, sizeof(ga));
   FusedFwdArgs& g = ga.f;
+  g.net = sdf_net_args(L);
   g.pts = pts; g.M = M; g.packed = packed;
   g.w3 = reinterpret_cast<const x3raw*>(packed + total);
-  g.nh = nh; g.skip = 4; g.pe = 39; g.multires = 6; g.Ep = 64; g.scale = 1.f;
   if (save) {
     CK(hipMalloc(&state, (size_t)M * 256 * 4 * 2 * nh));
     CK(hipMalloc(&x4, (size_t)M * 16));
     CK(hipMalloc(&ebuf, (size_t)M * 64 * 4));
   }
   for (int l = 0; l < nh; ++l) {
-    g.n_real[l] = (l + 1 == 4) ? 217 : 256;
-    g.Kp[l] = l == 0 ? 64 : 256;
-    g.w_off[l] = w_off[l]; g.b_off[l] = b_off[l];
-    ga.st.nks[l] = g.Kp[l] / 16;
+    ga.st.nks[l] = L.hid[l].Kp / 16;
     ga.st.boff[l] = (unsigned)(6 * w_off[l]);
     if (save) { g.a[l] = state + (size_t)(2 * l) * M * 256; g.D[l] = state + (size_t)(2 * l + 1) * M * 256; }
   }
   ga.st.nmat = nh;
-  g.wsdf_off = wsdf; g.bsdf_off = bsdf;
   g.sdf = sdf; g.x4 = x4; g.e = ebuf;
   ga.stamps = stamps;
   int* errw;
