@@ -415,6 +415,26 @@ int rnb_render_bwd_inputs(const rnb_model_desc* desc, const float* packed, const
                           const rnb_render_grads* gout, const rnb_render_input_grads* igrads, float* packed_grad,
                           float* variance_grad, void* ws, size_t ws_bytes, rnb_stream_t stream);
 
+/* ---- whole-image rendering ------------------------------------------------------------------------
+ * rnb_render_maps: a forward-only render that returns per-ray IMAGES instead of the training dictionary — what
+ * validate_image (exp_runner.py:460-470) reduces from weights / gradients / inside_sphere with torch ops per batch, plus
+ * the albedo and depth maps.  Same inputs, modes, flags and limits as rnb_render_fwd (a larger S or light count is refused
+ * with the same messages before any launch) and the same launches up to the composite, so for the same inputs color,
+ * weight_sum and weight_max are bit-equal to rnb_render_fwd's.  No [B,S] array is written: the per-sample output pointers
+ * of `args` are ignored (they may be NULL).  Always forward-only: the workspace is the one
+ * rnb_render_workspace_bytes(desc, B, S, flags | RNB_FLAG_FORWARD_ONLY) sizes, RNB_FLAG_INPUT_GRADS is RNB_E_INVALID.
+ * Every map is optional (NULL = not wanted); all NULL is RNB_E_INVALID. */
+typedef struct rnb_render_maps_out {
+  float* color;       /* MVPS: [L,B,C]  CORE: [B,3] (background included): color_fine of the wrapper */
+  float* normal;      /* [B,3]  sum_s w_s n_s [|p_s| < 1]                                            */
+  float* albedo;      /* [B,C]  sum_s w_s albedo_s ; MVPS with the albedo network only, else RNB_E_INVALID */
+  float* depth;       /* [B]    sum_s w_s (z_s + dists_s / 2)                                        */
+  float* weight_sum;  /* [B] */
+  float* weight_max;  /* [B] */
+} rnb_render_maps_out;
+int rnb_render_maps(const rnb_model_desc* desc, const float* packed, const rnb_render_args* args,
+                    const rnb_render_maps_out* maps, void* ws, size_t ws_bytes, rnb_stream_t stream);
+
 /* Name/duration of the heaviest kernel family, for bench.py's roofline line: fills `flops` with the
  * algorithmic MLP FLOPs of one rnb_render_fwd+bwd (+ sampling) at the given shape. */
 int rnb_algorithmic_flops(const rnb_model_desc* desc, int64_t B, int32_t flags, double* train_flops,
@@ -462,6 +482,21 @@ int rnb_gen_rays_at_view(const float* intrinsics_inv, const float* pose, const f
                          const float* light_directions, const int64_t* pixels_x, const int64_t* pixels_y, int64_t B,
                          int32_t n_lights, int32_t H, int32_t W, float* data, float* true_rgb,
                          float* true_rgb_warmup, float* lights_dir, float* near, float* far, rnb_stream_t stream);
+
+/* Rays of a whole view (Dataset.gen_rays_at / gen_rays_between, models/dataset.py:300-326, :401-446) with the per-pixel
+ * gathers of validate_image (exp_runner.py:409-410, :448), one launch: the rays [first, first + n) of the row-major
+ * Hl x Wl grid whose pixel coordinates are tx [Wl] and ty [Hl] (device floats: torch.linspace(0, W - 1, W // l) made by
+ * the caller, so the coordinates carry torch's bits).  intrinsics_inv / pose as rnb_gen_rays_at_view (pose may be an
+ * interpolated one).  The optional sources mask [H,W,mask_channels], images, images_warmup, light_directions [n_lights,
+ * H,W,3] are read at (rintf(ty), rintf(tx)): round-half-to-even, as torch.round.  `light`: one light index, or -1 for
+ * all n_lights; Lo = 1 or n_lights.
+ * Outputs: data [n,7] = rays_o | rays_v | mask (mask column 0 when mask is NULL); true_rgb, true_rgb_warmup, lights_dir
+ * [Lo,n,3] (each NULL with or without its source); near, far [n] (both or neither). */
+int rnb_gen_rays_grid(const float* intrinsics_inv, const float* pose, const float* tx, const float* ty, int32_t Wl,
+                      int32_t Hl, int64_t first, int64_t n, const float* images, const float* images_warmup,
+                      const float* mask, int32_t mask_channels, const float* light_directions, int32_t n_lights,
+                      int32_t light, int32_t H, int32_t W, float* data, float* true_rgb, float* true_rgb_warmup,
+                      float* lights_dir, float* near, float* far, rnb_stream_t stream);
 
 /* The loss of train_rnb (exp_runner.py:241-258) and its gradients with respect to the renderer outputs, one
  * launch:  loss = sum|(color_fine - true_rgb) * mask| / ((sum(mask) + 1e-5) * n_lights)

@@ -851,6 +851,48 @@ RNB_API int rnb_render_fwd(const rnb_model_desc* desc, const float* packed, cons
   return RNB_OK;
 }
 
+// Whole-image rendering: rnb_render_fwd's launches up to the composite, then the per-ray maps (composite_maps_kernel).
+RNB_API int rnb_render_maps(const rnb_model_desc* desc, const float* packed, const rnb_render_args* a,
+                            const rnb_render_maps_out* m, void* ws, size_t ws_bytes, rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(a, "args");
+  RNB_REQUIRE(m, "maps");
+  hipStream_t s = (hipStream_t)stream;
+  if (a->flags & RNB_FLAG_INPUT_GRADS)
+    RNB_FAIL(RNB_E_INVALID, "rnb_render_maps is forward-only: RNB_FLAG_INPUT_GRADS has no meaning here");
+  if (!(m->color || m->normal || m->albedo || m->depth || m->weight_sum || m->weight_max))
+    RNB_FAIL(RNB_E_INVALID, "rnb_render_maps: no map requested (every output pointer is NULL)");
+  rnb_render_args fa = *a;
+  fa.flags |= RNB_FLAG_FORWARD_ONLY;   // the workspace of rnb_render_workspace_bytes(..., flags | RNB_FLAG_FORWARD_ONLY)
+  Layout L;
+  RenderBufs rb;
+  RNB_TRY(render_setup(desc, &fa, ws, ws_bytes, &L, &rb));
+  const int mode = render_mode_of(fa.flags, L);
+  const bool use_color = (mode & PM_WITH_COLOR) != 0;
+  if (m->albedo && !((fa.flags & RNB_MODE_MVPS) && use_color))
+    RNB_FAIL(RNB_E_INVALID, "rnb_render_maps: the albedo map needs RNB_MODE_MVPS with the albedo network "
+                            "(not RNB_MODE_CORE, not RNB_FLAG_NO_ALBEDO)");
+  RNB_TRY(launch_fine_points(fa.rays_o, fa.rays_d, fa.z_vals, fa.B, fa.S, 2.0f / (float)desc->n_samples, rb.pts,
+                             rb.dists, rb.pb.smax, s));
+  RNB_TRY(forward_points(L, packed, rb.pts, fa.B * fa.S, rb.pb, true, use_color, true, nullptr, s));
+  RNB_TRY(reverse_points(L, packed, rb.pb, false, s));
+  if (use_color) RNB_TRY(color_points(L, packed, rb.pb, rb.pts, s));
+  CompMapsArgs g;
+  memset(&g, 0, sizeof(g));
+  g.f = comp_args_of(L, &fa, rb);
+  // of CompArgs' outputs the maps kernel writes these three; the per-sample pointers of `a` are ignored
+  g.f.weights = g.f.cdf = g.f.gradients = g.f.inside = g.f.s_val = g.f.gerr_part = g.f.sdf_out = g.f.albedo_out = nullptr;
+  g.f.color_fine = m->color;
+  g.f.weight_sum = m->weight_sum;
+  g.f.weight_max = m->weight_max;
+  g.z = fa.z_vals;
+  g.normal = m->normal;
+  g.albedo = m->albedo;
+  g.depth = m->depth;
+  RNB_TRY(launch_composite_maps(g, s));
+  return RNB_OK;
+}
+
 // rnb_render_bwd (ig == nullptr) and rnb_render_bwd_inputs
 static int render_bwd_body(const rnb_model_desc* desc, const float* packed, const rnb_render_args* a,
                            const rnb_render_grads* gout, const rnb_render_input_grads* ig, float* packed_grad,

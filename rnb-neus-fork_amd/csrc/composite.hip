@@ -176,6 +176,123 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(CompArgs a) {
   }
 }
 
+// Whole-image rendering (rnb_render_maps): the per-ray images of exp_runner.py:460-470 and of RNb-NeuS evaluation, reduced
+// where composite_fwd_kernel would store its [B,S] arrays.  A kernel of its own (composite_fwd_kernel's code and registers
+// are not touched); the weights, the colour, weight_sum and weight_max are formed by the same expressions in the same
+// order as there (eval_sample, the 64-sample carry of wave_scan_mul, load_light, the fmaf chain, wave_sum), so those
+// three outputs carry composite_fwd_kernel's bits.  Per lane the new sums are fused adds over the ray's 64-sample
+// chunks, then the wave_sum butterfly:
+//   normal = sum_s (w_s [|p_s| < 1]) n_s       albedo = sum_s albedo_s w_s       depth = sum_s w_s (z_s + dists_s / 2)
+__global__ __launch_bounds__(64) void composite_maps_kernel(CompMapsArgs g) {
+  const CompArgs& a = g.f;
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int S = a.S;
+  const bool mvps = (a.flags & RNB_MODE_MVPS) != 0;
+  const bool relu_sh = (a.flags & RNB_FLAG_RELU_SHADING) != 0;
+  const bool no_alb = (a.flags & RNB_FLAG_NO_ALBEDO) != 0;
+  const bool want_color = a.color_fine != nullptr;
+  const float inv_s = inv_s_from_variance(a.variance, nullptr);
+  const float d0 = a.rays_d[b * 3], d1 = a.rays_d[b * 3 + 1], d2 = a.rays_d[b * 3 + 2];
+  float Lv[kMaxL][3];
+  if (mvps && want_color)
+    for (int l = 0; l < a.L; ++l) load_light(a, l, b, Lv[l]);
+
+  float carry = 1.0f;              // transmittance entering the current 64-sample chunk
+  float col[kMaxL][4];
+#pragma unroll
+  for (int l = 0; l < kMaxL; ++l)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) col[l][c] = 0.f;
+  float wsum = 0.f, wmax = -1.f;
+  float nacc[3] = {0.f, 0.f, 0.f}, aacc[4] = {0.f, 0.f, 0.f, 0.f}, dacc = 0.f;
+
+  for (int j0 = 0; j0 < S; j0 += 64) {
+    const int j = j0 + lane;
+    const bool on = j < S;
+    const int64_t p = b * S + (on ? j : S - 1);
+    const float s = a.sdf[p];
+    const float n0 = a.nrm[p * 4], n1 = a.nrm[p * 4 + 1], n2 = a.nrm[p * 4 + 2];
+    const SampleState st = eval_sample(s, n0, n1, n2, d0, d1, d2, a.dists[p], inv_s, a.cos_anneal);
+    const float x = on ? (1.0f - st.alpha + 1e-7f) : 1.0f;
+    const float incl = wave_scan_mul(x, lane);
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 1.0f;
+    const float T = carry * excl;
+    carry = carry * __shfl(incl, 63, 64);
+    const float w = on ? st.alpha * T : 0.f;
+    const float px = a.pts[p * 3], py = a.pts[p * 3 + 1], pz = a.pts[p * 3 + 2];
+    const float pn = sqrtf(px * px + py * py + pz * pz);
+    if (on) {
+      wsum += w;
+      wmax = max_nan(wmax, w);
+      if (g.normal) {   // inside_sphere as a FACTOR (exp_runner.py:467-468): w * {0, 1} is exact, 0 * NaN stays NaN
+        const float wi = w * (pn < 1.0f ? 1.f : 0.f);
+        nacc[0] = fmaf(wi, n0, nacc[0]); nacc[1] = fmaf(wi, n1, nacc[1]); nacc[2] = fmaf(wi, n2, nacc[2]);
+      }
+      if (g.albedo) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) aacc[c] = fmaf(a.alb[p * 4 + c], w, aacc[c]);
+      }
+      if (g.depth) dacc = fmaf(w, g.z[p] + a.dists[p] * 0.5f, dacc);
+      if (want_color) {
+        float al[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) al[c] = no_alb ? 1.0f : a.alb[p * 4 + c];
+        if (mvps) {
+          for (int l = 0; l < a.L; ++l) {
+            float sh = n0 * Lv[l][0] + n1 * Lv[l][1] + n2 * Lv[l][2];
+            if (relu_sh) sh = relu_nan(sh);
+            const float ws = w * sh;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) col[l][c] = fmaf(al[c], ws, col[l][c]);
+          }
+        } else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) col[0][c] = fmaf(a.alb[p * 4 + c], w, col[0][c]);
+        }
+      }
+    }
+  }
+  wsum = wave_sum(wsum);
+  wmax = wave_max(wmax);
+  if (want_color) {
+    const int nl = mvps ? a.L : 1;
+    for (int l = 0; l < nl; ++l)
+      for (int c = 0; c < a.C; ++c) {
+        float v = wave_sum(col[l][c]);
+        if (lane == 0) {
+          if (mvps) a.color_fine[((int64_t)l * a.B + b) * a.C + c] = v;
+          else if (c < 3) {
+            if (a.bg) v += a.bg[c] * (1.0f - wsum);
+            a.color_fine[b * 3 + c] = v;
+          }
+        }
+      }
+  }
+  if (g.normal) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float v = wave_sum(nacc[d]);
+      if (lane == 0) g.normal[b * 3 + d] = v;
+    }
+  }
+  if (g.albedo) {
+    for (int c = 0; c < a.C; ++c) {
+      const float v = wave_sum(aacc[c]);
+      if (lane == 0) g.albedo[b * a.C + c] = v;
+    }
+  }
+  if (g.depth) {
+    const float v = wave_sum(dacc);
+    if (lane == 0) g.depth[b] = v;
+  }
+  if (lane == 0) {
+    if (a.weight_sum) a.weight_sum[b] = wsum;
+    if (a.weight_max) a.weight_max[b] = wmax;
+  }
+}
+
 // gradient_error = sum_b num_b / (sum_b den_b + 1e-5); keeps the denominator for the backward.
 // (Round 5 folded this into composite_fwd_kernel — the last workgroup to arrive did the sum — and measured it: the ticket
 // atomic that every one of the 512 one-wave workgroups must wait for took the kernel from 15 to 36 us; a 5 us launch is cheaper.)
@@ -539,6 +656,15 @@ int launch_composite_fwd(const CompArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(composite_fwd_kernel, dim3((unsigned)a.B), dim3(64), 0, s, a);
   RNB_CHECK_LAUNCH();
   hipLaunchKernelGGL(gerr_finalize_kernel, dim3(1), dim3(256), 0, s, a.gerr_part, a.B, a.gerr, a.gerr_den, a.gerr_partial);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+int launch_composite_maps(const CompMapsArgs& g, hipStream_t s) {
+  if (g.f.S > kMaxS) RNB_FAIL(RNB_E_INVALID, "samples per ray %d > %d", g.f.S, kMaxS);
+  if (g.f.L > kMaxL) RNB_FAIL(RNB_E_INVALID, "n_lights %d > %d", g.f.L, kMaxL);
+  if (g.depth != nullptr && g.z == nullptr) RNB_FAIL(RNB_E_NULL, "composite maps: depth needs z_vals");
+  hipLaunchKernelGGL(composite_maps_kernel, dim3((unsigned)g.f.B), dim3(64), 0, s, g);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

@@ -72,6 +72,75 @@ __global__ void raygen_kernel(RayGenArgs g) {
   }
 }
 
+// Whole views (gen_rays_at / gen_rays_between, models/dataset.py:300-326, :401-446): the same arithmetic in the same order
+// on float pixel coordinates, gathers at the rounded pixel (exp_runner.py:409-410: pixels.round().long()).
+struct RayGridArgs {
+  const float* kinv;       // [4,4]
+  const float* pose;       // [4,4]
+  const float* tx;         // [Wl] pixel x of a grid column
+  const float* ty;         // [Hl] pixel y of a grid row
+  const float* images;     // [L,H,W,3] or NULL
+  const float* images_wu;  // [L,H,W,3] or NULL
+  const float* mask;       // [H,W,Cm] or NULL
+  const float* lights;     // [L,H,W,3] or NULL
+  int64_t first, n;        // rays [first, first + n) of the row-major Hl x Wl grid
+  int Wl, L, light, H, W, Cm;
+  float* data;             // [n,7]
+  float* rgb;              // [Lo,n,3] or NULL (Lo = L, or 1 with light >= 0)
+  float* rgb_wu;
+  float* lights_out;
+  float* near;             // [n] or NULL
+  float* far;
+};
+
+__global__ void raygen_grid_kernel(RayGridArgs g) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= g.n) return;
+  const int64_t i = g.first + b;
+  const int64_t iy = i / g.Wl;
+  const float fx = g.tx[i - iy * g.Wl], fy = g.ty[iy];
+  float p[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) p[r] = g.kinv[r * 4 + 0] * fx + g.kinv[r * 4 + 1] * fy + g.kinv[r * 4 + 2] * 1.f;
+  const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+  float v[3] = {p[0] / nrm, p[1] / nrm, p[2] / nrm};
+  float d[3], o[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    d[r] = g.pose[r * 4 + 0] * v[0] + g.pose[r * 4 + 1] * v[1] + g.pose[r * 4 + 2] * v[2];
+    o[r] = g.pose[r * 4 + 3];
+  }
+  // nearest pixel, ties to even (torch.round); the clamp only guards the gathers against coordinates outside the image
+  const int64_t x = min(max((int64_t)rintf(fx), (int64_t)0), (int64_t)g.W - 1);
+  const int64_t y = min(max((int64_t)rintf(fy), (int64_t)0), (int64_t)g.H - 1);
+  const int64_t pix = y * g.W + x;
+  float* row = g.data + b * 7;
+  row[0] = o[0]; row[1] = o[1]; row[2] = o[2];
+  row[3] = d[0]; row[4] = d[1]; row[5] = d[2];
+  row[6] = g.mask ? g.mask[pix * g.Cm] : 0.f;
+  if (g.near) {
+    const float a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    const float bq = 2.f * (o[0] * d[0] + o[1] * d[1] + o[2] * d[2]);
+    const float mid = 0.5f * (-bq) / a;
+    g.near[b] = mid - 1.f;
+    g.far[b] = mid + 1.f;
+  }
+  const int64_t plane = (int64_t)g.H * g.W * 3;
+  const int Lo = g.light < 0 ? g.L : 1;
+  for (int lo = 0; lo < Lo; ++lo) {
+    const int l = g.light < 0 ? lo : g.light;
+    const int64_t src = l * plane + pix * 3;
+    const int64_t dst = ((int64_t)lo * g.n + b) * 3;
+    if (g.rgb) { g.rgb[dst] = g.images[src]; g.rgb[dst + 1] = g.images[src + 1]; g.rgb[dst + 2] = g.images[src + 2]; }
+    if (g.rgb_wu) {
+      g.rgb_wu[dst] = g.images_wu[src]; g.rgb_wu[dst + 1] = g.images_wu[src + 1]; g.rgb_wu[dst + 2] = g.images_wu[src + 2];
+    }
+    if (g.lights_out) {
+      g.lights_out[dst] = g.lights[src]; g.lights_out[dst + 1] = g.lights[src + 1]; g.lights_out[dst + 2] = g.lights[src + 2];
+    }
+  }
+}
+
 }  // namespace rnb
 
 #define RNB_API extern "C" __attribute__((visibility("default")))
@@ -93,6 +162,30 @@ RNB_API int rnb_gen_rays_at_view(const float* intrinsics_inv, const float* pose,
   RayGenArgs g{intrinsics_inv, pose, images, images_warmup, mask, light_directions, pixels_x, pixels_y, B,
                n_lights, H, W, mask_channels, data, true_rgb, true_rgb_warmup, lights_dir, near, far};
   hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+RNB_API int rnb_gen_rays_grid(const float* intrinsics_inv, const float* pose, const float* tx, const float* ty, int32_t Wl,
+                              int32_t Hl, int64_t first, int64_t n, const float* images, const float* images_warmup,
+                              const float* mask, int32_t mask_channels, const float* light_directions,
+                              int32_t n_lights, int32_t light, int32_t H, int32_t W, float* data, float* true_rgb,
+                              float* true_rgb_warmup, float* lights_dir, float* near, float* far, rnb_stream_t stream) {
+  using namespace rnb;
+  if (!intrinsics_inv || !pose || !tx || !ty || !data) RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid: NULL pointer");
+  if ((true_rgb && !images) || (true_rgb_warmup && !images_warmup) || (lights_dir && !light_directions) ||
+      ((near == nullptr) != (far == nullptr)))
+    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid: output requested without its source");
+  if (Wl < 1 || Hl < 1 || n_lights < 0 || H < 1 || W < 1 || (mask && mask_channels < 1))
+    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid: bad shape (grid %d x %d, L %d, H %d, W %d)", Hl, Wl, n_lights, H, W);
+  if (first < 0 || n < 1 || first + n > (int64_t)Hl * Wl)
+    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid: rays [%lld, %lld) outside the %d x %d grid", (long long)first,
+             (long long)(first + n), Hl, Wl);
+  if (light < -1 || light >= n_lights)
+    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid: light %d out of range (n_lights %d; -1 = all)", light, n_lights);
+  RayGridArgs g{intrinsics_inv, pose, tx, ty, images, images_warmup, mask, light_directions, first, n, Wl, n_lights,
+                light, H, W, mask_channels, data, true_rgb, true_rgb_warmup, lights_dir, near, far};
+  hipLaunchKernelGGL(raygen_grid_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

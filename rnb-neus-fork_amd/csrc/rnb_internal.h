@@ -549,9 +549,20 @@ struct CompBwdArgs {
   float* ig_dists;           // [B,S]   d loss / d dists through the alpha estimate
 };
 
+// rnb_render_maps: the inputs of CompArgs; of its outputs only color_fine, weight_sum and weight_max are written (each may
+// be nullptr), the per-sample ones are never touched
+struct CompMapsArgs {
+  CompArgs f;
+  const float* z;          // [B,S] (depth)
+  float* normal;           // [B,3] or nullptr
+  float* albedo;           // [B,C] or nullptr
+  float* depth;            // [B] or nullptr
+};
+
 int launch_fine_points(const float* rays_o, const float* rays_d, const float* z, int64_t B, int S, float sample_dist,
                        float* pts, float* dists, unsigned* smax_to_zero, hipStream_t s);
 int launch_composite_fwd(const CompArgs& a, hipStream_t s);
+int launch_composite_maps(const CompMapsArgs& g, hipStream_t s);
 int launch_composite_bwd(const CompBwdArgs& g, hipStream_t s);
 // limits of the per-ray kernels, defined once: composite.hip sizes its LDS rows and light registers by them, and api.hip
 // refuses a larger S or light count in the workspace query and in render_setup, before anything is launched

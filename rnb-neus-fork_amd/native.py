@@ -17,6 +17,8 @@ FLAG_NO_ALBEDO = 4
 FLAG_LIGHT_PER_RAY = 8
 FLAG_FORWARD_ONLY = 16
 FLAG_INPUT_GRADS = 32
+# lights of a render_rnb* call (include/rnbneus.h: kMaxRenderLights)
+MAX_RENDER_LIGHTS = 8
 
 # flags of the point-wise autograd calls (include/rnbneus.h)
 POINTS_FEATURE = 1
@@ -73,6 +75,11 @@ class RenderArgs(C.Structure):
         ("sdf", C.c_void_p), ("sampled_albedo", C.c_void_p),
         ("gerr_partial", C.c_void_p), ("gerr_den_global", C.c_void_p),
     ]
+
+
+class RenderMapsOut(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("depth", C.c_void_p),
+                ("weight_sum", C.c_void_p), ("weight_max", C.c_void_p)]
 
 
 class GridDesc(C.Structure):
@@ -164,6 +171,8 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnb_render_workspace_bytes": (C.c_int, [_P(ModelDesc), C.c_int64, C.c_int32, C.c_int32, _P(C.c_int64)]),
     "rnb_render_fwd": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(RenderArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnb_render_maps": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(RenderArgs), _P(RenderMapsOut), C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
     "rnb_render_bwd": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(RenderArgs), _P(RenderGrads), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnb_render_bwd_inputs": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(RenderArgs), _P(RenderGrads),
@@ -177,6 +186,10 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "rnb_gen_rays_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnb_loss_rnb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),

@@ -8,11 +8,16 @@ pixel indices back to the CPU to gather the per-pixel light directions; `near_fa
 a 200-view 1024^2 capture: 288 GB of HBM hold them all) and produces everything a step consumes with one launch
 (`rnb_gen_rays_at_view`).  Same method names, argument meaning and return tuple as the reference's `Dataset`, so
 `exp_runner.py:174-180` works unchanged on it; `pixels_x` / `pixels_y` may be passed in so that tests can use the
-reference's own draws."""
+reference's own draws.
+
+Whole views (`validate_image`, `render_novel_image`: exp_runner.py:389-558) come from one more kernel,
+`rnb_gen_rays_grid`: `gen_rays_at` / `gen_rays_between` are the reference's methods, `view_rays` gives any range of
+a view's rays together with near / far and the gathers at the rounded pixel, one launch per call."""
 from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import native
@@ -133,3 +138,158 @@ class DeviceRays:
             lights_dir = lights.reshape(self.n_lights, batch_size, 1, 3)
         return {"rays_o": data[:, :3], "rays_d": data[:, 3:6], "mask": data[:, 6:7], "near": near, "far": far,
                 "true_rgb": rgb_wu if warmup else rgb, "lights_dir": lights_dir, "pixels_x": px, "pixels_y": py}
+
+    # ------------------------------------------------------------------ whole views, one launch per call
+    def _grid(self, resolution_level):
+        l = int(resolution_level)
+        if l < 1 or self.W // l < 1 or self.H // l < 1:
+            raise ValueError(f"resolution_level {resolution_level} leaves no pixel of a {self.H} x {self.W} image")
+        # dataset.py:307-308, made by torch so that the coordinates carry torch's bits (cached per level)
+        cache = self.__dict__.setdefault("_grid_cache", {})
+        if l not in cache:
+            tx = torch.linspace(0, self.W - 1, self.W // l).to(self.device)
+            ty = torch.linspace(0, self.H - 1, self.H // l).to(self.device)
+            # (+ the coordinates of every ray of the row-major grid: view_rays returns slices of them)
+            cache[l] = (tx, ty, tx.repeat(ty.numel()), ty.repeat_interleave(tx.numel()))
+        return cache[l]
+
+    def view_rays(self, img_idx=None, pose=None, resolution_level=1, light=None, warmup=False, first=0, count=None):
+        """Rays `[first, first + count)` (default: all) of the row-major `H // l x W // l` grid of a view, with what a
+        render of them consumes, one launch: a dict of `rays_o`, `rays_d` [n,3], `near`, `far` [n,1], `mask` [n,1],
+        `lights_dir` (shaped for `render_rnb`: [Lo,n,1,3], or with `warmup` for `render_rnb_warmup`: [Lo,1,1,3]),
+        `true_rgb` [Lo,n,3] (the nearest pixel of `images`, or of `images_warmup`), `pixels_x`, `pixels_y` [n] (the float
+        grid coordinates), `H`, `W` (the grid's size).  `light`: one light index or None for all (Lo = 1 or n_lights).
+        `pose` [4,4]: a camera-to-world pose other than a view's own (`gen_rays_between`); the intrinsics are then view
+        0's (dataset.py:414) unless `img_idx` is given too, and mask / lights_dir / true_rgb are None when it is not."""
+        tx, ty, px_all, py_all = self._grid(resolution_level)
+        Wl, Hl = tx.numel(), ty.numel()
+        first = int(first)
+        n = Hl * Wl - first if count is None else int(count)
+        if first < 0 or n < 1 or first + n > Hl * Wl:
+            raise IndexError(f"rays [{first}, {first + n}) are not inside the {Hl} x {Wl} grid")
+        gather = img_idx is not None
+        v = int(img_idx) if gather else 0
+        if not 0 <= v < self.n_images:
+            raise IndexError(f"img_idx {v} out of range (n_images {self.n_images})")
+        L = self.n_lights
+        li = -1 if light is None else int(light)
+        if not -1 <= li < L or (light is not None and li < 0):
+            raise IndexError(f"light {light} out of range (n_lights {L})")
+        Lo = L if li < 0 else 1
+        if pose is None:
+            if not gather:
+                raise ValueError("view_rays needs img_idx or pose")
+            pose_t = self.pose_all[v]
+        else:
+            pose_t = torch.as_tensor(pose).to(device=self.device, dtype=torch.float32).reshape(4, 4).contiguous()
+        images = (self.images_warmup if warmup else self.images) if gather else None
+        if gather and warmup and images is None:
+            raise ValueError("DeviceRays was built without images_warmup")
+        want_lights = gather and not warmup and self.light_directions is not None
+        f32 = dict(dtype=torch.float32, device=self.device)
+        data = torch.empty(n, 7, **f32)
+        near, far = torch.empty(n, 1, **f32), torch.empty(n, 1, **f32)
+        rgb = torch.empty(Lo, n, 3, **f32) if gather else None
+        lights = torch.empty(Lo, n, 3, **f32) if want_lights else None
+        with native.on_device(data) as stream:
+            native.check(native.load().rnb_gen_rays_grid(
+                native.ptr(self.intrinsics_all_inv[v]), native.ptr(pose_t), native.ptr(tx), native.ptr(ty), Wl, Hl, first, n,
+                native.ptr(images[v]) if gather and not warmup else None,
+                native.ptr(images[v]) if gather and warmup else None,
+                native.ptr(self.masks[v]) if gather else None, self.masks.shape[-1],
+                native.ptr(self.light_directions[v]) if want_lights else None, L, li, self.H, self.W, native.ptr(data),
+                native.ptr(rgb) if gather and not warmup else None, native.ptr(rgb) if gather and warmup else None,
+                native.ptr(lights), native.ptr(near), native.ptr(far), stream))
+        lights_dir = None
+        if gather and warmup:
+            if self.light_directions_warmup is None:
+                raise ValueError("DeviceRays was built without light_directions_warmup")
+            lw = self.light_directions_warmup[v]
+            lights_dir = (lw if li < 0 else lw[li:li + 1]).reshape(Lo, 1, 1, 3)
+        elif want_lights:
+            lights_dir = lights.reshape(Lo, n, 1, 3)
+        return {"rays_o": data[:, :3], "rays_d": data[:, 3:6], "mask": data[:, 6:7] if gather else None, "near": near,
+                "far": far, "true_rgb": rgb, "lights_dir": lights_dir, "pixels_x": px_all[first:first + n],
+                "pixels_y": py_all[first:first + n], "H": Hl, "W": Wl}
+
+    def gen_rays_at(self, img_idx, resolution_level=1):
+        """models/dataset.py:300-326: (rays_o [Hl,Wl,3], rays_d [Hl,Wl,3], pixels_x [Hl,Wl], pixels_y [Hl,Wl]) on the
+        device."""
+        r = self.view_rays(img_idx, resolution_level=resolution_level)
+        Hl, Wl = r["H"], r["W"]
+        return (r["rays_o"].reshape(Hl, Wl, 3), r["rays_d"].reshape(Hl, Wl, 3), r["pixels_x"].reshape(Hl, Wl),
+                r["pixels_y"].reshape(Hl, Wl))
+
+    def pose_between(self, idx_0, idx_1, ratio):
+        """The interpolated camera-to-world pose of `gen_rays_between` (float32 [4,4] numpy array, `interpolate_pose`)."""
+        return interpolate_pose(self.pose_all[int(idx_0)].detach().cpu().numpy(),
+                                self.pose_all[int(idx_1)].detach().cpu().numpy(), ratio)
+
+    def gen_rays_between(self, idx_0, idx_1, ratio, resolution_level=1):
+        """models/dataset.py:401-446: (rays_o [Hl,Wl,3], rays_d [Hl,Wl,3]) of the pose interpolated between two views
+        (`pose_between`), with view 0's intrinsics as in the reference; the rays come from the same kernel."""
+        r = self.view_rays(pose=self.pose_between(idx_0, idx_1, ratio), resolution_level=resolution_level)
+        return r["rays_o"].reshape(r["H"], r["W"], 3), r["rays_d"].reshape(r["H"], r["W"], 3)
+
+
+def interpolate_pose(pose_0, pose_1, ratio):
+    """The interpolated camera-to-world pose of models/dataset.py:418-437 from two float32 [4,4] poses, built on the host
+    as there: both poses inverted in float32, their rotations slerped (float64, the arithmetic of scipy's Slerp: R0 times
+    the rotation of R0^T R1 with its angle scaled by `ratio`) and their translations lerped, assembled in float32 and
+    inverted.  Returns a float32 [4,4] numpy array."""
+    pose_0 = np.linalg.inv(np.asarray(pose_0, dtype=np.float32))
+    pose_1 = np.linalg.inv(np.asarray(pose_1, dtype=np.float32))
+    rot = _slerp(pose_0[:3, :3].astype(np.float64), pose_1[:3, :3].astype(np.float64), float(ratio))
+    pose = np.diag([1.0, 1.0, 1.0, 1.0]).astype(np.float32)
+    pose[:3, :3] = rot
+    pose[:3, 3] = ((1.0 - ratio) * pose_0 + ratio * pose_1)[:3, 3]
+    return np.linalg.inv(pose)
+
+
+def _quat_from_matrix(m):
+    """Unit quaternion (x, y, z, w) of a 3x3 matrix's nearest rotation (float64; the largest-component branch)."""
+    u, _, vt = np.linalg.svd(m)
+    m = u @ np.diag([1.0, 1.0, np.linalg.det(u @ vt)]) @ vt
+    t = np.trace(m)
+    c = [m[0, 0], m[1, 1], m[2, 2], t]
+    k = int(np.argmax(c))
+    q = np.empty(4)
+    if k == 3:
+        q[:] = (m[2, 1] - m[1, 2], m[0, 2] - m[2, 0], m[1, 0] - m[0, 1], 1.0 + t)
+    else:
+        i, j, l = k, (k + 1) % 3, (k + 2) % 3
+        q[i] = 1.0 - t + 2.0 * m[i, i]
+        q[j] = m[j, i] + m[i, j]
+        q[l] = m[l, i] + m[i, l]
+        q[3] = m[l, j] - m[j, l]
+    return q / np.linalg.norm(q)
+
+
+def _quat_mul(a, b):
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz])
+
+
+def _quat_to_matrix(q):
+    x, y, z, w = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def _slerp(r0, r1, t):
+    """Rotation matrix R0 exp(t log(R0^T R1)) (numpy float64): spherical interpolation between two rotations along the
+    shorter arc, t = 0 -> R0, t = 1 -> R1."""
+    q0, q1 = _quat_from_matrix(r0), _quat_from_matrix(r1)
+    d = _quat_mul(q0 * np.array([-1.0, -1.0, -1.0, 1.0]), q1)     # q0^-1 q1
+    if d[3] < 0:
+        d = -d
+    s = np.linalg.norm(d[:3])
+    angle = 2.0 * np.arctan2(s, d[3])
+    if s < 1e-300:
+        return _quat_to_matrix(q0)
+    half = 0.5 * t * angle
+    step = np.concatenate([d[:3] / s * np.sin(half), [np.cos(half)]])
+    return _quat_to_matrix(_quat_mul(q0, step))

@@ -40,6 +40,15 @@ _MESH_BACKEND_LOGGED = False
 DEFAULT_SPARSE_BRICK = 8
 
 
+# whole-image rendering (render_maps / render_image)
+_MAPS_API = {"render": native.MODE_CORE, "render_rnb": native.MODE_MVPS,
+             "render_rnb_warmup": native.MODE_MVPS | native.FLAG_RELU_SHADING}
+_MAPS_KNOWN = ("color", "normal", "albedo", "depth", "weight_sum", "weight_max")
+DEFAULT_MAPS = ("color", "normal", "albedo", "depth", "weight_sum")
+# rays per launch of a whole-image render: where profiles/image_render.txt shows the throughput flatten
+DEFAULT_CHUNK_RAYS = 1024
+
+
 def _requires_grad(t):
     return isinstance(t, torch.Tensor) and t.requires_grad
 
@@ -427,6 +436,209 @@ class NeuSRenderer:
         flags = native.MODE_MVPS | (native.FLAG_NO_ALBEDO if no_albedo else 0)
         return self._run(rays_o, rays_d, near, far, lights_dir, perturb_overwrite, background_rgb, cos_anneal_ratio,
                          flags, t_rand, z_vals)
+
+    # ------------------------------------------------------------------ whole images (forward only)
+    def _maps_begin(self, n_rays, S, api, no_albedo, maps, n_lights, chunk_rays, background_rgb, cos_anneal_ratio, dev,
+                    keep_z):
+        """Everything the chunks of one whole-image render share: flags, packed weights, the preallocated outputs and
+        ONE workspace of the one-chunk size."""
+        if api not in _MAPS_API:
+            raise ValueError(f"render_maps: unknown api {api!r} (one of {sorted(_MAPS_API)})")
+        if self.sdf_network.lin0.bias.device != dev:
+            raise RuntimeError(f"NeuSRenderer: rays live on {dev} but the networks on "
+                               f"{self.sdf_network.lin0.bias.device}")
+        flags = _MAPS_API[api]
+        mvps = bool(flags & native.MODE_MVPS)
+        if mvps and no_albedo:
+            flags |= native.FLAG_NO_ALBEDO
+        use_color = not (mvps and no_albedo)
+        has_albedo = mvps and use_color
+        if maps is DEFAULT_MAPS:          # the default set: every map this mode has
+            maps = tuple(m for m in maps if m != "albedo" or has_albedo)
+        maps = tuple(maps)
+        unknown = [m for m in maps if m not in _MAPS_KNOWN]
+        if unknown or not maps:
+            raise ValueError(f"render_maps: maps must be a non-empty subset of {_MAPS_KNOWN}, not {maps}")
+        if "albedo" in maps and not has_albedo:
+            raise ValueError("render_maps: the albedo map exists for render_rnb / render_rnb_warmup with the albedo network "
+                             "only (not api='render', not no_albedo=True)")
+        # (a larger S than kMaxS is refused by the workspace query below; the light count only by the call itself, which
+        # without explicit depths would come after the sampler's launches)
+        if mvps and n_lights > native.MAX_RENDER_LIGHTS:
+            raise ValueError(f"render_maps: n_lights {n_lights} > {native.MAX_RENDER_LIGHTS} (kMaxRenderLights)")
+        chunk = max(1, min(int(chunk_rays), n_rays))
+        Cd = self.desc.col_d_out
+        f32 = dict(dtype=torch.float32, device=dev)
+        shapes = {"color": (n_lights, n_rays, Cd) if mvps else (n_rays, 3), "normal": (n_rays, 3), "albedo": (n_rays, Cd),
+                  "depth": (n_rays, 1), "weight_sum": (n_rays, 1), "weight_max": (n_rays, 1)}
+        out = {m: torch.empty(shapes[m], **f32) for m in maps}
+        if keep_z:
+            out["z_vals"] = torch.empty(n_rays, S, **f32)
+        nbytes = C.c_int64()
+        native.check(native.load().rnb_render_workspace_bytes(C.byref(self.desc), chunk, S, flags | native.FLAG_FORWARD_ONLY,
+                                                              C.byref(nbytes)))
+        bg = None
+        if background_rgb is not None and not mvps:
+            bg = background_rgb.detach().to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+        return dict(flags=flags, mvps=mvps, maps=maps, out=out, chunk=chunk, S=S, L=n_lights, Cd=Cd, dev=dev, bg=bg,
+                    packed=self._pack(use_color), ws=torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=dev),
+                    cos=float(cos_anneal_ratio), variance=self.deviation_network.variance.detach().reshape(1))
+
+    def _maps_chunk(self, st, i0, rays_o, rays_d, z_vals, lights):
+        """One chunk of a whole-image render into rows [i0, i0 + n) of the outputs; the workspace is the shared one (stream
+        order makes the reuse safe: every chunk's kernels are enqueued behind the previous chunk's)."""
+        n = rays_o.shape[0]
+        out, flags = st["out"], st["flags"]
+        args = native.RenderArgs()
+        args.B, args.S, args.n_lights, args.flags = n, st["S"], st["L"] if st["mvps"] else 1, flags
+        args.cos_anneal_ratio = st["cos"]
+        args.rays_o, args.rays_d, args.z_vals = rays_o.data_ptr(), rays_d.data_ptr(), z_vals.data_ptr()
+        args.variance = st["variance"].data_ptr()
+        args.background_rgb = st["bg"].data_ptr() if st["bg"] is not None else None
+        if st["mvps"]:
+            if lights.numel() != st["L"] * 3:
+                args.flags |= native.FLAG_LIGHT_PER_RAY
+            args.lights_dir = lights.data_ptr()
+        m = native.RenderMapsOut()
+        block = None
+        for k in st["maps"]:
+            if k == "color" and st["mvps"]:
+                if n == out[k].shape[1]:
+                    m.color = out[k].data_ptr()
+                else:   # [L,B,C] colour: the kernel writes the chunk's contiguous [L,n,C] block, copied into its columns below
+                    block = torch.empty(st["L"], n, st["Cd"], dtype=torch.float32, device=st["dev"])
+                    m.color = block.data_ptr()
+            else:
+                setattr(m, k, out[k][i0:i0 + n].data_ptr())
+        native.same_device(st["packed"], rays_o, rays_d, z_vals, lights, st["ws"])
+        with native.on_device(st["dev"]) as stream:
+            native.check(native.load().rnb_render_maps(C.byref(self.desc), native.ptr(st["packed"]), C.byref(args),
+                                                       C.byref(m), native.ptr(st["ws"]), st["ws"].numel(), stream))
+        if block is not None:
+            out["color"][:, i0:i0 + n].copy_(block)
+        if "z_vals" in out:
+            out["z_vals"][i0:i0 + n].copy_(z_vals)
+
+    @staticmethod
+    def _maps_lights(lights_dir, n_rays, dev):
+        if lights_dir is None:
+            raise ValueError("render_maps: render_rnb / render_rnb_warmup need lights_dir")
+        L = lights_dir.shape[0]
+        lt = lights_dir.detach().to(device=dev, dtype=torch.float32)
+        if lt.numel() == L * 3:
+            return lt.reshape(L, 3).contiguous(), False
+        return lt.reshape(L, n_rays, 3), True
+
+    @torch.no_grad()
+    def render_maps(self, rays_o, rays_d, near, far, lights_dir=None, *, api="render_rnb", perturb_overwrite=-1,
+                    background_rgb=None, cos_anneal_ratio=0.0, no_albedo=False, t_rand=None, z_vals=None,
+                    chunk_rays=DEFAULT_CHUNK_RAYS, maps=DEFAULT_MAPS, return_z_vals=False):
+        """Forward-only render of ANY number of rays to per-ray maps (`rnb_render_maps`): what `validate_image`
+        (exp_runner.py:460-470) reduces from the training dictionary with torch ops and a `.cpu()` per batch.  `api` names
+        the wrapper whose arithmetic is wanted ("render", "render_rnb", "render_rnb_warmup"); the other arguments are that
+        wrapper's.  Returns a dict with the requested `maps`:
+          color [L,B,C] (render: [B,3], background included) — `color_fine` of the wrapper, bit for bit when one chunk
+          holds the same rays; normal [B,3] = sum_s w n [|p| < 1]; albedo [B,C] = sum_s w albedo (render_rnb* with the
+          albedo network only; the default `maps` leaves it out where it does not exist, asking for it there raises);
+          depth [B,1] = sum_s w (z + dists / 2); weight_sum, weight_max [B,1]; z_vals [B,S] with `return_z_vals`.
+        The rays run in chunks of `chunk_rays` through ONE workspace of the one-chunk size, allocated once (stream order
+        makes the reuse safe), and every chunk's maps are written straight into rows of the preallocated outputs — except
+        [L,B,C] colour, whose per-chunk [L,n,C] block is copied into its columns (the kernel has no output stride).
+        Workspace: `rnb_render_workspace_bytes(desc, chunk_rays, S, flags | RNB_FLAG_FORWARD_ONLY)` — about 30 KB per
+        sample point at the shipped shape (256-wide, 8 layers), i.e. ~4 GB per 1024-ray chunk of 128 samples, whatever the
+        image size.  Runs under no_grad whatever the caller's grad mode (outputs carry no grad_fn, no `.grad` is touched),
+        for every `set_variant`, and is never collective under `set_data_parallel`."""
+        if not rays_o.is_cuda:
+            raise RuntimeError("NeuSRenderer: rays must be on the GPU (no CPU path; librnbneus_hip.so only)")
+        dev = rays_o.device
+        N = rays_o.shape[0]
+        rays_o = rays_o.detach().to(torch.float32).contiguous()
+        rays_d = rays_d.detach().to(torch.float32).contiguous()
+        mvps = bool(_MAPS_API.get(api, 0) & native.MODE_MVPS)
+        lights, per_ray = self._maps_lights(lights_dir, N, dev) if mvps else (None, False)
+        if z_vals is not None:
+            z_vals = z_vals.detach().to(torch.float32).contiguous()
+        S = z_vals.shape[1] if z_vals is not None else self.n_samples + self.n_importance
+        st = self._maps_begin(N, S, api, no_albedo, maps, lights.shape[0] if mvps else 1, chunk_rays, background_rgb,
+                              cos_anneal_ratio, dev, return_z_vals)
+        perturb = self.perturb if perturb_overwrite < 0 else perturb_overwrite
+        near = near.detach().reshape(N)
+        far = far.detach().reshape(N)
+        if t_rand is not None:
+            t_rand = t_rand.detach().reshape(N, 1)
+        for i0 in range(0, N, st["chunk"]):
+            i1 = min(N, i0 + st["chunk"])
+            o, d = rays_o[i0:i1], rays_d[i0:i1]
+            if z_vals is None:
+                z = self.sample_z_vals(o, d, near[i0:i1], far[i0:i1], st["packed"], perturb,
+                                       None if t_rand is None else t_rand[i0:i1])
+            else:
+                z = z_vals[i0:i1]
+            self._maps_chunk(st, i0, o, d, z, lights[:, i0:i1].contiguous() if per_ray else lights)
+        return st["out"]
+
+    @torch.no_grad()
+    def render_image(self, rays, img_idx=None, *, pose=None, light=None, resolution_level=1, warmup=False, api=None,
+                     perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0, no_albedo=False,
+                     chunk_rays=DEFAULT_CHUNK_RAYS, maps=DEFAULT_MAPS, return_z_vals=False, to_host=False):
+        """One whole view as images, everything on the device (`validate_image` / `render_novel_image`,
+        exp_runner.py:389-558): per chunk of `chunk_rays` rays, `rays.view_rays` (rays, near / far, the lights at the
+        rounded pixel: one launch), the sampler and `rnb_render_maps` into rows of the preallocated images.
+        `rays`: a `DeviceRays`; `img_idx` a view of it, or `pose` [4,4] for a novel view (`rays.pose_between`; no lights:
+        api="render").  `light`: one light index or None for all (Lo = 1 or n_lights); `warmup`: the warm-up lights and
+        images.  `api` defaults to "render_rnb_warmup" with `warmup`, "render" for a pose-only view, else "render_rnb".
+        Returns `color` [Lo,Hl,Wl,C] (render: [Hl,Wl,3]), `normal` [Hl,Wl,3], `albedo` [Hl,Wl,C], `depth`, `weight_sum`,
+        `weight_max` [Hl,Wl] (those asked for in `maps`), `mask` [Hl,Wl] and `true_rgb` [Lo,Hl,Wl,3] (None for a pose-only
+        view) and with `return_z_vals` `z_vals` [Hl*Wl,S].  No host synchronisation, unless `to_host=True` asks for numpy
+        copies: then exactly one, after the last chunk.  The other keywords are `render_maps`'."""
+        gather = img_idx is not None
+        if api is None:
+            api = "render_rnb_warmup" if warmup else ("render_rnb" if gather else "render")
+        mvps = bool(_MAPS_API.get(api, 0) & native.MODE_MVPS)
+        dev = rays.device
+        tx, ty = rays._grid(resolution_level)[:2]
+        Hl, Wl = ty.numel(), tx.numel()
+        N = Hl * Wl
+        if mvps and (not gather or (rays.light_directions_warmup if warmup else rays.light_directions) is None):
+            raise ValueError(f"render_image: api={api!r} needs the lights of a view (img_idx), or api='render'")
+        n_rgb = rays.n_lights if light is None else 1
+        Lo = n_rgb if mvps else 1
+        S = self.n_samples + self.n_importance
+        st = self._maps_begin(N, S, api, no_albedo, maps, Lo, chunk_rays, background_rgb, cos_anneal_ratio, dev,
+                              return_z_vals)
+        perturb = self.perturb if perturb_overwrite < 0 else perturb_overwrite
+        f32 = dict(dtype=torch.float32, device=dev)
+        mask = torch.empty(N, 1, **f32) if gather else None
+        true_rgb = torch.empty(n_rgb, N, 3, **f32) if gather else None
+        for i0 in range(0, N, st["chunk"]):
+            n = min(N, i0 + st["chunk"]) - i0
+            r = rays.view_rays(img_idx, pose, resolution_level, light, warmup, i0, n)
+            o, d = r["rays_o"].contiguous(), r["rays_d"].contiguous()
+            z = self.sample_z_vals(o, d, r["near"], r["far"], st["packed"], perturb)
+            lights = None
+            if mvps:
+                lights, _ = self._maps_lights(r["lights_dir"], n, dev)
+                lights = lights.contiguous()
+            self._maps_chunk(st, i0, o, d, z, lights)
+            if gather:
+                mask[i0:i0 + n].copy_(r["mask"])
+                true_rgb[:, i0:i0 + n].copy_(r["true_rgb"])
+        img = {}
+        for k, v in st["out"].items():
+            if k == "color":
+                img[k] = v.reshape(Lo, Hl, Wl, -1) if mvps else v.reshape(Hl, Wl, 3)
+            elif k == "z_vals":
+                img[k] = v
+            else:
+                img[k] = v.reshape(Hl, Wl, -1) if k in ("normal", "albedo") else v.reshape(Hl, Wl)
+        img["mask"] = mask.reshape(Hl, Wl) if gather else None
+        img["true_rgb"] = true_rgb.reshape(-1, Hl, Wl, 3) if gather else None
+        if to_host:
+            host = {k: (None if v is None else torch.empty(v.shape, dtype=v.dtype, pin_memory=True).copy_(v, non_blocking=True))
+                    for k, v in img.items()}
+            torch.cuda.current_stream(dev).synchronize()    # the one synchronisation of a whole image
+            img = {k: (None if v is None else v.numpy()) for k, v in host.items()}
+        return img
 
     def color(self, points, normals, view_dirs, feature_vectors):
         """RenderingNetwork.forward through this renderer's packed weights (view_dirs unused in
