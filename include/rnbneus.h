@@ -498,6 +498,50 @@ int rnb_gen_rays_grid(const float* intrinsics_inv, const float* pose, const floa
                       int32_t light, int32_t H, int32_t W, float* data, float* true_rgb, float* true_rgb_warmup,
                       float* lights_dir, float* near, float* far, rnb_stream_t stream);
 
+/* Source mode of the two calls above: the same outputs computed per requested pixel from a view's normal, albedo and
+ * mask maps (7 B per pixel as 8-bit images) instead of gathered from the finished stacks that Dataset.__init__ and
+ * Dataset.gen_light_directions build on the host (models/dataset.py:100-298; 112 B per pixel).
+ *   decode   integer elements: c = v / (float)M, M = 255 (U8) or 65535 (U16); normal n = 2c - 1 with its y and z
+ *            components negated, albedo = c, mask = (c > 0.5) ? 1 : 0 (dataset.py:48-68, :134-136).  F32 normals and
+ *            albedo are taken as already decoded (the reference's camera convention); an F32 mask is binarised (> 0.5).
+ *   frame    a = n/|n|, negated when a_z < 0 (a = (0,0,1) for a zero normal).  b1, b2 = the branch-free basis of Duff
+ *            et al., "Building an Orthonormal Basis, Revisited" (JCGT 2017) around a with sign = +1:
+ *              q = -1 / (1 + a_z), r = a_x a_y q, b1 = (1 + a_x^2 q, r, -a_x), b2 = (r, 1 + a_y^2 q, -a_y);  b1 x b2 = a.
+ *            This choice is part of the contract: lights_dir is a reproducible function of the pixel's normal.  The
+ *            reference's frame has the same third axis and an arbitrary basis of the plane across it (what LAPACK's SVD
+ *            returned for a repeated singular value), so its lights equal these up to a per-pixel rotation about a.
+ *   lights   l_k = u_k.x b1 + u_k.y b2 + u_k.z a with u_k = local_lights[k];  lights_dir_k = view_pose[:3,:3] l_k
+ *   colours  true_rgb_k = albedo max(n . l_k, 0);  true_rgb_warmup_k = albedo max(n . w_k, 0), w_k = warmup_lights_cam[k]
+ *            (the raw n, not a; albedo = 1 when albedo is NULL: the reference's no_albedo).  A NaN normal gives NaN.
+ * IEEE sqrt and division; rays, near / far and the data layout are those of the stack-mode calls, bit for bit. */
+enum { RNB_SOURCE_U8 = 0, RNB_SOURCE_U16 = 1, RNB_SOURCE_F32 = 2 };
+typedef struct rnb_source_maps {
+  const void* normals;   /* [H,W,3] of normals_type */
+  const void* albedo;    /* [H,W,3] of normals_type, or NULL (no_albedo) */
+  const void* mask;      /* [H,W,mask_channels] of mask_type; channel 0 is used */
+  int32_t normals_type;  /* RNB_SOURCE_*: element type of normals and albedo */
+  int32_t mask_type;     /* RNB_SOURCE_* */
+  int32_t H, W, mask_channels;
+  int32_t n_lights;      /* 1 .. 8 (kMaxRenderLights) */
+  float local_lights[8][3];      /* u_k: the main phase's lights in the per-pixel frame (b1, b2, a) */
+  float warmup_lights_cam[8][3]; /* w_k: the warm-up phase's fixed camera-space lights */
+} rnb_source_maps_t;
+/* rnb_gen_rays_at_view on source maps.  pose is the view's own: it makes the rays and rotates the lights.
+ * Outputs as rnb_gen_rays_at_view (true_rgb, true_rgb_warmup, lights_dir each optional; near, far both or neither).
+ * RNB_E_NULL / RNB_E_INVALID before any launch: a NULL required pointer, an unknown type code, n_lights outside 1..8,
+ * H, W, mask_channels or B below 1, near without far. */
+int rnb_gen_rays_at_view_from_maps(const float* intrinsics_inv, const float* pose, const rnb_source_maps_t* source,
+                                   const int64_t* pixels_x, const int64_t* pixels_y, int64_t B, float* data,
+                                   float* true_rgb, float* true_rgb_warmup, float* lights_dir, float* near, float* far,
+                                   rnb_stream_t stream);
+/* rnb_gen_rays_grid on source maps, read at the rintf-rounded, clamped pixel.  pose makes the rays (it may be an
+ * interpolated one); view_pose is the pose of the view the maps belong to and rotates its lights to world space.
+ * Also refused before any launch: rays [first, first + n) outside the Hl x Wl grid, light outside -1 .. n_lights - 1. */
+int rnb_gen_rays_grid_from_maps(const float* intrinsics_inv, const float* pose, const float* view_pose, const float* tx,
+                                const float* ty, int32_t Wl, int32_t Hl, int64_t first, int64_t n,
+                                const rnb_source_maps_t* source, int32_t light, float* data, float* true_rgb,
+                                float* true_rgb_warmup, float* lights_dir, float* near, float* far, rnb_stream_t stream);
+
 /* The loss of train_rnb (exp_runner.py:241-258) and its gradients with respect to the renderer outputs, one
  * launch:  loss = sum|(color_fine - true_rgb) * mask| / ((sum(mask) + 1e-5) * n_lights)
  *               + igr_weight * gradient_error

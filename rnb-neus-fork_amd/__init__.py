@@ -18,11 +18,12 @@ from .fields import NeRF, RenderingNetwork, SDFNetwork, SingleVarianceNetwork, m
 from .renderer import NeuSRenderer  # noqa: F401
 from .losses import rnb_loss  # noqa: F401
 from .optim import FlatAdam  # noqa: F401
-from .raygen import DeviceRays  # noqa: F401
+from .raygen import DeviceRays, cameras_from_projections  # noqa: F401
 from .mcubes import marching_cubes  # noqa: F401
 
 __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetwork", "NeRF", "get_embedder",
-           "native", "build_from_named_params", "rnb_loss", "FlatAdam", "DeviceRays", "marching_cubes"]
+           "native", "build_from_named_params", "rnb_loss", "FlatAdam", "DeviceRays", "cameras_from_projections",
+           "marching_cubes"]
 
 
 def build_from_named_params(mc, params, device):

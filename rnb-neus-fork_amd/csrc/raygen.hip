@@ -8,6 +8,45 @@
 
 namespace rnb {
 
+// The ray arithmetic every kernel of this file shares, so that stack mode and source mode give the same bits.
+// p = Kinv[:3,:3] (x, y, 1) (dataset.py:365-367; same left-to-right accumulation as a 3-term dot product),
+// rays_v = R p / ||p||, rays_o = t (dataset.py:369-373)
+__device__ __forceinline__ void ray_through(const float* kinv, const float* pose, float fx, float fy, float o[3], float d[3]) {
+  float p[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) p[r] = kinv[r * 4 + 0] * fx + kinv[r * 4 + 1] * fy + kinv[r * 4 + 2] * 1.f;
+  const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+  float v[3] = {p[0] / nrm, p[1] / nrm, p[2] / nrm};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    d[r] = pose[r * 4 + 0] * v[0] + pose[r * 4 + 1] * v[1] + pose[r * 4 + 2] * v[2];
+    o[r] = pose[r * 4 + 3];
+  }
+}
+
+// data row b = rays_o | rays_v | mask (dataset.py:376) and near / far of the unit sphere (dataset.py:448-458)
+__device__ __forceinline__ void store_ray(float* data, float* near, float* far, int64_t b, const float o[3], const float d[3],
+                                          float mask) {
+  float* row = data + b * 7;
+  row[0] = o[0]; row[1] = o[1]; row[2] = o[2];
+  row[3] = d[0]; row[4] = d[1]; row[5] = d[2];
+  row[6] = mask;
+  if (near) {
+    const float a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    const float bq = 2.f * (o[0] * d[0] + o[1] * d[1] + o[2] * d[2]);
+    const float mid = 0.5f * (-bq) / a;
+    near[b] = mid - 1.f;
+    far[b] = mid + 1.f;
+  }
+}
+
+// nearest pixel, ties to even (torch.round); the clamp only guards the gathers against coordinates outside the image
+__device__ __forceinline__ int64_t nearest_pixel(float fx, float fy, int H, int W) {
+  const int64_t x = min(max((int64_t)rintf(fx), (int64_t)0), (int64_t)W - 1);
+  const int64_t y = min(max((int64_t)rintf(fy), (int64_t)0), (int64_t)H - 1);
+  return y * W + x;
+}
+
 struct RayGenArgs {
   const float* kinv;       // [4,4] inverse intrinsics of the view (row-major)
   const float* pose;       // [4,4] camera-to-world pose of the view
@@ -31,33 +70,10 @@ __global__ void raygen_kernel(RayGenArgs g) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= g.B) return;
   const int64_t x = g.px[b], y = g.py[b];
-  // p = Kinv[:3,:3] (x, y, 1)   (dataset.py:365-367); same left-to-right accumulation as a 3-term dot product
-  const float fx = (float)x, fy = (float)y;
-  float p[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) p[r] = g.kinv[r * 4 + 0] * fx + g.kinv[r * 4 + 1] * fy + g.kinv[r * 4 + 2] * 1.f;
-  // rays_v = p / ||p||          (dataset.py:369)
-  const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-  float v[3] = {p[0] / nrm, p[1] / nrm, p[2] / nrm};
-  // rays_v = R v ; rays_o = t   (dataset.py:371-373)
   float d[3], o[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    d[r] = g.pose[r * 4 + 0] * v[0] + g.pose[r * 4 + 1] * v[1] + g.pose[r * 4 + 2] * v[2];
-    o[r] = g.pose[r * 4 + 3];
-  }
+  ray_through(g.kinv, g.pose, (float)x, (float)y, o, d);
   const int64_t pix = y * g.W + x;
-  float* row = g.data + b * 7;
-  row[0] = o[0]; row[1] = o[1]; row[2] = o[2];
-  row[3] = d[0]; row[4] = d[1]; row[5] = d[2];
-  row[6] = g.mask[pix * g.Cm];
-  if (g.near) {
-    const float a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-    const float bq = 2.f * (o[0] * d[0] + o[1] * d[1] + o[2] * d[2]);
-    const float mid = 0.5f * (-bq) / a;
-    g.near[b] = mid - 1.f;
-    g.far[b] = mid + 1.f;
-  }
+  store_ray(g.data, g.near, g.far, b, o, d, g.mask[pix * g.Cm]);
   const int64_t plane = (int64_t)g.H * g.W * 3;
   for (int l = 0; l < g.L; ++l) {
     const int64_t src = l * plane + pix * 3;
@@ -99,32 +115,10 @@ __global__ void raygen_grid_kernel(RayGridArgs g) {
   const int64_t i = g.first + b;
   const int64_t iy = i / g.Wl;
   const float fx = g.tx[i - iy * g.Wl], fy = g.ty[iy];
-  float p[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) p[r] = g.kinv[r * 4 + 0] * fx + g.kinv[r * 4 + 1] * fy + g.kinv[r * 4 + 2] * 1.f;
-  const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-  float v[3] = {p[0] / nrm, p[1] / nrm, p[2] / nrm};
   float d[3], o[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    d[r] = g.pose[r * 4 + 0] * v[0] + g.pose[r * 4 + 1] * v[1] + g.pose[r * 4 + 2] * v[2];
-    o[r] = g.pose[r * 4 + 3];
-  }
-  // nearest pixel, ties to even (torch.round); the clamp only guards the gathers against coordinates outside the image
-  const int64_t x = min(max((int64_t)rintf(fx), (int64_t)0), (int64_t)g.W - 1);
-  const int64_t y = min(max((int64_t)rintf(fy), (int64_t)0), (int64_t)g.H - 1);
-  const int64_t pix = y * g.W + x;
-  float* row = g.data + b * 7;
-  row[0] = o[0]; row[1] = o[1]; row[2] = o[2];
-  row[3] = d[0]; row[4] = d[1]; row[5] = d[2];
-  row[6] = g.mask ? g.mask[pix * g.Cm] : 0.f;
-  if (g.near) {
-    const float a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-    const float bq = 2.f * (o[0] * d[0] + o[1] * d[1] + o[2] * d[2]);
-    const float mid = 0.5f * (-bq) / a;
-    g.near[b] = mid - 1.f;
-    g.far[b] = mid + 1.f;
-  }
+  ray_through(g.kinv, g.pose, fx, fy, o, d);
+  const int64_t pix = nearest_pixel(fx, fy, g.H, g.W);
+  store_ray(g.data, g.near, g.far, b, o, d, g.mask ? g.mask[pix * g.Cm] : 0.f);
   const int64_t plane = (int64_t)g.H * g.W * 3;
   const int Lo = g.light < 0 ? g.L : 1;
   for (int lo = 0; lo < Lo; ++lo) {
@@ -139,6 +133,163 @@ __global__ void raygen_grid_kernel(RayGridArgs g) {
       g.lights_out[dst] = g.lights[src]; g.lights_out[dst + 1] = g.lights[src + 1]; g.lights_out[dst + 2] = g.lights[src + 2];
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Source mode: the same outputs computed from a view's normal / albedo / mask maps instead of gathered from the finished
+// stacks of Dataset.__init__ (models/dataset.py:100-298).  Everything in those stacks is a function of one pixel:
+//   decode     c = v / M (M = 255 or 65535), normal n = 2c - 1 with y and z negated, albedo = c, mask = (c > 0.5)
+//              (dataset.py:48-68, :134-136)
+//   frame      gen_light_directions(normal) rotates the fixed lights u_k by a rotation R whose third column is
+//              a = +-n/|n| with a_z >= 0; its first two columns are whatever basis LAPACK's SVD of n n^T returned for the
+//              repeated zero singular value.  Here they are b1, b2 of Duff et al., "Building an Orthonormal Basis,
+//              Revisited" (sign = +1, non-singular because a_z >= 0; b1 x b2 = a): a pure function of the normal.
+//   lights     l_k = u_k.x b1 + u_k.y b2 + u_k.z a (camera space), lights_dir_k = view_pose[:3,:3] l_k
+//   colours    albedo max(n . l_k, 0) and albedo max(n . w_k, 0) for the warm-up lights w_k, with the raw n (relu_nan: a
+//              NaN stays NaN, as with np.maximum)
+// IEEE sqrt and division throughout (this file is compiled without contraction).
+__device__ __forceinline__ void load3(const void* base, int type, int64_t at, float c[3]) {
+  if (type == RNB_SOURCE_U8) {
+    const uint8_t* q = (const uint8_t*)base + at;
+    c[0] = (float)q[0] / 255.f; c[1] = (float)q[1] / 255.f; c[2] = (float)q[2] / 255.f;
+  } else if (type == RNB_SOURCE_U16) {
+    const uint16_t* q = (const uint16_t*)base + at;
+    c[0] = (float)q[0] / 65535.f; c[1] = (float)q[1] / 65535.f; c[2] = (float)q[2] / 65535.f;
+  } else {
+    const float* q = (const float*)base + at;
+    c[0] = q[0]; c[1] = q[1]; c[2] = q[2];
+  }
+}
+
+__device__ __forceinline__ float source_mask(const rnb_source_maps_t& s, int64_t pix) {
+  const int64_t at = pix * s.mask_channels;
+  float c;
+  if (s.mask_type == RNB_SOURCE_U8) c = (float)((const uint8_t*)s.mask)[at] / 255.f;
+  else if (s.mask_type == RNB_SOURCE_U16) c = (float)((const uint16_t*)s.mask)[at] / 65535.f;
+  else c = ((const float*)s.mask)[at];
+  return c > 0.5f ? 1.f : 0.f;
+}
+
+// Colours and lights of pixel `pix` for the lights [l0, l0 + Lo), written to row b of [Lo, stride, 3] outputs.
+__device__ __forceinline__ void source_targets(const rnb_source_maps_t& s, const float* view_pose, int64_t pix, int l0, int Lo,
+                                               int64_t stride, int64_t b, float* rgb, float* rgb_wu, float* lights_out) {
+  float n[3], alb[3] = {1.f, 1.f, 1.f};
+  if (s.normals_type == RNB_SOURCE_F32) {
+    load3(s.normals, RNB_SOURCE_F32, pix * 3, n);
+  } else {
+    float c[3];
+    load3(s.normals, s.normals_type, pix * 3, c);
+    n[0] = 2.f * c[0] - 1.f; n[1] = -(2.f * c[1] - 1.f); n[2] = -(2.f * c[2] - 1.f);
+  }
+  if (s.albedo) load3(s.albedo, s.normals_type, pix * 3, alb);
+  float a[3] = {0.f, 0.f, 1.f}, b1[3], b2[3];
+  if (rgb || lights_out) {
+    const float len = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (len != 0.f) { a[0] = n[0] / len; a[1] = n[1] / len; a[2] = n[2] / len; }   // (a NaN normal stays NaN)
+    if (a[2] < 0.f) { a[0] = -a[0]; a[1] = -a[1]; a[2] = -a[2]; }
+    const float q = -1.f / (1.f + a[2]);
+    const float r = a[0] * a[1] * q;
+    b1[0] = 1.f + a[0] * a[0] * q; b1[1] = r; b1[2] = -a[0];
+    b2[0] = r; b2[1] = 1.f + a[1] * a[1] * q; b2[2] = -a[1];
+  }
+  for (int lo = 0; lo < Lo; ++lo) {
+    const int l = l0 + lo;
+    const int64_t dst = ((int64_t)lo * stride + b) * 3;
+    if (rgb || lights_out) {
+      const float* u = s.local_lights[l];
+      float lc[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) lc[k] = u[0] * b1[k] + u[1] * b2[k] + u[2] * a[k];
+      if (rgb) {
+        const float shade = relu_nan(n[0] * lc[0] + n[1] * lc[1] + n[2] * lc[2]);
+        rgb[dst] = alb[0] * shade; rgb[dst + 1] = alb[1] * shade; rgb[dst + 2] = alb[2] * shade;
+      }
+      if (lights_out) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          lights_out[dst + k] = view_pose[k * 4 + 0] * lc[0] + view_pose[k * 4 + 1] * lc[1] + view_pose[k * 4 + 2] * lc[2];
+      }
+    }
+    if (rgb_wu) {
+      const float* w = s.warmup_lights_cam[l];
+      const float shade = relu_nan(n[0] * w[0] + n[1] * w[1] + n[2] * w[2]);
+      rgb_wu[dst] = alb[0] * shade; rgb_wu[dst + 1] = alb[1] * shade; rgb_wu[dst + 2] = alb[2] * shade;
+    }
+  }
+}
+
+struct RayGenMapsArgs {
+  const float* kinv;       // [4,4]
+  const float* pose;       // [4,4] the view's pose: rays and lights
+  rnb_source_maps_t src;
+  const int64_t* px;       // [B]
+  const int64_t* py;       // [B]
+  int64_t B;
+  float* data;             // [B,7]
+  float* rgb;              // [L,B,3] or NULL
+  float* rgb_wu;           // [L,B,3] or NULL
+  float* lights_out;       // [L,B,3] or NULL
+  float* near;             // [B] or NULL
+  float* far;
+};
+
+__global__ void raygen_maps_kernel(RayGenMapsArgs g) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= g.B) return;
+  const int64_t x = g.px[b], y = g.py[b];
+  float d[3], o[3];
+  ray_through(g.kinv, g.pose, (float)x, (float)y, o, d);
+  const int64_t pix = y * g.src.W + x;
+  store_ray(g.data, g.near, g.far, b, o, d, source_mask(g.src, pix));
+  if (g.rgb || g.rgb_wu || g.lights_out)
+    source_targets(g.src, g.pose, pix, 0, g.src.n_lights, g.B, b, g.rgb, g.rgb_wu, g.lights_out);
+}
+
+struct RayGridMapsArgs {
+  const float* kinv;       // [4,4]
+  const float* pose;       // [4,4] pose of the rays (may be an interpolated one)
+  const float* view_pose;  // [4,4] pose of the view the maps belong to: rotates its lights to world space
+  const float* tx;         // [Wl]
+  const float* ty;         // [Hl]
+  rnb_source_maps_t src;
+  int64_t first, n;
+  int Wl, light;
+  float* data;             // [n,7]
+  float* rgb;              // [Lo,n,3] or NULL
+  float* rgb_wu;
+  float* lights_out;
+  float* near;             // [n] or NULL
+  float* far;
+};
+
+__global__ void raygen_grid_maps_kernel(RayGridMapsArgs g) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= g.n) return;
+  const int64_t i = g.first + b;
+  const int64_t iy = i / g.Wl;
+  const float fx = g.tx[i - iy * g.Wl], fy = g.ty[iy];
+  float d[3], o[3];
+  ray_through(g.kinv, g.pose, fx, fy, o, d);
+  const int64_t pix = nearest_pixel(fx, fy, g.src.H, g.src.W);
+  store_ray(g.data, g.near, g.far, b, o, d, source_mask(g.src, pix));
+  if (g.rgb || g.rgb_wu || g.lights_out)
+    source_targets(g.src, g.view_pose, pix, g.light < 0 ? 0 : g.light, g.light < 0 ? g.src.n_lights : 1, g.n, b, g.rgb,
+                   g.rgb_wu, g.lights_out);
+}
+
+// the checks both source-mode entry points share (before any launch)
+static int check_source_maps(const char* who, const rnb_source_maps_t* src) {
+  if (!src) RNB_FAIL(RNB_E_NULL, "%s: NULL source maps", who);
+  if (!src->normals || !src->mask) RNB_FAIL(RNB_E_NULL, "%s: NULL normals or mask", who);
+  if (src->normals_type < RNB_SOURCE_U8 || src->normals_type > RNB_SOURCE_F32 || src->mask_type < RNB_SOURCE_U8 ||
+      src->mask_type > RNB_SOURCE_F32)
+    RNB_FAIL(RNB_E_INVALID, "%s: unknown element type code (normals / albedo %d, mask %d)", who, src->normals_type,
+             src->mask_type);
+  if (src->n_lights < 1 || src->n_lights > kMaxRenderLights)
+    RNB_FAIL(RNB_E_INVALID, "%s: n_lights %d outside 1..kMaxRenderLights (%d)", who, src->n_lights, kMaxRenderLights);
+  if (src->H < 1 || src->W < 1 || src->mask_channels < 1)
+    RNB_FAIL(RNB_E_INVALID, "%s: bad shape (H %d, W %d, mask channels %d)", who, src->H, src->W, src->mask_channels);
+  return RNB_OK;
 }
 
 }  // namespace rnb
@@ -186,6 +337,47 @@ RNB_API int rnb_gen_rays_grid(const float* intrinsics_inv, const float* pose, co
   RayGridArgs g{intrinsics_inv, pose, tx, ty, images, images_warmup, mask, light_directions, first, n, Wl, n_lights,
                 light, H, W, mask_channels, data, true_rgb, true_rgb_warmup, lights_dir, near, far};
   hipLaunchKernelGGL(raygen_grid_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+RNB_API int rnb_gen_rays_at_view_from_maps(const float* intrinsics_inv, const float* pose, const rnb_source_maps_t* source,
+                                           const int64_t* pixels_x, const int64_t* pixels_y, int64_t B, float* data,
+                                           float* true_rgb, float* true_rgb_warmup, float* lights_dir, float* near, float* far,
+                                           rnb_stream_t stream) {
+  using namespace rnb;
+  if (!intrinsics_inv || !pose || !pixels_x || !pixels_y || !data)
+    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_at_view_from_maps: NULL pointer");
+  RNB_TRY(check_source_maps("rnb_gen_rays_at_view_from_maps", source));
+  if ((near == nullptr) != (far == nullptr))
+    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_at_view_from_maps: near and far come together");
+  if (B < 1) RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_at_view_from_maps: bad shape (B %lld)", (long long)B);
+  RayGenMapsArgs g{intrinsics_inv, pose, *source, pixels_x, pixels_y, B, data, true_rgb, true_rgb_warmup, lights_dir, near, far};
+  hipLaunchKernelGGL(raygen_maps_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+RNB_API int rnb_gen_rays_grid_from_maps(const float* intrinsics_inv, const float* pose, const float* view_pose,
+                                        const float* tx, const float* ty, int32_t Wl, int32_t Hl, int64_t first, int64_t n,
+                                        const rnb_source_maps_t* source, int32_t light, float* data, float* true_rgb,
+                                        float* true_rgb_warmup, float* lights_dir, float* near, float* far,
+                                        rnb_stream_t stream) {
+  using namespace rnb;
+  if (!intrinsics_inv || !pose || !view_pose || !tx || !ty || !data)
+    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid_from_maps: NULL pointer");
+  RNB_TRY(check_source_maps("rnb_gen_rays_grid_from_maps", source));
+  if ((near == nullptr) != (far == nullptr)) RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid_from_maps: near and far come together");
+  if (Wl < 1 || Hl < 1) RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid_from_maps: bad shape (grid %d x %d)", Hl, Wl);
+  if (first < 0 || n < 1 || first + n > (int64_t)Hl * Wl)
+    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid_from_maps: rays [%lld, %lld) outside the %d x %d grid", (long long)first,
+             (long long)(first + n), Hl, Wl);
+  if (light < -1 || light >= source->n_lights)
+    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid_from_maps: light %d out of range (n_lights %d; -1 = all)", light,
+             source->n_lights);
+  RayGridMapsArgs g{intrinsics_inv, pose, view_pose, tx, ty, *source, first, n, Wl, light, data, true_rgb, true_rgb_warmup,
+                    lights_dir, near, far};
+  hipLaunchKernelGGL(raygen_grid_maps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

@@ -110,6 +110,17 @@ def brick_geometry(res: int, brick: int) -> dict:
             "rows": (n1 ** 3 + 63) // 64 * 64, "bricks_total": nb ** 3}
 
 
+# rnb_source_maps_t element type codes (include/rnbneus.h)
+SOURCE_U8, SOURCE_U16, SOURCE_F32 = 0, 1, 2
+
+
+class SourceMaps(C.Structure):
+    _fields_ = [("normals", C.c_void_p), ("albedo", C.c_void_p), ("mask", C.c_void_p), ("normals_type", C.c_int32),
+                ("mask_type", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("mask_channels", C.c_int32),
+                ("n_lights", C.c_int32), ("local_lights", (C.c_float * 3) * MAX_RENDER_LIGHTS),
+                ("warmup_lights_cam", (C.c_float * 3) * MAX_RENDER_LIGHTS)]
+
+
 class RenderGrads(C.Structure):
     _fields_ = [("color_fine", C.c_void_p), ("weights", C.c_void_p), ("cdf_fine", C.c_void_p),
                 ("gradients", C.c_void_p), ("weight_sum", C.c_void_p), ("weight_max", C.c_void_p),
@@ -190,6 +201,12 @@ _SIGNATURES = {
                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_gen_rays_at_view_from_maps": (C.c_int, [C.c_void_p, C.c_void_p, _P(SourceMaps), C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "rnb_gen_rays_grid_from_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_int32, C.c_int64, C.c_int64, _P(SourceMaps), C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnb_loss_rnb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),

@@ -12,7 +12,13 @@ reference's own draws.
 
 Whole views (`validate_image`, `render_novel_image`: exp_runner.py:389-558) come from one more kernel,
 `rnb_gen_rays_grid`: `gen_rays_at` / `gen_rays_between` are the reference's methods, `view_rays` gives any range of
-a view's rays together with near / far and the gathers at the rounded pixel, one launch per call."""
+a view's rays together with near / far and the gathers at the rounded pixel, one launch per call.
+
+Source mode (`DeviceRays.from_source_maps`): instead of the finished stacks of `Dataset.__init__` (27 floats and a mask
+float per pixel) the object keeps the capture's normal, albedo and mask maps in their own dtype (7 bytes per pixel as
+8-bit images) and the kernels `rnb_gen_rays_at_view_from_maps` / `rnb_gen_rays_grid_from_maps` compute lights and colours
+for the pixels they are asked for (include/rnbneus.h states the arithmetic).  Every method keeps its signature and return
+shapes.  `cameras_from_projections` is the reference's `load_K_Rt_from_P` without OpenCV."""
 from __future__ import annotations
 
 import ctypes as C
@@ -46,6 +52,7 @@ class DeviceRays:
             self.masks = self.masks.unsqueeze(-1)
         if self.masks.shape[:3] != (self.n_images, self.H, self.W):
             raise ValueError(f"masks {tuple(self.masks.shape)} do not match images {tuple(self.images.shape)}")
+        self.normals = self.albedos = None                          # source mode only (from_source_maps)
 
     @classmethod
     def from_dataset(cls, dataset, device="cuda"):
@@ -53,6 +60,94 @@ class DeviceRays:
         return cls(dataset.images, getattr(dataset, "images_warmup", None), dataset.masks,
                    getattr(dataset, "light_directions", None), getattr(dataset, "light_directions_warmup", None),
                    dataset.intrinsics_all_inv, dataset.pose_all, device)
+
+    @classmethod
+    def from_source_maps(cls, normals, albedos, masks, intrinsics_all_inv, pose_all, device="cuda", tilt_deg=(0, 120, 240),
+                         slant_deg=54.74, slant_warmup_deg=30):
+        """Source mode: keeps the capture's maps on the device in their own dtype and computes lights and colours in the
+        ray kernels.  `normals`, `albedos` [V,H,W,3] (RGB order, as the reference's `load_image` returns them; `albedos`
+        None = the reference's `no_albedo`), `masks` [V,H,W] or [V,H,W,Cm]: torch tensors or numpy arrays of dtype uint8,
+        uint16 (PNG values) or float32 (already decoded: normals in the reference's camera convention).  The lights are
+        the reference's tilt / slant table (`light_tables`).  `images`, `images_warmup` and `light_directions` are None;
+        `materialize` computes a view's."""
+        normals, albedos, masks = _as_map(normals, "normals"), _as_map(albedos, "albedos"), _as_map(masks, "masks")
+        if normals.dim() != 4 or normals.shape[-1] != 3:
+            raise ValueError(f"normals {tuple(normals.shape)} are not [V, H, W, 3]")
+        V, H, W = normals.shape[:3]
+        if albedos is not None and (albedos.shape != normals.shape or albedos.dtype != normals.dtype):
+            raise ValueError(f"albedos {tuple(albedos.shape)} {albedos.dtype} do not match normals {tuple(normals.shape)} "
+                             f"{normals.dtype}")
+        if masks.dim() == 3:
+            masks = masks.unsqueeze(-1)
+        if masks.dim() != 4 or masks.shape[:3] != (V, H, W) or masks.shape[3] < 1:
+            raise ValueError(f"masks {tuple(masks.shape)} do not match normals {tuple(normals.shape)}")
+        intrinsics_all_inv, pose_all = torch.as_tensor(intrinsics_all_inv), torch.as_tensor(pose_all)
+        if intrinsics_all_inv.shape != (V, 4, 4) or pose_all.shape != (V, 4, 4):
+            raise ValueError(f"intrinsics_all_inv {tuple(intrinsics_all_inv.shape)} / pose_all {tuple(pose_all.shape)} are not "
+                             f"[{V}, 4, 4]")
+        local, warm = light_tables(tilt_deg, slant_deg, slant_warmup_deg)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("DeviceRays: the source maps must live on the GPU (there is no CPU path)")
+        self = cls.__new__(cls)
+        self.device = dev
+        self.images = self.images_warmup = self.light_directions = None
+        self.normals = normals.to(dev).contiguous()                 # [V, H, W, 3] uint8 / uint16 / float32
+        self.albedos = None if albedos is None else albedos.to(dev).contiguous()
+        self.masks = masks.to(dev).contiguous()                     # [V, H, W, Cm]
+        self.intrinsics_all_inv = intrinsics_all_inv.to(device=dev, dtype=torch.float32).contiguous()
+        self.pose_all = pose_all.to(device=dev, dtype=torch.float32).contiguous()
+        # dataset.py:207-211: pose[:3,:3] @ w_k in float64 (a float32 pose, the float64 lights), then float32
+        rot = pose_all.detach().to(device="cpu", dtype=torch.float32)[:, :3, :3].double()
+        self.light_directions_warmup = torch.einsum("vij,lj->vli", rot, torch.from_numpy(warm)).float().to(dev).contiguous()
+        self.n_images, self.n_lights, self.H, self.W = V, local.shape[0], H, W
+        self._local_lights, self._warmup_lights_cam = local.astype(np.float32), warm.astype(np.float32)
+        self._source_structs = {}
+        return self
+
+    @property
+    def source_mode(self):
+        return self.normals is not None
+
+    def has_lights(self, warmup=False):
+        """Whether the lights of `render_rnb_warmup` (`warmup`) or of `render_rnb` can be produced."""
+        if warmup:
+            return self.light_directions_warmup is not None
+        return self.source_mode or self.light_directions is not None
+
+    def resident_bytes(self):
+        """Bytes this object holds in device memory (either mode)."""
+        held = (self.images, self.images_warmup, self.masks, self.light_directions, self.light_directions_warmup,
+                self.intrinsics_all_inv, self.pose_all, self.normals, self.albedos)
+        return sum(t.numel() * t.element_size() for t in held if t is not None)
+
+    def _source(self, v):
+        """rnb_source_maps_t of view `v` (built once per view)."""
+        st = self._source_structs.get(v)
+        if st is None:
+            st = native.SourceMaps()
+            st.normals = self.normals[v].data_ptr()
+            st.albedo = None if self.albedos is None else self.albedos[v].data_ptr()
+            st.mask = self.masks[v].data_ptr()
+            st.normals_type, st.mask_type = _TYPE_CODES[self.normals.dtype], _TYPE_CODES[self.masks.dtype]
+            st.H, st.W, st.mask_channels, st.n_lights = self.H, self.W, self.masks.shape[-1], self.n_lights
+            for k in range(self.n_lights):
+                for c in range(3):
+                    st.local_lights[k][c] = float(self._local_lights[k, c])
+                    st.warmup_lights_cam[k][c] = float(self._warmup_lights_cam[k, c])
+            self._source_structs[v] = st
+        return st
+
+    def materialize(self, img_idx):
+        """Source mode: the reference's per-view tensors of view `img_idx`, computed by the whole-view kernel at
+        resolution_level 1: a dict of `images`, `images_warmup`, `light_directions` [L,H,W,3] and `mask` [H,W,1]."""
+        if not self.source_mode:
+            raise ValueError("materialize: this DeviceRays already holds the stacks (it was not built from source maps)")
+        L, H, W = self.n_lights, self.H, self.W
+        main = self.view_rays(img_idx, resolution_level=1)
+        warm = self.view_rays(img_idx, resolution_level=1, warmup=True)
+        return {"images": main["true_rgb"].reshape(L, H, W, 3), "images_warmup": warm["true_rgb"].reshape(L, H, W, 3),
+                "light_directions": main["lights_dir"].reshape(L, H, W, 3), "mask": main["mask"].reshape(H, W, 1)}
 
     # ------------------------------------------------------------------------------------------------
     def _pixels(self, batch_size, pixels_x, pixels_y):
@@ -88,6 +183,13 @@ class DeviceRays:
         lights = torch.empty(L, B, 3, **f32) if want_lights else None
         near = torch.empty(B, 1, **f32) if want_near_far else None
         far = torch.empty(B, 1, **f32) if want_near_far else None
+        if self.source_mode:
+            with native.on_device(data) as stream:
+                native.check(native.load().rnb_gen_rays_at_view_from_maps(
+                    native.ptr(self.intrinsics_all_inv[v]), native.ptr(self.pose_all[v]), C.byref(self._source(v)),
+                    native.ptr(pixels_x), native.ptr(pixels_y), B, native.ptr(data), native.ptr(rgb), native.ptr(rgb_wu),
+                    native.ptr(lights), native.ptr(near), native.ptr(far), stream))
+            return data, rgb, rgb_wu, lights, near, far
         if want_warmup and self.images_warmup is None:
             raise ValueError("DeviceRays was built without images_warmup")
         if want_lights and self.light_directions is None:
@@ -108,7 +210,8 @@ class DeviceRays:
         """models/dataset.py:351-376: returns (data [B,7], images_warmup [L,B,3], images [L,B,3], pixels_x,
         pixels_y), all on the device."""
         px, py = self._pixels(batch_size, pixels_x, pixels_y)
-        data, rgb, rgb_wu, _, _, _ = self._launch(img_idx, px, py, True, self.images_warmup is not None, False, False)
+        data, rgb, rgb_wu, _, _, _ = self._launch(img_idx, px, py, True, self.source_mode or self.images_warmup is not None,
+                                                  False, False)
         return data, rgb_wu, rgb, px, py
 
     def near_far_from_sphere(self, rays_o, rays_d):
@@ -182,24 +285,32 @@ class DeviceRays:
             pose_t = self.pose_all[v]
         else:
             pose_t = torch.as_tensor(pose).to(device=self.device, dtype=torch.float32).reshape(4, 4).contiguous()
+        source = gather and self.source_mode
         images = (self.images_warmup if warmup else self.images) if gather else None
-        if gather and warmup and images is None:
+        if gather and warmup and images is None and not source:
             raise ValueError("DeviceRays was built without images_warmup")
-        want_lights = gather and not warmup and self.light_directions is not None
+        want_lights = gather and not warmup and self.has_lights()
         f32 = dict(dtype=torch.float32, device=self.device)
         data = torch.empty(n, 7, **f32)
         near, far = torch.empty(n, 1, **f32), torch.empty(n, 1, **f32)
         rgb = torch.empty(Lo, n, 3, **f32) if gather else None
         lights = torch.empty(Lo, n, 3, **f32) if want_lights else None
         with native.on_device(data) as stream:
-            native.check(native.load().rnb_gen_rays_grid(
-                native.ptr(self.intrinsics_all_inv[v]), native.ptr(pose_t), native.ptr(tx), native.ptr(ty), Wl, Hl, first, n,
-                native.ptr(images[v]) if gather and not warmup else None,
-                native.ptr(images[v]) if gather and warmup else None,
-                native.ptr(self.masks[v]) if gather else None, self.masks.shape[-1],
-                native.ptr(self.light_directions[v]) if want_lights else None, L, li, self.H, self.W, native.ptr(data),
-                native.ptr(rgb) if gather and not warmup else None, native.ptr(rgb) if gather and warmup else None,
-                native.ptr(lights), native.ptr(near), native.ptr(far), stream))
+            if source:
+                native.check(native.load().rnb_gen_rays_grid_from_maps(
+                    native.ptr(self.intrinsics_all_inv[v]), native.ptr(pose_t), native.ptr(self.pose_all[v]), native.ptr(tx),
+                    native.ptr(ty), Wl, Hl, first, n, C.byref(self._source(v)), li, native.ptr(data),
+                    None if warmup else native.ptr(rgb), native.ptr(rgb) if warmup else None, native.ptr(lights),
+                    native.ptr(near), native.ptr(far), stream))
+            else:
+                native.check(native.load().rnb_gen_rays_grid(
+                    native.ptr(self.intrinsics_all_inv[v]), native.ptr(pose_t), native.ptr(tx), native.ptr(ty), Wl, Hl, first,
+                    n, native.ptr(images[v]) if gather and not warmup else None,
+                    native.ptr(images[v]) if gather and warmup else None,
+                    native.ptr(self.masks[v]) if gather else None, self.masks.shape[-1],
+                    native.ptr(self.light_directions[v]) if want_lights else None, L, li, self.H, self.W, native.ptr(data),
+                    native.ptr(rgb) if gather and not warmup else None, native.ptr(rgb) if gather and warmup else None,
+                    native.ptr(lights), native.ptr(near), native.ptr(far), stream))
         lights_dir = None
         if gather and warmup:
             if self.light_directions_warmup is None:
@@ -230,6 +341,62 @@ class DeviceRays:
         (`pose_between`), with view 0's intrinsics as in the reference; the rays come from the same kernel."""
         r = self.view_rays(pose=self.pose_between(idx_0, idx_1, ratio), resolution_level=resolution_level)
         return r["rays_o"].reshape(r["H"], r["W"], 3), r["rays_d"].reshape(r["H"], r["W"], 3)
+
+
+_TYPE_CODES = {torch.uint8: native.SOURCE_U8, torch.uint16: native.SOURCE_U16, torch.float32: native.SOURCE_F32}
+
+
+def _as_map(a, name):
+    """A source map as a torch tensor of one of the three element types (None passes)."""
+    if a is None:
+        return None
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if not isinstance(t, torch.Tensor) or t.dtype not in _TYPE_CODES:
+        raise ValueError(f"{name} must be uint8, uint16 or float32 (got {getattr(t, 'dtype', type(t).__name__)})")
+    return t
+
+
+def light_tables(tilt_deg=(0, 120, 240), slant_deg=54.74, slant_warmup_deg=30):
+    """The two light tables of `Dataset.gen_light_directions` (models/dataset.py:255-266) as float64 [L,3] arrays:
+    u_k = -(sin s cos t_k, sin s sin t_k, cos s) with s = `slant_deg` (the main phase's lights in the per-pixel frame) and
+    with s = `slant_warmup_deg` (the warm-up phase's camera-space lights).  rnb_source_maps_t takes them rounded to
+    float32."""
+    tilt = np.radians(np.asarray(tilt_deg, dtype=np.float64).reshape(-1))
+    if not 1 <= tilt.shape[0] <= native.MAX_RENDER_LIGHTS:
+        raise ValueError(f"{tilt.shape[0]} lights: a render takes 1 to {native.MAX_RENDER_LIGHTS}")
+
+    def table(slant_deg):
+        slant = np.radians(np.full(tilt.shape, float(slant_deg)))
+        return (-np.array([np.sin(slant) * np.cos(tilt), np.sin(slant) * np.sin(tilt), np.cos(slant)])).transpose().copy()
+
+    return table(slant_deg), table(slant_warmup_deg)
+
+
+def _rq3(m):
+    """RQ decomposition of a 3x3 matrix (float64): m = r q, r upper triangular with a positive diagonal, q orthogonal."""
+    flip = np.eye(3)[::-1]
+    q0, r0 = np.linalg.qr((flip @ m).T)
+    r, q = flip @ r0.T @ flip, flip @ q0.T
+    sign = np.where(np.diag(r) < 0, -1.0, 1.0)
+    return r * sign[None, :], q * sign[:, None]
+
+
+def cameras_from_projections(world_mats, scale_mats):
+    """`(intrinsics_all [V,4,4], pose_all [V,4,4])` (float32 tensors) from a capture's `world_mat_i` / `scale_mat_i`
+    (cameras.npz), as models/dataset.py:13-46 and :197-205 derive them with OpenCV's decomposeProjectionMatrix:
+    P = (world_mat @ scale_mat)[:3,:4] in float32, P[:3,:3] = K R by an RQ decomposition (float64, K's diagonal made
+    positive), intrinsics = K / K[2,2], pose[:3,:3] = R^T, pose[:3,3] = the camera centre (P (C, 1) = 0)."""
+    intrinsics, poses = [], []
+    for world_mat, scale_mat in zip(world_mats, scale_mats):
+        P = (np.asarray(world_mat, dtype=np.float32) @ np.asarray(scale_mat, dtype=np.float32))[:3, :4].astype(np.float64)
+        K, R = _rq3(P[:, :3])
+        intr, pose = np.eye(4), np.eye(4)
+        intr[:3, :3] = K / K[2, 2]
+        pose[:3, :3] = R.T
+        pose[:3, 3] = -np.linalg.solve(P[:, :3], P[:, 3])
+        intrinsics.append(intr)
+        poses.append(pose)
+    return (torch.from_numpy(np.stack(intrinsics)).float(), torch.from_numpy(np.stack(poses)).float())
 
 
 def interpolate_pose(pose_0, pose_1, ratio):

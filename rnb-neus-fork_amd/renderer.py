@@ -599,7 +599,7 @@ class NeuSRenderer:
         tx, ty = rays._grid(resolution_level)[:2]
         Hl, Wl = ty.numel(), tx.numel()
         N = Hl * Wl
-        if mvps and (not gather or (rays.light_directions_warmup if warmup else rays.light_directions) is None):
+        if mvps and (not gather or not rays.has_lights(warmup)):
             raise ValueError(f"render_image: api={api!r} needs the lights of a view (img_idx), or api='render'")
         n_rgb = rays.n_lights if light is None else 1
         Lo = n_rgb if mvps else 1
