@@ -1,39 +1,52 @@
-"""bf16-emulating statement of the fine pass: oracle/explicit.py plus the roundings of csrc/bf16.hip.
+"""bf16-emulating statement of the fine pass: oracle/explicit.py plus the roundings of the bf16 route's kernels
+(csrc/bf16_common.hip.h, bf16_sweeps.hip, bf16_color.hip, bf16_dw.hip).
 
 TEST INFRASTRUCTURE ONLY (same rules as oracle/rnb_oracle.py).  RNB_VARIANT_BF16 keeps fp32 master weights, fp32
 epilogues and fp32 accumulation; only what enters an MFMA or goes to HBM per point is rounded to bf16, round to nearest
-even (bf16.hip:21-22).  That arithmetic is deterministic up to summation order, so it can be copied on the CPU: the
-sweeps of `FinePass` with `rb` applied at exactly the sites where the kernels round, and nowhere else.
+even (the header comment of bf16_common.hip.h).  That arithmetic is deterministic up to summation order, so it can be
+copied on the CPU: the sweeps of `FinePass` with `rb` applied at exactly the sites where the kernels round, and nowhere
+else.
 
-Rounding sites (`rb(x) = x.to(bfloat16).to(x.dtype)`; the name is the key of `Bf16FinePass.sites`):
+Rounding sites (`rb(x) = x.to(bfloat16).to(x.dtype)`; the name is the key of `Bf16FinePass.sites`).  "where" names the
+kernel and the call that rounds: `pack2` and `to_bf` (bf16_common.hip.h) are the only two conversions, `k8_store_quad`
+packs with `pack2`.  F, R, RA, FB = bf_forward_kernel, bf_reverse_kernel, bf_ra_kernel, bf_fb_kernel (bf16_sweeps.hip);
+albedo fwd / bwd = bf_color_fwd_kernel / bf_color_bwd_kernel (bf16_color.hip).
 
-  site    tensor                                   where (csrc/bf16.hip)                      consumed by
-  ------  ---------------------------------------  -----------------------------------------  -----------------------------
-  w       every MFMA weight matrix (W, W^T) of     bf_pack_kernel :1356 (pack2)               F, R, RA, FB, feature head,
-          the SDF hidden layers, the feature                                                  albedo hidden layers (fwd, bwd)
-          head and the albedo hidden layers
-  pe      network input x and its PE columns       F :303, :316; skip PE columns :369 -> :373  F layer 0, skip layer, dW_0
-  act     a_l = softplus(z_l)                       F :373 (LDS), :375 (K8 save)               F, sdf head, feature head, dW,
-                                                                                              sdf-head backward
-  D       D_l = sigmoid(100 z_l)                    F :376                                     R, RA, FB
-  gz      gz_l (R seed and sweep)                   R :490, :493, :536, :537                   R, RA, dW
-  feat    feature head output (bf16 albedo path)    F :420 (cin8)                              albedo layer 0 (fwd, dW)
-  cpe     pe(p), pe(n) columns of the albedo input  albedo fwd :806, :816, :817                albedo layer 0 (fwd, dW)
-  cact    albedo hidden activations                 albedo fwd :847, :849                      albedo fwd, output layer, dW,
-                                                                                              relu masks of the backward
-  zc      albedo pre-activation adjoints            albedo bwd :922, :924, :945, :947          albedo bwd products, dW, db
-  fbar    feature adjoint                           albedo bwd :963 (bf16 albedo path),        FB head product, feature dW,
-                                                    FB :700 (fp32 albedo path)                 feature db
-  geb     u_0 = J_pe nbar                           RA :595, :607 (u_0 K8)                     RA layer 0, skip layer, dW_0
-  u       u_{l+1}                                   RA :658, :659                              RA, dW, sdf-head backward
-  zR      zR_l                                      RA :660                                    FB
-  zb      zb_l                                      FB :737, :739                              FB, dW, db
+  site    tensor                                  where                                     consumed by
+  ------  --------------------------------------- ----------------------------------------  -----------------------------
+  w       every MFMA weight matrix (W, W^T) of    bf_pack_kernel (pack2)                    F, R, RA, FB, feature head,
+          the SDF hidden layers, the feature                                                albedo hidden layers (fwd,
+          head and the albedo hidden layers                                                 bwd)
+  pe      network input x and its PE columns      F: the encoding block (to_bf); the skip   F layer 0, skip layer, dW_0
+                                                  layer's PE columns: epilogue, LDS store
+  act     a_l = softplus(z_l)                     F epilogue: LDS store (to_bf) and the     F, sdf head, feature head, dW,
+                                                  K8 save of g.a[l]                         sdf-head backward
+  D       D_l = sigmoid(100 z_l)                  F epilogue: K8 save of g.D[l]             R, RA, FB
+  gz      gz_l (R seed and sweep)                 R seed (pack2, to_bf); R epilogue: LDS    R, RA, dW
+                                                  store and K8 save of g.gz[l - 1]
+  feat    feature head output (bf16 albedo path)  F feature head: K8 store into cin8        albedo layer 0 (fwd, dW)
+  cpe     pe(p), pe(n) columns of the albedo      albedo fwd: the encoding block (to_bf)    albedo layer 0 (fwd, dW)
+          input
+  cact    albedo hidden activations               albedo fwd epilogue: LDS store, K8 save   albedo fwd, output layer, dW,
+                                                  of g.ac8[l]                               relu masks of the backward
+  zc      albedo pre-activation adjoints          albedo bwd: the zc_{nc-1} block and the   albedo bwd products, dW, db
+                                                  layer epilogue (LDS store, K8 save)
+  fbar    feature adjoint                         albedo bwd: K8 store of g.fbar8 (bf16     FB head product, feature dW,
+                                                  albedo path); FB: the load of g.fbar      feature db
+                                                  (pack2; fp32 albedo path)
+  geb     u_0 = J_pe nbar                         RA: the load of g.geb (to_bf), u_0 in K8  RA layer 0, skip layer, dW_0
+  u       u_{l+1}                                 RA epilogue: LDS store, K8 save of        RA, dW, sdf-head backward
+                                                  g.u[l + 1]
+  zR      zR_l                                    RA epilogue: K8 save of g.zR[l]           FB
+  zb      zb_l                                    FB epilogue: LDS store, K8 save of        FB, dW, db
+                                                  g.zb[l]
 
-Not rounded, as on the device: the sdf-head row and the albedo output layer (fp32 weights on bf16 activations,
-:386-:402, :855-:882), every epilogue (softplus, its derivative, sigmoid, ReLU masks, the composite and its backward),
-g_e and the normal (:530, :553, :558-:574), the skip connection's g_e share, the fp32 accumulators, every dW / db sum
-and the weight-norm backward.  The albedo network runs in bf16 only where `bf16_color_supported` (bf16.hip:1364)
-holds; otherwise it is the fp32 path (layers.hip), as on the device.
+Not rounded, as on the device: the sdf-head row and the albedo output layer (fp32 weights on bf16 activations: the "sdf
+head" block of F, the "output layer + sigmoid" block of the albedo fwd), every epilogue (softplus, its derivative,
+sigmoid, ReLU masks, the composite and its backward), g_e and the normal (the GE tile of R and its last block), the skip
+connection's g_e share, the fp32 accumulators, every dW / db sum and the weight-norm backward.  The albedo network runs
+in bf16 only where `bf16_color_supported` (bf16_color.hip) holds; otherwise it is the fp32 path (layers.hip), as on the
+device.
 
 Weights: `weights_from_packed` reads the device's own fp32 effective weights (the fp32 part of `packed`, after
 rnb_weightnorm_fwd: the skip layer's 1/sqrt(2) folded in, the albedo layer-0 columns permuted to [feature | pe(p) |
@@ -121,7 +134,7 @@ def packed_layout(mc: O.ModelConf) -> dict:
 
 
 def bf16_color_supported(mc: O.ModelConf) -> bool:
-    """csrc/bf16.hip:1364 on the layout of `mc`."""
+    """`bf16_color_supported` (csrc/bf16_color.hip) on the layout of `mc`."""
     L = packed_layout(mc)
     cc = mc.color
     if L["F"] != 256 or cc.d_hidden != 256:
@@ -132,7 +145,7 @@ def bf16_color_supported(mc: O.ModelConf) -> bool:
 
 
 def mirror_matrices(mc: O.ModelConf):
-    """(name, float offset, N, K) of every matrix bf16_pack_weights mirrors (bf16.hip:1435-1461)."""
+    """(name, float offset, N, K) of every matrix bf16_pack_weights mirrors (csrc/bf16_sweeps.hip), in its order."""
     L = packed_layout(mc)
     out = []
     for l, e in enumerate(L["hid"]):
@@ -146,7 +159,8 @@ def mirror_matrices(mc: O.ModelConf):
 
 
 def unfragment(u16: torch.Tensor, N: int, K: int) -> torch.Tensor:
-    """bf16 bits of one mirrored matrix in MFMA-fragment order (bf16.hip:63-64: fragment (nt, ks) = 64 units of 8 values,
+    """bf16 bits of one mirrored matrix in MFMA-fragment order (the matrix loop of bf16_common.hip.h and
+    `bf_pack_kernel`: fragment (nt, ks) = 64 units of 8 values,
     unit (h, c) = W[32 nt + c][16 ks + 8 h .. +8]) -> fp32 [N][K] row-major."""
     f = (u16.to(torch.int32) & 0xFFFF) << 16
     f = f.view(torch.float32).reshape(N // 32, K // 16, 2, 32, 8)     # nt, ks, h, c, j
@@ -259,7 +273,7 @@ class Bf16FinePass(FinePass):
             ins.append(h)
             z = h @ self.W[l].t() + self.b[l]
             t = 100.0 * z
-            # bf16.hip softplus_aD_fast; at 100 z > 20 a == z and D == 1 in fp32 (PyTorch's threshold in FinePass)
+            # softplus_aD_fast; at 100 z > 20 a == z and D == 1 in fp32 (PyTorch's threshold in FinePass)
             D.append(self.r("D", torch.where(t > 20.0, torch.ones_like(z), torch.sigmoid(t))))
             h = self.r("act", softplus100(z))
             acts.append(h)
@@ -316,8 +330,8 @@ class Bf16FinePass(FinePass):
 
     # ------------------------------------------------------------------ C' RA FB dW
     def _color_backward(self, albbar, grads):
-        """C' of the bf16 albedo kernels (bf16.hip:887-981, :985-1027, the dW jobs :1642-1651): returns
-        (fbar, the normal's share of the input adjoint)."""
+        """C' of the bf16 albedo kernels (bf16_color.hip: bf_color_bwd_kernel, bf_color_out_bwd_kernel; the albedo dW
+        jobs of bf16_dw_list in bf16_dw.hip): returns (fbar, the normal's share of the input adjoint)."""
         cc = self.cc
         nl = cc.n_layers + 1
         zo = albbar * self.albedo * (1 - self.albedo) if cc.squeeze_out else albbar
@@ -346,7 +360,7 @@ class Bf16FinePass(FinePass):
             if self.color_bf16:
                 fbar, pen_bar = self._color_backward(albbar, grads)
             else:
-                # fp32 albedo path (layers.hip): FinePass's C'; FB rounds the feature adjoint as it loads it (:700)
+                # fp32 albedo path (layers.hip): FinePass's C'; FB rounds the feature adjoint as it loads it (FB)
                 zb = albbar * self.albedo * (1 - self.albedo) if cc.squeeze_out else albbar
                 nl = cc.n_layers + 1
                 for l in range(nl - 1, -1, -1):
@@ -361,7 +375,7 @@ class Bf16FinePass(FinePass):
                 pen_bar = inb[:, pe_d:2 * pe_d]
             m = cc.multires_view
             nbar = nbar + (pe_jt(self.normal, pen_bar, m) if m > 0 else pen_bar)
-        # RA (bf16.hip:579-665): u_0 = geb; u_{l+1} = (u_l W_l^T) D_l, zR_l = 100 (u_l W_l^T - u_{l+1}) gz_l
+        # RA (bf_ra_kernel): u_0 = geb; u_{l+1} = (u_l W_l^T) D_l, zR_l = 100 (u_l W_l^T - u_{l+1}) gz_l
         geb = self.r("geb", pe_j(self.x, nbar, sc.multires) if sc.multires > 0 else nbar)
         u = geb
         us, zR = [], []
@@ -373,12 +387,12 @@ class Bf16FinePass(FinePass):
             un = v * self.D[l]
             zR.append(self.r("zR", ((v - un) * self.gz[l]) * 100.0))
             u = self.r("u", un)
-        # sdf-head row (bf16.hip:1304-1337): dw_sdf = sum (sbar / scale) a_last + u_last, db_sdf = sum sbar / scale
+        # sdf-head row (bf_sdf_head_bwd_kernel): dw_sdf = sum (sbar / scale) a_last + u_last, db_sdf = sum sbar / scale
         sb = sbar * (1.0 / sc.scale)
         a_last = self.acts[-1]
         dW_out = [self._sum_rows(sb[:, None] * a_last + u)]
         db_out = [self._sum_rows(sb[:, None])]
-        # FB (bf16.hip:668-747): ab = fbar W_feat + (sbar / scale) w_sdf; zb_l = ab D_l + zR_l; ab = zb_l W_l
+        # FB (bf_fb_kernel): ab = fbar W_feat + (sbar / scale) w_sdf; zb_l = ab D_l + zR_l; ab = zb_l W_l
         ab = sb[:, None] * self.wsdf[None, :]
         if fbar is not None:
             ab = fbar @ self.Wf + ab
@@ -394,7 +408,7 @@ class Bf16FinePass(FinePass):
         for l in range(n_lin - 2, -1, -1):
             zb = self.r("zb", ab[:, :self.W[l].shape[0]] * self.D[l] + zR[l])
             zbs[l] = zb
-            # dW job of layer l (bf16.hip:1631-1638): gz_l^T u_l + zb_l^T in_l, bias from zb_l
+            # dW job of layer l (bf16_dw_list, bf16_dw.hip): gz_l^T u_l + zb_l^T in_l, bias from zb_l
             dW = self._sum_rows(self.gz[l], us[l]) + self._sum_rows(zb, self.ins[l])
             if l == skip:
                 dW = dW * RS2           # the device's W_skip carries 1/sqrt(2); the parameter's gradient does not

@@ -1,7 +1,8 @@
 // The explicit backward of both networks for every route, given pb.sbar, pb.nbar, pb.albbar (from the composite backward or
 // a point-wise autograd call): a list of stages, each dispatched on Layout::route to the route's own kernels (layers.hip,
-// fused_bwd.hip, color_h2.hip, bf16.hip), then the weight-gradient jobs (dw.hip).  The point-wise kernels here are the
-// ones more than one route launches; the input adjoints of the point-wise autograd calls follow.
+// fused_bwd.hip, color_h2.hip, bf16_sweeps.hip, bf16_color.hip), then the weight-gradient jobs (dw.hip; bf16_dw.hip).  The
+// point-wise kernels here are the ones more than one route launches; the input adjoints of the point-wise autograd calls
+// follow.
 #include "gemm.hip.h"
 #include "rnb_internal.h"
 
@@ -262,7 +263,7 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
   const Route& r = L.route;
   RNB_TRY(check_route_buffers(L, pb, parts));
   RNB_TRY(dw_zero_partials(L, pb, parts, s));
-  // the weight-gradient jobs (dw.hip) follow every other launch of the backward; bf16_color_backward's are bf16_backward's
+  // the weight-gradient jobs (dw.hip) follow every other launch of the backward; bf16_color_backward's are bf16_dw_backward's
   BwdParts dw_parts = parts;
   dw_parts.albedo = parts.albedo && r.color != COLOR_BF16;
   // ---- C': albedo network backward ---------------------------------------------------------------
@@ -276,16 +277,20 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
   if (!parts.sdf) return dw_backward(L, pb, dw_parts, 0, packed_grad, s);
   // ---- nbar (+ albedo-net contribution) -> geb = u_0 -----------------------------------------------
   if (parts.normal && !(parts.albedo && r.color == COLOR_H2)) RNB_TRY(launch_nbar_geb(L, pb, parts.albedo, s));
-  if (r.sdf == SDF_BF16) {
-    // RNB_VARIANT_BF16: RA, the sdf-head row, FB and every weight gradient of the SDF network (+ feature head) run as
-    // bf16 sweeps on the bf16 saved state; the albedo net's own (fp32) weight-gradient jobs go first
+  const bool bf = r.sdf == SDF_BF16;   // (the render path only: every part is on, api.hip refuses the point-wise calls)
+  if (bf) {
+    // The albedo net's fp32 weight-gradient jobs (fp32 albedo kernels behind bf16 SDF sweeps) run HERE, before RA, not at
+    // the end: bf16_dw_backward reuses pb.dw_part from its base and, in the deterministic variant, zeroes all of it and
+    // fills it with its own slabs.  The fp32 split-K kernels ACCUMULATE into slabs that dw_zero_partials zeroed above; run
+    // after the bf16 jobs they would add onto dirty slabs.
     dw_parts.sdf = false;
     RNB_TRY(dw_backward(L, pb, dw_parts, 0, packed_grad, s));
-    return bf16_backward(L, packed, pb, parts.albedo, packed_grad, s);
   }
   // ---- RA: adjoint of the reverse sweep, forward layer order -----------------------------------------
   int u_tiles = 0;
-  if (!parts.normal) {   // nbar == 0: RA's outputs are zero; FB adds zR_l, the layers' weight gradients skip the u pairs
+  if (bf) {
+    RNB_TRY(bf16_ra(L, packed, pb, s));
+  } else if (!parts.normal) {   // nbar == 0: RA's outputs are zero; FB adds zR_l, the layers' weight gradients skip the u pairs
     for (int l = 0; l < L.nh; ++l) RNB_CHECK_HIP(hipMemsetAsync(pb.zR[l], 0, (size_t)pb.Mp * L.Hp * sizeof(float), s));
   } else if (r.sdf == SDF_FUSED) {
     RNB_TRY(fused_ra(L, packed, pb, s, &u_tiles));
@@ -294,10 +299,16 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
   }
   // ---- sdf-head row gradient ---------------------------------------------------------------------
   int sdfh_slabs = 0;
-  RNB_TRY(launch_sdf_head_bwd(L, pb, parts.normal && r.sdf == SDF_LAYERS, u_tiles, packed_grad, &sdfh_slabs, s));
-  // ---- FB: all zb_l (one launch on the fused route) ------------------------------------------------
-  if (r.sdf == SDF_FUSED) RNB_TRY(fused_fb(L, packed, pb, parts.feat, s));
-  else RNB_TRY(layers_fb(L, packed, pb, parts.feat, s));
+  if (bf) RNB_TRY(bf16_sdf_head_bwd(L, pb, packed_grad, s));
+  else RNB_TRY(launch_sdf_head_bwd(L, pb, parts.normal && r.sdf == SDF_LAYERS, u_tiles, packed_grad, &sdfh_slabs, s));
+  // ---- FB: all zb_l (one launch on the fused and bf16 routes) ----------------------------------------
+  switch (r.sdf) {
+    case SDF_BF16: RNB_TRY(bf16_fb(L, packed, pb, parts.albedo, s)); break;
+    case SDF_FUSED: RNB_TRY(fused_fb(L, packed, pb, parts.feat, s)); break;
+    case SDF_LAYERS: RNB_TRY(layers_fb(L, packed, pb, parts.feat, s)); break;
+  }
+  // ---- dW --------------------------------------------------------------------------------------------
+  if (bf) return bf16_dw_backward(L, pb, parts.albedo, packed_grad, s);
   return dw_backward(L, pb, dw_parts, sdfh_slabs, packed_grad, s);
 }
 

@@ -109,7 +109,7 @@ int make_layout(const rnb_model_desc* d, Layout* L) {
   if (d->variant & RNB_VARIANT_BF16) {
     if (!fused_supported(*L))
       RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 needs the 256-wide SDF network shape (d_hidden 256, feature width 225..256)");
-    // bf16.hip multiplies layer 0 as 64 PE columns (Ep = 64: multires 5 or 6); with Ep = 32 it read past the matrix
+    // bf16_sweeps.hip multiplies layer 0 as 64 PE columns (Ep = 64: multires 5 or 6); with Ep = 32 it read past the matrix
     if (L->Ep != 64) RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 needs 33..40 positional-encoding columns (multires 5 or 6), got %d", L->pe);
     // a skip connection at layer 1: the albedo weight gradients are 8-11 x further from the bf16 emulation than its fp32 form
     if (L->skip == 1) RNB_FAIL(RNB_E_INVALID, "RNB_VARIANT_BF16 does not support a skip connection at layer 1");
@@ -158,7 +158,7 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
   pb->Mp = pad_rows(M);
   const int64_t Mp = pb->Mp;
   const bool bf = L.route.sdf == SDF_BF16;
-  // RNB_VARIANT_BF16: the per-point state of the SDF sweeps is bf16 (K8 layout, bf16.hip): half the bytes
+  // RNB_VARIANT_BF16: the per-point state of the SDF sweeps is bf16 (K8 layout, bf16_common.hip.h): half the bytes
   auto take_state = [&](int64_t n) { return bf ? reinterpret_cast<float*>(c.take<uint16_t>(n)) : c.take<float>(n); };
   pb->x = c.take<float>(Mp * 4);
   pb->e = c.take<float>(Mp * L.Ep);

@@ -49,8 +49,8 @@ inline double mm_flops(int64_t M, const Lin& ln) { return 2.0 * (double)M * ln.N
 
 // The kernel route of each network: a function of the descriptor alone, decided once by make_layout.  Forward, backward
 // and carve_points all read it, so the buffers carved, the sweeps that fill them and the backward that reads them agree.
-enum SdfRoute { SDF_LAYERS, SDF_FUSED, SDF_BF16 };   // per-layer chain (layers.hip) | fused.hip / fused_bwd.hip | bf16.hip
-enum ColorRoute { COLOR_NONE, COLOR_LAYERS, COLOR_H2, COLOR_BF16 };   // no albedo net | layers.hip | color_h2.hip | bf16.hip
+enum SdfRoute { SDF_LAYERS, SDF_FUSED, SDF_BF16 };   // per-layer chain (layers.hip) | fused.hip / fused_bwd.hip | bf16_sweeps.hip
+enum ColorRoute { COLOR_NONE, COLOR_LAYERS, COLOR_H2, COLOR_BF16 };   // no albedo net | layers.hip | color_h2.hip | bf16_color.hip
 struct Route {
   SdfRoute sdf;
   ColorRoute color;
@@ -92,7 +92,7 @@ struct Layout {
 
 int make_layout(const rnb_model_desc* d, Layout* L);
 
-// The SDF network as its sweep kernels read it (fused.hip / fused_bwd.hip, sweep_mv.hip, bf16.hip): the layer table of the
+// The SDF network as its sweep kernels read it (fused.hip / fused_bwd.hip, sweep_mv.hip, bf16_sweeps.hip): the layer table of the
 // Layout, by value inside every sweep's argument struct.  Offsets are float offsets into the packed buffer.
 struct SdfNetArgs {
   int nh, skip, pe, multires, Ep;
@@ -225,7 +225,7 @@ __device__ inline int64_t grid_out_index(const GridGen& g, int64_t row, int64_t 
   return grid_locate(g, row, M, ix, iy, iz);
 }
 
-// ---- the front and the tail the forward sweeps share (fused.hip, sweep_mv.hip, bf16.hip) ----
+// ---- the front and the tail the forward sweeps share (fused.hip, sweep_mv.hip, bf16_sweeps.hip) ----
 // The scaled point of row `row` of a sweep over M rows: the grid sample of the row (grid.on: dense slab, brick list or
 // brick-corner lattice) or row `row` of pts, times scale; masked and padding rows compute on the origin.
 __device__ inline void sweep_point(const GridGen& grid, const float* pts, int64_t row, int64_t M, float scale, float (&x)[3]) {
@@ -471,17 +471,23 @@ int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipSt
 int64_t color_h2_part_floats(const Layout& L, int64_t M);
 constexpr int kSdfHeadSlabs = 64;   // row slabs of sdf_head_bwd_kernel's partial sums (summed in slab order: no atomics)
 
-// ---- RNB_VARIANT_BF16 (bf16.hip): bf16-operand sweeps of the 256-wide network, saved state in bf16 "K8" layout ----
+// ---- RNB_VARIANT_BF16 (bf16_common.hip.h): bf16-operand sweeps of the 256-wide network, saved state in bf16 "K8" layout ----
 inline bool is_bf16(const Layout& L) { return (L.variant & RNB_VARIANT_BF16) != 0; }
+// bf16_sweeps.hip: the weight mirror and the SDF network's sweeps
 int bf16_pack_weights(const Layout& L, float* packed, hipStream_t s);
 int bf16_forward(const Layout& L, const float* packed, const float* pts, int64_t M, PointBufs& pb, bool save, bool need_feat,
                  hipStream_t s, const GridGen* grid = nullptr, bool feat_k8 = false);
 int bf16_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s);
+int bf16_ra(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s);
+int bf16_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_color, hipStream_t s);
+// bf16_color.hip: the albedo network
 bool bf16_color_supported(const Layout& L);
 int bf16_color_forward(const Layout& L, const float* packed, PointBufs& pb, const float* pts, hipStream_t s);
 int bf16_color_backward(const Layout& L, const float* packed, PointBufs& pb, float* packed_grad, hipStream_t s);
-int bf16_backward(const Layout& L, const float* packed, PointBufs& pb, bool with_color, float* packed_grad, hipStream_t s);
-// floats of bf16_backward's ordered-reduction slabs over M points (deterministic variant)
+// bf16_dw.hip: the sdf-head row's gradient and the grouped weight-gradient launch
+int bf16_sdf_head_bwd(const Layout& L, PointBufs& pb, float* packed_grad, hipStream_t s);
+int bf16_dw_backward(const Layout& L, PointBufs& pb, bool with_color, float* packed_grad, hipStream_t s);
+// floats of bf16_dw_backward's ordered-reduction slabs over M points (deterministic variant)
 int64_t bf16_dw_floats(const Layout& L, int64_t M, bool with_color);
 
 // ---- sampling / composite ------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """RNB_VARIANT_BF16 (BASELINE config 5: 256 samples per ray, bf16): the SDF-network sweeps with bf16 operands on
-v_mfma_f32_32x32x16_bf16, fp32 accumulators and bf16 saved state (csrc/bf16.hip), against the FP32 oracle (SURVEY 8c:
+v_mfma_f32_32x32x16_bf16, fp32 accumulators and bf16 saved state (csrc/bf16_*.hip), against the FP32 oracle (SURVEY 8c:
 "bf16 config: reported separately vs an fp32 oracle").
 
 Tolerances (stated in DESIGN.md 4b, measured values printed with `pytest -s`).  bf16 keeps 8 significant bits: every

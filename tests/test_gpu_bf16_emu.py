@@ -1,4 +1,4 @@
-"""RNB_VARIANT_BF16 (csrc/bf16.hip) against the bf16-emulating statement (oracle/bf16_emu.py): the same roundings at
+"""RNB_VARIANT_BF16 (csrc/bf16_*.hip) against the bf16-emulating statement (oracle/bf16_emu.py): the same roundings at
 the same sites on the device's own fp32 weights, so device and emulation differ only by summation order and the rare
 bf16 rounding that order flips.  tests/test_gpu_bf16.py stays as the coarse check against the fp32 oracle.
 

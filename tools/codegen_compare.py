@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Device code of two checkouts, kernel by kernel (no GPU needed): the check of a refactor that must not change a kernel.
 
-    python tools/codegen_compare.py PARENT_TREE CHANGE_TREE fused fused_bwd sweep_mv bf16 ... > profiles/<name>_codegen.txt
+    python tools/codegen_compare.py PARENT_TREE CHANGE_TREE fused fused_bwd sweep_mv ... > profiles/<name>_codegen.txt
+    python tools/codegen_compare.py PARENT_TREE CHANGE_TREE bf16=bf16_sweeps+bf16_color+bf16_dw backward dw
 
+An argument is a unit both trees have, or PARENT_UNITS=CHANGE_UNITS ('+' between units) where kernels moved between units:
+the kernels are then matched by symbol across the union of the units of each side.
 Compiles csrc/<unit>.hip of both trees with the library's flags (buildid.py: COMMON_FLAGS + the unit's EXTRA_FLAGS) plus
 `--cuda-device-only -S`, and compares per kernel: the resource counts of the code object's metadata (registers, spills, LDS,
 scratch) and the number of MFMA, vector-memory load / store, LDS and barrier instructions — any difference there is a FAIL.
@@ -75,18 +78,33 @@ def demangle(names):
 
 
 def main():
-    parent, change, units = sys.argv[1], sys.argv[2], sys.argv[3:]
+    parent, change = sys.argv[1], sys.argv[2]
+    groups = []   # (parent units, change units)
+    for arg in sys.argv[3:]:
+        pu, _, cu = arg.partition("=")
+        groups.append((pu.split("+"), (cu or pu).split("+")))
     tmp = tempfile.mkdtemp()
-    jobs = [(t, u, os.path.join(tmp, f"{tag}_{u}.s")) for u in units for tag, t in (("p", parent), ("c", change))]
+    jobs = [(t, u, os.path.join(tmp, f"{tag}_{u}.s")) for g in groups for tag, t, us in (("p", parent, g[0]), ("c", change, g[1]))
+            for u in us]
     with concurrent.futures.ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(lambda j: compile_unit(*j), jobs))
+
+    def parse_union(tag, units):
+        meta, bodies = {}, {}
+        for u in units:
+            m, b = parse(os.path.join(tmp, f"{tag}_{u}.s"))
+            meta.update(m)
+            bodies.update(b)
+        return meta, bodies
+
     bad = 0
-    for u in units:
-        pm, pb = parse(os.path.join(tmp, f"p_{u}.s"))
-        cm, cb = parse(os.path.join(tmp, f"c_{u}.s"))
+    for punits, cunits in groups:
+        pm, pb = parse_union("p", punits)
+        cm, cb = parse_union("c", cunits)
         same_syms = sorted(pm) == sorted(cm)
-        print(f"== {u}.hip: {len(pm)} kernels at the parent, {len(cm)} at the change; sorted symbol lists "
-              f"{'identical' if same_syms else 'DIFFER'}")
+        name = lambda us: " + ".join(u + ".hip" for u in us)
+        print(f"== {name(cunits) if punits == cunits else name(punits) + ' -> ' + name(cunits)}: {len(pm)} kernels at the parent, "
+              f"{len(cm)} at the change; sorted symbol lists {'identical' if same_syms else 'DIFFER'}")
         if not same_syms:
             bad += 1
             for n in sorted(set(pm) ^ set(cm)):
