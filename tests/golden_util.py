@@ -6,16 +6,22 @@ import numpy as np
 import torch
 
 from oracle import rnb_oracle as O
+from tests.parity import GRAD_CAP, K_GRAD
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-# Calibrated gradient bounds are `min(GRAD_CAP, max(1e-4, 3 * rel32s))` (tests/test_gpu_parity.py).  A tensor whose
-# fp32 REFERENCE gradient is further than GRAD_CAP / 3 from the reference's fp64 gradient is something fp32 cannot
+# Calibrated gradient bounds are parity.grad_bound(rel32s), capped at GRAD_CAP (tests/parity.py).  A tensor whose
+# fp32 REFERENCE gradient is further than GRAD_CAP / K_GRAD from the reference's fp64 gradient is something fp32 cannot
 # resolve: it is not a parity target and must be listed here explicitly (fixture -> tensor names), otherwise the
 # fixture refuses to load.  No committed fixture needs an entry (largest rel32s: 2.6e-3, tiny_warmup_sharp
 # dev.variance).
-GRAD_CAP = 1e-2
 UNRESOLVED_BY_FP32 = {}
+
+# tests/golden/image_rays_small.npz: largest element difference between `interpolate_pose` and the reference's recorded pose
+# over the fixture's three ratios, measured on the CPU: 0.0 (bit-equal: same float32 inversions, and the float64 slerp rounds
+# to the same float32 rotation).  The bound is four times that and may not exceed 1e-5 (tests/test_image_render_host.py).
+POSE_DIFF_MEASURED = 0.0
+POSE_BOUND = 4.0 * POSE_DIFF_MEASURED
 
 
 def case_names():
@@ -84,9 +90,9 @@ class Golden:
         self.rel32s = {k[7:]: float(z[k]) for k in z.files if k.startswith("rel32s.")}
         dropped = set(UNRESOLVED_BY_FP32.get(name, ()))
         for k, r in self.rel32s.items():
-            if r > GRAD_CAP / 3.0 and k not in dropped:
+            if r > GRAD_CAP / K_GRAD and k not in dropped:
                 raise ValueError(f"fixture {name}: the fp32 reference's own gradient of {k} is {r:.2e} (rel-L2) from "
-                                 f"its fp64 run — beyond GRAD_CAP / 3 = {GRAD_CAP / 3.0:.1e}; list it in "
+                                 f"its fp64 run — beyond GRAD_CAP / K_GRAD = {GRAD_CAP / K_GRAD:.1e}; list it in "
                                  "UNRESOLVED_BY_FP32 to drop it explicitly")
         for k in dropped:
             self.grad64.pop(k, None)

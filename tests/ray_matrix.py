@@ -131,6 +131,8 @@ BF16_ROW_NAMES = ["65+64/1", "129+39/3", "64+448/7"]
 # explicit depths: S of the forward-only renders, and of the z_vals.grad cases
 Z_VALS_S = [1, 2, 63, 65, 100, 129, 190, 511, 512]
 Z_GRAD_S = [2, 63, 65, 129, 190]
+# every float output of a render (the explicit-depth forwards check each; the input-gradient cases weight each in their loss)
+FLOAT_OUTS = ("color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights", "gradient_error")
 
 
 def up_sample_pairs():

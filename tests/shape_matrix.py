@@ -184,8 +184,20 @@ def oracle_points(p, mc, pts, normals, feats, dt):
     return out, nrm, alb
 
 
-
-
 def step_batch(B=64):
     """the rays of every shape's end-to-end step"""
     return O.synthetic_batch(B, seed=11, step=1, warmup=False)
+
+
+def desc_of(mc, **variant):
+    """rnb_model_desc of `mc` as the drop-in classes write it (fields.model_desc), with the given variant bits."""
+    import rnb_neus_fork_amd as R     # (the table itself needs no library)
+    s, c = mc.sdf, mc.color
+    sdf = R.SDFNetwork(d_in=3, d_out=s.d_out, d_hidden=s.d_hidden, n_layers=s.n_layers, skip_in=s.skip_in,
+                       multires=s.multires, bias=s.bias, scale=s.scale, weight_norm=s.weight_norm)
+    col = R.RenderingNetwork(d_feature=c.d_feature, mode=c.mode, d_in=c.d_in, d_out=c.d_out, d_hidden=c.d_hidden,
+                             n_layers=c.n_layers, weight_norm=c.weight_norm, multires_view=c.multires_view,
+                             squeeze_out=c.squeeze_out)
+    d = R.model_desc(sdf, col)
+    d.variant = R.native.variant_bits(**variant)
+    return d

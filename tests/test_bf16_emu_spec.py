@@ -12,6 +12,7 @@ from oracle import rnb_oracle as O
 from oracle.bf16_emu import SITES, Bf16FinePass, rb, weights_from_params
 from oracle.explicit import FinePass
 from tests.golden_util import Golden
+from tests.parity import rel_l2
 
 OUT_KEYS = ["color_fine", "weights", "weight_sum", "weight_max", "gradients", "gradient_error", "cdf_fine", "s_val"]
 
@@ -47,10 +48,6 @@ def _run(fp, b, z, lights, kw, cot=None):
     return out, fp.backward(cot), cot
 
 
-def _rel(a, b):
-    return float((a - b).norm() / b.norm().clamp_min(1e-300))
-
-
 @pytest.mark.parametrize("name", ["tiny_main_sharp", "tiny_warmup_sharp", "tiny_main_noalbedo", "tiny_render_bg",
                                   "full_main_sharp"])
 def test_unrounded_emulation_is_the_explicit_statement(name):
@@ -67,7 +64,7 @@ def test_unrounded_emulation_is_the_explicit_statement(name):
             if float(v.norm()) == 0.0:
                 assert float(gr_e[k].norm()) == 0.0, k
                 continue
-            assert _rel(gr_e[k], v) < 1e-10, f"{k}: {_rel(gr_e[k], v):.2e}"
+            assert rel_l2(gr_e[k], v) < 1e-10, f"{k}: {rel_l2(gr_e[k], v):.2e}"
 
 
 def test_every_rounding_site_is_live():
@@ -157,7 +154,7 @@ def test_emu64_is_about_bf16_error_from_fp64():
     print(f"emu64 vs unrounded fp64: normals {e_n:.2e}, render outputs {e_w:.2e}")
     assert 1e-4 < e_n <= 1e-1
     assert 1e-4 < e_w <= 3e-2
-    rels = {k: _rel(gr[k], ref_gr[k]) for k in ref_gr if float(ref_gr[k].norm()) > 0}
+    rels = {k: rel_l2(gr[k], ref_gr[k]) for k in ref_gr if float(ref_gr[k].norm()) > 0}
     worst = max(rels, key=rels.get)
     print(f"emu64 vs unrounded fp64: gradient rel-L2 median {sorted(rels.values())[len(rels) // 2]:.2e}, "
           f"worst {worst} {rels[worst]:.2e}")

@@ -15,23 +15,13 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device
 
 pytestmark = pytest.mark.gpu
 
 SDF_ATOL, NRM_ATOL, NRM_RMS, OUT_ATOL = 1e-2, 1e-1, 2e-2, 3e-2
 GRAD_COS_MIN, GRAD_REL_MAX = 0.99, 0.15
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available()
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _model(R, seed=0, sharpen=False, render=None):
@@ -47,7 +37,7 @@ def _model(R, seed=0, sharpen=False, render=None):
     else:
         torch.manual_seed(seed)
         p = O.init_params(mc)
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(mc, p, device())
     ren.set_variant(bf16=True)
     return mc, p, sdf, dev, col, ren
 
@@ -56,9 +46,9 @@ def test_bf16_needs_the_256_wide_network(R):
     mc = O.ModelConf(sdf=O.SDFConf(d_out=65, d_hidden=64), color=O.ColorConf(d_feature=64, d_hidden=64))
     torch.manual_seed(0)
     p = O.init_params(mc)
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(mc, p, device())
     ren.set_variant(bf16=True)
-    b = {k: v.to(_dev()) for k, v in O.synthetic_batch(4, seed=1, step=0).items()}
+    b = {k: v.to(device()) for k, v in O.synthetic_batch(4, seed=1, step=0).items()}
     with pytest.raises(R.native.NativeError, match="256-wide"):
         ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], t_rand=b["t_rand"])
 
@@ -70,11 +60,11 @@ def test_bf16_pointwise_sdf_and_normal(R, sharpen):
     pts = (torch.rand(5000, 3, generator=g) * 2 - 1) * 0.9
     from rnb_neus_fork_amd import runtime
     packed = ren._pack(True)
-    out = runtime.sdf_forward(ren.desc, packed, pts.to(_dev()), True).cpu()
+    out = runtime.sdf_forward(ren.desc, packed, pts.to(device()), True).cpu()
     ref = O.sdf_forward(p, mc.sdf, pts)
     e_sdf = float((out[:, 0] - ref[:, 0]).abs().max())
     e_feat = float((out[:, 1:] - ref[:, 1:]).abs().max())
-    nrm = runtime.sdf_gradient(ren.desc, packed, pts.to(_dev())).cpu()
+    nrm = runtime.sdf_gradient(ren.desc, packed, pts.to(device())).cpu()
     nref = O.sdf_gradient(p, mc.sdf, pts, create_graph=False)
     e_n = float((nrm - nref).abs().max())
     rms_n = float((nrm - nref).pow(2).mean().sqrt())
@@ -90,7 +80,7 @@ def test_bf16_render_256_samples_vs_fp32_oracle(R, api, no_albedo):
     mc, p, sdf, dev, col, ren = _model(R, seed=2, sharpen=True, render=rc)
     warm = api == "render_rnb_warmup"
     batch = O.synthetic_batch(48, seed=41, step=1, warmup=warm)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    b = {k: v.to(device()) for k, v in batch.items()}
     fn = ren.render_rnb_warmup if warm else ren.render_rnb
     out = fn(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0, t_rand=b["t_rand"],
              no_albedo=no_albedo)
@@ -140,7 +130,7 @@ def test_bf16_render_256_samples_vs_fp32_oracle(R, api, no_albedo):
 def test_bf16_deterministic_variant_is_bit_reproducible(R):
     mc, p, sdf, dev, col, ren = _model(R, seed=3, sharpen=True)
     ren.set_variant(bf16=True, deterministic=True)
-    b = {k: v.to(_dev()) for k, v in O.synthetic_batch(64, seed=6, step=2).items()}
+    b = {k: v.to(device()) for k, v in O.synthetic_batch(64, seed=6, step=2).items()}
     params = list(sdf.parameters()) + list(dev.parameters()) + list(col.parameters())
     runs, z = [], None
     for _ in range(3):
@@ -161,7 +151,7 @@ def test_bf16_ragged_ray_counts(R):
     mc, p, sdf, dev, col, ren = _model(R, seed=4, sharpen=True, render=rc)
     for B in (1, 3, 37):
         batch = O.synthetic_batch(B, seed=50 + B, step=0)
-        b = {k: v.to(_dev()) for k, v in batch.items()}
+        b = {k: v.to(device()) for k, v in batch.items()}
         for q in list(sdf.parameters()) + list(col.parameters()):
             q.grad = None
         out = ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0,

@@ -2,7 +2,8 @@
 the same sites on the device's own fp32 weights, so device and emulation differ only by summation order and the rare
 bf16 rounding that order flips.  tests/test_gpu_bf16.py stays as the coarse check against the fp32 oracle.
 
-Bound rule, the form of `_step_against_fp64` in tests/test_gpu_parity.py, per output tensor (rms over points) and per
+Bound rule (its constants and the step itself are tests/bf16_emu_step.py), the form of `step_against_fp64` in
+tests/gpu_support.py, per output tensor (rms over points) and per
 gradient tensor (rel-L2):
 
     err(device, emu64) <= min(K * max_i err(emu32_i, emu64) + FLOOR, CAP)
@@ -28,84 +29,11 @@ import torch
 from oracle import rnb_oracle as O
 from oracle.bf16_emu import Bf16FinePass, bf16_color_supported, mirror_matrices, packed_layout, unfragment, \
     weights_from_packed
+from tests.bf16_emu_step import MODES, OLD, Check, linspace_at, model, packed_weights, step
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device
 
 pytestmark = pytest.mark.gpu
-
-K = 4.0
-FLOOR_RMS, FLOOR_LOSS, FLOOR_GRAD = 5e-5, 2e-5, 1e-4
-# tests/test_gpu_bf16.py's bounds (SDF_ATOL, 3 SDF_ATOL for features, NRM_ATOL, OUT_ATOL, the loss's rel, GRAD_REL_MAX)
-OLD = {"sdf": 1e-2, "feature": 3e-2, "normal": 1e-1, "out": 3e-2, "loss": 2e-2, "grad": 0.15}
-OUT_KEYS = ("color_fine", "weights", "weight_sum", "cdf_fine", "gradients", "gradient_error")
-MODES = ((torch.float32, "mm"), (torch.float32, "tiles"))
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available()
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    torch.set_num_threads(16)
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _model(R, mc, seed=0, sharpen=False, params=None, **variant):
-    """`params`: the named parameters to build from (else the sharpened fixture's or a geometric init of `seed`)."""
-    if params is not None:
-        p = {k: v.clone() for k, v in params.items()}
-    elif sharpen:
-        from tests.golden_util import Golden
-        p = Golden("full_main_sharp").params()
-        with torch.no_grad():
-            p["dev.variance"].fill_(0.3)     # inv_s = e^3, as in tests/test_gpu_bf16.py
-    else:
-        torch.manual_seed(seed)
-        p = O.init_params(mc)
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
-    ren.set_variant(bf16=True, **variant)
-    return p, sdf, dev, col, ren
-
-
-def _packed(ren, mc):
-    packed = ren._pack(True)
-    total = packed_layout(mc)["total"]
-    assert packed.numel() == total + total // 2, "RNB_VARIANT_BF16: fp32 weights + one bf16 mirror"
-    return packed.cpu(), total
-
-
-class _Check:
-    """Collects err(device), the emu32 errors and the bound of every quantity; prints all, then asserts all."""
-
-    def __init__(self, tag):
-        self.tag, self.rows = tag, []
-
-    def add(self, name, e_dev, e32, floor, cap):
-        bound = min(K * max(e32) + floor, cap)
-        self.rows.append((name, e_dev, max(e32), bound))
-
-    def output(self, name, dev, ref, others, old_bound):
-        """A point-wise output: rms calibrated against emu32 (capped at old / 10), max-abs within old / 2."""
-        dev, ref = dev.detach().cpu().double(), ref.detach().double()
-        others = [o.detach().double() for o in others]
-        rms = lambda a: float((a - ref).pow(2).mean().sqrt())
-        self.add(name + " rms", rms(dev), [rms(o) for o in others], FLOOR_RMS, old_bound / 10)
-        mx = lambda a: float((a - ref).abs().max())
-        self.rows.append((name + " max", mx(dev), max(mx(o) for o in others), old_bound / 2))
-
-    def finish(self):
-        for name, e, e32, bound in self.rows:
-            print(f"BF16EMU {self.tag} {name}: device {e:.3e}, emu32 {e32:.3e}, ratio {e / max(e32, 1e-30):.2f}, "
-                  f"bound {bound:.3e}")
-        bad = [f"{n}: {e:.3e} > {b:.3e}" for n, e, _, b in self.rows if not e <= b]
-        assert not bad, f"{self.tag}: " + "; ".join(bad)
-
-
-def _rel(a, b):
-    b = b.detach().double()
-    return float((a.detach().cpu().double() - b).norm() / b.norm().clamp_min(1e-300))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
@@ -113,8 +41,8 @@ def test_bf16_weight_mirror_is_exact(R):
     """The bf16 mirror rnb_weightnorm_fwd appends to `packed` is rb(fp32 weights) bit for bit, every matrix (SDF hidden
     layers and their transposes, the feature head, the albedo hidden layers), after undoing the fragment order."""
     mc = O.ModelConf()
-    p, sdf, dev, col, ren = _model(R, mc, seed=9)
-    packed, total = _packed(ren, mc)
+    p, sdf, dev, col, ren = model(R, mc, seed=9)
+    packed, total = packed_weights(ren, mc)
     mirror = packed[total:].view(torch.int16)
     mats = mirror_matrices(mc)
     assert len(mats) == 2 * (mc.sdf.n_layers + 1 + mc.color.n_layers)
@@ -134,14 +62,14 @@ def test_bf16_weight_mirror_is_exact(R):
                                           (5000, 2, True), (65536 + 37, 2, False), (65536 + 37, 1, True)])
 def test_bf16_pointwise_sdf_and_normal_vs_emulation(R, n, ti, sharpen):
     mc = O.ModelConf()
-    p, sdf, dev, col, ren = _model(R, mc, seed=1, sharpen=sharpen, fwd_ti=ti, bwd_ti=ti)
+    p, sdf, dev, col, ren = model(R, mc, seed=1, sharpen=sharpen, fwd_ti=ti, bwd_ti=ti)
     from rnb_neus_fork_amd import runtime
     g = torch.Generator().manual_seed(n)
     pts = (torch.rand(n, 3, generator=g) * 2 - 1) * 0.9
-    packed, total = _packed(ren, mc)
-    pk = packed.to(_dev())
-    out = runtime.sdf_forward(ren.desc, pk, pts.to(_dev()), True).cpu()
-    nrm = runtime.sdf_gradient(ren.desc, pk, pts.to(_dev())).cpu()
+    packed, total = packed_weights(ren, mc)
+    pk = packed.to(device())
+    out = runtime.sdf_forward(ren.desc, pk, pts.to(device()), True).cpu()
+    nrm = runtime.sdf_gradient(ren.desc, pk, pts.to(device())).cpu()
     w = weights_from_packed(packed[:total], mc)
     res = []
     for dt, order in ((torch.float64, "mm"),) + MODES:
@@ -149,86 +77,13 @@ def test_bf16_pointwise_sdf_and_normal_vs_emulation(R, n, ti, sharpen):
         s_, f_, n_ = fp.forward_points(pts, use_color=False)
         res.append((s_.double(), fp.feat_fp32.double(), n_.double()))
     ref = res[0]
-    chk = _Check(f"pointwise n={n} ti={ti} sharpen={sharpen}")
+    chk = Check(f"pointwise n={n} ti={ti} sharpen={sharpen}")
     for i, (name, d) in enumerate((("sdf", out[:, :1]), ("feature", out[:, 1:]), ("normal", nrm))):
         chk.output(name, d, ref[i], [r[i] for r in res[1:]], OLD[name])
     chk.finish()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3, 4
-def _loss(api, out, b):
-    if api == "render":
-        return (out["color_fine"] - b["true_rgb"][0]).abs().mean() + 0.1 * out["gradient_error"] \
-            + 0.1 * torch.nn.functional.binary_cross_entropy(out["weight_sum"].clip(1e-3, 1 - 1e-3),
-                                                             (b["mask"] > 0.5).to(out["weight_sum"].dtype))
-    return O.rnb_loss(out, b["true_rgb"], b["mask"])[0]
-
-
-def _emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order):
-    fp = Bf16FinePass(p, mc, w, dtype=dt, order=order)
-    warm = api == "render_rnb_warmup"
-    if api == "render":
-        out = fp.forward(batch["rays_o"], batch["rays_d"], z, None, cos_anneal_ratio=1.0, relu_shading=False,
-                         no_albedo=False, mvps=False, background_rgb=bg)
-    else:
-        out = fp.forward(batch["rays_o"], batch["rays_d"], z, batch["lights_dir"], cos_anneal_ratio=1.0,
-                         relu_shading=warm, no_albedo=no_albedo, mvps=True)
-    leaves = {k: out[k].detach().clone().requires_grad_(True) for k in ("color_fine", "weight_sum", "gradient_error")}
-    bt = {k: v.to(dt) for k, v in batch.items()}
-    loss = _loss(api, {**out, **leaves}, bt)
-    loss.backward()
-    grads = fp.backward({k: v.grad for k, v in leaves.items()})
-    return out, float(loss), grads
-
-
-def _step(R, mc, B, api="render_rnb", no_albedo=False, sharpen=True, seed=2, tag="", params=None, **variant):
-    p, sdf, dev, col, ren = _model(R, mc, seed=seed, sharpen=sharpen, params=params, **variant)
-    warm = api == "render_rnb_warmup"
-    batch = O.synthetic_batch(B, seed=40 + B, step=1, warmup=warm)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
-    bg = None
-    if api == "render":
-        bg = torch.tensor([0.2, 0.5, 0.8])
-        out = ren.render(b["rays_o"], b["rays_d"], b["near"], b["far"], background_rgb=bg.to(_dev()), cos_anneal_ratio=1.0,
-                         t_rand=b["t_rand"])
-    else:
-        fn = ren.render_rnb_warmup if warm else ren.render_rnb
-        out = fn(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0, t_rand=b["t_rand"],
-                 no_albedo=no_albedo)
-    loss = _loss(api, out, b)
-    loss.backward()
-    torch.cuda.synchronize()
-    z = ren.last_z_vals.cpu()
-    packed, total = _packed(ren, mc)
-    w = weights_from_packed(packed[:total], mc)
-    emu = [_emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order)
-           for dt, order in ((torch.float64, "mm"),) + MODES]
-    (o64, l64, g64), rest = emu[0], emu[1:]
-    chk = _Check(tag or f"{api} B={B} S={z.shape[1]} no_albedo={no_albedo} {variant}")
-    for k in OUT_KEYS:
-        assert bool(torch.isfinite(out[k]).all()), k
-        chk.output(k, out[k], o64[k], [o[k] for o, _, _ in rest], OLD["normal"] if k == "gradients" else OLD["out"])
-    chk.add("loss", abs(float(loss) - l64) / abs(l64), [abs(l - l64) / abs(l64) for _, l, _ in rest], FLOOR_LOSS,
-            OLD["loss"] / 10)
-    named = {("sdf." + k): v for k, v in sdf.named_parameters()}
-    named["dev.variance"] = dev.variance
-    named.update({("color." + k): v for k, v in col.named_parameters()})
-    n_checked = 0
-    for k, v in named.items():
-        if k not in g64:
-            assert v.grad is None or float(v.grad.abs().max()) == 0.0, f"{k}: a gradient the emulation does not have"
-            continue
-        assert v.grad is not None, f"{k}: no device gradient"
-        ref = g64[k].reshape(v.shape)
-        if float(ref.norm()) == 0.0:
-            assert float(v.grad.abs().max()) == 0.0, k
-            continue
-        chk.add(k, _rel(v.grad, ref), [_rel(g[k].reshape(v.shape), ref) for _, _, g in rest], FLOOR_GRAD, OLD["grad"] / 10)
-        n_checked += 1
-    chk.finish()
-    return n_checked
-
-
 CONF5 = O.RenderConf(n_samples=128, n_importance=128, up_sample_steps=4)
 RAGGED = O.RenderConf(n_samples=16, n_importance=8, up_sample_steps=4)     # S = 24
 
@@ -237,7 +92,7 @@ RAGGED = O.RenderConf(n_samples=16, n_importance=8, up_sample_steps=4)     # S =
                                            ("render", False)])
 def test_bf16_step_config5_vs_emulation(R, api, no_albedo):
     """BASELINE config 5's shape (48 rays x (128 + 128) samples), every output, the loss and every gradient."""
-    n = _step(R, O.ModelConf(render=CONF5), 48, api, no_albedo)
+    n = step(R, O.ModelConf(render=CONF5), 48, api, no_albedo)
     assert n >= (19 if no_albedo else 25)
 
 
@@ -245,15 +100,15 @@ def test_bf16_step_config5_vs_emulation(R, api, no_albedo):
 @pytest.mark.parametrize("B", [1, 3, 37])
 def test_bf16_step_ragged_vs_emulation(R, B, det):
     """B x 24 points: never a multiple of the 64-point tiles (the partial last tile of every sweep and dW job)."""
-    _step(R, O.ModelConf(render=RAGGED), B, deterministic=det)
+    step(R, O.ModelConf(render=RAGGED), B, deterministic=det)
 
 
 def test_bf16_step_deterministic_config5_vs_emulation(R):
-    _step(R, O.ModelConf(render=CONF5), 48, deterministic=True)
+    step(R, O.ModelConf(render=CONF5), 48, deterministic=True)
 
 
 def test_bf16_step_b512_vs_emulation(R):
-    _step(R, O.ModelConf(render=O.RenderConf(n_samples=32, n_importance=32, up_sample_steps=4)), 512)
+    step(R, O.ModelConf(render=O.RenderConf(n_samples=32, n_importance=32, up_sample_steps=4)), 512)
 
 
 @pytest.mark.parametrize("n_layers,multires_view,bf16_albedo", [(3, 4, True), (2, 6, False)])
@@ -264,26 +119,16 @@ def test_bf16_albedo_shapes_vs_emulation(R, n_layers, multires_view, bf16_albedo
     assert bf16_color_supported(mc) == bf16_albedo
     L = packed_layout(mc)
     assert (L["Cinp"] <= 320) == bf16_albedo
-    n = _step(R, mc, 37, sharpen=False, seed=7, tag=f"albedo n_layers={n_layers} multires_view={multires_view}")
+    n = step(R, mc, 37, sharpen=False, seed=7, tag=f"albedo n_layers={n_layers} multires_view={multires_view}")
     assert n == 3 * (mc.sdf.n_layers + 1) + 1 + 3 * (n_layers + 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5
-def _linspace_at(lo, hi, res, i):
-    """rnb_internal.h linspace_at in exact fp32: step = fp32((hi - lo) / (res - 1)), then one fused multiply-add."""
-    lo32, hi32 = torch.tensor(lo, dtype=torch.float32), torch.tensor(hi, dtype=torch.float32)
-    step = (hi32 - lo32) / torch.tensor(float(res - 1), dtype=torch.float32)
-    i = torch.as_tensor(i, dtype=torch.float64)
-    a = step.double() * i + lo32.double()
-    b = -step.double() * (res - 1 - i) + hi32.double()
-    return torch.where(i < res // 2, a, b).float()
-
-
 def test_bf16_sdf_grid_vs_emulation(R):
     """rnb_sdf_grid under the bf16 variant (api.hip:213): odd resolution 70, an x-slab subset, the bounds of
     tests/test_gpu_edges.py, against the emulation on the grid coordinates the kernel generates."""
     mc = O.ModelConf()
-    p, sdf, dev, col, ren = _model(R, mc, seed=3, sharpen=True)
+    p, sdf, dev, col, ren = model(R, mc, seed=3, sharpen=True)
     lib = R.native.load()
     res, x0, x1 = 70, 23, 51
     lo, hi = [-1.0, -0.9, -0.8], [1.0, 0.9, 1.1]
@@ -292,18 +137,18 @@ def test_bf16_sdf_grid_vs_emulation(R):
         gd.bound_min[d], gd.bound_max[d] = lo[d], hi[d]
     gd.resolution, gd.x_begin, gd.x_end, gd.out_scale = res, x0, x1, -1.0
     packed = ren._pack(False)
-    vol = torch.full((x1 - x0, res, res), float("nan"), dtype=torch.float32, device=_dev())
+    vol = torch.full((x1 - x0, res, res), float("nan"), dtype=torch.float32, device=device())
     nbytes = C.c_int64()
     R.native.check(lib.rnb_sdf_grid_workspace_bytes(C.byref(ren.desc), C.byref(gd), C.byref(nbytes)))
-    ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=_dev())
+    ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=device())
     with R.native.on_device(vol) as stream:
         R.native.check(lib.rnb_sdf_grid(C.byref(ren.desc), R.native.ptr(packed), C.byref(gd), R.native.ptr(vol),
                                         R.native.ptr(ws), ws.numel(), stream))
     torch.cuda.synchronize()
     vol = vol.cpu()
     assert bool(torch.isfinite(vol).all())
-    xs = [_linspace_at(lo[0], hi[0], res, torch.arange(x0, x1)), _linspace_at(lo[1], hi[1], res, torch.arange(res)),
-          _linspace_at(lo[2], hi[2], res, torch.arange(res))]
+    xs = [linspace_at(lo[0], hi[0], res, torch.arange(x0, x1)), linspace_at(lo[1], hi[1], res, torch.arange(res)),
+          linspace_at(lo[2], hi[2], res, torch.arange(res))]
     xx, yy, zz = torch.meshgrid(*xs, indexing="ij")
     pts = torch.stack([xx.reshape(-1), yy.reshape(-1), zz.reshape(-1)], dim=-1)
     pk = packed.cpu()
@@ -313,6 +158,6 @@ def test_bf16_sdf_grid_vs_emulation(R):
     for dt, order in ((torch.float64, "mm"),) + MODES:
         fp = Bf16FinePass(p, mc, w, dtype=dt, order=order)
         res_.append(-fp.forward_points(pts, use_color=False)[0].double().reshape(vol.shape))
-    chk = _Check(f"sdf_grid res={res} x={x0}..{x1}")
+    chk = Check(f"sdf_grid res={res} x={x0}..{x1}")
     chk.output("sdf", vol, res_[0], res_[1:], OLD["sdf"])
     chk.finish()

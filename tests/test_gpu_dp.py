@@ -6,20 +6,15 @@ gradients.  Transport: on the one-GPU test box the two ranks share device 0 over
 driver's 8-GPU node) the same workers run one rank per GPU over the `nccl` backend = RCCL
 (`test_exact_data_parallel_over_rccl`, skipped on one-GPU boxes)."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.gpu_support import free_port
+
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _init(rank, world, port, backend="gloo"):
@@ -77,7 +72,7 @@ def test_two_rank_gradients_are_the_mean_of_local_gradients():
     assert torch.cuda.is_available()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -173,7 +168,7 @@ def test_exact_data_parallel_step_equals_the_single_process_step():
     """"so that G-GPU results equal the 1-GPU result on the same rays" — gradient rel-L2 <= 1e-5."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_exact_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -192,7 +187,7 @@ def test_exact_data_parallel_step_equals_the_single_process_step():
 def _run_exact(backend):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_exact_worker, args=(r, 2, port, q, backend)) for r in range(2)]
     for p in procs:
         p.start()
@@ -250,7 +245,7 @@ def test_rccl_single_rank_smoke():
     which proves RCCL loads, builds a communicator and reduces on this software stack before the scaling bench needs it."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    p = ctx.Process(target=_rccl_one_rank_worker, args=(_free_port(), q))
+    p = ctx.Process(target=_rccl_one_rank_worker, args=(free_port(), q))
     p.start()
     same, backend = q.get(timeout=300)
     p.join(timeout=60)
@@ -278,7 +273,7 @@ def test_extract_fields_sharded_over_ranks_equals_single_rank():
     """the SDF grid shards by x-slab; every rank ends up with the full volume."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_grid_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -1,25 +1,15 @@
 """GPU edge cases of the renderer interface: ragged and tiny ray counts, a large batch (max size the bench
 shape is sharded from), shard consistency (the property the data-parallel split relies on), the SDF grid query
-of extract_fields and an empty batch.  Tolerances as in test_gpu_parity.py."""
+of extract_fields and an empty batch.  Tolerances as in test_gpu_parity.py's point-wise tests."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _tiny(R, seed=0):
@@ -29,7 +19,7 @@ def _tiny(R, seed=0):
     p = O.init_params(mc)
     with torch.no_grad():
         p["dev.variance"].fill_(0.4)
-    return mc, p, R.build_from_named_params(mc, p, _dev())
+    return mc, p, R.build_from_named_params(mc, p, device())
 
 
 @pytest.mark.parametrize("B", [1, 3, 37, 129])
@@ -37,7 +27,7 @@ def test_ragged_ray_counts_match_oracle(R, B):
     """Ray counts that are not a multiple of any tile size (points are padded to 128 internally)."""
     mc, p, (sdf, dev, col, ren) = _tiny(R)
     batch = O.synthetic_batch(B, seed=11, step=B)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    b = {k: v.to(device()) for k, v in batch.items()}
     out = ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=0.7,
                          t_rand=b["t_rand"])
     assert out["color_fine"].shape == (3, B, 3) and out["weights"].shape == (B, 32)
@@ -62,7 +52,7 @@ def test_shards_of_a_batch_render_like_the_whole_batch(R):
     (what parallel.shard_batch relies on); 4096 rays = the largest per-GPU batch of BASELINE's configs."""
     mc, p, (sdf, dev, col, ren) = _tiny(R, seed=2)
     batch = O.synthetic_batch(4096, seed=13, step=1)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    b = {k: v.to(device()) for k, v in batch.items()}
     with torch.no_grad():
         whole = ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0,
                                t_rand=b["t_rand"])
@@ -110,25 +100,25 @@ def test_extract_fields_matches_the_reference_volume(R):
         render=O.RenderConf(n_samples=int(r[0]), n_importance=int(r[1]), n_outside=int(r[2]), up_sample_steps=int(r[3]),
                             perturb=float(rf[0])), init_val=float(rf[1]))
     p = {k[2:]: torch.from_numpy(z[k]).clone() for k in z.files if k.startswith("w.")}
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(mc, p, device())
     res = int(z["resolution"])
     u = ren.extract_fields(torch.from_numpy(z["bound_min"]), torch.from_numpy(z["bound_max"]), res)
     ref = z["u"]
     assert u.shape == ref.shape == (res, res, res)
     np.testing.assert_allclose(u, ref, rtol=1e-4, atol=2e-5)
-    v_dev, t_dev = R.marching_cubes(torch.from_numpy(u).to(_dev()), 0.0)
+    v_dev, t_dev = R.marching_cubes(torch.from_numpy(u).to(device()), 0.0)
     v_ref, t_ref = M.marching_cubes(ref, 0.0)
     assert abs(len(v_dev) - len(v_ref)) <= max(4, len(v_ref) // 500) and len(v_ref) > 1000
 
 
 def test_empty_batch_is_rejected_cleanly(R):
     mc, p, (sdf, dev, col, ren) = _tiny(R)
-    e = torch.zeros(0, 3, device=_dev())
+    e = torch.zeros(0, 3, device=device())
     with pytest.raises((RuntimeError, ValueError, R.native.NativeError)):
-        ren.render_rnb(e, e, e[:, :1], e[:, :1], torch.zeros(3, 0, 1, 3, device=_dev()), cos_anneal_ratio=1.0)
+        ren.render_rnb(e, e, e[:, :1], e[:, :1], torch.zeros(3, 0, 1, 3, device=device()), cos_anneal_ratio=1.0)
     # the renderer is still usable afterwards
     batch = O.synthetic_batch(4, seed=1, step=0)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    b = {k: v.to(device()) for k, v in batch.items()}
     out = ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0,
                          t_rand=b["t_rand"])
     assert bool(torch.isfinite(out["color_fine"]).all())
@@ -143,10 +133,10 @@ def test_large_batch_gradients_are_additive_over_shards(R):
     p = O.init_params(mc)
     with torch.no_grad():
         p["dev.variance"].fill_(0.35)
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(mc, p, device())
     leaves = list(sdf.parameters()) + list(dev.parameters()) + list(col.parameters())
     batch = O.synthetic_batch(4096, seed=17, step=2)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    b = {k: v.to(device()) for k, v in batch.items()}
 
     def grads(lo, hi, z):
         for x in leaves:
@@ -187,10 +177,10 @@ def test_validate_image_call_shape_one_light_ragged_chunks(R, warmup):
     with torch.no_grad():
         for lo in range(0, B, chunk):
             hi = min(B, lo + chunk)
-            b = {k: batch[k][lo:hi].to(_dev()) for k in ("rays_o", "rays_d", "near", "far", "t_rand")}
+            b = {k: batch[k][lo:hi].to(device()) for k in ("rays_o", "rays_d", "near", "far", "t_rand")}
             lights = one if warmup else per_ray[:, lo:hi]
             fn = ren.render_rnb_warmup if warmup else ren.render_rnb
-            out = fn(b["rays_o"], b["rays_d"], b["near"], b["far"], lights.to(_dev()), cos_anneal_ratio=1.0,
+            out = fn(b["rays_o"], b["rays_d"], b["near"], b["far"], lights.to(device()), cos_anneal_ratio=1.0,
                      t_rand=b["t_rand"])
             assert out["color_fine"].shape == (1, hi - lo, 3)
             assert out["gradients"].shape == (hi - lo, 32, 3) and out["inside_sphere"].shape == (hi - lo, 32)

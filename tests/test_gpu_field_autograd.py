@@ -2,17 +2,17 @@
 
 Losses on sdf_network(x), .gradient(x) (the eikonal term: the reference's create_graph=True double backward) and
 color_network(p, n, n, f) are differentiated natively (rnb_sdf_backward / rnb_color_backward + rnb_weightnorm_bwd) and
-compared with torch autograd through oracle/rnb_oracle.py in fp64, with the calibrated rule of test_gpu_parity.py: outputs
-within K_OUT x the fp32 oracle's own max error + FLOOR_OUT, gradients within _grad_bound(rel-L2 of fp32 vs fp64).  States
+compared with torch autograd through oracle/rnb_oracle.py in fp64, with the calibrated rule of tests/parity.py: outputs
+by check_value (the fp32 oracle's own max error calibrates), gradients by check_grad (rel-L2 of fp32 vs fp64 calibrates).  States
 are shape_matrix.live_params, so the encoding's columns carry weight."""
-import ctypes as C
-
 import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import ALBEDO_H2_CLASSES, device, profile_classes
+from tests.parity import check_grad, check_value, rel_l2
 from tests.shape_matrix import BY_NAME, live_params, points
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT, _grad_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -20,52 +20,28 @@ SDF_SHAPES = ["default_64x64", "no_skip", "skip1", "skip7", "scale3", "multires0
 COLOR_SHAPES = ["default_64x64", "mview0", "albedo_nl1", "feat128"]
 SIZES = [1, 63, 4097]
 FUSED_CLASSES = {"R_sweep", "FB_sweep", "RA_sweep", "dW(x3: 256x256 + narrow jobs)"}
-ALBEDO_H2_CLASSES = {"albedo_fwd", "albedo_bwd"}
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _build(R, name):
     shape = BY_NAME[name]
     p = live_params(shape.mc, shape.seed)
-    sdf, devn, col, ren = R.build_from_named_params(shape.mc, p, _dev())
+    sdf, devn, col, ren = R.build_from_named_params(shape.mc, p, device())
     sdf.set_autograd(True)
     col.set_autograd(True)
     return shape, p, sdf, col, ren
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-300))
-
-
-def _check_out(got, r64, r32, what):
-    bound = K_OUT * float((r32.double() - r64).abs().max()) + FLOOR_OUT * max(1.0, float(r64.abs().max()))
-    err = float((got.double() - r64).abs().max())
-    assert err <= bound, f"{what}: max err {err:.3g} > bound {bound:.3g}"
 
 
 def _check_grad(got, g64, g32, what):
     if float(g64.abs().max()) == 0.0:
         assert float(got.abs().max()) == 0.0, f"{what}: non-zero gradient where the oracle's is zero"
         return
-    err, bound = _rel(got, g64), _grad_bound(_rel(g32, g64))
-    assert err <= bound, f"{what}: rel-L2 {err:.3g} > bound {bound:.3g}"
+    check_grad(what, got, g64, rel_l2(g32, g64))
 
 
 def _oracle(p, prefix, inputs, fn, dt):
     """(output, {leaf: grad}, [input grads]) of loss = fn(q, *xs)[1] by torch autograd in dtype dt on the device."""
-    q = {k: v.to(_dev(), dt).detach().requires_grad_(k.startswith(prefix)) for k, v in p.items()}
-    xs = [t.to(_dev(), dt).detach().requires_grad_(True) for t in inputs]
+    q = {k: v.to(device(), dt).detach().requires_grad_(k.startswith(prefix)) for k, v in p.items()}
+    xs = [t.to(device(), dt).detach().requires_grad_(True) for t in inputs]
     with torch.enable_grad():
         out, loss = fn(q, *xs)
         keys = [k for k in q if k.startswith(prefix)]
@@ -118,11 +94,11 @@ def test_sdf_feature_loss_and_eikonal_against_fp64(R, name):
         o64, g64, (x64,) = _oracle(p, "sdf.", [x0], loss1, torch.float64)
         o32, g32, (x32,) = _oracle(p, "sdf.", [x0], loss1, torch.float32)
         _zero(sdf)
-        x = x0.to(_dev()).requires_grad_(True)
+        x = x0.to(device()).requires_grad_(True)
         out = sdf(x)
         assert out.grad_fn is not None and out.shape == (n, conf.d_out)
-        _check_out(out.detach(), o64, o32, f"{name} n={n} forward")
-        ((w.to(_dev()) * out[:, :1]).sum() + (W.to(_dev()) * out[:, 1:]).sum()).backward()
+        check_value(f"{name} n={n} forward", out.detach(), o64, o32)
+        ((w.to(device()) * out[:, :1]).sum() + (W.to(device()) * out[:, 1:]).sum()).backward()
         _compare_leaves(_native_leaf_grads(sdf, "sdf"), g64, g32, f"{name} n={n} case1")
         _check_grad(x.grad, x64, x32, f"{name} n={n} case1 x.grad")
         # case 2: the eikonal loss on gradient(x) (the Hessian term in x.grad)
@@ -130,18 +106,18 @@ def test_sdf_feature_loss_and_eikonal_against_fp64(R, name):
         n64, g64, (x64,) = _oracle(p, "sdf.", [x0], loss2, torch.float64)
         n32, g32, (x32,) = _oracle(p, "sdf.", [x0], loss2, torch.float32)
         _zero(sdf)
-        x = x0.to(_dev()).requires_grad_(True)
+        x = x0.to(device()).requires_grad_(True)
         g = sdf.gradient(x)
         assert g.shape == (n, 1, 3) and g.grad_fn is not None
-        _check_out(g.detach().reshape(n, 3), n64, n32, f"{name} n={n} gradient")
+        check_value(f"{name} n={n} gradient", g.detach().reshape(n, 3), n64, n32)
         ((g.norm(dim=-1) - 1) ** 2).mean().backward()
         _compare_leaves(_native_leaf_grads(sdf, "sdf"), g64, g32, f"{name} n={n} eikonal")
         _check_grad(x.grad, x64, x32, f"{name} n={n} eikonal x.grad")
         # sdf(): the sdf column alone, parameters only (x does not require grad: no x adjoint work)
         _zero(sdf)
-        xs = x0.to(_dev())
+        xs = x0.to(device())
         s = sdf.sdf(xs)
-        (w.to(_dev()) * s).sum().backward()
+        (w.to(device()) * s).sum().backward()
         assert xs.grad is None and sdf.lin0.bias.grad is not None
 
 
@@ -159,12 +135,12 @@ def test_color_loss_against_fp64(R, name):
         a64, g64, i64 = _oracle(p, "color.", [p0, nr0, f0], loss, torch.float64)
         a32, g32, i32 = _oracle(p, "color.", [p0, nr0, f0], loss, torch.float32)
         _zero(col)
-        pp, nn_, ff = (t.to(_dev()).requires_grad_(True) for t in (p0, nr0, f0))
-        vd = nr0.to(_dev()).requires_grad_(True)
+        pp, nn_, ff = (t.to(device()).requires_grad_(True) for t in (p0, nr0, f0))
+        vd = nr0.to(device()).requires_grad_(True)
         a = col(pp, nn_, vd, ff)
         assert a.grad_fn is not None
-        _check_out(a.detach(), a64, a32, f"{name} n={n} albedo")
-        (Wc.to(_dev()) * a).sum().backward()
+        check_value(f"{name} n={n} albedo", a.detach(), a64, a32)
+        (Wc.to(device()) * a).sum().backward()
         _compare_leaves(_native_leaf_grads(col, "color"), g64, g32, f"{name} n={n} color")
         for t, r64, r32, what in zip((pp, nn_, ff), i64, i32, ("points", "normals", "feats")):
             _check_grad(t.grad, r64, r32, f"{name} n={n} {what}.grad")
@@ -187,7 +163,7 @@ def test_validate_mesh_texture_sequence(R, name):
     for n in SIZES + ([4096, 100_000] if name == "default_64x64" else []):
         v0 = points(n, seed=n + 11)
         with torch.no_grad():
-            ref = _mesh_texture(sdf, col, v0.to(_dev()))
+            ref = _mesh_texture(sdf, col, v0.to(device()))
         Wa = _weights(n, cc.d_out, 6)
 
         def chain(q, v):
@@ -201,14 +177,14 @@ def test_validate_mesh_texture_sequence(R, name):
         if profile:
             lib.rnb_profile_enable(1)
         try:
-            alb = _mesh_texture(sdf, col, v0.to(_dev()))
+            alb = _mesh_texture(sdf, col, v0.to(device()))
             assert alb.grad_fn is not None
-            _check_out(alb.detach(), a64, a32, f"{name} n={n} texture")
-            _check_out(ref, a64, a32, f"{name} n={n} texture (no_grad)")
-            (Wa.to(_dev()) * alb).sum().backward()
+            check_value(f"{name} n={n} texture", alb.detach(), a64, a32)
+            check_value(f"{name} n={n} texture (no_grad)", ref, a64, a32)
+            (Wa.to(device()) * alb).sum().backward()
             if profile:
                 torch.cuda.synchronize()
-                classes = _profile_classes(R)
+                classes = profile_classes(R)
                 assert FUSED_CLASSES <= classes, f"fused sweeps missing: {sorted(FUSED_CLASSES - classes)}"
                 assert ALBEDO_H2_CLASSES <= classes, "the fused albedo sweeps did not run"
         finally:
@@ -221,21 +197,11 @@ def test_validate_mesh_texture_sequence(R, name):
         assert float(sdf.lin0.bias.grad.abs().max()) > 0
 
 
-def _profile_classes(R):
-    lib = R.native.load()
-    ms, cnt, fl = C.c_double(), C.c_int64(), C.c_double()
-    R.native.check(lib.rnb_profile_collect(C.byref(ms), C.byref(cnt), C.byref(fl)))
-    need = lib.rnb_profile_report(None, 0)
-    buf = C.create_string_buffer(int(need) + 16)
-    lib.rnb_profile_report(buf, len(buf))
-    return {ln.rsplit(" ", 3)[0] for ln in buf.value.decode().splitlines()}
-
-
 # ------------------------------------------------------------------------------------------------------- case 5
 def test_render_loss_and_eikonal_accumulate(R):
     shape, p, sdf, col, ren = _build(R, "default_64x64")
-    b = {k: v.to(_dev()) for k, v in O.synthetic_batch(64, seed=3, step=1).items()}
-    x0 = points(4097, seed=5).to(_dev())
+    b = {k: v.to(device()) for k, v in O.synthetic_batch(64, seed=3, step=1).items()}
+    x0 = points(4097, seed=5).to(device())
 
     def render_loss():
         out = ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0,
@@ -254,7 +220,7 @@ def test_render_loss_and_eikonal_accumulate(R):
         grads.append({k: v.grad.clone() for k, v in sdf.named_parameters()})
     for k in grads[0]:
         want = grads[0][k] + grads[1][k]
-        assert _rel(grads[2][k], want) <= 1e-5, f"{k}: render + eikonal in one backward != the sum of the two"
+        assert rel_l2(grads[2][k], want) <= 1e-5, f"{k}: render + eikonal in one backward != the sum of the two"
     assert float(grads[1]["lin0.bias"].abs().max()) > 0 and float(grads[0]["lin0.bias"].abs().max()) > 0
 
 
@@ -262,10 +228,10 @@ def test_render_loss_and_eikonal_accumulate(R):
 def test_adjoint_scale_determinism_and_lifetime(R):
     shape, p, sdf, col, ren = _build(R, "default_64x64")
     n = 4096   # (a multiple of the weight-gradient chunk: every reduction of the default arithmetic is ordered, no atomics)
-    x0 = points(n, seed=9).to(_dev())
-    f0 = 0.5 * _weights(n, 256, 4).to(_dev())
-    nr0 = torch.nn.functional.normalize(_weights(n, 3, 3), dim=-1).to(_dev())
-    W, Wn, Wc = _weights(n, 257, 2).to(_dev()), _weights(n, 3, 8).to(_dev()), _weights(n, 3, 5).to(_dev())
+    x0 = points(n, seed=9).to(device())
+    f0 = 0.5 * _weights(n, 256, 4).to(device())
+    nr0 = torch.nn.functional.normalize(_weights(n, 3, 3), dim=-1).to(device())
+    W, Wn, Wc = _weights(n, 257, 2).to(device()), _weights(n, 3, 8).to(device()), _weights(n, 3, 5).to(device())
 
     def run(scale):
         _zero(sdf, col)

@@ -1,6 +1,6 @@
 """Whole views on the device: rnb_gen_rays_grid / DeviceRays.gen_rays_at, gen_rays_between, view_rays against the reference's
 own rays (tests/golden/image_rays_small.npz, tools/gen_image_golden.py), and NeuSRenderer.render_image against the CPU
-oracle on the device's depths by the calibrated output rule of tests/test_gpu_parity.py."""
+oracle on the device's depths by the calibrated output rule of tests/parity.py."""
 import os
 
 import numpy as np
@@ -8,23 +8,14 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
-from tests.golden_util import Golden
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT
-from tests.test_image_render_host import POSE_BOUND
+from tests import parity as P
+from tests.golden_util import POSE_BOUND, Golden
+from tests.gpu_support import R  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "image_rays_small.npz")
 DS_KEYS = ("images", "images_warmup", "masks", "light_directions", "light_directions_warmup", "intrinsics_all_inv", "pose_all")
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    torch.set_num_threads(16)
-    return pkg
 
 
 @pytest.fixture(scope="module")
@@ -90,7 +81,7 @@ def test_view_rays_ranges_concatenate_to_the_full_call(R, fx):
 
 
 def test_gen_rays_between_is_the_references(R, fx):
-    """the bounds of gen_rays_at widened by three times the measured pose difference (tests/test_image_render_host.py:
+    """the bounds of gen_rays_at widened by three times the measured pose difference (tests/golden_util.py POSE_BOUND:
     0.0, so rays_o stays bit-equal)"""
     dr = _rays(R, fx)
     for i in range(3):
@@ -107,11 +98,10 @@ def test_gen_rays_between_is_the_references(R, fx):
 
 # ------------------------------------------------------------------------------------------------------------------- 8
 def _rule(got, ref32, ref64, what):
-    e_hip = float((got.double().cpu().reshape(ref64.shape) - ref64).abs().max())
-    e_ref = float((ref32.double() - ref64).abs().max())
-    bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(ref64.abs().max()))
+    got = got.reshape(ref64.shape)
+    e_hip, e_ref, bound = P.value_errors(got, ref64, ref32)
     print(f"IMAGE {what}: |hip - fp64| {e_hip:.3e}, fp32 oracle {e_ref:.3e}, bound {bound:.3e}")
-    assert e_hip <= bound, f"{what}: |hip - fp64| {e_hip:.3e} > {bound:.3e} (fp32 oracle: {e_ref:.3e})"
+    P.check_value(what, got, ref64, ref32)
 
 
 def _oracle_maps(p, mc, rays, lights, z, dt):
@@ -180,7 +170,7 @@ def test_chunkings_agree(R, view1):
         bound = float((ora[64][1][k] - ora[176][1][k]).abs().max())
         for c in (64, 176):
             r32, r64 = ora[c]
-            bound += K_OUT * float((r32[k].double() - r64[k]).abs().max()) + FLOOR_OUT * max(1.0, float(r64[k].abs().max()))
+            bound += P.value_bound(r64[k], P.max_err(r32[k], r64[k]))
         d = float((a[k].double() - b[k].double()).abs().max())
         print(f"IMAGE chunkings {k}: differ by {d:.3e}, bound {bound:.3e}")
         assert d <= bound, f"{k}: the chunkings differ by {d:.3e} > {bound:.3e}"

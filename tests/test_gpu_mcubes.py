@@ -8,19 +8,13 @@ import torch
 
 from oracle import mc_oracle as M
 from oracle import rnb_oracle as O
-from tests.test_mc_oracle import _check_on_surface, _sphere, _torus
+from tests.gpu_support import R  # noqa: F401
+from tests.mc_shapes import check_on_surface, sphere, torus
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def R():
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _device(R, u, thr=0.0):
+def _on_device(R, u, thr=0.0):
     v, t = R.marching_cubes(torch.from_numpy(u).cuda(), thr)
     torch.cuda.synchronize()
     return v.cpu().numpy(), t.cpu().numpy()
@@ -28,15 +22,15 @@ def _device(R, u, thr=0.0):
 
 @pytest.mark.parametrize("shape,chi,n", [("sphere", 2, 40), ("torus", 0, 40), ("sphere", 2, 131)])
 def test_analytic_volumes_match_the_oracle_and_are_closed_manifolds(R, shape, chi, n):
-    u = -(_sphere(n) if shape == "sphere" else _torus(n))
-    v, t = _device(R, u)
+    u = -(sphere(n) if shape == "sphere" else torus(n))
+    v, t = _on_device(R, u)
     vo, to = M.marching_cubes(u, 0.0)
     assert t.dtype == np.int32 and v.dtype == np.float64
     assert np.array_equal(t, to), "triangles: bit-equal to the oracle (same tables, same order)"
     assert np.array_equal(v, vo), "vertices: bit-equal (double interpolation of the same two fp32 samples)"
     V, E, F, euler, closed = M.mesh_report(v, t)
     assert closed and euler == chi and V == len(v)
-    _check_on_surface(u, v, 0.0)
+    check_on_surface(u, v, 0.0)
 
 
 def test_noise_volume_non_cubic_grid_and_threshold(R):
@@ -44,24 +38,24 @@ def test_noise_volume_non_cubic_grid_and_threshold(R):
     u = rng.standard_normal((37, 21, 50)).astype(np.float32)         # every case, ambiguous faces, ragged tiles
     u[0], u[-1], u[:, 0], u[:, -1], u[:, :, 0], u[:, :, -1] = 2, 2, 2, 2, 2, 2
     for thr in (0.0, 0.37):
-        v, t = _device(R, u, thr)
+        v, t = _on_device(R, u, thr)
         vo, to = M.marching_cubes(u, thr)
         assert np.array_equal(t, to) and np.array_equal(v, vo)
         assert M.mesh_report(v, t)[4], "closed, consistently oriented manifold on all 256 cases"
     # open surfaces (the iso-surface leaves the grid) still agree with the oracle
     u2 = rng.standard_normal((9, 8, 7)).astype(np.float32)
-    v, t = _device(R, u2)
+    v, t = _on_device(R, u2)
     vo, to = M.marching_cubes(u2, 0.0)
     assert np.array_equal(t, to) and np.array_equal(v, vo)
 
 
 def test_empty_full_and_nan_volumes(R):
     for val in (1.0, -1.0):
-        v, t = _device(R, np.full((5, 6, 7), val, dtype=np.float32))
+        v, t = _on_device(R, np.full((5, 6, 7), val, dtype=np.float32))
         assert v.shape == (0, 3) and t.shape == (0, 3)
-    u = -_sphere(24)
+    u = -sphere(24)
     u[3, 4, 5] = np.nan                                   # NaN counts as outside: no crossing against outside neighbours
-    v, t = _device(R, u)
+    v, t = _on_device(R, u)
     vo, to = M.marching_cubes(u, 0.0)
     assert np.array_equal(t, to) and np.array_equal(v, vo, equal_nan=True)
     with pytest.raises(RuntimeError):

@@ -9,8 +9,8 @@ outlier anywhere else kept the fixed scale, and beyond 65520 / 2^6 = 1023.75 the
 
 Every case below asserts on the host that its outlier sits where such a vote does not look, at both tile heights the sweeps
 use (64 rows: TI=2; 32 rows: TI=1, small batches and the sampling forwards), and holds the device to the fp64 oracle with the
-calibration of tests/test_gpu_parity.py, per row group:
-    in-range rows   max|hip - ref64| <= K_OUT * max|ref32 - ref64| + FLOOR_OUT * max(1, max|ref64|)   (over those rows only;
+calibration of tests/parity.py, per row group:
+    in-range rows   the output rule (parity.check_value) with its factor K_OUT                         (over those rows only;
                     this includes the outlier's neighbours, which now run at their tile's smaller scale)
     outlier rows    the same with factor 10 (sin(2^5 x) of x ~ 1e3 is ill-conditioned in ANY fp32, as in
                     test_x2h_has_no_operand_range's coordinates of 3000)"""
@@ -20,7 +20,9 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT, _step_against_fp64
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device, step_against_fp64
+from tests.parity import K_OUT, check_value, value_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -28,18 +30,6 @@ LIMIT = 256.0              # kH2ActLimit: a tile holding a value at or beyond it
 OLD_HI = 65520.0 / 64.0    # beyond this the fixed scale 2^6 rounds the fp16 hi plane to inf
 K_ILL = 10.0               # the outlier's own rows (ill-conditioned in any fp32; the existing factor of the range test)
 TILE_HEIGHTS = (32, 64)
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _tiles(v, T):
@@ -102,13 +92,9 @@ def _check_rows(tag, what, got, ref64, ref32, ill):
     for group, rows, k in (("in-range", ~ill, K_OUT), ("outlier", ill, K_ILL)):
         if not bool(rows.any()):
             continue
-        r64 = ref64[rows]
-        e_hip = float((got[rows] - r64).abs().max())
-        e_ref = float((ref32[rows].double() - r64).abs().max())
-        bound = k * e_ref + FLOOR_OUT * max(1.0, float(r64.abs().max()))
-        ratios[group] = e_hip / max(e_ref, 1e-30)
-        assert e_hip <= bound, (f"{tag}: {what}, {group} rows: |hip - fp64| {e_hip:.3e} > {bound:.3e} "
-                                f"(fp32 CPU oracle: {e_ref:.3e}, ratio {ratios[group]:.2f}, factor {k})")
+        e_hip, e_ref, _ = value_errors(got[rows], ref64[rows], ref32[rows], k=k)
+        ratios[group] = e_hip / max(e_ref, 1e-30)     # (printed as a multiple of the fp32 oracle's error, not of the bound)
+        check_value(f"{tag}: {what}, {group} rows (factor {k})", got[rows], ref64[rows], ref32[rows], k=k)
     return ratios
 
 
@@ -117,13 +103,13 @@ def _points_desc(R, sdf, ti, x2h):
     the library's choice) and the arithmetic chosen (x2h=False: six bf16 terms, which have their range by construction)"""
     desc = R.runtime.model_desc(sdf, None)
     desc.variant = R.native.variant_bits(fwd_ti=ti or 0, bwd_ti=ti or 0, x2h=None if x2h else False)
-    return desc, R.runtime.pack_weights(desc, sdf, None, _dev())
+    return desc, R.runtime.pack_weights(desc, sdf, None, device())
 
 
 @torch.no_grad()
 def _query(R, sdf, pts, ti, x2h=True):
     """(sdf, normal) of the device.  ti=None with x2h: the public SDFNetwork.sdf / .gradient"""
-    pts = pts.to(_dev())
+    pts = pts.to(device())
     if ti is None:
         assert x2h
         return sdf.sdf(pts), sdf.gradient(pts).reshape(-1, 3)
@@ -137,7 +123,7 @@ def net(R):
     mc = O.ModelConf()
     torch.manual_seed(6)
     p = O.init_params(mc)
-    sdf, devn, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, devn, col, ren = R.build_from_named_params(mc, p, device())
     gen = torch.Generator().manual_seed(2)
     pts = torch.rand(4096 + 37, 3, generator=gen) * 2 - 1
     torch.set_num_threads(16)
@@ -228,7 +214,7 @@ def test_reverse_seed_column_pushed(R, net, j):
     w[j] = 3.0e4
     p["sdf.lin8.weight_v"][0] = w
     p["sdf.lin8.weight_g"][0] = w.norm()
-    sdf, devn, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, devn, col, ren = R.build_from_named_params(mc, p, device())
     pts = net["pts"][:4096]
     named = _named_sdf(sdf, torch.float32)
     seed = _seed(named, mc.sdf, pts)
@@ -295,13 +281,13 @@ def _train_setup(R, p=None):
     if p is None:
         torch.manual_seed(6)
         p = O.init_params(mc)
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(mc, p, device())
     return mc, p, sdf, dev, col, ren, O.synthetic_batch(64, seed=41, step=3, warmup=False)
 
 
 @torch.no_grad()
-def _device_z(ren, batch):
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+def _sampled_z(ren, batch):
+    b = {k: v.to(device()) for k, v in batch.items()}
     ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0, t_rand=b["t_rand"])
     return ren.last_z_vals.detach().cpu().clone()
 
@@ -313,7 +299,7 @@ def test_train_step_with_far_samples(R, ti):
     those rays is row 0 of a tile at both heights and in range; the rows behind it are far beyond 1023.  Outputs
     and all 37 parameter gradients against fp64 at the calibrated bounds."""
     mc, p, sdf, dev, col, ren, batch = _train_setup(R)
-    z = _device_z(ren, batch)
+    z = _sampled_z(ren, batch)
     S = z.shape[1]
     assert S == 128
     o, d = batch["rays_o"], batch["rays_d"]
@@ -328,7 +314,7 @@ def test_train_step_with_far_samples(R, ti):
     if ti:
         ren.set_variant(fwd_ti=ti)
     ren.track_range = True
-    out = _step_against_fp64(R, mc, p, sdf, dev, col, ren, batch, f"far samples, fwd_ti={ti}", survey=False, z_vals=z)
+    out = step_against_fp64(R, mc, p, sdf, dev, col, ren, batch, f"far samples, fwd_ti={ti}", survey=False, z_vals=z)
     rep = ren.range_report()
     ren.track_range = False
     print(f"OPRANGE far samples, fwd_ti={ti}: " + ", ".join(f"{k} {v:.4g}" for k, v in rep.items()))
@@ -353,14 +339,14 @@ def test_train_step_with_pushed_sdf_column(R, j):
         p["sdf.lin8.weight_g"][0] = w.norm()
         p["sdf.lin8.bias"][0] -= 3.0e4 * math.log(2.0) / 100.0
     mc, p, sdf, dev, col, ren, batch = _train_setup(R, p)
-    z = _device_z(ren, batch)
+    z = _sampled_z(ren, batch)
     pts = (batch["rays_o"][:, None, :] + batch["rays_d"][:, None, :] * z[..., None]).reshape(-1, 3)
     seed = _seed(_named_sdf(sdf, torch.float32), mc.sdf, pts)
     assert float(seed[:, j].abs().min()) > 1.4e4
     for T in TILE_HEIGHTS:
         assert _seed_vote_misses(seed, T), f"tile height {T}: the construction drifted"
     ren.track_range = True
-    out = _step_against_fp64(R, mc, p, sdf, dev, col, ren, batch, f"w_sdf[{j}] = 3e4", survey=False, z_vals=z)
+    out = step_against_fp64(R, mc, p, sdf, dev, col, ren, batch, f"w_sdf[{j}] = 3e4", survey=False, z_vals=z)
     rep = ren.range_report()
     ren.track_range = False
     print(f"OPRANGE w_sdf[{j}] = 3e4 step: " + ", ".join(f"{k} {v:.4g}" for k, v in rep.items()))

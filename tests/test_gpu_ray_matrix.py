@@ -23,11 +23,13 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests import parity as P
 from tests import ray_matrix as M
+from tests.bf16_emu_step import step as bf16_step
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import ALBEDO_H2_CLASSES, FUSED_CLASSES, assert_has_surface, device, device_sampling_trace, \
+    explicit_depths, profile_classes, step_against_fp64
 from tests.shape_matrix import BY_NAME as SHAPE_BY_NAME, live_params, step_batch
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT, _assert_has_surface, _device_sampling_trace, _step_against_fp64
-from tests.test_gpu_render_input_grads import FLOAT_OUTS
-from tests.test_gpu_shapes import ALBEDO_H2_CLASSES, FUSED_CLASSES, _profile_classes
 
 pytestmark = pytest.mark.gpu
 
@@ -36,23 +38,10 @@ FUSED = SHAPE_BY_NAME["default_64x64"]
 SENTINEL_I = -7
 
 
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    torch.set_num_threads(16)
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
 def _build(R, shape, row):
     mc = replace(shape.mc, render=row.render_conf)
     p = live_params(mc, shape.seed)
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(mc, p, device())
     return mc, p, sdf, dev, col, ren
 
 
@@ -70,7 +59,7 @@ def _fp64_default():
 def _run_up_sample_step(R, ref, n_new, inv_s):
     """rnb_up_sample_step on the reference's inputs; every output pre-filled with a sentinel"""
     lib = R.native.load()
-    d = _dev()
+    d = device()
     z_in, sdf_in = ref["z"].to(d), ref["sdf"].to(d)
     ro, rd = ref["rays_o"].to(d), ref["rays_d"].to(d)
     B, n = z_in.shape
@@ -113,12 +102,9 @@ def _check_up_sample_case(R, n, n_new, inv_s, tag):
     # the new depths: the output rule against the fp64 oracle
     with _fp64_default():
         o64 = O.up_sample(ref["rays_o"].double(), ref["rays_d"].double(), ref["z"].double(), ref["sdf"].double(), n_new, inv_s)
-    e_hip = float((new_z.double() - o64).abs().max())
-    e_ref = float((ref["new_z"].double() - o64).abs().max())
-    bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(o64.abs().max()))
+    e_hip, e_ref, bound = P.value_errors(new_z, o64, ref["new_z"])
     print(f"UPSAMPLE {tag}: new_z |hip - fp64| {e_hip:.3e}, fp32 oracle {e_ref:.3e}, bound {bound:.3e}")
-    assert e_hip <= bound, f"{tag}: new_z: |hip - fp64| {e_hip:.3e} > {bound:.3e} (fp32 oracle: {e_ref:.3e})"
-    return exempt.numel(), k, flipped_exempt, e_hip / bound
+    return exempt.numel(), k, flipped_exempt, P.check_value(f"{tag}: new_z", new_z, o64, ref["new_z"])
 
 
 _UP_TOTALS = {"samples": 0, "exempt": 0}
@@ -196,9 +182,9 @@ def _row_step(R, shape, row, B, batch_step=1):
     tag = f"{row.name} {shape.name}"
     lib.rnb_profile_enable(1)
     try:
-        out = _step_against_fp64(R, mc, p, sdf, dev, col, ren, _batch(row, B, batch_step), tag, survey=False, stats=stats,
+        out = step_against_fp64(R, mc, p, sdf, dev, col, ren, _batch(row, B, batch_step), tag, survey=False, stats=stats,
                                  loss_rule="calibrated")
-        classes = _profile_classes(R)
+        classes = profile_classes(R)
     finally:
         lib.rnb_profile_enable(0)
     assert tuple(ren.last_z_vals.shape) == (B, row.S)
@@ -231,7 +217,7 @@ FUSED_BATCH_STEP = {"64+448/7": 2}
 
 @pytest.mark.parametrize("row", FUSED_ROWS, ids=[r.name for r in FUSED_ROWS])
 def test_train_step_fused_sweeps(R, row):
-    """64 rays on the shipped shape (with 16 its state renders weight_sum 0.28, below _assert_has_surface's 0.3)"""
+    """64 rays on the shipped shape (with 16 its state renders weight_sum 0.28, below assert_has_surface's 0.3)"""
     classes = _row_step(R, FUSED, row, 64, FUSED_BATCH_STEP.get(row.name, 1))
     assert FUSED_CLASSES <= classes and ALBEDO_H2_CLASSES <= classes, sorted(classes)
 
@@ -258,7 +244,7 @@ def test_sampling_equals_the_composed_loop(R, shape, row):
     B = 48
     mc, p, sdf, dev, col, ren = _build(R, shape, row)
     batch = step_batch(B)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    b = {k: v.to(device()) for k, v in batch.items()}
     packed = ren._pack(False)
     z = ren.sample_z_vals(b["rays_o"], b["rays_d"], b["near"], b["far"], packed, 1.0, b["t_rand"])
     ren0 = R.NeuSRenderer(None, sdf, dev, col, n_samples=row.n_samples, n_importance=0, n_outside=0, up_sample_steps=1,
@@ -275,7 +261,7 @@ def test_sampling_equals_the_composed_loop(R, shape, row):
         assert torch.equal(z, z0)
         print(f"RAYROW {row.name} sampling [{shape.name}]: initial depths bit-exact (no importance samples)")
         return
-    inds_all, z_composed = _device_sampling_trace(R, SimpleNamespace(mc=mc), sdf, b, z0)
+    inds_all, z_composed = device_sampling_trace(R, SimpleNamespace(mc=mc), sdf, b, z0)
     assert [tuple(i.shape) for i in inds_all] == [(B, row.n_new)] * row.up_sample_steps
     for i, n in zip(inds_all, row.step_n):
         assert int(i.min()) >= 0 and int(i.max()) <= n
@@ -295,8 +281,8 @@ def test_initial_depths_on_the_unit_interval_are_torch_linspace(R):
     (tests/test_ray_matrix_host.py restates both splits on the CPU)."""
     mc, p, sdf, dev, col, ren = _build(R, W32, M.BY_NAME["2+0"])
     packed = ren._pack(False)
-    b = {k: v.to(_dev()) for k, v in step_batch(2).items()}
-    near, far = torch.zeros(2, 1, device=_dev()), torch.ones(2, 1, device=_dev())
+    b = {k: v.to(device()) for k, v in step_batch(2).items()}
+    near, far = torch.zeros(2, 1, device=device()), torch.ones(2, 1, device=device())
     wrong = []
     for n in range(2, M.K_MAX_S + 1):
         r = R.NeuSRenderer(None, sdf, dev, col, n_samples=n, n_importance=0, n_outside=0, up_sample_steps=1, perturb=0.0)
@@ -307,12 +293,6 @@ def test_initial_depths_on_the_unit_interval_are_torch_linspace(R):
 
 
 # ------------------------------------------------------------------------------------------------------------------- 5
-def _explicit_depths(batch, S):
-    gen = torch.Generator().manual_seed(104729 + S)
-    u = torch.sort(torch.rand(batch["near"].shape[0], S, generator=gen), dim=-1).values
-    return (batch["near"] + (batch["far"] - batch["near"]) * u).contiguous()
-
-
 def _oracle_render(p, mc, api, batch, z, bg, dt):
     q = {k: v.to(dt) for k, v in p.items()}
     x = {k: v.to(dt) for k, v in batch.items()}
@@ -333,36 +313,32 @@ def test_explicit_depths_forward_against_fp64(R, shape, S):
     B = 16
     mc = shape.mc
     p = live_params(mc, shape.seed)
-    sdf, dev, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(mc, p, device())
     batch = step_batch(B)
-    z = _explicit_depths(batch, S)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    z = explicit_depths(batch, S, seed=104729 + S)
+    b = {k: v.to(device()) for k, v in batch.items()}
     bg = torch.tensor([0.2, 0.5, 0.8])
     worst = ("", 0.0)
     for api in ("render", "render_rnb", "render_rnb_warmup"):
         with torch.no_grad():
             if api == "render":
-                out = ren.render(b["rays_o"], b["rays_d"], b["near"], b["far"], background_rgb=bg.to(_dev()),
-                                 cos_anneal_ratio=0.5, z_vals=z.to(_dev()))
+                out = ren.render(b["rays_o"], b["rays_d"], b["near"], b["far"], background_rgb=bg.to(device()),
+                                 cos_anneal_ratio=0.5, z_vals=z.to(device()))
             else:
                 fn = ren.render_rnb_warmup if api == "render_rnb_warmup" else ren.render_rnb
                 out = fn(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=0.5,
-                         z_vals=z.to(_dev()))
+                         z_vals=z.to(device()))
         torch.cuda.synchronize()
         r64 = _oracle_render(p, mc, api, batch, z, bg, torch.float64)
         r32 = _oracle_render(p, mc, api, batch, z, bg, torch.float32)
         if S >= 63:
-            _assert_has_surface(r64)
+            assert_has_surface(r64)
         assert torch.equal(out["inside_sphere"].cpu(), r32["inside_sphere"].reshape(B, S))
-        for k in FLOAT_OUTS:
-            got = out[k].detach().cpu().double()
-            a64, a32 = r64[k].reshape(got.shape), r32[k].reshape(got.shape).double()
-            assert bool(torch.isfinite(got).all()), f"S={S} {api} {k}: not finite"
-            e_hip, e_ref = float((got - a64).abs().max()), float((a32 - a64).abs().max())
-            bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(a64.abs().max()))
-            if e_hip / bound > worst[1]:
-                worst = (f"{api} {k}", e_hip / bound)
-            assert e_hip <= bound, f"S={S} {shape.name} {api} {k}: |hip - fp64| {e_hip:.3e} > {bound:.3e} (fp32 oracle: {e_ref:.3e})"
+        for k in M.FLOAT_OUTS:
+            ratio = P.check_value(f"S={S} {shape.name} {api} {k}", out[k], r64[k].reshape(out[k].shape),
+                                  r32[k].reshape(out[k].shape))
+            if ratio > worst[1]:
+                worst = (f"{api} {k}", ratio)
     print(f"RAYROW z{S} explicit depths [{shape.name}]: worst output {worst[0]} {worst[1]:.2f} of its bound")
 
 
@@ -379,9 +355,10 @@ def test_refused_rows_are_refused_before_any_launch(R, shape, row):
     B = 16
     mc, p, sdf, dev, col, ren = _build(R, shape, row)
     batch = O.synthetic_batch(B, n_lights=row.n_lights, seed=11, step=1, warmup=False)
-    b = {k: v.to(_dev()) for k, v in batch.items()}
+    b = {k: v.to(device()) for k, v in batch.items()}
     # (the 9-light row renders at explicit depths too: its own sampling would be a legitimate launch before the refusal)
-    z = None if row.refused_by == "sample_query" else _explicit_depths(batch, row.z_vals_S or 32).to(_dev())
+    S = row.z_vals_S or 32
+    z = None if row.refused_by == "sample_query" else explicit_depths(batch, S, seed=104729 + S).to(device())
     ren.last_z_vals = None
     for api in ("render_rnb", "render"):
         lib.rnb_profile_enable(1)
@@ -392,7 +369,7 @@ def test_refused_rows_are_refused_before_any_launch(R, shape, row):
                 else:
                     ren.render_rnb(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], t_rand=b["t_rand"], z_vals=z)
             torch.cuda.synchronize()
-            classes = _profile_classes(R)
+            classes = profile_classes(R)
         finally:
             lib.rnb_profile_enable(0)
         assert classes == set(), f"{row.name} {api}: kernels ran before the refusal: {sorted(classes)}"
@@ -414,7 +391,6 @@ def test_bf16_step_against_emulation(R, row):
     outside for the last SDF layer alone — sdf.lin8.weight_g 2.4e-2 and 3.1e-2 from the fp64 emulation against bounds of
     1.5e-2 and 8.1e-3, the emulation's own fp32 orders 8.8e-3 and 2.0e-3 — the most cancelling gradient of the network over
     2,064 and 8,192 points.)"""
-    from tests.test_gpu_bf16_emu import _step
     mc = O.ModelConf(render=row.render_conf)
-    n = _step(R, mc, 48, tag=f"RAYROW {row.name} bf16 S={row.S}")
+    n = bf16_step(R, mc, 48, tag=f"RAYROW {row.name} bf16 S={row.S}")
     assert n >= 25

@@ -6,7 +6,6 @@ The oracle's sdf_gradient detaches its input; the reference's gradient() (models
 points when they require grad, so the normal's Hessian-vector term is part of the reference's ray gradient.  Every oracle
 call here runs with a graph-keeping normal (_graph_normal, monkeypatched in)."""
 import os
-import socket
 from dataclasses import replace
 
 import pytest
@@ -15,23 +14,16 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import rnb_oracle as O
-from tests.ray_matrix import Z_GRAD_S
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device, explicit_depths, free_port
+from tests.parity import check_grad, check_value, grad_bound, rel_l2
+from tests.ray_matrix import FLOAT_OUTS, Z_GRAD_S
 from tests.shape_matrix import BY_NAME, live_params, step_batch
-from tests.test_gpu_parity import _grad_bound
 
 pytestmark = pytest.mark.gpu
 
 B = 64
 SHAPES = ["default_64x64", "feat128", "scale3"]
-FLOAT_OUTS = ("color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights", "gradient_error")
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
 
 
 @pytest.fixture
@@ -45,15 +37,11 @@ def graph_normal(monkeypatch):
     monkeypatch.setattr(O, "sdf_gradient", _graph_normal)
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
 def _build(R, name, render=None):
     shape = BY_NAME[name]
     mc = shape.mc if render is None else replace(shape.mc, render=render)
     p = live_params(mc, shape.seed)
-    sdf, devn, col, ren = R.build_from_named_params(mc, p, _dev())
+    sdf, devn, col, ren = R.build_from_named_params(mc, p, device())
     return mc, p, sdf, devn, col, ren
 
 
@@ -90,7 +78,7 @@ def _native(ren, case, b, want, variant=None):
         q.grad = None
     for q in list(ren.color_network.parameters()) + list(ren.deviation_network.parameters()):
         q.grad = None
-    x = {k: v.to(_dev()).detach().requires_grad_(k in want) for k, v in b.items()}
+    x = {k: v.to(device()).detach().requires_grad_(k in want) for k, v in b.items()}
     zv = x.get("z_vals")     # explicit depths (an input like the others: it may require grad), else the device samples
     if case == "render":
         out = ren.render(x["rays_o"], x["rays_d"], x["near"], x["far"], background_rgb=x["bg"], cos_anneal_ratio=0.5,
@@ -122,19 +110,14 @@ def _oracle(p, mc, case, b, want, z, dt, outs=None):
     return {k: x[k].grad for k in want}
 
 
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-300))
-
-
 def _check(mine, g64, g32, tag):
     for k in g64:
         assert mine[k] is not None, f"{tag} {k}: no gradient"
-        assert mine[k].shape == g64[k].shape, f"{tag} {k}: shape {tuple(mine[k].shape)} != {tuple(g64[k].shape)}"
         assert bool(torch.isfinite(mine[k]).all()), f"{tag} {k}: not finite"
         assert float(g64[k].norm()) > 0.0, f"{tag} {k}: the fp64 gradient vanishes: not a parity target"
-        err, bound = _rel(mine[k].cpu(), g64[k]), _grad_bound(_rel(g32[k], g64[k]))
-        print(f"{tag} {k}: rel-L2 {err:.2e} (bound {bound:.2e})")
-        assert err <= bound, f"{tag} {k}: rel-L2 {err:.3g} > bound {bound:.3g}"
+        rel32 = rel_l2(g32[k], g64[k])
+        print(f"{tag} {k}: rel-L2 {rel_l2(mine[k].cpu(), g64[k]):.2e} (bound {grad_bound(rel32):.2e})")
+        check_grad(f"{tag} {k}", mine[k].cpu(), g64[k], rel32)
 
 
 # ------------------------------------------------------------------------------------------------------------ case 1
@@ -160,7 +143,7 @@ def test_near_far_with_no_importance_samples(R, graph_normal):
     want = ("rays_o", "rays_d", "near", "far")
 
     def native():
-        x = {k: v.to(_dev()).detach().requires_grad_(k in ("rays_o", "rays_d", "lights_dir")) for k, v in b.items()}
+        x = {k: v.to(device()).detach().requires_grad_(k in ("rays_o", "rays_d", "lights_dir")) for k, v in b.items()}
         near, far = O.near_far_from_sphere(x["rays_o"], x["rays_d"])
         near.retain_grad()
         far.retain_grad()
@@ -195,13 +178,6 @@ def test_near_far_with_no_importance_samples(R, graph_normal):
 BZ = 32
 
 
-def _explicit_depths(batch, S, seed=0):
-    """sorted non-uniform depths [B, S] between near and far"""
-    gen = torch.Generator().manual_seed(7919 * S + seed)
-    u = torch.sort(torch.rand(batch["near"].shape[0], S, generator=gen), dim=-1).values
-    return (batch["near"] + (batch["far"] - batch["near"]) * u).contiguous()
-
-
 def _check_chunk_boundaries(mine, g64, g32, S, tag):
     """the samples on either side of every 64-sample chunk boundary, as a tensor of their own: what carry_D feeds"""
     cols = [c for j0 in range(64, S, 64) for c in (j0 - 1, j0)]
@@ -215,7 +191,7 @@ def _check_chunk_boundaries(mine, g64, g32, S, tag):
 def test_explicit_depth_gradients_against_fp64(R, graph_normal, S, case):
     mc, p, sdf, devn, col, ren = _build(R, "default_64x64")
     b, want = _case_inputs(case, step_batch(BZ))
-    b["z_vals"] = _explicit_depths(b, S)
+    b["z_vals"] = explicit_depths(b, S, seed=7919 * S)
     want = want + ("z_vals",)
     out, mine = _native(ren, case, b, want)
     assert tuple(mine["z_vals"].shape) == (BZ, S)
@@ -231,8 +207,7 @@ def test_explicit_depth_gradients_against_fp64(R, graph_normal, S, case):
 @pytest.mark.parametrize("L", [1, 2, 5, 8])
 def test_light_counts_at_a_carry_and_a_ragged_chunk(R, graph_normal, L, per_ray):
     """1, 2, 5 and kMaxRenderLights = 8 lights at S = 129 explicit depths, shared [L,1,1,3] and per ray [L,B,1,3]:
-    lights_dir.grad (with rays and z_vals) by _grad_bound, color_fine per light by the output rule of test_gpu_parity.py"""
-    from tests.test_gpu_parity import FLOOR_OUT, K_OUT
+    lights_dir.grad (with rays and z_vals) by the gradient rule, color_fine per light by the output rule of tests/parity.py"""
     S = 129
     mc, p, sdf, devn, col, ren = _build(R, "default_64x64")
     b = dict(O.synthetic_batch(BZ, n_lights=L, seed=11, step=1, warmup=False))
@@ -240,7 +215,7 @@ def test_light_counts_at_a_carry_and_a_ragged_chunk(R, graph_normal, L, per_ray)
         gen = torch.Generator().manual_seed(40 + L)
         lt = torch.randn(L, 1, 1, 3, generator=gen)
         b["lights_dir"] = (lt / lt.norm(dim=-1, keepdim=True)).contiguous()
-    b["z_vals"] = _explicit_depths(b, S)
+    b["z_vals"] = explicit_depths(b, S, seed=7919 * S)
     want = ("rays_o", "rays_d", "lights_dir", "z_vals")
     out, mine = _native(ren, "rnb", b, want)
     assert tuple(out["color_fine"].shape) == (L, BZ, 3) and tuple(mine["lights_dir"].shape) == tuple(b["lights_dir"].shape)
@@ -253,11 +228,8 @@ def test_light_counts_at_a_carry_and_a_ragged_chunk(R, graph_normal, L, per_ray)
     _check_chunk_boundaries(mine, g64, g32, S, tag)
     for l in range(L):
         r64 = o64["color_fine"][l]
-        e_hip = float((out["color_fine"][l].detach().cpu().double() - r64).abs().max())
-        e_ref = float((o32["color_fine"][l].double() - r64).abs().max())
-        bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(r64.abs().max()))
         assert float(r64.abs().max()) > 1e-3, f"{tag}: light {l} renders nothing"
-        assert e_hip <= bound, f"{tag}: color_fine[{l}]: |hip - fp64| {e_hip:.3e} > {bound:.3e} (fp32 oracle: {e_ref:.3e})"
+        check_value(f"{tag}: color_fine[{l}]", out["color_fine"][l], r64, o32["color_fine"][l])
 
 
 # ------------------------------------------------------------------------------------------------------------ cases 3-5
@@ -308,7 +280,7 @@ def test_input_gradients_are_bit_reproducible(R, variant):
 def test_bf16_refuses_input_gradients_before_any_launch(R):
     mc, p, sdf, devn, col, ren = _build(R, "default_64x64")
     ren.set_variant(bf16=True)
-    b = {k: v.to(_dev()) for k, v in step_batch(B).items()}
+    b = {k: v.to(device()) for k, v in step_batch(B).items()}
     ren.last_z_vals = None
     with pytest.raises(RuntimeError, match="bf16.*no input adjoints"):
         ren.render_rnb(b["rays_o"].requires_grad_(True), b["rays_d"], b["near"], b["far"], b["lights_dir"],
@@ -320,12 +292,6 @@ def test_bf16_refuses_input_gradients_before_any_launch(R):
 
 
 # ------------------------------------------------------------------------------------------------------------ case 7
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _dp_worker(rank, world, port, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -368,7 +334,7 @@ def _dp_worker(rank, world, port, q):
 def test_data_parallel_input_gradients_are_shard_local(R):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
     for pr in procs:
         pr.start()

@@ -4,7 +4,7 @@
   2. normal, albedo and depth against the float64 sums of the existing forward's own per-sample outputs, at a bound derived
      from the kernel's arithmetic, over S = 1 .. 512, 1 / 3 / 8 lights (shared and per ray, with and without the warm-up's
      ReLU) and B = 1, 65 — with a guard that the inside-sphere mask matters in every case;
-  3. every golden fixture against the reference's fp32 / fp64 outputs by the calibrated rule of tests/test_gpu_parity.py;
+  3. every golden fixture against the reference's fp32 / fp64 outputs by the calibrated rule of tests/parity.py;
   4. refusals before any launch, and grad mode;
   5. the workspace is one chunk's, whatever the number of rays.
 """
@@ -15,9 +15,10 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests import parity as P
 from tests.golden_util import Golden, case_names
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT
-from tests.test_gpu_shapes import _profile_classes
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device, profile_classes
 
 pytestmark = pytest.mark.gpu
 
@@ -26,22 +27,9 @@ BIT_CASES = ["tiny_main_sharp", "tiny_warmup_sharp", "tiny_render_bg", "tiny_mai
 RNB_E_INVALID = -1
 
 
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    torch.set_num_threads(16)
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
 def _build(R, g):
     p = g.params()
-    sdf, dev, col, ren = R.build_from_named_params(g.mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(g.mc, p, device())
     return p, sdf, dev, col, ren
 
 
@@ -73,8 +61,8 @@ def _golden_pair(R, name, variant=None, **kw):
     p, sdf, dev, col, ren = _build(R, g)
     if variant:
         ren.set_variant(**variant)
-    b = {k: v.to(_dev()) for k, v in g.batch.items()}
-    z = g.z_fine.to(_dev())
+    b = {k: v.to(device()) for k, v in g.batch.items()}
+    z = g.z_fine.to(device())
     bg = b.get("background_rgb")
     ref = _wrapper(ren, g.api, b, z, g.cos_anneal_ratio, g.no_albedo, bg)
     got = _maps(ren, g.api, b, z, g.cos_anneal_ratio, g.no_albedo, bg, **kw)
@@ -105,8 +93,8 @@ def _rebuild_args(R, name, variant):
     p, sdf, dev, col, ren = _build(R, g)
     if variant:
         ren.set_variant(**variant)
-    b = {k: v.to(_dev()) for k, v in g.batch.items()}
-    return ren, g.api, b, g.z_fine.to(_dev()), g.cos_anneal_ratio, g.no_albedo, b.get("background_rgb")
+    b = {k: v.to(device()) for k, v in g.batch.items()}
+    return ren, g.api, b, g.z_fine.to(device()), g.cos_anneal_ratio, g.no_albedo, b.get("background_rgb")
 
 
 # ------------------------------------------------------------------------------------------------------------------- 2
@@ -186,14 +174,14 @@ def _check_reductions(got, terms, S, tag):
 def test_reductions_against_the_per_sample_outputs(R, S, B):
     g = Golden("tiny_main_sharp")
     p, sdf, dev, col, ren = _build(R, g)
-    rays = {k: v[:B].to(_dev()) for k, v in matrix_rays().items()}
-    z = matrix_depths(S, B).to(_dev())
+    rays = {k: v[:B].to(device()) for k, v in matrix_rays().items()}
+    z = matrix_depths(S, B).to(device())
     ns = g.mc.render.n_samples
     first = True
     for L in MATRIX_L:
         for per_ray in (False, True):
             for api in ("render_rnb", "render_rnb_warmup"):
-                b = dict(rays, lights_dir=matrix_lights(L, per_ray, B).to(_dev()))
+                b = dict(rays, lights_dir=matrix_lights(L, per_ray, B).to(device()))
                 ref = _wrapper(ren, api, b, z, 0.5)
                 got = _maps(ren, api, b, z, 0.5, maps=("color", "normal", "albedo", "depth", "weight_sum", "weight_max"))
                 tag = f"S={S} B={B} L={L} {'per-ray' if per_ray else 'shared'} {api}"
@@ -220,11 +208,10 @@ def test_reductions_against_the_per_sample_outputs(R, S, B):
 
 # ------------------------------------------------------------------------------------------------------------------- 3
 def _rule(got, ref32, ref64, what):
-    e_hip = float((got.double().cpu().reshape(ref64.shape) - ref64).abs().max())
-    e_ref = float((ref32.double() - ref64).abs().max())
-    bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(ref64.abs().max()))
+    got = got.reshape(ref64.shape)
+    e_hip, e_ref, bound = P.value_errors(got, ref64, ref32)
     print(f"MAPS {what}: |hip - fp64| {e_hip:.3e}, fp32 reference {e_ref:.3e}, bound {bound:.3e}")
-    assert e_hip <= bound, f"{what}: |hip - fp64| {e_hip:.3e} > {bound:.3e} (fp32 reference: {e_ref:.3e})"
+    P.check_value(what, got, ref64, ref32)
 
 
 def _mid(z, n_samples):
@@ -272,7 +259,7 @@ def _raw_call(R, ren, b, z, flags, n_lights, maps_ptrs, lights=None):
     nbytes = C.c_int64()
     R.native.check(lib.rnb_render_workspace_bytes(C.byref(ren.desc), B, min(S, 512), R.native.FLAG_FORWARD_ONLY | (flags & 7),
                                                   C.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=_dev())
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device())
     var = ren.deviation_network.variance.detach().reshape(1)
     a = R.native.RenderArgs()
     a.B, a.S, a.n_lights, a.flags, a.cos_anneal_ratio = B, S, n_lights, flags, 0.5
@@ -281,7 +268,7 @@ def _raw_call(R, ren, b, z, flags, n_lights, maps_ptrs, lights=None):
     m = R.native.RenderMapsOut()
     for k, t in maps_ptrs.items():
         setattr(m, k, t.data_ptr())
-    with R.native.on_device(_dev()) as stream:
+    with R.native.on_device(device()) as stream:
         rc = lib.rnb_render_maps(C.byref(ren.desc), R.native.ptr(packed), C.byref(a), C.byref(m), R.native.ptr(ws),
                                  ws.numel(), stream)
     return rc, lib.rnb_last_error_string().decode()
@@ -292,12 +279,12 @@ def test_refusals_come_before_any_launch(R):
     p, sdf, dev, col, ren = _build(R, g)
     N = R.native
     B = 4
-    rays = {k: v[:B].to(_dev()) for k, v in matrix_rays().items()}
-    z = matrix_depths(64, B).to(_dev())
-    z513 = torch.sort(torch.rand(B, 513), dim=-1).values.to(_dev())
-    l3 = matrix_lights(3, False, B).reshape(3, 3).to(_dev())
-    l9 = matrix_lights(9, False, B).reshape(9, 3).to(_dev())
-    f32 = dict(dtype=torch.float32, device=_dev())
+    rays = {k: v[:B].to(device()) for k, v in matrix_rays().items()}
+    z = matrix_depths(64, B).to(device())
+    z513 = torch.sort(torch.rand(B, 513), dim=-1).values.to(device())
+    l3 = matrix_lights(3, False, B).reshape(3, 3).to(device())
+    l9 = matrix_lights(9, False, B).reshape(9, 3).to(device())
+    f32 = dict(dtype=torch.float32, device=device())
     col3, alb, wsum = torch.empty(3, B, 3, **f32), torch.empty(B, 3, **f32), torch.empty(B, **f32)
     lib = N.load()
     lib.rnb_profile_enable(1)
@@ -327,7 +314,7 @@ def test_refusals_come_before_any_launch(R):
         with pytest.raises(ValueError, match="kMaxRenderLights"):
             _maps(ren, "render_rnb", dict(rays, lights_dir=l9.reshape(9, 1, 1, 3)), z, 0.5)
         torch.cuda.synchronize()
-        classes = _profile_classes(R)
+        classes = profile_classes(R)
     finally:
         lib.rnb_profile_enable(0)
     assert classes == set(), f"kernels ran before a refusal: {sorted(classes)}"
@@ -341,16 +328,16 @@ def test_no_graph_under_enable_grad(R):
     p, sdf, dev, col, ren = _build(R, g)
     leaves = list(sdf.parameters()) + list(col.parameters()) + [dev.variance]
     assert all(t.requires_grad for t in leaves)
-    b = {k: v.to(_dev()) for k, v in g.batch.items()}
+    b = {k: v.to(device()) for k, v in g.batch.items()}
     b["rays_o"] = b["rays_o"].clone().requires_grad_(True)
     with torch.enable_grad():
-        out = _maps(ren, g.api, b, g.z_fine.to(_dev()), g.cos_anneal_ratio, return_z_vals=True)
+        out = _maps(ren, g.api, b, g.z_fine.to(device()), g.cos_anneal_ratio, return_z_vals=True)
         assert torch.is_grad_enabled(), "the caller's grad mode is restored"
     assert set(out) == {"color", "normal", "albedo", "depth", "weight_sum", "z_vals"}
     for k, v in out.items():
         assert not v.requires_grad and v.grad_fn is None, k
     assert all(t.grad is None for t in leaves) and b["rays_o"].grad is None
-    assert torch.equal(out["z_vals"], g.z_fine.to(_dev()))
+    assert torch.equal(out["z_vals"], g.z_fine.to(device()))
 
 
 # ------------------------------------------------------------------------------------------------------------------- 5
@@ -361,8 +348,8 @@ def test_workspace_is_one_chunks_whatever_the_ray_count(R):
     gen = torch.Generator().manual_seed(5)
     src = matrix_rays()
     idx = torch.randint(0, 65, (256,), generator=gen)
-    rays = {k: v[idx].to(_dev()) for k, v in src.items()}
-    lights = matrix_lights(L, False, 1).to(_dev())
+    rays = {k: v[idx].to(device()) for k, v in src.items()}
+    lights = matrix_lights(L, False, 1).to(device())
 
     def peak_rise(n):
         r = {k: v[:n].contiguous() for k, v in rays.items()}

@@ -3,7 +3,7 @@
 The fused x2h kernels are compiled for a 256-wide network but read the skip position, pe, Ep, the layer count, the feature
 width and the SDF scale at run time; the per-layer GEMMs take any width.  Each shape runs here in a live state
 (shape_matrix.live_params: no zero block, so the PE columns of lin0 and of the skip layer carry a share of every Jacobian)
-with the calibrated rule of tests/test_gpu_parity.py (K_OUT, FLOOR_OUT for outputs; K_GRAD, GRAD_CAP for gradients):
+with the calibrated rule of tests/parity.py (K_OUT, FLOOR_OUT for outputs; K_GRAD, GRAD_CAP for gradients):
   - point-wise SDF + feature, normal and albedo at 1, 63 and 4097 points, at both tile heights of the fused sweeps and,
     where sweep_mv_supported holds, through the M/V kernels (RNB_VARIANT_REG_TILE);
   - one end-to-end train step (sampling, fine pass, loss, backward; every parameter gradient), with the kernel classes it
@@ -16,32 +16,20 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests.bf16_emu_step import linspace_at, step as bf16_step
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import ALBEDO_H2_CLASSES, FUSED_CLASSES, device, profile_classes, step_against_fp64
+from tests.parity import check_value
 from tests.shape_matrix import BY_NAME, SHAPES, live_params, oracle_points, points, step_batch
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT, _step_against_fp64
 
 pytestmark = pytest.mark.gpu
 
 RENDER_SHAPES = [s for s in SHAPES if s.render]
-FUSED_CLASSES = {"F_sweep(save)", "R_sweep", "FB_sweep", "RA_sweep", "dW(x3: 256x256 + narrow jobs)"}
-ALBEDO_H2_CLASSES = {"albedo_fwd", "albedo_bwd"}
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    torch.set_num_threads(16)
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _build(R, shape):
     p = live_params(shape.mc, shape.seed)
-    sdf, dev, col, ren = R.build_from_named_params(shape.mc, p, _dev())
+    sdf, dev, col, ren = R.build_from_named_params(shape.mc, p, device())
     return p, sdf, dev, col, ren
 
 
@@ -54,18 +42,6 @@ def _point_variants(shape):
     if shape.mv:
         out.append(("mv", dict(reg_tile=True)))
     return out
-
-
-def _ratio(tag, what, got, r64, r32):
-    """|hip - fp64| as a fraction of the calibrated bound; asserts <= 1"""
-    got = got.detach().cpu().double()
-    assert got.shape == r64.shape, f"{tag}: {what}: shape {tuple(got.shape)} != {tuple(r64.shape)}"
-    assert bool(torch.isfinite(got).all()), f"{tag}: {what}: not finite"
-    e_hip = float((got - r64).abs().max())
-    e_ref = float((r32.double() - r64).abs().max())
-    bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(r64.abs().max()))
-    assert e_hip <= bound, f"{tag}: {what}: |hip - fp64| {e_hip:.3e} > {bound:.3e} (fp32 CPU oracle: {e_ref:.3e})"
-    return e_hip / bound
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
@@ -86,18 +62,18 @@ def test_pointwise_against_fp64(R, shape):
             desc = R.model_desc(sdf, col)
             desc.variant = R.native.variant_bits(**kw)
             with torch.no_grad():
-                packed = R.runtime.pack_weights(desc, sdf, col, _dev())
-                out = R.runtime.sdf_forward(desc, packed, pts.to(_dev()), True)
-                only = R.runtime.sdf_forward(desc, packed, pts.to(_dev()), False)
-                grad = R.runtime.sdf_gradient(desc, packed, pts.to(_dev()))
-                alb = R.runtime.color_forward(desc, packed, pts.to(_dev()), nrm.to(_dev()), feats.to(_dev()))
+                packed = R.runtime.pack_weights(desc, sdf, col, device())
+                out = R.runtime.sdf_forward(desc, packed, pts.to(device()), True)
+                only = R.runtime.sdf_forward(desc, packed, pts.to(device()), False)
+                grad = R.runtime.sdf_gradient(desc, packed, pts.to(device()))
+                alb = R.runtime.color_forward(desc, packed, pts.to(device()), nrm.to(device()), feats.to(device()))
             torch.cuda.synchronize()
             tag = f"{shape.name} {vtag} n={n}"
             assert torch.equal(only, out[:, :1]), f"{tag}: sdf-only and sdf + feature sweeps must agree bit for bit"
             for what, got, a64, a32 in (("sdf", out[:, :1], r64[0][:, :1], r32[0][:, :1]),
                                         ("feature", out[:, 1:], r64[0][:, 1:], r32[0][:, 1:]),
                                         ("normal", grad, r64[1], r32[1]), ("albedo", alb, r64[2], r32[2])):
-                r = _ratio(tag, what, got, a64, a32)
+                r = check_value(f"{tag}: {what}", got, a64, a32)
                 if r >= worst.get(vtag, ("", -1.0))[1]:
                     worst[vtag] = (f"{what} n={n}", r)
     print(f"SHAPE {shape.name} point-wise [{shape.path}]: " + "; ".join(
@@ -105,16 +81,6 @@ def test_pointwise_against_fp64(R, shape):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2
-def _profile_classes(R):
-    lib = R.native.load()
-    ms, n, fl = C.c_double(), C.c_int64(), C.c_double()
-    R.native.check(lib.rnb_profile_collect(C.byref(ms), C.byref(n), C.byref(fl)))
-    need = lib.rnb_profile_report(None, 0)
-    buf = C.create_string_buffer(int(need) + 16)
-    lib.rnb_profile_report(buf, len(buf))
-    return {ln.rsplit(" ", 3)[0] for ln in buf.value.decode().splitlines()}
-
-
 def _step_variants(shape):
     """M/V and LDS-tile kernels differ only in the forward-only sweeps (the sampling passes), and the profile does not
     tell them apart: where sweep_mv_supported holds (Ep = 64, 2..8 hidden layers of >= 192 outputs, a 256-row feature head
@@ -134,8 +100,8 @@ def test_train_step_against_fp64(R, shape):
         tag = f"{shape.name} {vtag}"
         lib.rnb_profile_enable(1)
         try:
-            _step_against_fp64(R, shape.mc, p, sdf, dev, col, ren, step_batch(), tag, survey=False, stats=stats)
-            classes = _profile_classes(R)
+            step_against_fp64(R, shape.mc, p, sdf, dev, col, ren, step_batch(), tag, survey=False, stats=stats)
+            classes = profile_classes(R)
         finally:
             lib.rnb_profile_enable(0)
         print(f"SHAPE {tag} step [{shape.path}]: classes {sorted(classes)}; worst output {stats['worst_out'][0]} "
@@ -157,7 +123,6 @@ def test_train_step_against_fp64(R, shape):
 @pytest.mark.parametrize("name", ["no_skip", "multires0", "scale3", "w100"])
 def test_sdf_grid_against_fp64(R, name):
     """rnb_sdf_grid (odd resolution, an x-slab) against the oracle on the coordinates the kernel generates"""
-    from tests.test_gpu_bf16_emu import _linspace_at
     shape = BY_NAME[name]
     p, sdf, dev, col, ren = _build(R, shape)
     lib = R.native.load()
@@ -168,16 +133,16 @@ def test_sdf_grid_against_fp64(R, name):
         gd.bound_min[d], gd.bound_max[d] = lo[d], hi[d]
     gd.resolution, gd.x_begin, gd.x_end, gd.out_scale = res, x0, x1, -1.0
     packed = ren._pack(False)
-    vol = torch.full((x1 - x0, res, res), float("nan"), dtype=torch.float32, device=_dev())
+    vol = torch.full((x1 - x0, res, res), float("nan"), dtype=torch.float32, device=device())
     nbytes = C.c_int64()
     R.native.check(lib.rnb_sdf_grid_workspace_bytes(C.byref(ren.desc), C.byref(gd), C.byref(nbytes)))
-    ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=_dev())
+    ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=device())
     with R.native.on_device(vol) as stream:
         R.native.check(lib.rnb_sdf_grid(C.byref(ren.desc), R.native.ptr(packed), C.byref(gd), R.native.ptr(vol),
                                         R.native.ptr(ws), ws.numel(), stream))
     torch.cuda.synchronize()
-    xs = [_linspace_at(lo[0], hi[0], res, torch.arange(x0, x1)), _linspace_at(lo[1], hi[1], res, torch.arange(res)),
-          _linspace_at(lo[2], hi[2], res, torch.arange(res))]
+    xs = [linspace_at(lo[0], hi[0], res, torch.arange(x0, x1)), linspace_at(lo[1], hi[1], res, torch.arange(res)),
+          linspace_at(lo[2], hi[2], res, torch.arange(res))]
     xx, yy, zz = torch.meshgrid(*xs, indexing="ij")
     pts = torch.stack([xx.reshape(-1), yy.reshape(-1), zz.reshape(-1)], dim=-1)
     ref = {}
@@ -185,7 +150,7 @@ def test_sdf_grid_against_fp64(R, name):
         q = {k: v.to(dt) for k, v in p.items()}
         with torch.no_grad():
             ref[dt] = -O.sdf_forward(q, shape.mc.sdf, pts.to(dt))[:, :1].reshape(vol.shape)
-    r = _ratio(f"grid {name}", "sdf", vol, ref[torch.float64], ref[torch.float32])
+    r = check_value(f"grid {name}: sdf", vol, ref[torch.float64], ref[torch.float32])
     print(f"SHAPE {name} sdf_grid [{shape.path}]: worst {r:.2f} of its bound")
 
 
@@ -195,8 +160,7 @@ def test_bf16_step_against_emulation(R, name):
     """RNB_VARIANT_BF16 on four fused shapes other than the shipped one, one train step against oracle/bf16_emu.py with
     the rule of tests/test_gpu_bf16_emu.py (feature width 255: the fp32 albedo kernels behind the bf16 SDF sweeps).
     Skip at layer 1, Ep = 32 and feature widths below 225 are refused by make_layout (tests/test_shape_paths.py)."""
-    from tests.test_gpu_bf16_emu import _step
     shape = BY_NAME[name]
     assert shape.bf16
-    n = _step(R, shape.mc, 64, params=live_params(shape.mc, shape.seed), tag=f"shape {name}")
+    n = bf16_step(R, shape.mc, 64, params=live_params(shape.mc, shape.seed), tag=f"shape {name}")
     assert n == len(O.param_order(shape.mc))

@@ -12,20 +12,13 @@ import torch
 
 from tests import source_maps_util as U
 from tests.golden_util import Golden
+from tests.gpu_support import R  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 H, W = 13, 11
 RAY_KEYS = ("rays_o", "rays_d", "near", "far", "mask", "pixels_x", "pixels_y")
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
 
 
 @pytest.fixture(scope="module")

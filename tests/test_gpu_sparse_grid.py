@@ -19,23 +19,14 @@ import torch
 from oracle import mc_oracle as M
 from oracle import rnb_oracle as O
 from tests.golden_util import Golden
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device
 
 pytestmark = pytest.mark.gpu
 
 LO, HI = torch.tensor([-1.01, -1.01, -1.01]), torch.tensor([1.01, 1.01, 1.01])
 GRIDS = [(70, 8, 0.0), (97, 8, 0.0), (193, 8, 0.0), (257, 16, 0.0), (97, 8, 0.05)]   # (resolution, brick, threshold)
 MODELS = ["sharp", "geo", "tiny", "sharp_bf16"]
-
-
-@pytest.fixture(scope="module")
-def R():
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _params(which):
@@ -62,7 +53,7 @@ _REN = {}
 def _renderer(R, which):
     if which not in _REN:
         mc, p = _params(which)
-        ren = R.build_from_named_params(mc, p, _dev())[3]
+        ren = R.build_from_named_params(mc, p, device())[3]
         if which == "sharp_bf16":
             ren.set_variant(bf16=True)
         _REN[which] = ren
@@ -171,7 +162,7 @@ def test_other_arithmetic_variants_of_the_fused_route(R, variant):
     """The six-term and fp32-MFMA forms of the fused sweep and the M/V sweep carry the same brick mode: dense and sparse are
     compared within the variant."""
     mc, p = _params("sharp")
-    ren = R.build_from_named_params(mc, p, _dev())[3]
+    ren = R.build_from_named_params(mc, p, device())[3]
     ren.set_variant(**variant)
     ud = ren.extract_fields(LO, HI, 97, to_host=False)
     u_np = ud.cpu().numpy()
@@ -218,7 +209,7 @@ def test_nan_weights_give_an_all_nan_volume_and_an_empty_mesh(R):
     mc, p = _params("geo")
     with torch.no_grad():
         p["sdf.lin0.weight_v"][3, 1] = float("nan")
-    ren = R.build_from_named_params(mc, p, _dev())[3]
+    ren = R.build_from_named_params(mc, p, device())[3]
     ud = ren.extract_fields(LO, HI, 70, to_host=False)
     assert torch.isnan(ud).all()
     us, info = ren.extract_fields_sparse(LO, HI, 70, brick=8, margin=0.0)
@@ -260,15 +251,15 @@ def test_refusals_leave_the_renderer_usable(R):
         ren.set_data_parallel(enabled=False)
     # the raw ABI: every refusal comes with RNB_E_INVALID and a message, from the sizing query and from the calls
     packed = ren._pack(False)
-    n = torch.full((1,), 77, dtype=torch.int64, device=_dev())
-    ws = torch.empty(1 << 20, dtype=torch.uint8, device=_dev())
-    vol = torch.empty(33, 33, 33, device=_dev())
+    n = torch.full((1,), 77, dtype=torch.int64, device=device())
+    ws = torch.empty(1 << 20, dtype=torch.uint8, device=device())
+    vol = torch.empty(33, 33, 33, device=device())
     nbytes = C.c_int64()
     bad = [dict(x=(0, 16)), dict(x=(1, 33)), dict(bs=5), dict(bs=0), dict(margin=-1.0), dict(margin=float("nan")),
            dict(res=1)]
     for kw in bad:
         gd, sd = _raw(R, ren, kw.get("res", 33), kw.get("bs", 8), kw.get("margin", 1.0), kw.get("x"))
-        with R.native.on_device(_dev()) as stream:
+        with R.native.on_device(device()) as stream:
             rcs = [lib.rnb_sdf_grid_sparse_workspace_bytes(C.byref(ren.desc), C.byref(gd), C.byref(sd), C.byref(nbytes)),
                    lib.rnb_sdf_grid_sparse_seed(C.byref(ren.desc), R.native.ptr(packed), C.byref(gd), C.byref(sd),
                                                 R.native.ptr(ws), ws.numel(), R.native.ptr(n), stream),
@@ -284,7 +275,7 @@ def test_refusals_leave_the_renderer_usable(R):
     # and the renderer still works
     ud = ren.extract_fields(LO, HI, 33, to_host=False)
     us, info = ren.extract_fields_sparse(LO, HI, 33, brick=4, margin=0.0)
-    act = torch.from_numpy(_sample_mask(info["mask"].cpu().numpy(), 33, 4)).to(_dev())
+    act = torch.from_numpy(_sample_mask(info["mask"].cpu().numpy(), 33, 4)).to(device())
     assert act.any() and torch.equal(us[act], ud[act])
 
 
@@ -299,10 +290,10 @@ def test_workspace_query_is_honest(R, which):
     R.native.check(lib.rnb_sdf_grid_sparse_workspace_bytes(C.byref(ren.desc), C.byref(gd), C.byref(sd), C.byref(nbytes)))
     need = nbytes.value
     assert need >= 10 ** 3 * 4 + 9 ** 3 * 5            # lattice + list + one state byte per brick
-    ws = torch.empty(need, dtype=torch.uint8, device=_dev())
-    n = torch.full((1,), 77, dtype=torch.int64, device=_dev())
-    vol = torch.empty(70, 70, 70, device=_dev())
-    with R.native.on_device(_dev()) as stream:
+    ws = torch.empty(need, dtype=torch.uint8, device=device())
+    n = torch.full((1,), 77, dtype=torch.int64, device=device())
+    vol = torch.empty(70, 70, 70, device=device())
+    with R.native.on_device(device()) as stream:
         rc = lib.rnb_sdf_grid_sparse_seed(C.byref(ren.desc), R.native.ptr(packed), C.byref(gd), C.byref(sd),
                                           R.native.ptr(ws), need - 1, R.native.ptr(n), stream)
         assert rc == -2 and b"workspace too small" in lib.rnb_last_error_string()

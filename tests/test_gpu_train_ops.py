@@ -5,16 +5,9 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests.gpu_support import R  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
 
 
 def _fake_render_out(B, L, seed, edge=False):

@@ -1,15 +1,16 @@
 """rnb_loss_kernel and adam_kernel (csrc/train.hip) called directly, against the fp64 references of tests/train_ops_ref.py,
 at the shapes and values where they can break.  tests/test_train_ops_host.py pins the references and the inputs.
 
-Rule for a value (constants of tests/test_gpu_parity.py; ref32 is the same reference in fp32 on the CPU):
-    |dev - ref64| <= K_OUT * |ref32 - ref64| + FLOOR_OUT * max(1, |ref64|)
+Rule for a value: the output rule of tests/parity.py (ref32 is the same reference in fp32 on the CPU),
 for the loss, each of its three parts, and each gradient tensor by max-abs.  Every case prints its errors as fractions of
 their bounds in lines starting with TRAINOPS (the lines profiles/train_ops_edges.txt is for)."""
 import pytest
 import torch
 
+from tests import parity as P
 from tests import train_ops_ref as T
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device
 
 pytestmark = pytest.mark.gpu
 
@@ -17,35 +18,19 @@ PARTS = ("color_loss", "eikonal_loss", "mask_loss")
 RNB_E_INVALID = -1
 
 
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
 def _rule(tag, name, dev, r64, r32):
     """the value rule on one scalar or (by max-abs) one tensor; returns error / bound"""
-    dev, r64, r32 = dev.detach().cpu().double(), r64.double(), r32.double()
-    assert dev.shape == r64.shape, f"{tag} {name}: shape {tuple(dev.shape)} vs {tuple(r64.shape)}"
-    e_dev = float((dev - r64).abs().max())
-    e_ref = float((r32 - r64).abs().max())
-    bound = K_OUT * e_ref + FLOOR_OUT * max(1.0, float(r64.abs().max()))
+    r64 = r64.double()
+    e_dev, e_ref, bound = P.value_errors(dev, r64, r32)
     print(f"TRAINOPS {tag} {name}: |dev - fp64| {e_dev:.3e}  fp32 ref {e_ref:.3e}  bound {bound:.3e}  ratio {e_dev / bound:.3f}")
-    assert e_dev <= bound, f"{tag} {name}: |dev - fp64| {e_dev:.3e} > {bound:.3e} (fp32 reference: {e_ref:.3e})"
-    return e_dev / bound
+    return P.check_value(f"{tag} {name}", dev, r64, r32)
 
 
 # ----------------------------------------------------------------------------------------------------------------- loss
 def _loss_direct(R, inp, igr_w, mask_w, batch_global=None, eik_share=1.0):
     """rnb_loss_rnb (or rnb_loss_rnb_shard with batch_global) on fp32 inputs; outputs pre-filled with NaN"""
     lib = R.native.load()
-    d = _dev()
+    d = device()
     color, rgb, mask, ws, ge = [t.to(torch.float32).contiguous().to(d) for t in inp]
     L, B, Cd = color.shape
     ge = ge.reshape(1)
@@ -136,7 +121,7 @@ def test_loss_kernel_non_finite_inputs(R, special):
 def test_loss_wrapper_backward_and_layouts(R):
     """R.rnb_loss: an upstream gradient other than 1, a second backward, and the [B, 3] / fp64 / bool / non-contiguous
     inputs, which give the contiguous fp32 call's numbers bit for bit"""
-    d = _dev()
+    d = device()
     B, L, Cd = 65, 2, 3
     inp = T.loss_inputs(B, L, Cd, seed=7)
     color, rgb, mask, ws, ge = inp
@@ -236,7 +221,7 @@ def _check_adam(tag, dev, r64, r32, betas):
     worst = _rule(tag, "p", dev[0], r64[0], r32[0])
     for name, k, beta in (("exp_avg", 1, betas[0]), ("exp_avg_sq", 2, betas[1])):
         e_dev, e_ref = T.rel_l2(dev[k].cpu(), r64[k]), T.rel_l2(r32[k], r64[k])
-        bound = max(K_OUT * e_ref, T.adam_moment_floor(beta))
+        bound = max(P.ref_term(e_ref), T.adam_moment_floor(beta))
         print(f"TRAINOPS {tag} {name}: relL2 {e_dev:.3e}  fp32 ref {e_ref:.3e}  bound {bound:.3e}  ratio {e_dev / bound:.3f}")
         assert e_dev <= bound, f"{tag} {name}: relL2 {e_dev:.3e} > {bound:.3e} (fp32 reference: {e_ref:.3e})"
         worst = max(worst, e_dev / bound)
@@ -249,7 +234,7 @@ def test_adam_step_direct(R, n, setting):
     """three rnb_adam_step calls on buffers 64 floats longer than n: the tails stay untouched, the values follow the
     references; then a step with lr = 0"""
     betas, eps, wd, _ = T.ADAM_SETTINGS[setting]
-    d = _dev()
+    d = device()
     gen = torch.Generator().manual_seed(n)
     p0 = torch.randn(n, generator=gen)
     grads = [(torch.randn(n, generator=gen) + 0.3) * (10.0 if it == 1 else 1e-3) for it in range(3)]
@@ -277,7 +262,7 @@ def test_adam_step_direct(R, n, setting):
 
 
 def test_adam_step_argument_checks(R):
-    d = _dev()
+    d = device()
     bufs = [torch.full((TAIL,), SENTINEL, device=d) for _ in range(4)]
     hp = (1e-3, (0.9, 0.999), 1e-8, 0.0)
     assert _adam_direct(R, bufs[0], bufs[1], bufs[2], bufs[3], 0, *hp, 1) == 0             # n = 0: nothing to do
@@ -289,7 +274,7 @@ def test_adam_step_argument_checks(R):
 
 def _flat_adam(R, p0, setting, lr=T.ADAM_BASE_LR):
     betas, eps, wd, _ = T.ADAM_SETTINGS[setting]
-    ps = [torch.nn.Parameter(r.clone().to(_dev())) for r in p0]
+    ps = [torch.nn.Parameter(r.clone().to(device())) for r in p0]
     return ps, R.FlatAdam(ps, lr=lr, betas=betas, eps=eps, weight_decay=wd)
 
 
@@ -316,7 +301,7 @@ def test_flat_adam_long_run(R, setting):
     (p64, m64, v64), (p32, m32, v32) = T.adam_long_refs(setting)
     p0 = T.adam_params0()
     ps, opt = _flat_adam(R, p0, setting)
-    _flat_steps(opt, ps, T.adam_grad_sequence(steps).to(_dev()), [T.adam_lr(it, steps) for it in range(steps)])
+    _flat_steps(opt, ps, T.adam_grad_sequence(steps).to(device()), [T.adam_lr(it, steps) for it in range(steps)])
     assert opt.step_count == steps
     p, m, v = _flat_state(opt, ps)
     for k, scale in enumerate(T.ADAM_SCALES):
@@ -337,7 +322,7 @@ def test_flat_adam_resume(R):
     """a run resumed from state_dict() continues like the original bit for bit; the same state continues inside
     torch.optim.Adam, and a torch.optim.Adam state continues inside FlatAdam, within the rules of the long run"""
     betas, eps, wd, _ = T.ADAM_SETTINGS[RESUME]
-    d = _dev()
+    d = device()
     steps = 20
     seq = T.adam_grad_sequence(steps)
     seq_dev = seq.to(d)

@@ -16,25 +16,15 @@ import torch
 
 from oracle.bf16_emu import packed_layout
 from tests import train_ops_ref as T
+from tests.gpu_support import R  # noqa: F401
+from tests.gpu_support import device
+from tests.parity import check_value
 from tests.shape_matrix import BY_NAME
-from tests.test_gpu_parity import FLOOR_OUT, K_OUT
 
 pytestmark = pytest.mark.gpu
 
 WN = [BY_NAME[n] for n in T.WN_SHAPES]
 SENTINEL_BITS = 0x7FC0BEEF      # a quiet NaN with a payload no arithmetic produces: "this float was never written"
-
-
-@pytest.fixture(scope="module")
-def R():
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rnb_neus_fork_amd as pkg
-    pkg.native.load()
-    return pkg
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,13 +40,13 @@ def _ref(name, zero_row):
 def _forward(R, shape, p, generic):
     """rnb_weightnorm_fwd of both networks into a sentinel-filled buffer; returns (fp32 buffer on the host, total)"""
     from rnb_neus_fork_amd.fields import _mlp_struct
-    sdf, _, col, _ = R.build_from_named_params(shape.mc, p, _dev())
+    sdf, _, col, _ = R.build_from_named_params(shape.mc, p, device())
     desc = R.model_desc(sdf, col)
     desc.variant = R.native.variant_bits(generic=generic)
     n = R.runtime.packed_floats(desc)
     total = packed_layout(shape.mc)["total"]
     assert n == total if generic else n >= total
-    packed = torch.full((n,), SENTINEL_BITS, dtype=torch.int32, device=_dev()).view(torch.float32)
+    packed = torch.full((n,), SENTINEL_BITS, dtype=torch.int32, device=device()).view(torch.float32)
     sp, cp = _mlp_struct(sdf.lins(), sdf.weight_norm), _mlp_struct(col.lins(), col.weight_norm)
     with R.native.on_device(packed) as stream:
         R.native.check(R.native.load().rnb_weightnorm_fwd(C.byref(desc), C.byref(sp), C.byref(cp), R.native.ptr(packed),
@@ -140,15 +130,6 @@ def test_weightnorm_fwd_default_variant_writes_the_same_fp32_part(R, shape):
     assert torch.equal(_bits(default[:total]), _bits(generic)), f"{shape.name}: the fp32 part differs between the variants"
 
 
-def _rule(tag, dev, g64, g32, floor_scale=None):
-    dev, g64, g32 = dev.double(), g64.double(), g32.double()
-    e_dev, e_ref = float((dev - g64).abs().max()), float((g32 - g64).abs().max())
-    mag = float(g64.abs().max())
-    bound = K_OUT * e_ref + FLOOR_OUT * (max(1.0, mag) if floor_scale is None else floor_scale)
-    assert e_dev <= bound, f"{tag}: |dev - fp64| {e_dev:.3e} > {bound:.3e} (fp32 autograd: {e_ref:.3e})"
-    return e_dev / bound
-
-
 @pytest.mark.parametrize("shape", WN, ids=lambda s: s.name)
 def test_weightnorm_bwd_every_leaf(R, shape):
     mc = shape.mc
@@ -164,7 +145,7 @@ def test_weightnorm_bwd_every_leaf(R, shape):
         grads[dt] = {k: v.grad for k, v in q.items()}
     # the packed gradient as the renderer's backward hands it over (default variant: the mirrors lie behind `total`): c in
     # the real W and bias slots, NaN everywhere else
-    sdf, _, col, _ = R.build_from_named_params(mc, p, _dev())
+    sdf, _, col, _ = R.build_from_named_params(mc, p, device())
     desc = R.model_desc(sdf, col)
     n = R.runtime.packed_floats(desc)
     pgrad = torch.full((n,), float("nan"))
@@ -174,7 +155,7 @@ def test_weightnorm_bwd_every_leaf(R, shape):
         pgrad[e.b_slots] = c[e.b_slots]
         b_slots.setdefault(e.prefix, []).append(e.b_slots)
     assert bool(torch.isnan(pgrad[L["bsdf"] + 1:L["bsdf"] + 32]).all()) and int(torch.isfinite(pgrad).sum()) < total
-    pgrad = pgrad.to(_dev())
+    pgrad = pgrad.to(device())
     worst = ("", 0.0)
     for net, prefix, color in ((sdf, "sdf", False), (col, "color", True)):
         out = R.runtime._leaf_grads(desc, net, pgrad, color=color)
@@ -195,10 +176,10 @@ def test_weightnorm_bwd_every_leaf(R, shape):
             if name.endswith(".weight_v") and pre in T.edited_layers(mc):
                 assert bool((g[T.ROW_G_ZERO] == 0).all()), f"{name}: dv of the g = 0 row is not exactly 0"
                 for row in (T.ROW_V_TINY, T.ROW_V_HUGE):     # dv scales inversely with v: relative to the row's own size
-                    r = _rule(f"{shape.name} {name} row {row}", g[row], g64[row], g32[row],
-                              floor_scale=float(g64[row].abs().max()))
+                    r = check_value(f"{shape.name} {name} row {row}", g[row], g64[row], g32[row],
+                                    floor_scale=float(g64[row].abs().max()))
                     worst = max(worst, (f"{name}[{row}]", r), key=lambda t: t[1])
                     rest[row] = False
-            r = _rule(f"{shape.name} {name}", g[rest], g64[rest], g32[rest])
+            r = check_value(f"{shape.name} {name}", g[rest], g64[rest], g32[rest])
             worst = max(worst, (name, r), key=lambda t: t[1])
     print(f"WEIGHTNORM bwd {shape.name}: worst error / bound {worst[1]:.3f} ({worst[0]})")

@@ -8,13 +8,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.golden_util import POSE_BOUND
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "image_rays_small.npz")
 RNB_E_INVALID, RNB_E_NULL = -1, -4
-# largest element difference between `interpolate_pose` and the reference's recorded pose over the fixture's three
-# ratios, measured on the CPU: 0.0 (bit-equal: same float32 inversions, and the float64 slerp rounds to the same
-# float32 rotation).  The bound is four times that and may not exceed 1e-5.
-POSE_DIFF_MEASURED = 0.0
-POSE_BOUND = 4.0 * POSE_DIFF_MEASURED
 
 
 @pytest.fixture(scope="module")

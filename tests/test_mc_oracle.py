@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_mc_tables as G  # noqa: E402
 from oracle import mc_oracle as M  # noqa: E402
+from tests.mc_shapes import check_on_surface, sphere, torus  # noqa: E402
 
 
 def test_committed_tables_are_the_generated_ones():
@@ -38,47 +39,16 @@ def test_every_case_is_face_consistent_and_covers_its_crossed_edges():
     assert tri[1] == [(0, 8, 3)] and tri[2] == [(0, 1, 9)] and tri[4] == [(1, 2, 10)]   # ... and its first rows
 
 
-def _grid(n, lo=-1.0, hi=1.0):
-    ax = np.linspace(lo, hi, n, dtype=np.float32)
-    return np.meshgrid(ax, ax, ax, indexing="ij")
-
-
-def _sphere(n, r=0.6, c=(0.05, -0.02, 0.03)):
-    x, y, z = _grid(n)
-    return (np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2) - r).astype(np.float32)
-
-
-def _torus(n, R=0.55, r=0.22):
-    x, y, z = _grid(n)
-    return (np.sqrt((np.sqrt(x * x + y * y) - R) ** 2 + z * z) - r).astype(np.float32)
-
-
-def _check_on_surface(u, verts, threshold):
-    """Each vertex lies on ONE grid edge, where the linear interpolant of the two samples equals the threshold."""
-    base = np.floor(verts + 1e-12).astype(np.int64)
-    frac = verts - base
-    axis = np.argmax(frac, axis=1)
-    assert ((frac > 0).sum(axis=1) <= 1).all(), "a vertex moves along one axis only"
-    i0 = tuple(base.T)
-    nb = base.copy()
-    nb[np.arange(len(nb)), axis] += 1
-    nb = np.minimum(nb, np.array(u.shape) - 1)
-    f0, f1 = u[i0].astype(np.float64), u[tuple(nb.T)].astype(np.float64)
-    t = frac[np.arange(len(frac)), axis]
-    val = f0 + t * (f1 - f0)
-    assert np.abs(val - threshold).max() < 1e-6
-
-
 @pytest.mark.parametrize("shape,chi", [("sphere", 2), ("torus", 0)])
 def test_oracle_on_analytic_volumes(shape, chi):
     n = 40
-    u = -(_sphere(n) if shape == "sphere" else _torus(n))          # the reference meshes u = -sdf at threshold 0
+    u = -(sphere(n) if shape == "sphere" else torus(n))          # the reference meshes u = -sdf at threshold 0
     verts, tris = M.marching_cubes(u, 0.0)
     assert len(verts) > 500 and tris.max() == len(verts) - 1
     V, E, F, euler, closed = M.mesh_report(verts, tris)
     assert closed, "every edge must be shared by exactly two triangles, traversed in opposite directions"
     assert V == len(verts) and euler == chi
-    _check_on_surface(u, verts, 0.0)
+    check_on_surface(u, verts, 0.0)
     # orientation: the right-hand normal points towards smaller u = towards growing SDF = out of the object
     p = verts[tris.astype(np.int64)]
     nrm = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
@@ -106,7 +76,7 @@ def test_oracle_watertight_on_random_volumes():
     verts, tris = M.marching_cubes(u, 0.0)
     _, _, _, _, closed = M.mesh_report(verts, tris)
     assert closed
-    _check_on_surface(u, verts, 0.0)
+    check_on_surface(u, verts, 0.0)
     # non-cubic grid and a non-zero threshold on a ramp: one plane of quads
     x = np.broadcast_to(np.arange(5, dtype=np.float32)[:, None, None], (5, 4, 3)).copy()
     v, t = M.marching_cubes(x, 1.25)

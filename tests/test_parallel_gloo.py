@@ -1,7 +1,6 @@
 """The N>1 path on CPU: world_size-2 gloo processes exercise ray sharding and the flat-gradient
 all-reduce helper used by the renderer's backward (RCCL on the GPU box)."""
 import os
-import socket
 
 import pytest
 import torch
@@ -9,12 +8,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import rnb_oracle as O
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+from tests.gpu_support import free_port
 
 
 def _worker(rank, world, port, q):
@@ -68,7 +62,7 @@ def _worker(rank, world, port, q):
 def _run(target, world, *extra):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=target, args=(r, world, port, q) + extra) for r in range(world)]
     for p in procs:
         p.start()

@@ -10,8 +10,7 @@ import torch
 import rnb_neus_fork_amd as R
 from oracle import rnb_oracle as O
 from tests import ray_matrix as M
-from tests.shape_matrix import BY_NAME as SHAPE_BY_NAME, live_params
-from tests.test_shape_paths import desc_of
+from tests.shape_matrix import BY_NAME as SHAPE_BY_NAME, desc_of, live_params
 
 W32 = SHAPE_BY_NAME["w32"]
 SHAPES = [W32, SHAPE_BY_NAME["default_64x64"]]

@@ -10,20 +10,8 @@ import torch
 import rnb_neus_fork_amd as R
 from oracle import rnb_oracle as O
 from oracle.bf16_emu import packed_layout
-from tests.shape_matrix import SHAPES, live_params, oracle_points, pe_columns, points, step_batch, zero_blocks
-
-
-def desc_of(mc, **variant):
-    """rnb_model_desc of `mc` as the drop-in classes write it (fields.model_desc), with the given variant bits."""
-    s, c = mc.sdf, mc.color
-    sdf = R.SDFNetwork(d_in=3, d_out=s.d_out, d_hidden=s.d_hidden, n_layers=s.n_layers, skip_in=s.skip_in,
-                       multires=s.multires, bias=s.bias, scale=s.scale, weight_norm=s.weight_norm)
-    col = R.RenderingNetwork(d_feature=c.d_feature, mode=c.mode, d_in=c.d_in, d_out=c.d_out, d_hidden=c.d_hidden,
-                             n_layers=c.n_layers, weight_norm=c.weight_norm, multires_view=c.multires_view,
-                             squeeze_out=c.squeeze_out)
-    d = R.model_desc(sdf, col)
-    d.variant = R.native.variant_bits(**variant)
-    return d
+from tests.gpu_support import assert_has_surface
+from tests.shape_matrix import SHAPES, desc_of, live_params, oracle_points, pe_columns, points, step_batch, zero_blocks
 
 
 def _packed_floats(mc, **variant):
@@ -69,7 +57,7 @@ def test_shape_takes_the_tabled_path(shape):
 def test_shape_state_is_live_and_the_oracle_resolves_it(shape):
     """live_params: no zero block, PE columns live, variance in [0.3, 0.4]; the fp32 oracle within a few ulps of the fp64
     one on a few points (so the calibrated bounds of the GPU tests are not set by a degenerate yardstick); and the step
-    batch renders a surface (tests/test_gpu_parity.py _assert_has_surface, on the oracle's own sampling)."""
+    batch renders a surface (tests/gpu_support.py assert_has_surface, on the oracle's own sampling)."""
     mc = shape.mc
     p = live_params(mc, shape.seed)
     assert zero_blocks(p, mc) == [], shape.name
@@ -87,9 +75,8 @@ def test_shape_state_is_live_and_the_oracle_resolves_it(shape):
         assert a.shape == b.shape
         torch.testing.assert_close(a.double(), b, rtol=1e-5, atol=1e-5, msg=lambda m: f"{shape.name} {name}: {m}")
     if shape.render:
-        from tests.test_gpu_parity import _assert_has_surface
         b = step_batch()
         with torch.no_grad():
             out = O.render_rnb(p, mc, b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0,
                                t_rand=b["t_rand"])
-        _assert_has_surface(out)
+        assert_has_surface(out)

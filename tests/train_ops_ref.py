@@ -4,7 +4,7 @@
 A plain module (no device imports) shared by tests/test_train_ops_host.py (host: the references against the oracle and
 torch, and every condition the device tests place on their inputs), tests/test_gpu_train_ops_edges.py and
 tests/test_gpu_weightnorm.py.  Every reference takes a `dtype`: float64 is the yardstick, float32 is "what a plain fp32
-implementation of the same formula gives", whose distance from fp64 calibrates the bounds (tests/test_gpu_parity.py)."""
+implementation of the same formula gives", whose distance from fp64 calibrates the bounds (tests/parity.py)."""
 from __future__ import annotations
 
 import functools
@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle.bf16_emu import RS2, packed_layout
+from tests.parity import rel_l2  # noqa: F401  (the tests take it as train_ops_ref.rel_l2)
 
 # ----------------------------------------------------------------------------------------------------------------- loss
 # The clip bounds of `weight_sum.clip(1e-3, 1.0 - 1e-3)` as an fp32 run sees them.  float32(1) - float32(1e-3) ==
@@ -235,11 +236,6 @@ def adam_moment_floor(beta):
     """The kernel forms 1.f - beta from the fp32 beta (2^-24 relative off the double 1 - beta, divided by 1 - beta): an
     EMA built on it differs from the ideal one by up to 2^-24 / (1 - beta), relative.  Four times that."""
     return 4.0 * 2.0 ** -24 / (1.0 - beta)
-
-
-def rel_l2(a, ref):
-    a, ref = a.double(), ref.double()
-    return float((a - ref).norm() / ref.norm().clamp_min(1e-300))
 
 
 # ---------------------------------------------------------------------------------------------------------- weight norm

@@ -1,7 +1,7 @@
 import sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-import tests.test_gpu_convergence as T
+import tests.convergence_run as T
 import rnb_neus_fork_amd as R
 z = np.load(os.path.join(T.GOLDEN, "convergence_ref.npz"), allow_pickle=False)
 ref, alt = z["losses"], z["losses_alt"]
@@ -15,7 +15,7 @@ RUNS = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 for variant in ({}, {"x2h": False}, {"deterministic": True}, {"bf16": True}, {"bf16": True, "deterministic": True}):
     ps, pos, ml = [], [], []
     for i in range(RUNS):
-        losses, psnr, mask_l1 = T._train(R, z, variant)
+        losses, psnr, mask_l1 = T.train(R, z, variant)
         dec = losses.reshape(10, -1).mean(axis=1)
         ps.append(psnr); ml.append(mask_l1)
         pos.append(float(np.max(np.maximum(lo - dec, dec - hi) / dec_ref)))
