@@ -542,6 +542,31 @@ int rnb_gen_rays_grid_from_maps(const float* intrinsics_inv, const float* pose, 
                                 const rnb_source_maps_t* source, int32_t light, float* data, float* true_rgb,
                                 float* true_rgb_warmup, float* lights_dir, float* near, float* far, rnb_stream_t stream);
 
+/* Camera adjoint of rnb_gen_rays_at_view / rnb_gen_rays_at_view_from_maps: d loss / d pose and d loss / d intrinsics_inv
+ * from the adjoints of the rays, near / far and (source mode) the per-ray lights those calls produced, one launch.
+ *   intrinsics_inv, pose [4,4]: the ones the forward used; pixels_x, pixels_y [B] int64: the forward's;
+ *   lights_dir [n_lights,B,3]: the forward's output of the source-mode call (lights_dir = pose[:3,:3] l_cam), or NULL:
+ *            stack-mode lights are gathered, not rotated, and have no camera adjoint;
+ *   rays_o_bar, rays_d_bar [B,3], lights_bar [n_lights,B,3], near_bar, far_bar [B]: d loss / d output, each NULL = zero.
+ * Per ray, recomputed from its pixel (x, y) in the forward's arithmetic:
+ *   p = Kinv[:3,:3] (x, y, 1), n = |p|, v = p / n, d = R v, o = t, a = d.d, mid = -(o.d) / a  (near / far = mid -+ 1)
+ *   m_bar = near_bar + far_bar;   o_bar += -m_bar d / a;   d_bar += -m_bar o / a + 2 m_bar (o.d) d / a^2
+ *   pose_bar[:3,3]  = sum_b o_bar_b
+ *   pose_bar[:3,:3] = sum_b d_bar_b v_b^T + sum_{l,b} lights_bar_{l,b} (R^T lights_dir_{l,b})^T
+ *   v_bar = R^T d_bar;   p_bar = (v_bar - v (v.v_bar)) / n;   intrinsics_inv_bar[:3,:3] = sum_b p_bar_b (x, y, 1)^T
+ * (R^T lights_dir recovers l_cam for an orthonormal R.)  Outputs: pose_bar [4,4]; intrinsics_inv_bar [4,4] or NULL (not
+ * wanted); their last row, and intrinsics_inv_bar's last column, are written as 0: all 16 entries are defined.
+ * The sums run in a fixed order without floating-point atomics (one workgroup: lane-local sums in ray order, a shuffle
+ * butterfly, the waves in wave order), so the result's bits depend on the inputs only.  Gradients are those of the rays
+ * given: under data parallelism they are shard-local like every other input gradient (no collective).
+ * RNB_E_NULL / RNB_E_INVALID before any launch: a NULL required pointer (intrinsics_inv, pose, pixels, pose_bar),
+ * lights_bar without lights_dir, B < 1, n_lights outside 0..8 (1..8 with lights_dir). */
+int rnb_gen_rays_camera_bwd(const float* intrinsics_inv, const float* pose, const int64_t* pixels_x,
+                            const int64_t* pixels_y, int64_t B, const float* lights_dir, int32_t n_lights,
+                            const float* rays_o_bar, const float* rays_d_bar, const float* lights_bar,
+                            const float* near_bar, const float* far_bar, float* pose_bar, float* intrinsics_inv_bar,
+                            rnb_stream_t stream);
+
 /* The loss of train_rnb (exp_runner.py:241-258) and its gradients with respect to the renderer outputs, one
  * launch:  loss = sum|(color_fine - true_rgb) * mask| / ((sum(mask) + 1e-5) * n_lights)
  *               + igr_weight * gradient_error

@@ -20,10 +20,11 @@ from .losses import rnb_loss  # noqa: F401
 from .optim import FlatAdam  # noqa: F401
 from .raygen import DeviceRays, cameras_from_projections  # noqa: F401
 from .mcubes import marching_cubes  # noqa: F401
+from .camera_refine import CameraRefinement  # noqa: F401
 
 __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetwork", "NeRF", "get_embedder",
            "native", "build_from_named_params", "rnb_loss", "FlatAdam", "DeviceRays", "cameras_from_projections",
-           "marching_cubes"]
+           "marching_cubes", "CameraRefinement"]
 
 
 def build_from_named_params(mc, params, device):

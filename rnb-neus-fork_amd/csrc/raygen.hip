@@ -11,6 +11,7 @@ namespace rnb {
 // The ray arithmetic every kernel of this file shares, so that stack mode and source mode give the same bits.
 // p = Kinv[:3,:3] (x, y, 1) (dataset.py:365-367; same left-to-right accumulation as a 3-term dot product),
 // rays_v = R p / ||p||, rays_o = t (dataset.py:369-373)
+// (camera_adjoint_kernel below repeats these lines operand by operand, because it also needs v and ||p||: keep the two in step)
 __device__ __forceinline__ void ray_through(const float* kinv, const float* pose, float fx, float fy, float o[3], float d[3]) {
   float p[3];
 #pragma unroll
@@ -292,9 +293,160 @@ static int check_source_maps(const char* who, const rnb_source_maps_t* src) {
   return RNB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Camera adjoint: d loss / d pose and d loss / d intrinsics_inv from the adjoints of what ray_through + store_ray (and,
+// in source mode, the light rotation of source_targets) made of them.  Per ray, recomputed from its pixel:
+//   p = Kinv[:3,:3] (x, y, 1), n = |p|, v = p / n, d = R v, o = t, a = d.d, mid = -(o.d) / a, near / far = mid -+ 1
+//   m_bar = near_bar + far_bar;  o_bar += -m_bar d / a;  d_bar += -m_bar o / a + 2 m_bar (o.d) d / a^2
+//   pose_bar[:3,3] = sum_b o_bar;  pose_bar[:3,:3] = sum_b d_bar v^T + sum_{l,b} l_bar (R^T l)^T   (lights = R l_cam)
+//   v_bar = R^T d_bar;  p_bar = (v_bar - v (v.v_bar)) / n;  intrinsics_inv_bar[:3,:3] = sum_b p_bar (x, y, 1)^T
+// One workgroup: every lane sums its rays b = lane, lane + 256, ... in that order (the ray's own terms, then its lights
+// in light order), a shuffle butterfly per wave, the four waves combined through LDS in wave order.  No atomics: the
+// bits depend on the inputs only.
+constexpr int kCamAdjThreads = 256;
+constexpr int kCamAdjTerms = 21;   // pose_bar[:3,:3] (9) | pose_bar[:3,3] (3) | intrinsics_inv_bar[:3,:3] (9)
+
+struct CameraAdjArgs {
+  const float* kinv;        // [4,4]
+  const float* pose;        // [4,4]
+  const int64_t* px;        // [B]
+  const int64_t* py;        // [B]
+  int64_t B;
+  const float* lights;      // [L,B,3] the forward's lights_dir, or NULL
+  int L;
+  const float* o_bar;       // [B,3] or NULL
+  const float* d_bar;       // [B,3] or NULL
+  const float* lights_bar;  // [L,B,3] or NULL
+  const float* near_bar;    // [B] or NULL
+  const float* far_bar;     // [B] or NULL
+  float* pose_bar;          // [4,4]
+  float* kinv_bar;          // [4,4] or NULL
+};
+
+__device__ __forceinline__ float cam_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(kCamAdjThreads) void camera_adjoint_kernel(CameraAdjArgs g) {
+  __shared__ float red[kCamAdjThreads / 64][kCamAdjTerms];
+  float acc[kCamAdjTerms];
+#pragma unroll
+  for (int k = 0; k < kCamAdjTerms; ++k) acc[k] = 0.f;
+  float R[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) R[r][c] = g.pose[r * 4 + c];
+  const bool with_lights = g.lights != nullptr && g.lights_bar != nullptr;
+  for (int64_t b = threadIdx.x; b < g.B; b += kCamAdjThreads) {
+    const float q[3] = {(float)g.px[b], (float)g.py[b], 1.f};
+    float p[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) p[r] = g.kinv[r * 4 + 0] * q[0] + g.kinv[r * 4 + 1] * q[1] + g.kinv[r * 4 + 2] * 1.f;
+    const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+    const float v[3] = {p[0] / nrm, p[1] / nrm, p[2] / nrm};
+    float d[3], o[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      d[r] = R[r][0] * v[0] + R[r][1] * v[1] + R[r][2] * v[2];
+      o[r] = g.pose[r * 4 + 3];
+    }
+    float ob[3] = {0.f, 0.f, 0.f}, db[3] = {0.f, 0.f, 0.f};
+    if (g.o_bar)
+      for (int r = 0; r < 3; ++r) ob[r] = g.o_bar[b * 3 + r];
+    if (g.d_bar)
+      for (int r = 0; r < 3; ++r) db[r] = g.d_bar[b * 3 + r];
+    const float mb = (g.near_bar ? g.near_bar[b] : 0.f) + (g.far_bar ? g.far_bar[b] : 0.f);
+    if (g.near_bar || g.far_bar) {
+      const float a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+      const float od = o[0] * d[0] + o[1] * d[1] + o[2] * d[2];
+      const float s = mb / a;
+      const float t = 2.f * s * od / a;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        ob[r] -= s * d[r];
+        db[r] += t * d[r] - s * o[r];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[r * 3 + c] += db[r] * v[c];
+      acc[9 + r] += ob[r];
+    }
+    if (g.kinv_bar) {
+      float vb[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) vb[c] = R[0][c] * db[0] + R[1][c] * db[1] + R[2][c] * db[2];
+      const float vv = v[0] * vb[0] + v[1] * vb[1] + v[2] * vb[2];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const float pb = (vb[r] - v[r] * vv) / nrm;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[12 + r * 3 + c] += pb * q[c];
+      }
+    }
+    if (with_lights) {
+      for (int l = 0; l < g.L; ++l) {
+        const int64_t at = ((int64_t)l * g.B + b) * 3;
+        const float lw[3] = {g.lights[at], g.lights[at + 1], g.lights[at + 2]};
+        const float lb[3] = {g.lights_bar[at], g.lights_bar[at + 1], g.lights_bar[at + 2]};
+        float lc[3];   // R^T l: the camera-space light the forward rotated
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lc[c] = R[0][c] * lw[0] + R[1][c] * lw[1] + R[2][c] * lw[2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[r * 3 + c] += lb[r] * lc[c];
+      }
+    }
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kCamAdjTerms; ++k) {
+    const float s = cam_wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < kCamAdjTerms) {
+    const float s = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    if (k < 9) g.pose_bar[(k / 3) * 4 + k % 3] = s;
+    else if (k < 12) g.pose_bar[(k - 9) * 4 + 3] = s;
+    else if (g.kinv_bar) g.kinv_bar[((k - 12) / 3) * 4 + (k - 12) % 3] = s;
+  } else if (k < kCamAdjTerms + 4) {
+    g.pose_bar[12 + (k - kCamAdjTerms)] = 0.f;                      // the pose's last row
+  } else if (k < kCamAdjTerms + 11 && g.kinv_bar) {
+    const int z = k - (kCamAdjTerms + 4);                           // intrinsics_inv's last column (3) and last row (4)
+    g.kinv_bar[z < 3 ? z * 4 + 3 : 12 + (z - 3)] = 0.f;
+  }
+}
+
 }  // namespace rnb
 
 #define RNB_API extern "C" __attribute__((visibility("default")))
+
+RNB_API int rnb_gen_rays_camera_bwd(const float* intrinsics_inv, const float* pose, const int64_t* pixels_x,
+                                    const int64_t* pixels_y, int64_t B, const float* lights_dir, int32_t n_lights,
+                                    const float* rays_o_bar, const float* rays_d_bar, const float* lights_bar,
+                                    const float* near_bar, const float* far_bar, float* pose_bar, float* intrinsics_inv_bar,
+                                    rnb_stream_t stream) {
+  using namespace rnb;
+  if (!intrinsics_inv || !pose || !pixels_x || !pixels_y || !pose_bar)
+    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_camera_bwd: NULL pointer");
+  if (lights_bar && !lights_dir) RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_camera_bwd: lights_bar without the forward's lights_dir");
+  if (B < 1) RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_camera_bwd: bad shape (B %lld)", (long long)B);
+  if (n_lights < 0 || n_lights > kMaxRenderLights || (lights_dir && n_lights < 1))
+    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_camera_bwd: n_lights %d outside %d..kMaxRenderLights (%d)", n_lights,
+             lights_dir ? 1 : 0, kMaxRenderLights);
+  CameraAdjArgs g{intrinsics_inv, pose, pixels_x, pixels_y, B, lights_dir, n_lights, rays_o_bar, rays_d_bar, lights_bar,
+                  near_bar, far_bar, pose_bar, intrinsics_inv_bar};
+  hipLaunchKernelGGL(camera_adjoint_kernel, dim3(1), dim3(kCamAdjThreads), 0, (hipStream_t)stream, g);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
 
 RNB_API int rnb_gen_rays_at_view(const float* intrinsics_inv, const float* pose, const float* images,
                                  const float* images_warmup, const float* mask, int32_t mask_channels,

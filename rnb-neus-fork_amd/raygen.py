@@ -29,6 +29,60 @@ import torch
 from . import native
 
 
+class _CameraRays(torch.autograd.Function):
+    """`DeviceRays.sample` with a camera that requires grad: the forward is the one ray launch, the backward is
+    `rnb_gen_rays_camera_bwd` (one launch).  rays_o, rays_d, near, far and, in source mode, the per-ray lights (the kernel
+    rotates them with the pose) are differentiable in `pose` and `intrinsics_inv`; mask and colours are not, and
+    stack-mode lights are gathers."""
+
+    @staticmethod
+    def forward(ctx, rays, v, px, py, warmup, pose, intrinsics_inv):
+        pose_c, kinv_c = _camera_matrix(pose, rays.device), _camera_matrix(intrinsics_inv, rays.device)
+        data, rgb, rgb_wu, lights, near, far = rays._launch(v, px, py, not warmup, warmup, not warmup, True, pose_c, kinv_c)
+        rays_o, rays_d, mask, true_rgb = data[:, :3], data[:, 3:6], data[:, 6:7], rgb_wu if warmup else rgb
+        rotated = lights is not None and rays.source_mode
+        ctx.save_for_backward(pose_c, kinv_c, px, py, lights if rotated else None)
+        ctx.n_lights = rays.n_lights if rotated else 0
+        ctx.set_materialize_grads(False)     # an output the step does not use sends no adjoint: NULL at the entry point
+        ctx.mark_non_differentiable(*(t for t in (mask, true_rgb, None if rotated else lights) if t is not None))
+        return rays_o, rays_d, near, far, mask, true_rgb, lights
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, o_bar, d_bar, near_bar, far_bar, _mask_bar, _rgb_bar, lights_bar):
+        pose, kinv, px, py, lights = ctx.saved_tensors
+        B = px.numel()
+
+        def adj(t, shape):
+            return None if t is None else t.to(torch.float32).reshape(shape).contiguous()
+
+        o_bar, d_bar = adj(o_bar, (B, 3)), adj(d_bar, (B, 3))
+        near_bar, far_bar = adj(near_bar, (B,)), adj(far_bar, (B,))
+        lights_bar = adj(lights_bar, (ctx.n_lights, B, 3)) if lights is not None else None
+        pose_bar = torch.empty(4, 4, dtype=torch.float32, device=pose.device)
+        kinv_bar = torch.empty_like(pose_bar) if ctx.needs_input_grad[6] else None
+        native.same_device(pose, kinv, px, py, lights, o_bar, d_bar, near_bar, far_bar, lights_bar)
+        with native.on_device(pose) as stream:
+            native.check(native.load().rnb_gen_rays_camera_bwd(
+                native.ptr(kinv), native.ptr(pose), native.ptr(px), native.ptr(py), B, native.ptr(lights), ctx.n_lights,
+                native.ptr(o_bar), native.ptr(d_bar), native.ptr(lights_bar), native.ptr(near_bar), native.ptr(far_bar),
+                native.ptr(pose_bar), native.ptr(kinv_bar), stream))
+        return None, None, None, None, None, pose_bar if ctx.needs_input_grad[5] else None, kinv_bar
+
+
+def _camera_matrix(t, device):
+    """A [4,4] camera matrix as the kernels read it: detached float32, contiguous, on `device`."""
+    t = torch.as_tensor(t).detach().to(device=device, dtype=torch.float32)
+    if tuple(t.shape) != (4, 4):
+        raise ValueError(f"a camera matrix is [4, 4], not {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _rotate(lights, rot):
+    """rot [3,3] applied to the last axis of `lights` (a broadcast product and a 3-term sum: exact for the identity)."""
+    return (lights.unsqueeze(-2) * rot).sum(-1)
+
+
 class DeviceRays:
     def __init__(self, images, images_warmup, masks, light_directions, light_directions_warmup, intrinsics_all_inv,
                  pose_all, device):
@@ -53,6 +107,7 @@ class DeviceRays:
         if self.masks.shape[:3] != (self.n_images, self.H, self.W):
             raise ValueError(f"masks {tuple(self.masks.shape)} do not match images {tuple(self.images.shape)}")
         self.normals = self.albedos = None                          # source mode only (from_source_maps)
+        self._refinement = None                                     # set_refinement
 
     @classmethod
     def from_dataset(cls, dataset, device="cuda"):
@@ -103,6 +158,7 @@ class DeviceRays:
         self.n_images, self.n_lights, self.H, self.W = V, local.shape[0], H, W
         self._local_lights, self._warmup_lights_cam = local.astype(np.float32), warm.astype(np.float32)
         self._source_structs = {}
+        self._refinement = None
         return self
 
     @property
@@ -170,7 +226,9 @@ class DeviceRays:
                 torch._assert_async(ok.all())
         return pixels_x, pixels_y
 
-    def _launch(self, img_idx, pixels_x, pixels_y, want_rgb, want_warmup, want_lights, want_near_far):
+    def _launch(self, img_idx, pixels_x, pixels_y, want_rgb, want_warmup, want_lights, want_near_far, pose=None,
+                intrinsics_inv=None):
+        """`pose`, `intrinsics_inv`: [4,4] float32 contiguous device tensors used instead of the view's stored ones."""
         B = pixels_x.numel()
         L = self.n_lights
         v = int(img_idx)
@@ -183,10 +241,12 @@ class DeviceRays:
         lights = torch.empty(L, B, 3, **f32) if want_lights else None
         near = torch.empty(B, 1, **f32) if want_near_far else None
         far = torch.empty(B, 1, **f32) if want_near_far else None
+        pose = self.pose_all[v] if pose is None else pose
+        intrinsics_inv = self.intrinsics_all_inv[v] if intrinsics_inv is None else intrinsics_inv
         if self.source_mode:
             with native.on_device(data) as stream:
                 native.check(native.load().rnb_gen_rays_at_view_from_maps(
-                    native.ptr(self.intrinsics_all_inv[v]), native.ptr(self.pose_all[v]), C.byref(self._source(v)),
+                    native.ptr(intrinsics_inv), native.ptr(pose), C.byref(self._source(v)),
                     native.ptr(pixels_x), native.ptr(pixels_y), B, native.ptr(data), native.ptr(rgb), native.ptr(rgb_wu),
                     native.ptr(lights), native.ptr(near), native.ptr(far), stream))
             return data, rgb, rgb_wu, lights, near, far
@@ -196,7 +256,7 @@ class DeviceRays:
             raise ValueError("DeviceRays was built without light_directions")
         with native.on_device(data) as stream:
             native.check(native.load().rnb_gen_rays_at_view(
-                native.ptr(self.intrinsics_all_inv[v]), native.ptr(self.pose_all[v]),
+                native.ptr(intrinsics_inv), native.ptr(pose),
                 native.ptr(self.images[v]) if want_rgb else None,
                 native.ptr(self.images_warmup[v]) if want_warmup else None,
                 native.ptr(self.masks[v]), self.masks.shape[-1],
@@ -228,19 +288,81 @@ class DeviceRays:
         return self._launch(img_idx, px, py, False, False, True, False)[3]
 
     # ------------------------------------------------------------------ everything for one step, one launch
-    def sample(self, img_idx, batch_size, warmup=False, pixels_x=None, pixels_y=None):
+    def set_refinement(self, refinement):
+        """A `CameraRefinement` (or None to remove it): `sample` then runs on `refinement.camera(v, ...)` of the view and
+        is differentiable in the module's parameters; `view_rays` and `render_image` use the same cameras, detached.  The
+        world-space lights this object holds were rotated by the stored poses, so they turn with the camera: the warm-up
+        lights [L,3] and the gathered stack-mode lights are rotated by Exp(w_v) with a torch op (differentiable by torch),
+        source-mode lights by the kernel with the refined pose.
+        Everything else stays on the stored cameras and the unrotated lights: the reference's own methods
+        `ps_gen_random_rays_at_view_on_all_lights` and `light_directions_at`, `materialize`, and `pose_between` /
+        `gen_rays_between` (the interpolation runs between stored poses; `gen_rays_at` goes through `view_rays` and is
+        refined).  `view_rays(pose=...)` without `img_idx` uses view 0's intrinsics as the reference does, refined when
+        the module refines the focal length.  Do not mix the two groups in one step."""
+        if refinement is not None and refinement.n_views != self.n_images:
+            raise ValueError(f"the refinement holds {refinement.n_views} views, this DeviceRays {self.n_images}")
+        self._refinement = refinement
+
+    def _camera(self, v, pose=None, intrinsics_inv=None):
+        """(pose, intrinsics_inv, rot) `sample` and `view_rays` run view `v` on: each matrix None where the stored one
+        holds, `rot` = Exp(w_v) where the lights this object holds have to follow the camera (else None).  A `pose` or
+        `intrinsics_inv` given by the caller is used as it is."""
+        ref = self._refinement
+        if ref is None or (pose is not None and intrinsics_inv is not None):
+            return pose, intrinsics_inv, None
+        r_pose, r_kinv = ref.camera(v, self.pose_all[v], self.intrinsics_all_inv[v])
+        if ref.focal_log_scale is None:
+            r_kinv = None
+        rot = ref.rotation(v) if pose is None else None
+        return r_pose if pose is None else pose, r_kinv if intrinsics_inv is None else intrinsics_inv, rot
+
+    def sample(self, img_idx, batch_size, warmup=False, pixels_x=None, pixels_y=None, pose=None, intrinsics_inv=None):
         """Inputs of one `train_rnb` step (exp_runner.py:174-220) as a dict: rays_o, rays_d, near, far, mask,
-        true_rgb, lights_dir (shaped for `render_rnb` / `render_rnb_warmup`), pixels_x, pixels_y."""
+        true_rgb, lights_dir (shaped for `render_rnb` / `render_rnb_warmup`), pixels_x, pixels_y.
+        `pose`, `intrinsics_inv`: [4,4] device tensors to use instead of the view's stored camera (or of the one
+        `set_refinement` composes).  Where a camera matrix requires grad, rays_o, rays_d, near, far and (source mode) the
+        per-ray lights_dir carry a graph to it whose backward is one native launch (`rnb_gen_rays_camera_bwd`); mask,
+        true_rgb and the pixels do not.  The gradients are those of this call's rays (shard-local under data parallelism).
+        Otherwise the launch and the returned views are the same as without the two arguments.  A matrix that requires
+        grad must be a float32 tensor on this object's device (its gradient is made there).  `pose[:3,:3]` is taken to be
+        a rotation: the source-mode light adjoint recovers the camera-space light as R^T l, so a scaled or sheared pose
+        gives rays and lights as computed but a wrong `pose.grad`."""
         px, py = self._pixels(batch_size, pixels_x, pixels_y)
-        data, rgb, rgb_wu, lights, near, far = self._launch(img_idx, px, py, not warmup, warmup, not warmup, True)
-        if warmup:
-            if self.light_directions_warmup is None:
-                raise ValueError("DeviceRays was built without light_directions_warmup")
-            lights_dir = self.light_directions_warmup[int(img_idx)].reshape(self.n_lights, 1, 1, 3)
+        v = int(img_idx)
+        if not 0 <= v < self.n_images:     # before `_camera` indexes the stacks (a negative index would wrap there)
+            raise IndexError(f"img_idx {v} out of range (n_images {self.n_images})")
+        if warmup and self.light_directions_warmup is None:
+            raise ValueError("DeviceRays was built without light_directions_warmup")
+        pose, intrinsics_inv, rot = self._camera(v, pose, intrinsics_inv)
+        need_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                    for t in (pose, intrinsics_inv))
+        if need_grad:
+            for name, t in (("pose", pose), ("intrinsics_inv", intrinsics_inv)):
+                if isinstance(t, torch.Tensor) and t.requires_grad and (t.device != self.device or t.dtype != torch.float32):
+                    raise ValueError(f"sample: {name} requires grad, so it must be a float32 tensor on {self.device} "
+                                     f"(got {t.dtype} on {t.device})")
+            rays_o, rays_d, near, far, mask, true_rgb, lights = _CameraRays.apply(
+                self, v, px, py, warmup, self.pose_all[v] if pose is None else pose,
+                self.intrinsics_all_inv[v] if intrinsics_inv is None else intrinsics_inv)
         else:
+            data, rgb, rgb_wu, lights, near, far = self._launch(
+                v, px, py, not warmup, warmup, not warmup, True,
+                None if pose is None else _camera_matrix(pose, self.device),
+                None if intrinsics_inv is None else _camera_matrix(intrinsics_inv, self.device))
+            rays_o, rays_d, mask, true_rgb = data[:, :3], data[:, 3:6], data[:, 6:7], rgb_wu if warmup else rgb
+        if rot is not None and not need_grad:
+            rot = rot.detach()
+        if warmup:
+            lights_dir = self.light_directions_warmup[v]
+            if rot is not None:
+                lights_dir = _rotate(lights_dir, rot)
+            lights_dir = lights_dir.reshape(self.n_lights, 1, 1, 3)
+        else:
+            if rot is not None and not self.source_mode:
+                lights = _rotate(lights, rot)
             lights_dir = lights.reshape(self.n_lights, batch_size, 1, 3)
-        return {"rays_o": data[:, :3], "rays_d": data[:, 3:6], "mask": data[:, 6:7], "near": near, "far": far,
-                "true_rgb": rgb_wu if warmup else rgb, "lights_dir": lights_dir, "pixels_x": px, "pixels_y": py}
+        return {"rays_o": rays_o, "rays_d": rays_d, "mask": mask, "near": near, "far": far,
+                "true_rgb": true_rgb, "lights_dir": lights_dir, "pixels_x": px, "pixels_y": py}
 
     # ------------------------------------------------------------------ whole views, one launch per call
     def _grid(self, resolution_level):
@@ -279,10 +401,15 @@ class DeviceRays:
         if not -1 <= li < L or (light is not None and li < 0):
             raise IndexError(f"light {light} out of range (n_lights {L})")
         Lo = L if li < 0 else 1
+        # the view's camera: the stored one, or the one `set_refinement` composes (forward only: detached)
+        with torch.no_grad():
+            view_pose, kinv, rot = self._camera(v)
+        view_pose = self.pose_all[v] if view_pose is None else _camera_matrix(view_pose, self.device)
+        kinv = self.intrinsics_all_inv[v] if kinv is None else _camera_matrix(kinv, self.device)
         if pose is None:
             if not gather:
                 raise ValueError("view_rays needs img_idx or pose")
-            pose_t = self.pose_all[v]
+            pose_t = view_pose
         else:
             pose_t = torch.as_tensor(pose).to(device=self.device, dtype=torch.float32).reshape(4, 4).contiguous()
         source = gather and self.source_mode
@@ -298,13 +425,13 @@ class DeviceRays:
         with native.on_device(data) as stream:
             if source:
                 native.check(native.load().rnb_gen_rays_grid_from_maps(
-                    native.ptr(self.intrinsics_all_inv[v]), native.ptr(pose_t), native.ptr(self.pose_all[v]), native.ptr(tx),
+                    native.ptr(kinv), native.ptr(pose_t), native.ptr(view_pose), native.ptr(tx),
                     native.ptr(ty), Wl, Hl, first, n, C.byref(self._source(v)), li, native.ptr(data),
                     None if warmup else native.ptr(rgb), native.ptr(rgb) if warmup else None, native.ptr(lights),
                     native.ptr(near), native.ptr(far), stream))
             else:
                 native.check(native.load().rnb_gen_rays_grid(
-                    native.ptr(self.intrinsics_all_inv[v]), native.ptr(pose_t), native.ptr(tx), native.ptr(ty), Wl, Hl, first,
+                    native.ptr(kinv), native.ptr(pose_t), native.ptr(tx), native.ptr(ty), Wl, Hl, first,
                     n, native.ptr(images[v]) if gather and not warmup else None,
                     native.ptr(images[v]) if gather and warmup else None,
                     native.ptr(self.masks[v]) if gather else None, self.masks.shape[-1],
@@ -316,8 +443,11 @@ class DeviceRays:
             if self.light_directions_warmup is None:
                 raise ValueError("DeviceRays was built without light_directions_warmup")
             lw = self.light_directions_warmup[v]
+            lw = lw if rot is None else _rotate(lw, rot)
             lights_dir = (lw if li < 0 else lw[li:li + 1]).reshape(Lo, 1, 1, 3)
         elif want_lights:
+            if rot is not None and not source:
+                lights = _rotate(lights, rot)
             lights_dir = lights.reshape(Lo, n, 1, 3)
         return {"rays_o": data[:, :3], "rays_d": data[:, 3:6], "mask": data[:, 6:7] if gather else None, "near": near,
                 "far": far, "true_rgb": rgb, "lights_dir": lights_dir, "pixels_x": px_all[first:first + n],
