@@ -32,6 +32,7 @@ static void dw_plan(int64_t M, int N, int K, int* v_out, int* splits_out, int* r
 // CU), each job's share of them proportional to its work (operand pairs), so every CU multiplies for the whole launch.
 // Partial gradients leave through plain stores into slabs that dw_reduce_kernel sums in split order: an fp32 atomic tail
 // of 256 KB per workgroup would cost ~50 us per round at the chip's ~1.3 TB/s atomic rate, with nothing to hide under.
+// (Restated in Python, with flush_staged's room clamp, by tests/point_matrix.py: a change here changes that table's rows.)
 static void dw_staged_plan(int64_t M, int npairs, int total_pairs, int* splits_out, int* rows_out) {
   int splits = total_pairs > 0 ? (256 * npairs) / total_pairs : 1;
   if (splits < 1) splits = 1;

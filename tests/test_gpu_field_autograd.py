@@ -9,10 +9,13 @@ import pytest
 import torch
 
 from oracle import rnb_oracle as O
+from tests.field_autograd_util import build as _build, check_grad_or_zero as _check_grad, compare_leaves as _compare_leaves, \
+    mesh_texture as _mesh_texture, native_leaf_grads as _native_leaf_grads, oracle as _oracle, oracle_normal as _oracle_normal, \
+    weights as _weights, zero_grads as _zero
 from tests.gpu_support import R  # noqa: F401
 from tests.gpu_support import ALBEDO_H2_CLASSES, device, profile_classes
-from tests.parity import check_grad, check_value, rel_l2
-from tests.shape_matrix import BY_NAME, live_params, points
+from tests.parity import check_value, rel_l2
+from tests.shape_matrix import points
 
 pytestmark = pytest.mark.gpu
 
@@ -20,64 +23,6 @@ SDF_SHAPES = ["default_64x64", "no_skip", "skip1", "skip7", "scale3", "multires0
 COLOR_SHAPES = ["default_64x64", "mview0", "albedo_nl1", "feat128"]
 SIZES = [1, 63, 4097]
 FUSED_CLASSES = {"R_sweep", "FB_sweep", "RA_sweep", "dW(x3: 256x256 + narrow jobs)"}
-
-
-def _build(R, name):
-    shape = BY_NAME[name]
-    p = live_params(shape.mc, shape.seed)
-    sdf, devn, col, ren = R.build_from_named_params(shape.mc, p, device())
-    sdf.set_autograd(True)
-    col.set_autograd(True)
-    return shape, p, sdf, col, ren
-
-
-def _check_grad(got, g64, g32, what):
-    if float(g64.abs().max()) == 0.0:
-        assert float(got.abs().max()) == 0.0, f"{what}: non-zero gradient where the oracle's is zero"
-        return
-    check_grad(what, got, g64, rel_l2(g32, g64))
-
-
-def _oracle(p, prefix, inputs, fn, dt):
-    """(output, {leaf: grad}, [input grads]) of loss = fn(q, *xs)[1] by torch autograd in dtype dt on the device."""
-    q = {k: v.to(device(), dt).detach().requires_grad_(k.startswith(prefix)) for k, v in p.items()}
-    xs = [t.to(device(), dt).detach().requires_grad_(True) for t in inputs]
-    with torch.enable_grad():
-        out, loss = fn(q, *xs)
-        keys = [k for k in q if k.startswith(prefix)]
-        ins = [q[k] for k in keys] + xs
-        gs = torch.autograd.grad(loss, ins, allow_unused=True)
-    gs = [torch.zeros_like(t) if g is None else g for g, t in zip(gs, ins)]   # (e.g. the sdf bias in an eikonal loss)
-    return out.detach(), dict(zip(keys, gs[:len(keys)])), list(gs[len(keys):])
-
-
-def _oracle_normal(q, conf, x):
-    """d sdf / d x with a graph (models/fields.py:114-127, create_graph=True), differentiable in x as well."""
-    y = O.sdf_only(q, conf, x)
-    (g,) = torch.autograd.grad(y, x, torch.ones_like(y), create_graph=True)
-    return g
-
-
-def _native_leaf_grads(net, prefix):
-    return {f"{prefix}.{k}": v.grad for k, v in net.named_parameters()}
-
-
-def _zero(*nets):
-    for net in nets:
-        for q in net.parameters():
-            q.grad = None
-
-
-def _compare_leaves(mine, g64, g32, tag):
-    assert set(mine) == set(g64), f"{tag}: leaves {sorted(set(mine) ^ set(g64))}"
-    for k in g64:
-        assert mine[k] is not None, f"{tag} {k}: no gradient"
-        _check_grad(mine[k], g64[k], g32[k], f"{tag} {k}")
-
-
-def _weights(n, width, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, width, generator=g)
 
 
 # ------------------------------------------------------------------------------------------------------- cases 1 and 2
@@ -148,13 +93,6 @@ def test_color_loss_against_fp64(R, name):
 
 
 # ------------------------------------------------------------------------------------------------------- case 4
-def _mesh_texture(sdf, col, v):
-    """Runner.validate_mesh_texture's three calls (exp_runner.py:584-615)."""
-    feats = sdf.sdf_hidden_appearance(v)[:, 1:]
-    normals = sdf.gradient(v).squeeze(1)
-    return col(v, normals, normals, feats)
-
-
 @pytest.mark.parametrize("name", ["default_64x64", "mview0"])
 def test_validate_mesh_texture_sequence(R, name):
     shape, p, sdf, col, ren = _build(R, name)
