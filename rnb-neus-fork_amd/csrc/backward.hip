@@ -4,6 +4,7 @@
 // point-wise kernels here are the ones more than one route launches; the input adjoints of the point-wise autograd calls
 // follow.
 #include "gemm.hip.h"
+#include "pe.hip.h"
 #include "rnb_internal.h"
 
 namespace rnb {
@@ -29,18 +30,7 @@ __global__ __launch_bounds__(64) void nbar_geb_kernel(const float* __restrict__ 
       const float* g = tile + lane * (Wc + 1) + (pen_off - blk_off);
 #pragma unroll
       for (int d = 0; d < 3; ++d) nb[d] = nbar_in[row * 4 + d] + g[d];
-      float f = 1.f;
-      int c = 3;
-      for (int k = 0; k < multires_view; ++k) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          float s, co;
-          sincosf(nrm[row * 4 + d] * f, &s, &co);
-          nb[d] += f * (g[c + d] * co - g[c + 3 + d] * s);
-        }
-        c += 6;
-        f *= 2.f;
-      }
+      pe_adjoint(nrm + row * 4, g, multires_view, 0, 1, nb);
     }
     __builtin_amdgcn_wave_barrier();   // every lane is done with the input tile before it is overwritten
   } else if (row < M) {
@@ -50,22 +40,12 @@ __global__ __launch_bounds__(64) void nbar_geb_kernel(const float* __restrict__ 
   float* o = tile + lane * (Ep + 1);
   o[0] = nb[0]; o[1] = nb[1]; o[2] = nb[2];
   float gm = fmaxf(fmaxf(fabsf(nb[0]), fabsf(nb[1])), fabsf(nb[2]));   // max |geb| of this row (rows >= M carry nb = 0)
-  int c = 3;
-  float f = 1.f;
-  for (int k = 0; k < multires; ++k) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      float s, co;
-      sincosf(x4[row * 4 + d] * f, &s, &co);
-      const float v0 = f * co * nb[d], v1 = -f * s * nb[d];
-      o[c + d] = v0;
-      o[c + 3 + d] = v1;
-      gm = fmaxf(gm, fmaxf(fabsf(v0), fabsf(v1)));
-    }
-    c += 6;
-    f *= 2.f;
-  }
-  for (; c < Ep; ++c) o[c] = 0.f;
+  pe_tangent(x4 + row * 4, nb, multires, 0, 1, [&](int c, float v0, float v1) {
+    o[c] = v0;
+    o[c + 3] = v1;
+    gm = fmaxf(gm, fmaxf(fabsf(v0), fabsf(v1)));
+  });
+  for (int c = 3 + 6 * multires; c < Ep; ++c) o[c] = 0.f;
   if (amax != nullptr) amax_commit(amax, gm, lane);   // the scale of layer 0's weight-gradient job (x2h)
   __builtin_amdgcn_wave_barrier();
   tile_store64(geb, Ep, r0, 0, Ep, tile, lane);
@@ -143,22 +123,8 @@ __global__ void sdf_xbar_kernel(const float* __restrict__ x4, const float* __res
   if (row >= M) return;
   const float* eb = ebar + row * Ep;
   float acc[3] = {eb[0], eb[1], eb[2]};
-  float f = 1.f;
-  int c = 3;
-  for (int k = 0; k < multires; ++k) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      float sn, co;
-      sincosf(x4[row * 4 + d] * f, &sn, &co);
-      acc[d] += f * (eb[c + d] * co - eb[c + 3 + d] * sn);
-      if (ge != nullptr) {
-        const float* g = ge + row * Ep;
-        acc[d] -= f * f * (g[c + d] * sn + g[c + 3 + d] * co) * nbar[row * 4 + d];
-      }
-    }
-    c += 6;
-    f *= 2.f;
-  }
+  const float* g = ge != nullptr ? ge + row * Ep : nullptr;
+  pe_adjoint_hess(x4 + row * 4, eb, g != nullptr, g, nbar + row * 4, multires, 0, 1, acc);
 #pragma unroll
   for (int d = 0; d < 3; ++d) xbar[row * 3 + d] = scale * acc[d];
 }
@@ -176,18 +142,7 @@ __global__ void color_input_bwd_kernel(const float* __restrict__ cinb, int Cinp,
     const float* g = cinb + row * Cinp + F + which * pev;
     const float* v = (which ? n4 : p4) + row * 4;
     float t[3] = {g[0], g[1], g[2]};
-    float f = 1.f;
-    int c = 3;
-    for (int k = 0; k < multires_view; ++k) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float sn, co;
-        sincosf(v[d] * f, &sn, &co);
-        t[d] += f * (g[c + d] * co - g[c + 3 + d] * sn);
-      }
-      c += 6;
-      f *= 2.f;
-    }
+    pe_adjoint(v, g, multires_view, 0, 1, t);
 #pragma unroll
     for (int d = 0; d < 3; ++d) out[row * 3 + d] = t[d];
   }

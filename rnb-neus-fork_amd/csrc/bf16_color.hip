@@ -1,6 +1,7 @@
 // RNB_VARIANT_BF16: the albedo network's forward and backward in bf16, used where it has the shipped shape
 // (bf16_color_supported); its hidden-layer weight gradients are jobs of bf16_dw.hip.  See bf16_common.hip.h.
 #include "bf16_common.hip.h"
+#include "pe.hip.h"
 
 namespace rnb {
 
@@ -65,16 +66,10 @@ __global__ __launch_bounds__(256, 2) void bf_color_fwd_kernel(BfColArgs g) {
       if (which == 1)
         for (int c = g.F + 2 * g.pev; c < g.Cinp; ++c) X[p * CP + c] = 0;
     }
-    for (int k = sub; k < g.multires_view; k += 2) {
-      const float f = (float)(1 << k);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float sn, co;
-        sincosf(v[d] * f, &sn, &co);
-        xr[3 + 6 * k + d] = to_bf(sn);
-        xr[3 + 6 * k + 3 + d] = to_bf(co);
-      }
-    }
+    pe_sincos(v, g.multires_view, sub, 2, [&](int c, float sn, float co) {
+      xr[c] = to_bf(sn);
+      xr[c + 3] = to_bf(co);
+    });
   }
   __syncthreads();
   // the pe columns of the input in K8 (Y operand of layer 0's weight gradient)

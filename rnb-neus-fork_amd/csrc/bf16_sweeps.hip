@@ -1,6 +1,7 @@
 // RNB_VARIANT_BF16: the four sweeps of the SDF network (F, R, RA, FB) and the packer of the bf16 weight mirror.  The route,
 // its number formats and the K8 layout of the saved state are described in bf16_common.hip.h.
 #include "bf16_common.hip.h"
+#include "pe.hip.h"
 
 namespace rnb {
 
@@ -286,18 +287,7 @@ __global__ __launch_bounds__(BfCfg<TI>::NT, TI == 1 ? 4 : 2) void bf_reverse_ker
     const int64_t row = row0 + tid;
     const float* ge = GE + tid * FEP;
     float n[3] = {ge[0], ge[1], ge[2]};
-    float f = 1.f;
-    int c = 3;
-    for (int k = 0; k < g.net.multires; ++k) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float s, co;
-        sincosf(g.x4[row * 4 + d] * f, &s, &co);
-        n[d] += f * (ge[c + d] * co - ge[c + 3 + d] * s);
-      }
-      c += 6;
-      f *= 2.f;
-    }
+    pe_adjoint(g.x4 + row * 4, ge, g.net.multires, 0, 1, n);
     g.nrm[row * 4] = n[0]; g.nrm[row * 4 + 1] = n[1]; g.nrm[row * 4 + 2] = n[2]; g.nrm[row * 4 + 3] = 0.f;
   }
 }

@@ -18,6 +18,7 @@
 // The gradient of the output layer (<= 4 rows) leaves as per-tile column sums (plain stores into a slab, summed in tile order
 // by dw_reduce_kernel): no atomics anywhere — the albedo network's gradients are bit-reproducible.
 #include "fused_common.hip.h"
+#include "pe.hip.h"
 
 namespace rnb {
 
@@ -162,16 +163,10 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
       if (which == 1)
         for (int c = 2 * g.pev; c < PW; ++c) X[p * FP + c] = 0.f;
     }
-    for (int k = sub; k < g.multires_view; k += 2) {
-      const float f = (float)(1 << k);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float sn, co;
-        sincosf(v[d] * f, &sn, &co);
-        xr[3 + 6 * k + d] = sn * kH2ActScale;
-        xr[3 + 6 * k + 3 + d] = co * kH2ActScale;
-      }
-    }
+    pe_sincos(v, g.multires_view, sub, 2, [&](int c, float sn, float co) {
+      xr[c] = sn * kH2ActScale;
+      xr[c + 3] = co * kH2ActScale;
+    });
     pm = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));   // (the only unbounded entries of the encoding)
     // (every wave leaves its own word: nothing to initialise; the layers' flags start from zero behind the same barrier)
     // (the ballot runs on every lane: under `lane == 0` it would see row 0 of the tile only)
@@ -451,18 +446,7 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
     {
       const float* gq = X + p * FP + g.pev;   // the pe(n) block of the adjoint
       float t[3] = {0.f, 0.f, 0.f};
-      if (ok) {
-        for (int k = q; k < g.multires_view; k += 4) {
-          const float f = (float)(1 << k);
-          const int c = 3 + 6 * k;
-#pragma unroll
-          for (int d = 0; d < 3; ++d) {
-            float sn, co;
-            sincosf(g.nrm[row * 4 + d] * f, &sn, &co);
-            t[d] += f * (gq[c + d] * co - gq[c + 3 + d] * sn);
-          }
-        }
-      }
+      if (ok) pe_adjoint(g.nrm + row * 4, gq, g.multires_view, q, 4, t);
 #pragma unroll
       for (int d = 0; d < 3; ++d) part[q * 3 + d] = t[d];
     }
@@ -478,17 +462,10 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
       o[0] = nb[0]; o[1] = nb[1]; o[2] = nb[2];
       for (int c = 3 + 6 * g.multires; c < g.Ep; ++c) o[c] = 0.f;
     }
-    for (int k = q; k < g.multires; k += 4) {
-      const float f = (float)(1 << k);
-      const int c = 3 + 6 * k;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float sn, co;
-        sincosf(g.x4[row * 4 + d] * f, &sn, &co);
-        o[c + d] = f * co * nb[d];
-        o[c + 3 + d] = -f * sn * nb[d];
-      }
-    }
+    pe_tangent(g.x4 + row * 4, nb, g.multires, q, 4, [&](int c, float v0, float v1) {
+      o[c] = v0;
+      o[c + 3] = v1;
+    });
   }
   __syncthreads();
   for (int idx = tid; idx < CT * (g.Ep / 4); idx += 256) {

@@ -5,6 +5,7 @@
 //   colour composite                            render: :265-267 ; render_rnb[_warmup]: :905-914 / :1009-1017
 //   eikonal term                                 models/renderer.py:270-272 (== :538-540)
 // and the explicit backward of all of it (oracle/explicit.py::composite_backward is the statement).
+#include "pe.hip.h"
 #include "rnb_internal.h"
 
 namespace rnb {
@@ -80,6 +81,36 @@ __device__ inline void load_light(const CompArgs& a, int l, int64_t b, float (&L
   const float* p = (a.flags & RNB_FLAG_LIGHT_PER_RAY) ? a.lights + ((int64_t)l * a.B + b) * 3 : a.lights + l * 3;
   Lv[0] = p[0]; Lv[1] = p[1]; Lv[2] = p[2];
 }
+
+// ---- the ray walk of the maps kernel and of pass 1 of the backward: one wave64 per ray, 64 samples per step ----
+// (composite_fwd_kernel keeps the same statements written out: see profiles/pe_raywalk_codegen.txt.)
+// One 64-sample chunk: the lane's sample j = j0 + lane (lanes past the ray's end compute on its last sample, `on` false),
+// its normal and SampleState, the transmittance T in front of it and its weight.
+struct RayChunk {
+  int j;
+  bool on;
+  int64_t p;       // index of the sample in the [B,S] arrays
+  float n0, n1, n2;
+  SampleState st;
+  float T, w;      // w = alpha T, 0 past the end
+  // (d0, d1, d2): the ray's direction; `carry`: the transmittance entering the chunk (1 at the ray's start), advanced to
+  // the next chunk's.
+  __device__ __forceinline__ RayChunk(const CompArgs& a, int64_t b, int j0, int lane, float d0, float d1, float d2, float inv_s,
+                                      float& carry) {
+    j = j0 + lane;
+    on = j < a.S;
+    p = b * a.S + (on ? j : a.S - 1);
+    n0 = a.nrm[p * 4]; n1 = a.nrm[p * 4 + 1]; n2 = a.nrm[p * 4 + 2];
+    st = eval_sample(a.sdf[p], n0, n1, n2, d0, d1, d2, a.dists[p], inv_s, a.cos_anneal);
+    const float x = on ? (1.0f - st.alpha + 1e-7f) : 1.0f;
+    const float incl = wave_scan_mul(x, lane);
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 1.0f;
+    T = carry * excl;
+    carry = carry * __shfl(incl, 63, 64);
+    w = on ? st.alpha * T : 0.f;
+  }
+};
 
 __global__ __launch_bounds__(64) void composite_fwd_kernel(CompArgs a) {
   const int lane = threadIdx.x;
@@ -177,17 +208,16 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(CompArgs a) {
 }
 
 // Whole-image rendering (rnb_render_maps): the per-ray images of exp_runner.py:460-470 and of RNb-NeuS evaluation, reduced
-// where composite_fwd_kernel would store its [B,S] arrays.  A kernel of its own (composite_fwd_kernel's code and registers
-// are not touched); the weights, the colour, weight_sum and weight_max are formed by the same expressions in the same
-// order as there (eval_sample, the 64-sample carry of wave_scan_mul, load_light, the fmaf chain, wave_sum), so those
-// three outputs carry composite_fwd_kernel's bits.  Per lane the new sums are fused adds over the ray's 64-sample
+// where composite_fwd_kernel would store its [B,S] arrays.  A kernel of its own: the weights come from the RayChunk walk
+// (composite_fwd_kernel's chunk step, statement for statement), the colour, weight_sum and weight_max are formed by the same
+// expressions in the same order as there (load_light, the fmaf chain, wave_sum), so those three outputs carry
+// composite_fwd_kernel's bits (tests/test_gpu_render_maps.py holds them to torch.equal).  Per lane the new sums are fused adds over the ray's 64-sample
 // chunks, then the wave_sum butterfly:
 //   normal = sum_s (w_s [|p_s| < 1]) n_s       albedo = sum_s albedo_s w_s       depth = sum_s w_s (z_s + dists_s / 2)
 __global__ __launch_bounds__(64) void composite_maps_kernel(CompMapsArgs g) {
   const CompArgs& a = g.f;
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
-  const int S = a.S;
   const bool mvps = (a.flags & RNB_MODE_MVPS) != 0;
   const bool relu_sh = (a.flags & RNB_FLAG_RELU_SHADING) != 0;
   const bool no_alb = (a.flags & RNB_FLAG_NO_ALBEDO) != 0;
@@ -207,23 +237,13 @@ __global__ __launch_bounds__(64) void composite_maps_kernel(CompMapsArgs g) {
   float wsum = 0.f, wmax = -1.f;
   float nacc[3] = {0.f, 0.f, 0.f}, aacc[4] = {0.f, 0.f, 0.f, 0.f}, dacc = 0.f;
 
-  for (int j0 = 0; j0 < S; j0 += 64) {
-    const int j = j0 + lane;
-    const bool on = j < S;
-    const int64_t p = b * S + (on ? j : S - 1);
-    const float s = a.sdf[p];
-    const float n0 = a.nrm[p * 4], n1 = a.nrm[p * 4 + 1], n2 = a.nrm[p * 4 + 2];
-    const SampleState st = eval_sample(s, n0, n1, n2, d0, d1, d2, a.dists[p], inv_s, a.cos_anneal);
-    const float x = on ? (1.0f - st.alpha + 1e-7f) : 1.0f;
-    const float incl = wave_scan_mul(x, lane);
-    float excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 1.0f;
-    const float T = carry * excl;
-    carry = carry * __shfl(incl, 63, 64);
-    const float w = on ? st.alpha * T : 0.f;
+  for (int j0 = 0; j0 < a.S; j0 += 64) {
+    const RayChunk k(a, b, j0, lane, d0, d1, d2, inv_s, carry);
+    const int64_t p = k.p;
+    const float n0 = k.n0, n1 = k.n1, n2 = k.n2, w = k.w;
     const float px = a.pts[p * 3], py = a.pts[p * 3 + 1], pz = a.pts[p * 3 + 2];
     const float pn = sqrtf(px * px + py * py + pz * pz);
-    if (on) {
+    if (k.on) {
       wsum += w;
       wmax = max_nan(wmax, w);
       if (g.normal) {   // inside_sphere as a FACTOR (exp_runner.py:467-468): w * {0, 1} is exact, 0 * NaN stays NaN
@@ -318,7 +338,7 @@ __global__ __launch_bounds__(256) void gerr_finalize_kernel(const float* __restr
 
 
 // IG: also the input adjoints of rnb_render_bwd_inputs (CompBwdArgs::ig_*, each may be nullptr).  The render backward
-// without them is the IG = false instance, composite_bwd_kernel, compiled from exactly the code it had before they existed.
+// without them is the IG = false instance, composite_bwd_kernel.
 template <bool IG>
 __device__ __forceinline__ void composite_bwd_body(const CompBwdArgs& g) {
   __shared__ float sAlpha[kMaxS], sT[kMaxS], sWbar[kMaxS], sSuf[kMaxS];
@@ -367,19 +387,11 @@ __device__ __forceinline__ void composite_bwd_body(const CompBwdArgs& g) {
     for (int l = 0; l < kMaxL; ++l) lbar[l][0] = lbar[l][1] = lbar[l][2] = 0.f;
   }
   for (int j0 = 0; j0 < S; j0 += 64) {
-    const int j = j0 + lane;
-    const bool on = j < S;
-    const int64_t p = b * S + (on ? j : S - 1);
-    const float n0 = a.nrm[p * 4], n1 = a.nrm[p * 4 + 1], n2 = a.nrm[p * 4 + 2];
-    const SampleState st = eval_sample(a.sdf[p], n0, n1, n2, d0, d1, d2, a.dists[p], inv_s, c_an);
-    const float x = on ? (1.0f - st.alpha + 1e-7f) : 1.0f;
-    const float incl = wave_scan_mul(x, lane);
-    float excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 1.0f;
-    const float T = carry * excl;
-    carry = carry * __shfl(incl, 63, 64);
-    if (on) {
-      const float w = st.alpha * T;
+    const RayChunk k(a, b, j0, lane, d0, d1, d2, inv_s, carry);
+    if (k.on) {
+      const int j = k.j;
+      const int64_t p = k.p;
+      const float n0 = k.n0, n1 = k.n1, n2 = k.n2, w = k.w;
       float wb = g_wsum + (g.g_weights ? g.g_weights[p] : 0.f);
       float nb0 = 0.f, nb1 = 0.f, nb2 = 0.f;
       float ab[4] = {0.f, 0.f, 0.f, 0.f};
@@ -408,8 +420,8 @@ __device__ __forceinline__ void composite_bwd_body(const CompBwdArgs& g) {
         for (int c = 0; c < 3; ++c) { wb = fmaf(Cb[0][c], al[c], wb); ab[c] = Cb[0][c] * w; }
         wb -= bg_dot;
       }
-      sAlpha[j] = st.alpha;
-      sT[j] = T;
+      sAlpha[j] = k.st.alpha;
+      sT[j] = k.T;
       sWbar[j] = wb;
       g.nbar[p * 4] = nb0; g.nbar[p * 4 + 1] = nb1; g.nbar[p * 4 + 2] = nb2; g.nbar[p * 4 + 3] = 0.f;
 #pragma unroll
@@ -520,7 +532,8 @@ __global__ __launch_bounds__(64) void composite_bwd_ig_kernel(CompBwdArgs g) { c
 // consumed (it never goes to HBM):
 //   nbar_tot = nbar + J_pe(n)^T cinb[pe(n)]                         (the normal's total adjoint: composite + albedo input)
 //   pbar     = scale ( J_pe(xs)^T ebar - sum_k ge_k d^2 pe_k / d xs^2 . nbar_tot ) + J_pe(p)^T cinb[pe(p)]
-// (sdf_xbar_kernel / color_input_bwd_kernel of the point-wise calls, backward.hip).  pts = o + d mid, mid = z + dists / 2,
+// (pe_adjoint and pe_adjoint_hess of pe.hip.h, as in the point-wise calls' kernels of backward.hip).  pts = o + d mid,
+// mid = z + dists / 2,
 // dists_s = z_{s+1} - z_s (the last one a constant), so with mbar_s = pbar_s . d and Dbar_s = dists_bar_s + mbar_s / 2:
 //   o_bar = sum_s pbar_s ;  d_bar = sum_s mid_s pbar_s + cos_d ;  z_bar_s = mbar_s - [s < S-1] Dbar_s + [s > 0] Dbar_{s-1}.
 // Sums are lane-local over the 64-sample chunks, then a shuffle butterfly: a fixed order.
@@ -543,20 +556,8 @@ __global__ __launch_bounds__(64) void ray_input_adjoint_kernel(RayAdjArgs r) {
       const float* gp = r.cinb + p * r.Cinp + r.F;
 #pragma unroll
       for (int d = 0; d < 3; ++d) { nt[d] += gn[d]; pb[d] = gp[d]; }
-      float f = 1.f;
-      int c = 3;
-      for (int k = 0; k < r.multires_view; ++k) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          float sn, co;
-          sincosf(r.nrm[p * 4 + d] * f, &sn, &co);
-          nt[d] += f * (gn[c + d] * co - gn[c + 3 + d] * sn);
-          sincosf(r.pts[p * 3 + d] * f, &sn, &co);
-          pb[d] += f * (gp[c + d] * co - gp[c + 3 + d] * sn);
-        }
-        c += 6;
-        f *= 2.f;
-      }
+      pe_adjoint(r.nrm + p * 4, gn, r.multires_view, 0, 1, nt);
+      pe_adjoint(r.pts + p * 3, gp, r.multires_view, 0, 1, pb);
     } else {
       pb[0] = pb[1] = pb[2] = 0.f;
     }
@@ -564,19 +565,7 @@ __global__ __launch_bounds__(64) void ray_input_adjoint_kernel(RayAdjArgs r) {
       const float* eb = r.ebar + p * r.Ep;
       const float* ge = r.ge + p * r.Ep;
       float acc[3] = {eb[0], eb[1], eb[2]};
-      float f = 1.f;
-      int c = 3;
-      for (int k = 0; k < r.multires; ++k) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          float sn, co;
-          sincosf(r.x4[p * 4 + d] * f, &sn, &co);
-          acc[d] += f * (eb[c + d] * co - eb[c + 3 + d] * sn);
-          acc[d] -= f * f * (ge[c + d] * sn + ge[c + 3 + d] * co) * nt[d];
-        }
-        c += 6;
-        f *= 2.f;
-      }
+      pe_adjoint_hess(r.x4 + p * 4, eb, true, ge, nt, r.multires, 0, 1, acc);
 #pragma unroll
       for (int d = 0; d < 3; ++d) pb[d] = on ? fmaf(r.scale, acc[d], pb[d]) : 0.f;
     }

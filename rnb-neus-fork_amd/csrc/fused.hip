@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "fused_common.hip.h"
+#include "pe.hip.h"
 
 // A/B switches (compile time): scalar instead of packed fp32 math in the forward epilogue (same operations element by element:
 // the same bits).  Six bf16 terms (round 2, one box, two runs each): packed 3.694 / 3.684 ms per step, scalar 3.71 / 3.78.

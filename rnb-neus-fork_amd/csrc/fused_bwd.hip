@@ -12,6 +12,7 @@
 // Mathematical statement: oracle/explicit.py.  The reverse-shaped products use the transposed weight
 // copies W^T that rnb_weightnorm_fwd emits, so every sweep streams weight rows the same way.
 #include "fused_common.hip.h"
+#include "pe.hip.h"
 
 namespace rnb {
 
@@ -217,18 +218,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TI == 2) ? 1 : 2) void fused_r
     const int64_t row = row0 + tid;
     const float* ge = GE + tid * FEP;
     float n[3] = {ge[0], ge[1], ge[2]};
-    float f = 1.f;
-    int c = 3;
-    for (int k = 0; k < g.net.multires; ++k) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float s, co;
-        sincosf(g.x4[row * 4 + d] * f, &s, &co);
-        n[d] += f * (ge[c + d] * co - ge[c + 3 + d] * s);
-      }
-      c += 6;
-      f *= 2.f;
-    }
+    pe_adjoint(g.x4 + row * 4, ge, g.net.multires, 0, 1, n);
     g.nrm[row * 4] = n[0]; g.nrm[row * 4 + 1] = n[1]; g.nrm[row * 4 + 2] = n[2]; g.nrm[row * 4 + 3] = 0.f;
     if (g.ge_out != nullptr)
       for (int c = 0; c < g.net.pe; ++c) g.ge_out[row * g.net.Ep + c] = ge[c];

@@ -4,6 +4,7 @@
 // reference lines each stage replaces (models/fields.py:82-127, :177-215; the backward replaces autograd's double backward
 // invoked at exp_runner.py:261).  The input adjoint's two products (launch_sdf_ebar) run here on every fp32 route.
 #include "gemm.hip.h"
+#include "pe.hip.h"
 #include "rnb_internal.h"
 
 namespace rnb {
@@ -26,20 +27,11 @@ __global__ void pe_points_kernel(const float* __restrict__ pts, int64_t M, int64
   x4[row * 4 + 0] = x[0]; x4[row * 4 + 1] = x[1]; x4[row * 4 + 2] = x[2]; x4[row * 4 + 3] = 0.f;
   float* er = e + row * Ep;
   er[0] = x[0]; er[1] = x[1]; er[2] = x[2];
-  int c = 3;
-  float f = 1.f;
-  for (int k = 0; k < multires; ++k) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      float s, co;
-      sincosf(x[d] * f, &s, &co);
-      er[c + d] = s;
-      er[c + 3 + d] = co;
-    }
-    c += 6;
-    f *= 2.f;
-  }
-  for (; c < Ep; ++c) er[c] = 0.f;
+  pe_sincos(x, multires, 0, 1, [&](int c, float s, float co) {
+    er[c] = s;
+    er[c + 3] = co;
+  });
+  for (int c = 3 + 6 * multires; c < Ep; ++c) er[c] = 0.f;
 }
 
 // sdf head: sdf = (a_last . w_sdf + b_sdf)/scale ; optionally seeds the reverse sweep gz_last = w_sdf * D
@@ -72,18 +64,7 @@ __global__ void normal_kernel(const float* __restrict__ x4, const float* __restr
   float n[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) n[d] = g[d];
-  float f = 1.f;
-  int c = 3;
-  for (int k = 0; k < multires; ++k) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      float s, co;
-      sincosf(x4[row * 4 + d] * f, &s, &co);
-      n[d] += f * (g[c + d] * co - g[c + 3 + d] * s);
-    }
-    c += 6;
-    f *= 2.f;
-  }
+  pe_adjoint(x4 + row * 4, g, multires, 0, 1, n);
   nrm[row * 4 + 0] = n[0]; nrm[row * 4 + 1] = n[1]; nrm[row * 4 + 2] = n[2]; nrm[row * 4 + 3] = 0.f;
 }
 
@@ -96,30 +77,21 @@ __global__ __launch_bounds__(64) void color_input_kernel(const float* __restrict
   extern __shared__ float tile[];
   const int lane = threadIdx.x, W = Cinp - F;
   const int64_t r0 = (int64_t)blockIdx.x * 64, row = r0 + lane;
-  float* cr = tile + lane * (W + 1);
-  int c = 0;
+  const int pev = 3 + 6 * multires;
   for (int which = 0; which < 2; ++which) {
+    float* cr = tile + lane * (W + 1) + which * pev;
     float v[3] = {0.f, 0.f, 0.f};
     if (row < M) {
       if (which == 0) { v[0] = pts[row * 3]; v[1] = pts[row * 3 + 1]; v[2] = pts[row * 3 + 2]; }
       else { v[0] = nrm[row * nrm_ld]; v[1] = nrm[row * nrm_ld + 1]; v[2] = nrm[row * nrm_ld + 2]; }
     }
-    cr[c] = v[0]; cr[c + 1] = v[1]; cr[c + 2] = v[2];
-    c += 3;
-    float f = 1.f;
-    for (int k = 0; k < multires; ++k) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        float s, co;
-        sincosf(v[d] * f, &s, &co);
-        cr[c + d] = s;
-        cr[c + 3 + d] = co;
-      }
-      c += 6;
-      f *= 2.f;
-    }
+    cr[0] = v[0]; cr[1] = v[1]; cr[2] = v[2];
+    pe_sincos(v, multires, 0, 1, [&](int c, float s, float co) {
+      cr[c] = s;
+      cr[c + 3] = co;
+    });
   }
-  for (; c < W; ++c) cr[c] = 0.f;
+  for (int c = 2 * pev; c < W; ++c) tile[lane * (W + 1) + c] = 0.f;
   __builtin_amdgcn_wave_barrier();
   tile_store64(cin, Cinp, r0, F, W, tile, lane);
 }

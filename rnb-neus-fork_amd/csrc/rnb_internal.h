@@ -257,20 +257,6 @@ __device__ inline void sweep_store_sdf(const GridGen& grid, float* sdf, int64_t 
     if (o >= 0) sdf[o] = v * grid.out_scale;
   }
 }
-// The sin / cos columns of the positional encoding [x, sin(2^k x), cos(2^k x)]_k of one point (models/embedder.py:40-46),
-// frequencies k = k0, k0 + kstep, ...: put(c, sin, cos) gets column c = 3 + 6 k + d of the sine; the cosine's is c + 3.
-template <class Put>
-__device__ inline void pe_sincos(const float (&x)[3], int multires, int k0, int kstep, Put put) {
-  for (int k = k0; k < multires; k += kstep) {
-    const float f = (float)(1 << k);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      float s, co;
-      sincosf(x[d] * f, &s, &co);
-      put(3 + 6 * k + d, s, co);
-    }
-  }
-}
 #endif
 
 // ---- workspace carving ------------------------------------------------------------------------

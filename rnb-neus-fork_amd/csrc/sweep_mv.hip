@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "fused_common.hip.h"
+#include "pe.hip.h"
 
 namespace rnb {
 

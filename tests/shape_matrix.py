@@ -91,6 +91,9 @@ SHAPES = [
        "sdf_scale 3 (bias 1.5 keeps the initial sphere at radius 0.5): inv_scale in the seed, R and FB"),
     _s("no_weight_norm", replace(_mc(weight_norm=False), color=O.ColorConf(weight_norm=False)), "x2h", True, True, True,
        "plain weights on both nets: no g / v split"),
+    _s("mview3", _mc(color=dict(multires_view=3)), "x2h", True, True, True,
+       "multires_view 3: pev = 21, Cin = 298, Cinp - F = 64: an odd octave count for color_h2's stride-2 encode, and no "
+       "octave for the fourth thread of a point in its stride-4 adjoint"),
     # ---- fused SDF sweeps, the albedo network as layer GEMMs --------------------------------------------------------------
     _s("mview0", _mc(color=dict(multires_view=0)), "x2h", True, False, True, "multires_view 0: Cin = 262, Cinp - F = 32"),
     _s("albedo_nl1", _mc(color=dict(n_layers=1)), "x2h", True, False, True, "one hidden albedo layer"),
