@@ -17,6 +17,8 @@
 // the per-matrix scale of the mirror (H2Tab).
 // The gradient of the output layer (<= 4 rows) leaves as per-tile column sums (plain stores into a slab, summed in tile order
 // by dw_reduce_kernel): no atomics anywhere — the albedo network's gradients are bit-reproducible.
+#include <type_traits>
+
 #include "fused_common.hip.h"
 #include "pe.hip.h"
 
@@ -59,6 +61,13 @@ constexpr int CT = 64;     // points per tile
 // relu with torch's NaN propagation (rnb_internal.h: relu_nan)
 __device__ inline float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }
 
+// the two bias values a wave's epilogue needs (columns n0 + cl, n0 + 32 + cl), requested ABOVE the layer's matrix loop: read
+// inside the epilogue they cost a wait for everything issued before them — the vector-memory counter covers loads and stores
+// alike and retires in issue order — i.e. for the first column tile's burst of stores
+__device__ inline void col_bias_request(const float* __restrict__ bias, int n0, int lane, float (&bc)[2]) {
+#pragma unroll
+  for (int tj = 0; tj < 2; ++tj) bc[tj] = bias[n0 + tj * 32 + (lane & 31)];
+}
 // hidden-layer epilogue of the forward: a = relu(acc * inv + b) -> tile (times kH2ActScale), HBM; returns the thread's max
 // m = 2 m + (a > 0): appends one bit of the relu mask — a compare into VCC and an add-with-carry.  After 32 elements the
 // first one appended sits in bit 31 (col_mask_bit).
@@ -69,7 +78,7 @@ __device__ inline void col_mask_push(unsigned& m, float a) {
 __device__ inline unsigned col_mask_bit(unsigned m, int ti, int r) { return (unsigned)(((int)(m << (ti * 16 + r))) >> 31); }
 
 template <bool MASK>
-__device__ inline float col_fwd_epilogue(const v16f (&acc)[2][2], float inv, const float* __restrict__ bias, float* X,
+__device__ inline float col_fwd_epilogue(const v16f (&acc)[2][2], float inv, const float (&bias)[2], float* X,
                                          float* __restrict__ out, int64_t row0, int n0, int lane, unsigned* __restrict__ mask_out) {
   const int h = lane >> 5, cl = lane & 31;
   const BufRsrc ro = tile_rsrc(out + (size_t)row0 * FH, CT * FH * 4);
@@ -77,7 +86,7 @@ __device__ inline float col_fwd_epilogue(const v16f (&acc)[2][2], float inv, con
 #pragma unroll
   for (int tj = 0; tj < 2; ++tj) {
     const int col = n0 + tj * 32 + cl;
-    const float bc = bias[col];
+    const float bc = bias[tj];
     [[maybe_unused]] unsigned mk = 0u;
     const unsigned voff = (unsigned)(4 * h * FH + col) * 4u;
 #pragma unroll
@@ -100,6 +109,17 @@ __device__ inline float col_fwd_epilogue(const v16f (&acc)[2][2], float inv, con
   return __builtin_bit_cast(float, amb);
 }
 
+// requests rows 32 T .. 32 T + 31 of a [64 x 256] tile in accumulator layout (no wait: prefetch_tile, one row half)
+template <int T>
+__device__ inline void prefetch_rows32(const BufRsrc rs, int n0, int lane, float (&v)[2][16]) {
+  const int h = lane >> 5, cl = lane & 31;
+#pragma unroll
+  for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      v[tj][r] = bload(rs, (unsigned)(4 * h * FH + n0 + tj * 32 + cl) * 4u, (T * 32 + (r & 3) + 8 * (r >> 2)) * FH * 4);
+}
+
 // after a layer's closing barrier: the tile's scale for the next product.  Common case: the flag is down, the tile keeps
 // kH2ActScale.  Flag up (some value reached kH2ActLimit): the waves exchange their maxima, rescale what they wrote and leave
 // the tile's maximum in PointBufs::smax (fused_common.hip.h).
@@ -113,7 +133,7 @@ __device__ inline void col_tile_rescale(int* flag, float am, float* wmx, float* 
     lds_barrier();
     const float tm = tile_max<4>(wmx);
     if (smax_slot != nullptr && tid == 0) amax_tile_commit(smax_slot, tm);
-    if (tid == 0) *reinterpret_cast<volatile int*>(flag) = 0;
+    if (tid == 0) h2_flag_write(flag, 0);
     x2h_dyn_scale(__builtin_bit_cast(unsigned, tm), sa, isa);
     const float f = sa * (1.f / kH2ActScale);
     for_each_acc<2, 2>(n0, lane, [&](int, int, int, int col, int, int row) { X[row * FP + col] *= f; });
@@ -234,32 +254,41 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
 #pragma unroll
       for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = acc[ti][tj] * f;
   }
+  float bc[2];
+  col_bias_request(g.packed + g.b_off[0], n0, lane, bc);
   mm.run_at<true>(X, W0, nks0, 0, ksF, n0, lane, acc, W1, FH >> 4, 0, n0);   // acc += feature . W0[:, 0 .. F]^T
   lds_barrier();   // in-place update: every wave has finished reading the tile
   {
     const float inv = isa * h2_iws_at(iwsv, g.id0);
-    const float am = col_fwd_epilogue<true>(acc, inv, g.packed + g.b_off[0], X, g.ac[0], row0, n0, lane,
+    const float am = col_fwd_epilogue<true>(acc, inv, bc, X, g.ac[0], row0, n0, lane,
                                             g.ac0_mask + ((size_t)blockIdx.x * NT + tid) * 2);
     h2_raise_flag(am, &ovf[1], lane);
     lds_barrier();
     col_tile_rescale(&ovf[1], am, wmx, X, n0, lane, wave, g.smax ? g.smax + SMAX_AC : nullptr, tid, sa, isa);
   }
+  col_bias_request(g.packed + g.b_off[1], n0, lane, bc);
   mm.run(X, W1, FH, n0, lane, acc, nullptr, 0, 0);
   lds_barrier();
+  // the output layer's weights and bias (fp32, 16 + 1 values per lane) are requested ahead of the last burst of stores for the
+  // same reason: the registers of the weight fragments are free from here on
+  float w[4][4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {   // (rows >= Co: row Co - 1 is read and dropped — no branch around a load)
+      const float t = g.packed[g.wo_off + (long long)min(c, g.Co - 1) * g.ldwo + lane + 64 * u];
+      w[c][u] = c < g.Co ? t : 0.f;
+    }
+  const float bo = g.packed[g.bo_off + min(lane, g.Co - 1)];   // (used by lanes < Co)
   {
     const float inv = isa * h2_iws_at(iwsv, g.id0 + 1);
-    const float am = col_fwd_epilogue<false>(acc, inv, g.packed + g.b_off[1], X, g.ac[1], row0, n0, lane, nullptr);
+    const float am = col_fwd_epilogue<false>(acc, inv, bc, X, g.ac[1], row0, n0, lane, nullptr);
     h2_raise_flag(am, &ovf[0], lane);
     lds_barrier();
     col_tile_rescale(&ovf[0], am, wmx, X, n0, lane, wave, g.smax ? g.smax + SMAX_AC + 1 : nullptr, tid, sa, isa);
   }
   // ---- output layer + sigmoid: fp32 weights on the VALU, 16 rows per wave ----
   {
-    float w[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w[c][u] = c < g.Co ? g.packed[g.wo_off + (long long)c * g.ldwo + lane + 64 * u] : 0.f;
     for (int rr = 0; rr < CT / 4; ++rr) {
       const int row = wave * (CT / 4) + rr;
       float sc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -277,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
         float v = 0.f;
         if (lane < g.Co) {
           const float s = lane == 0 ? sc[0] : lane == 1 ? sc[1] : lane == 2 ? sc[2] : sc[3];
-          v = __builtin_fmaf(s, isa, g.packed[g.bo_off + lane]);
+          v = __builtin_fmaf(s, isa, bo);
           if (g.squeeze) v = 1.f / (1.f + expf(-v));
         }
         g.alb[(row0 + row) * 4 + lane] = v;
@@ -313,9 +342,22 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
     for (int c = 0; c < 4; ++c) z[c] = (c < g.Co && tid < rows_ok) ? g4[c] * (g.squeeze ? a4[c] * (1.f - a4[c]) : 1.f) : 0.f;
     *reinterpret_cast<vf4*>(ZO + tid * 4) = z;
   }
-  AuxTile<2, 2> aA;
-  prefetch_tile<2, 2>(g.ac[1], row0, n0, lane, aA);
+  // ac_1 arrives in two halves of 32 rows.  Everything this phase loads is requested BEFORE its stores: the vector-memory
+  // counter covers loads and stores alike and retires in issue order, so a wait for a load issued behind a store is a wait
+  // for that store too (profiles/epilogue_waits_codegen.txt).  Order of issue: rows 0 .. 31 of ac_1, the mask of ac_0, the
+  // output layer's weights | barrier | rows 32 .. 63 of ac_1, the first weight steps of the product that follows | the stores.
+  const BufRsrc ra1 = tile_rsrc(g.ac[1] + (size_t)row0 * FH, CT * FH * 4);
+  float aA0[2][16], aA1[2][16];
+  prefetch_rows32<0>(ra1, n0, lane, aA0);
   const vu2 mk0 = *reinterpret_cast<const vu2*>(g.ac0_mask + ((size_t)blockIdx.x * 256 + tid) * 2);   // relu'(ac_0), this thread's bits
+  float wo[2][4];
+#pragma unroll
+  for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {   // (rows >= Co: row Co - 1 is read and dropped — no branch around a load)
+      const float w = g.packed[g.wo_off + (long long)min(c, g.Co - 1) * g.ldwo + n0 + tj * 32 + (lane & 31)];
+      wo[tj][c] = c < g.Co ? w : 0.f;
+    }
   __syncthreads();
   if (tid < g.Co) {   // d b_out of this tile
     float t = 0.f;
@@ -324,23 +366,23 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
   }
   v16f acc[2][2];
   X3Mma<2, 2, 2> mm;
+  prefetch_rows32<1>(ra1, n0, lane, aA1);
+  mm.request(W1T, FH, n0, lane);
+  __builtin_amdgcn_sched_barrier(0);
   // ---- zc_1 = (zo W_out) * relu'(ac_1);  d W_out of this tile = zo^T ac_1 ----
   {
     const int lane_a = opaque_lane(lane);
     const int h = lane_a >> 5, cl = lane_a & 31;
     const BufRsrc rz = tile_rsrc(g.zc[1] + (size_t)row0 * FH, CT * FH * 4);
-    float ds[2][4], wo[2][4];
+    float ds[2][4];
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        wo[tj][c] = c < g.Co ? g.packed[g.wo_off + (long long)c * g.ldwo + n0 + tj * 32 + cl] : 0.f;
-        ds[tj][c] = 0.f;
-      }
-    // (rows outermost: a row's zo is read once and used for both column tiles — with the column tiles outermost the
-    // compiler keeps all 32 rows' zo live across them: 128 registers, spilled)
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
+      for (int c = 0; c < 4; ++c) ds[tj][c] = 0.f;
+    // (rows outermost: a row's zo is read once and used for both column tiles; four rows at a time between scheduling
+    // barriers)
+    auto rows32 = [&](auto ti_c, const float (&a32)[2][16]) {
+      constexpr int ti = decltype(ti_c)::value;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int rowc = ti * 32 + (r & 3) + 8 * (r >> 2);
@@ -348,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
 #pragma unroll
         for (int tj = 0; tj < 2; ++tj) {
           const int col = n0 + tj * 32 + cl;
-          const float a = aA.v[ti][tj][r];
+          const float a = a32[tj][r];
           const float t = fmaf(zo[0], wo[tj][0], fmaf(zo[1], wo[tj][1], fmaf(zo[2], wo[tj][2], zo[3] * wo[tj][3])));
           const float z = a > 0.f ? t : 0.f;
           acc[ti][tj][r] = z;
@@ -356,7 +398,19 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) ds[tj][c] = fmaf(zo[c], a, ds[tj][c]);
         }
+        if ((r & 3) == 3) {
+          // (the column sums are pinned here: instruction selection otherwise moves the eight chains of 64 fma behind the
+          // loop, next to the shuffles that use them, and keeps every row's zo and the whole tile of ac_1 live until then)
+#pragma unroll
+          for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) asm volatile("" : "+v"(ds[tj][c]));
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
+    };
+    rows32(std::integral_constant<int, 0>{}, aA0);
+    rows32(std::integral_constant<int, 1>{}, aA1);
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
@@ -374,7 +428,6 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
     if (tid == 0 && g.amax != nullptr) amax_tile_commit(g.amax + AMAX_ZC + 1, tmax);
   }
   for_each_acc<2, 2>(n0, lane, [&](int tj, int ti, int r, int col, int, int row) { X[row * FP + col] = acc[ti][tj][r] * s; });
-  mm.request(W1T, FH, n0, lane);
   lds_barrier();
   // ---- zc_0 = (zc_1 W_1) * relu'(ac_0) ----
   mm.run(X, W1T, FH, n0, lane, acc, W0T, FH, n0);   // (its tail requests the first weight steps of the product after it)
@@ -400,6 +453,10 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
   lds_barrier();
   // ---- cinb = zc_0 W_0: the feature columns 0 .. 255 (the FB sweep's input, the feature head's weight gradient) ----
   const float unscale0 = inv * h2_iws_at(iwsv, g.id0);
+  // (the first weight steps of the encoding-column product are requested here, ahead of the store burst between the two
+  // products: its waits then leave those stores in flight)
+  X3Mma<1, 1, 2> mq;
+  mq.request(W0T, FH, g.F + 32 * (wave >> 1), lane);
   mm.run(X, W0T, FH, n0, lane, acc, nullptr, 0, 0);
   {
     const int lane_e = opaque_lane(lane);
@@ -416,9 +473,7 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
   // ---- ... and the 64 encoding columns F .. F + 63: four 32 x 32 blocks, one per wave (row half, column half) ----
   v16f pacc[1][1];
   {
-    X3Mma<1, 1, 2> mq;
     const int rt = wave & 1, ct = wave >> 1;
-    mq.request(W0T, FH, g.F + 32 * ct, lane);
     mq.run(X + rt * 32 * FP, W0T, FH, g.F + 32 * ct, lane, pacc, nullptr, 0, 0);
   }
   lds_barrier();   // every wave has finished reading zc_0: the tile becomes scratch

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     // speculatively on the fixed scale and is redone on the rare tile that needed another one
     [[maybe_unused]] int pend = 0;
     if constexpr (H2 && (RNB_H2_GUARD_AB == 0 || RNB_H2_GUARD_AB == 3)) {
-      if (l > 0) pend = *reinterpret_cast<const volatile int*>(&ovf[(l - 1) & 1]);
+      if (l > 0) pend = h2_flag_read(&ovf[(l - 1) & 1]);
     }
     // x2h: accumulator -> pre-activation: 1 / (scale of the tile x scale of this layer's matrix in the mirror)
 #if RNB_H2_GUARD_AB == 3   // (timing experiment only: the round-4 literal instead of the runtime factor)
@@ -161,6 +161,20 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
 #else
     [[maybe_unused]] float inv = H2 ? isa * h2_iws_at(iwsv, l) : 1.f;
 #endif
+    // What the epilogue reads from memory is requested HERE, above the matrix loop: the wave's bias values (columns n0 + cl,
+    // n0 + 32 + cl) and the layer's entries of the argument block.  The vector-memory counter covers loads and stores alike
+    // and retires in issue order: read inside the epilogue, the bias cost a wait for everything before it — the next layer's
+    // weight fragments requested by mm.run and, for the second column tile, the first one's burst of saved-state stores.
+    const float* bias = g.packed + g.net.b_off[l];
+    float bcv[TJ];
+#pragma unroll
+    for (int tj = 0; tj < TJ; ++tj) bcv[tj] = bias[n0 + tj * 32 + cl];
+    // saved state goes out through buffer stores: one 32-bit lane offset per column tile plus a
+    // compile-time row offset in the scalar operand (plain pointer stores cost a 64-bit VGPR address
+    // pair per element, i.e. 128 extra registers and spills)
+    const BufRsrc ra = tile_rsrc(SAVE ? g.a[l] + (size_t)row0 * FH : nullptr, FT * FH * 4);
+    const BufRsrc rD = tile_rsrc(SAVE ? g.D[l] + (size_t)row0 * FH : nullptr, FT * FH * 4);
+    const int n_real = g.net.n_real[l];
     if constexpr (X3) {   // the next product's first weight steps are requested before this layer's epilogue
       const x3raw* wn = l + 1 < g.net.nh ? g.w3 + WP * g.net.w_off[l + 1] : (g.with_feat ? g.w3 + WP * g.net.wf_off : nullptr);
       mm.run(X, g.w3 + WP * g.net.w_off[l], g.net.Kp[l], n0, lane, acc, wn, FH, n0);
@@ -177,13 +191,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
       }
     } else layer_mma_nt<TI, NoHook, TJ>(X, g.packed + g.net.w_off[l], g.net.Kp[l], n0, lane, acc);
     if constexpr (NBUF == 1) lds_barrier();   // every wave has finished reading the input activations
-    const float* bias = g.packed + g.net.b_off[l];
-    // saved state goes out through buffer stores: one 32-bit lane offset per column tile plus a
-    // compile-time row offset in the scalar operand (plain pointer stores cost a 64-bit VGPR address
-    // pair per element, i.e. 128 extra registers and spills)
-    const BufRsrc ra = tile_rsrc(SAVE ? g.a[l] + (size_t)row0 * FH : nullptr, FT * FH * 4);
-    const BufRsrc rD = tile_rsrc(SAVE ? g.D[l] + (size_t)row0 * FH : nullptr, FT * FH * 4);
-    const int n_real = g.net.n_real[l];
     const bool pe_tail = (l + 1 == g.net.skip);
     // x2h: max |.| of what this thread writes to the tile.  Softplus outputs are >= +0: ONE v_max3_i32 per pair of values
     // (h2_track2), no branch; the signed encoding columns of the one tile that carries the skip connection are tracked where
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
     auto column_tile = [&](auto full_c, int tj) {
       constexpr bool FULL = decltype(full_c)::value;
       const int col = n0 + tj * 32 + cl;
-      const float bc = bias[col];
+      const float bc = bcv[tj];
       const unsigned voff = (unsigned)(4 * h * FH + col) * 4u;
 #pragma unroll
       for (int ti = 0; ti < TI; ++ti) {
@@ -259,6 +266,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
 #pragma unroll
     for (int u = 0; u < 4; ++u) w[u] = ws[lane + 64 * u];
     const float bs = g.packed[g.net.bsdf_off];
+    // The butterfly leaves a row's sum in EVERY lane (a + b = b + a: the same bits in all of them): lane rr keeps row rr's, and
+    // the wave's FT / NW rows leave in one store behind the loop.  Stored row by row from lane 0, every row's look at `bs`
+    // (a load, as far as the wait counter knows) was a vmcnt(0) behind the previous row's store: up to 16 store round trips
+    // in a row per wave and tile (profiles/epilogue_waits_codegen.txt).
+    float mine = 0.f;
     for (int rr = 0; rr < FT / NW; ++rr) {
       const int row = wave * (FT / NW) + rr;
       float s = 0.f;
@@ -266,25 +278,29 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_forward_kernel
       for (int u = 0; u < 4; ++u) s = fmaf(X[row * FP + lane + 64 * u], w[u], s);
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if (lane == 0) {
-        const float v = (H2 ? __builtin_fmaf(s, isa, bs) : s + bs) / g.net.scale;
-        sweep_store_sdf(g.grid, g.sdf, row0, row, g.M, v);
-      }
+      if (lane == rr) mine = s;
+    }
+    if (lane < FT / NW) {
+      const float v = (H2 ? __builtin_fmaf(mine, isa, bs) : mine + bs) / g.net.scale;
+      sweep_store_sdf(g.grid, g.sdf, row0, wave * (FT / NW) + lane, g.M, v);
     }
   }
   // ---- feature head: rows 1.. of the output layer, written into the albedo network's input ------------
   if (g.with_feat) {
     [[maybe_unused]] const float inv = H2 ? isa * h2_iws_at(iwsv, g.net.nh) : 1.f;
+    const float* bias = g.packed + g.net.bf_off;
+    float bcv[TJ];   // (read above the matrix loop, like the hidden layers')
+#pragma unroll
+    for (int tj = 0; tj < TJ; ++tj) bcv[tj] = n0 + tj * 32 + cl < g.net.F ? bias[n0 + tj * 32 + cl] : 0.f;
     if constexpr (X3) mm.run(X, g.w3 + WP * g.net.wf_off, FH, n0, lane, acc, nullptr, 0, 0);   // (requested by the last hidden layer)
     else layer_mma_nt<TI, NoHook, TJ>(X, g.packed + g.net.wf_off, FH, n0, lane, acc);
-    const float* bias = g.packed + g.net.bf_off;
     const BufRsrc rc = tile_rsrc(g.cin + (size_t)row0 * g.net.Cinp, FT * g.net.Cinp * 4);
     const unsigned rowb = (unsigned)g.net.Cinp * 4u;   // bytes per row of the albedo-net input
 #pragma unroll
     for (int tj = 0; tj < TJ; ++tj) {
       const int col = n0 + tj * 32 + cl;
       if (col < g.net.F) {
-        const float bc = bias[col];
+        const float bc = bcv[tj];
         const unsigned voff = (unsigned)(4 * h) * rowb + (unsigned)col * 4u;
 #pragma unroll
         for (int ti = 0; ti < TI; ++ti) {

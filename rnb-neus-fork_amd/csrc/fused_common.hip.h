@@ -70,12 +70,24 @@ __device__ inline void h2_track2(int& m, float a, float b) {
   asm("v_max3_i32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(a), "v"(b));
 }
 // the waves of a workgroup agree on whether the tile just written needs a smaller scale: `mine` = this thread's maximum;
-// flag = one LDS word (zero unless raised; reset by the slow path)
+// flag = one LDS word (zero unless raised; reset by the slow path).
+// The word is read and written AS LDS (relaxed workgroup-scope accesses through an address-space pointer: ds_read_b32 /
+// ds_write_b32, counted by lgkmcnt alone).  Through a volatile generic pointer the read was a system-scope flat_load followed
+// at once by s_waitcnt vmcnt(0): a flat access counts on the vector-memory counter too, so every look at the flag waited for
+// the whole burst of saved-state stores before it and for the weight fragments requested ahead
+// (profiles/epilogue_waits_codegen.txt).  The barriers on either side (lds_barrier: a memory clobber) keep the accesses in place.
+typedef __attribute__((address_space(3))) int lds_int;
+__device__ inline int h2_flag_read(const int* flag) {   // (no wait here: the value is waited for where it is used)
+  return __hip_atomic_load((const lds_int*)flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ inline void h2_flag_write(int* flag, int v) {
+  __hip_atomic_store((lds_int*)flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 __device__ inline void h2_raise_flag(float mine, int* flag, int lane) {
-  if (__builtin_amdgcn_ballot_w64(mine >= kH2ActLimit) != 0 && lane == 0) *reinterpret_cast<volatile int*>(flag) = 1;
+  if (__builtin_amdgcn_ballot_w64(mine >= kH2ActLimit) != 0 && lane == 0) h2_flag_write(flag, 1);
 }
 __device__ inline bool h2_flag_up(const int* flag) {   // (expected down: the rescaling path is laid out off the hot path)
-  return __builtin_expect(__builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile int*>(flag)) != 0, 0);
+  return __builtin_expect(__builtin_amdgcn_readfirstlane(h2_flag_read(flag)) != 0, 0);
 }
 // The inverse scales of the mirror's matrices, one per lane (lane id = table id), loaded ONCE at the top of a kernel: a load
 // per layer would sit in the in-order vector-memory queue in front of that layer's weight fragments.  h2_iws_at picks a
