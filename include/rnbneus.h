@@ -469,7 +469,12 @@ int rnb_marching_cubes_emit(const float* volume, int32_t nx, int32_t ny, int32_t
                             void* workspace, size_t workspace_bytes, int64_t n_vertices, int64_t n_triangles,
                             double* vertices, int32_t* triangles, rnb_stream_t stream);
 
-/* Ray / target generation of one train_rnb step on the device: what Dataset.ps_gen_random_rays_at_view_on_all_lights
+/* The four rnb_gen_rays_* calls below that make rays are one kernel (csrc/raygen.hip) behind one set of checks: a front, the
+ * pixel list of a train step (_at_view) or a range of a whole view's grid (_grid), and the targets, gathered from the finished
+ * stacks or computed from the view's source maps (_from_maps).  The pixel-to-ray arithmetic exists once; it is unfused float32
+ * with IEEE sqrt and division, the same bits whatever the front and the targets.
+ *
+ * Ray / target generation of one train_rnb step on the device: what Dataset.ps_gen_random_rays_at_view_on_all_lights
  * (models/dataset.py:351-376), the per-pixel light gather (exp_runner.py:214-220) and near_far_from_sphere
  * (models/dataset.py:448-458) compute on the host, for one view whose tensors are resident in device memory.
  *   intrinsics_inv, pose [4,4] row-major (intrinsics_all_inv[img_idx], pose_all[img_idx]);

@@ -8,16 +8,17 @@
 
 namespace rnb {
 
-// The ray arithmetic every kernel of this file shares, so that stack mode and source mode give the same bits.
-// p = Kinv[:3,:3] (x, y, 1) (dataset.py:365-367; same left-to-right accumulation as a 3-term dot product),
-// rays_v = R p / ||p||, rays_o = t (dataset.py:369-373)
-// (camera_adjoint_kernel below repeats these lines operand by operand, because it also needs v and ||p||: keep the two in step)
-__device__ __forceinline__ void ray_through(const float* kinv, const float* pose, float fx, float fy, float o[3], float d[3]) {
+// The pixel-to-ray arithmetic, written once: the forward kernel and camera_adjoint_kernel both call it, so stack mode and
+// source mode give the same bits and the adjoint differentiates exactly what the forward computed.
+// p = Kinv[:3,:3] (x, y, 1) (dataset.py:365-367; same left-to-right accumulation as a 3-term dot product), nrm = ||p||,
+// v = p / nrm, rays_v = d = R v, rays_o = o = t (dataset.py:369-373).  `kinv`, `pose`: row-major [4,4] (or their first 3 rows).
+__device__ __forceinline__ void pixel_ray(const float* kinv, const float* pose, float fx, float fy, float& nrm, float v[3],
+                                          float o[3], float d[3]) {
   float p[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) p[r] = kinv[r * 4 + 0] * fx + kinv[r * 4 + 1] * fy + kinv[r * 4 + 2] * 1.f;
-  const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-  float v[3] = {p[0] / nrm, p[1] / nrm, p[2] / nrm};
+  nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+  v[0] = p[0] / nrm; v[1] = p[1] / nrm; v[2] = p[2] / nrm;
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     d[r] = pose[r * 4 + 0] * v[0] + pose[r * 4 + 1] * v[1] + pose[r * 4 + 2] * v[2];
@@ -48,83 +49,62 @@ __device__ __forceinline__ int64_t nearest_pixel(float fx, float fy, int H, int 
   return y * W + x;
 }
 
-struct RayGenArgs {
-  const float* kinv;       // [4,4] inverse intrinsics of the view (row-major)
-  const float* pose;       // [4,4] camera-to-world pose of the view
-  const float* images;     // [L,H,W,3] or NULL
-  const float* images_wu;  // [L,H,W,3] or NULL
-  const float* mask;       // [H,W,Cm]
-  const float* lights;     // [L,H,W,3] or NULL
-  const int64_t* px;       // [B]
-  const int64_t* py;       // [B]
-  int64_t B;
-  int L, H, W, Cm;
-  float* data;             // [B,7] = rays_o | rays_v | mask[..., :1]      (dataset.py:376)
-  float* rgb;              // [L,B,3] or NULL
-  float* rgb_wu;           // [L,B,3] or NULL
-  float* lights_out;       // [L,B,3] or NULL
-  float* near;             // [B] or NULL                                 (dataset.py:448-458)
-  float* far;              // [B] or NULL
+// One launch makes rays [0, n) of one of two fronts with one of two target sources (four instantiations of raygen_kernel):
+//   front    list: the integer pixels px[b], py[b] of a train step (dataset.py:351-376), gathers at y * W + x (the indices
+//                  are range-checked in Python), all lights.
+//            grid: rays [first, first + n) of the row-major Hl x Wl grid of a whole view (gen_rays_at / gen_rays_between,
+//                  dataset.py:300-326, :401-446) at the float coordinates tx, ty, gathers at the rounded pixel
+//                  (exp_runner.py:409-410: pixels.round().long()), all lights or the one light `light`.
+//   targets  stack: mask, colours and lights gathered from the finished stacks of Dataset.__init__.
+//            maps:  the same computed from the view's normal / albedo / mask maps (source mode, below).
+struct RayArgs {           // (what every instantiation reads comes first: these small kernels wait on their argument loads)
+  const float* kinv;       // [4,4] inverse intrinsics (row-major)
+  const float* pose;       // [4,4] camera-to-world pose of the rays (grid: may be an interpolated one)
+  const int64_t* px;       // list: [n]
+  const int64_t* py;       // list: [n]
+  int64_t n;               // rays of this launch
+  int L, H, W, Cm;         // (maps: L, H, W are the source's, filled in by launch_rays)
+  float* data;             // [n,7] = rays_o | rays_v | mask[..., :1]      (dataset.py:376)
+  float* rgb;              // [Lo,n,3] or NULL (Lo = L, or 1 with light >= 0)
+  float* rgb_wu;           // [Lo,n,3] or NULL
+  float* lights_out;       // [Lo,n,3] or NULL
+  float* near;             // [n] or NULL                                 (dataset.py:448-458)
+  float* far;              // [n] or NULL
+  rnb_source_maps_t src;   // maps (filled in by launch_rays)
+  const float* view_pose;  // grid + maps: [4,4] pose of the view the maps belong to (rotates its lights to world space)
+  const float* tx;         // grid: [Wl] pixel x of a grid column
+  const float* ty;         // grid: [Hl] pixel y of a grid row
+  int64_t first;           // grid
+  int Wl;                  // grid
+  int light;               // grid: one light, or -1 = all
+  const float* images;     // stack: [L,H,W,3] or NULL
+  const float* images_wu;  // stack: [L,H,W,3] or NULL
+  const float* mask;       // stack: [H,W,Cm], or NULL (grid: the pose-only view, mask 0)
+  const float* lights;     // stack: [L,H,W,3] or NULL
 };
 
-__global__ void raygen_kernel(RayGenArgs g) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= g.B) return;
-  const int64_t x = g.px[b], y = g.py[b];
-  float d[3], o[3];
-  ray_through(g.kinv, g.pose, (float)x, (float)y, o, d);
-  const int64_t pix = y * g.W + x;
-  store_ray(g.data, g.near, g.far, b, o, d, g.mask[pix * g.Cm]);
-  const int64_t plane = (int64_t)g.H * g.W * 3;
-  for (int l = 0; l < g.L; ++l) {
-    const int64_t src = l * plane + pix * 3;
-    const int64_t dst = ((int64_t)l * g.B + b) * 3;
-    if (g.rgb) { g.rgb[dst] = g.images[src]; g.rgb[dst + 1] = g.images[src + 1]; g.rgb[dst + 2] = g.images[src + 2]; }
-    if (g.rgb_wu) {
-      g.rgb_wu[dst] = g.images_wu[src]; g.rgb_wu[dst + 1] = g.images_wu[src + 1]; g.rgb_wu[dst + 2] = g.images_wu[src + 2];
-    }
-    if (g.lights_out) {
-      g.lights_out[dst] = g.lights[src]; g.lights_out[dst + 1] = g.lights[src + 1]; g.lights_out[dst + 2] = g.lights[src + 2];
-    }
+// the front: pixel coordinates of ray b and the pixel its targets come from
+template <bool GRID>
+__device__ __forceinline__ int64_t front_pixel(const RayArgs& g, int64_t b, float& fx, float& fy) {
+  if constexpr (GRID) {
+    const int64_t i = g.first + b;
+    const int64_t iy = i / g.Wl;
+    fx = g.tx[i - iy * g.Wl];
+    fy = g.ty[iy];
+    return nearest_pixel(fx, fy, g.H, g.W);
+  } else {
+    const int64_t x = g.px[b], y = g.py[b];
+    fx = (float)x;
+    fy = (float)y;
+    return y * g.W + x;
   }
 }
 
-// Whole views (gen_rays_at / gen_rays_between, models/dataset.py:300-326, :401-446): the same arithmetic in the same order
-// on float pixel coordinates, gathers at the rounded pixel (exp_runner.py:409-410: pixels.round().long()).
-struct RayGridArgs {
-  const float* kinv;       // [4,4]
-  const float* pose;       // [4,4]
-  const float* tx;         // [Wl] pixel x of a grid column
-  const float* ty;         // [Hl] pixel y of a grid row
-  const float* images;     // [L,H,W,3] or NULL
-  const float* images_wu;  // [L,H,W,3] or NULL
-  const float* mask;       // [H,W,Cm] or NULL
-  const float* lights;     // [L,H,W,3] or NULL
-  int64_t first, n;        // rays [first, first + n) of the row-major Hl x Wl grid
-  int Wl, L, light, H, W, Cm;
-  float* data;             // [n,7]
-  float* rgb;              // [Lo,n,3] or NULL (Lo = L, or 1 with light >= 0)
-  float* rgb_wu;
-  float* lights_out;
-  float* near;             // [n] or NULL
-  float* far;
-};
-
-__global__ void raygen_grid_kernel(RayGridArgs g) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= g.n) return;
-  const int64_t i = g.first + b;
-  const int64_t iy = i / g.Wl;
-  const float fx = g.tx[i - iy * g.Wl], fy = g.ty[iy];
-  float d[3], o[3];
-  ray_through(g.kinv, g.pose, fx, fy, o, d);
-  const int64_t pix = nearest_pixel(fx, fy, g.H, g.W);
-  store_ray(g.data, g.near, g.far, b, o, d, g.mask ? g.mask[pix * g.Cm] : 0.f);
+// stack targets: pixel `pix` of the lights [l0, l0 + Lo) gathered to row b of the [Lo, n, 3] outputs
+__device__ __forceinline__ void stack_targets(const RayArgs& g, int64_t pix, int l0, int Lo, int64_t b) {
   const int64_t plane = (int64_t)g.H * g.W * 3;
-  const int Lo = g.light < 0 ? g.L : 1;
   for (int lo = 0; lo < Lo; ++lo) {
-    const int l = g.light < 0 ? lo : g.light;
-    const int64_t src = l * plane + pix * 3;
+    const int64_t src = (l0 + lo) * plane + pix * 3;
     const int64_t dst = ((int64_t)lo * g.n + b) * 3;
     if (g.rgb) { g.rgb[dst] = g.images[src]; g.rgb[dst + 1] = g.images[src + 1]; g.rgb[dst + 2] = g.images[src + 2]; }
     if (g.rgb_wu) {
@@ -219,66 +199,26 @@ __device__ __forceinline__ void source_targets(const rnb_source_maps_t& s, const
   }
 }
 
-struct RayGenMapsArgs {
-  const float* kinv;       // [4,4]
-  const float* pose;       // [4,4] the view's pose: rays and lights
-  rnb_source_maps_t src;
-  const int64_t* px;       // [B]
-  const int64_t* py;       // [B]
-  int64_t B;
-  float* data;             // [B,7]
-  float* rgb;              // [L,B,3] or NULL
-  float* rgb_wu;           // [L,B,3] or NULL
-  float* lights_out;       // [L,B,3] or NULL
-  float* near;             // [B] or NULL
-  float* far;
-};
-
-__global__ void raygen_maps_kernel(RayGenMapsArgs g) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= g.B) return;
-  const int64_t x = g.px[b], y = g.py[b];
-  float d[3], o[3];
-  ray_through(g.kinv, g.pose, (float)x, (float)y, o, d);
-  const int64_t pix = y * g.src.W + x;
-  store_ray(g.data, g.near, g.far, b, o, d, source_mask(g.src, pix));
-  if (g.rgb || g.rgb_wu || g.lights_out)
-    source_targets(g.src, g.pose, pix, 0, g.src.n_lights, g.B, b, g.rgb, g.rgb_wu, g.lights_out);
-}
-
-struct RayGridMapsArgs {
-  const float* kinv;       // [4,4]
-  const float* pose;       // [4,4] pose of the rays (may be an interpolated one)
-  const float* view_pose;  // [4,4] pose of the view the maps belong to: rotates its lights to world space
-  const float* tx;         // [Wl]
-  const float* ty;         // [Hl]
-  rnb_source_maps_t src;
-  int64_t first, n;
-  int Wl, light;
-  float* data;             // [n,7]
-  float* rgb;              // [Lo,n,3] or NULL
-  float* rgb_wu;
-  float* lights_out;
-  float* near;             // [n] or NULL
-  float* far;
-};
-
-__global__ void raygen_grid_maps_kernel(RayGridMapsArgs g) {
+template <bool GRID, bool MAPS>
+__global__ void raygen_kernel(RayArgs g) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= g.n) return;
-  const int64_t i = g.first + b;
-  const int64_t iy = i / g.Wl;
-  const float fx = g.tx[i - iy * g.Wl], fy = g.ty[iy];
-  float d[3], o[3];
-  ray_through(g.kinv, g.pose, fx, fy, o, d);
-  const int64_t pix = nearest_pixel(fx, fy, g.src.H, g.src.W);
-  store_ray(g.data, g.near, g.far, b, o, d, source_mask(g.src, pix));
-  if (g.rgb || g.rgb_wu || g.lights_out)
-    source_targets(g.src, g.view_pose, pix, g.light < 0 ? 0 : g.light, g.light < 0 ? g.src.n_lights : 1, g.n, b, g.rgb,
-                   g.rgb_wu, g.lights_out);
+  float fx, fy, nrm, v[3], o[3], d[3];
+  const int64_t pix = front_pixel<GRID>(g, b, fx, fy);
+  pixel_ray(g.kinv, g.pose, fx, fy, nrm, v, o, d);
+  const int l0 = GRID && g.light >= 0 ? g.light : 0;
+  const int Lo = GRID && g.light >= 0 ? 1 : g.L;
+  if constexpr (MAPS) {
+    store_ray(g.data, g.near, g.far, b, o, d, source_mask(g.src, pix));
+    if (g.rgb || g.rgb_wu || g.lights_out)
+      source_targets(g.src, GRID ? g.view_pose : g.pose, pix, l0, Lo, g.n, b, g.rgb, g.rgb_wu, g.lights_out);
+  } else {
+    store_ray(g.data, g.near, g.far, b, o, d, g.mask ? g.mask[pix * g.Cm] : 0.f);
+    stack_targets(g, pix, l0, Lo, b);
+  }
 }
 
-// the checks both source-mode entry points share (before any launch)
+// the source maps' own checks (check_rays)
 static int check_source_maps(const char* who, const rnb_source_maps_t* src) {
   if (!src) RNB_FAIL(RNB_E_NULL, "%s: NULL source maps", who);
   if (!src->normals || !src->mask) RNB_FAIL(RNB_E_NULL, "%s: NULL normals or mask", who);
@@ -294,7 +234,7 @@ static int check_source_maps(const char* who, const rnb_source_maps_t* src) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Camera adjoint: d loss / d pose and d loss / d intrinsics_inv from the adjoints of what ray_through + store_ray (and,
+// Camera adjoint: d loss / d pose and d loss / d intrinsics_inv from the adjoints of what pixel_ray + store_ray (and,
 // in source mode, the light rotation of source_targets) made of them.  Per ray, recomputed from its pixel:
 //   p = Kinv[:3,:3] (x, y, 1), n = |p|, v = p / n, d = R v, o = t, a = d.d, mid = -(o.d) / a, near / far = mid -+ 1
 //   m_bar = near_bar + far_bar;  o_bar += -m_bar d / a;  d_bar += -m_bar o / a + 2 m_bar (o.d) d / a^2
@@ -334,25 +274,16 @@ __global__ __launch_bounds__(kCamAdjThreads) void camera_adjoint_kernel(CameraAd
   float acc[kCamAdjTerms];
 #pragma unroll
   for (int k = 0; k < kCamAdjTerms; ++k) acc[k] = 0.f;
-  float R[3][3];
+  float P[3][4];   // the pose's rotation | translation
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) R[r][c] = g.pose[r * 4 + c];
+    for (int c = 0; c < 4; ++c) P[r][c] = g.pose[r * 4 + c];
   const bool with_lights = g.lights != nullptr && g.lights_bar != nullptr;
   for (int64_t b = threadIdx.x; b < g.B; b += kCamAdjThreads) {
     const float q[3] = {(float)g.px[b], (float)g.py[b], 1.f};
-    float p[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) p[r] = g.kinv[r * 4 + 0] * q[0] + g.kinv[r * 4 + 1] * q[1] + g.kinv[r * 4 + 2] * 1.f;
-    const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-    const float v[3] = {p[0] / nrm, p[1] / nrm, p[2] / nrm};
-    float d[3], o[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      d[r] = R[r][0] * v[0] + R[r][1] * v[1] + R[r][2] * v[2];
-      o[r] = g.pose[r * 4 + 3];
-    }
+    float nrm, v[3], o[3], d[3];
+    pixel_ray(g.kinv, &P[0][0], q[0], q[1], nrm, v, o, d);
     float ob[3] = {0.f, 0.f, 0.f}, db[3] = {0.f, 0.f, 0.f};
     if (g.o_bar)
       for (int r = 0; r < 3; ++r) ob[r] = g.o_bar[b * 3 + r];
@@ -379,7 +310,7 @@ __global__ __launch_bounds__(kCamAdjThreads) void camera_adjoint_kernel(CameraAd
     if (g.kinv_bar) {
       float vb[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) vb[c] = R[0][c] * db[0] + R[1][c] * db[1] + R[2][c] * db[2];
+      for (int c = 0; c < 3; ++c) vb[c] = P[0][c] * db[0] + P[1][c] * db[1] + P[2][c] * db[2];
       const float vv = v[0] * vb[0] + v[1] * vb[1] + v[2] * vb[2];
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
@@ -395,7 +326,7 @@ __global__ __launch_bounds__(kCamAdjThreads) void camera_adjoint_kernel(CameraAd
         const float lb[3] = {g.lights_bar[at], g.lights_bar[at + 1], g.lights_bar[at + 2]};
         float lc[3];   // R^T l: the camera-space light the forward rotated
 #pragma unroll
-        for (int c = 0; c < 3; ++c) lc[c] = R[0][c] * lw[0] + R[1][c] * lw[1] + R[2][c] * lw[2];
+        for (int c = 0; c < 3; ++c) lc[c] = P[0][c] * lw[0] + P[1][c] * lw[1] + P[2][c] * lw[2];
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -448,25 +379,56 @@ RNB_API int rnb_gen_rays_camera_bwd(const float* intrinsics_inv, const float* po
   return RNB_OK;
 }
 
+// What the four forward entry points refuse (each message prefixed by the entry point's name), all before any launch.
+template <bool GRID, bool MAPS>
+static int check_rays(const char* who, const rnb::RayArgs& g, const rnb_source_maps_t* source, int Hl) {
+  using namespace rnb;
+  if (!g.kinv || !g.pose || !g.data || (GRID ? !g.tx || !g.ty : !g.px || !g.py) || (GRID && MAPS && !g.view_pose) ||
+      (!GRID && !MAPS && !g.mask))
+    RNB_FAIL(RNB_E_NULL, "%s: NULL pointer", who);
+  if (MAPS) RNB_TRY(check_source_maps(who, source));
+  else if ((g.rgb && !g.images) || (g.rgb_wu && !g.images_wu) || (g.lights_out && !g.lights))
+    RNB_FAIL(RNB_E_NULL, "%s: output requested without its source", who);
+  if ((g.near == nullptr) != (g.far == nullptr)) RNB_FAIL(RNB_E_NULL, "%s: near and far come together", who);
+  if (!MAPS && (g.L < 0 || g.H < 1 || g.W < 1 || (g.mask && g.Cm < 1)))
+    RNB_FAIL(RNB_E_INVALID, "%s: bad shape (L %d, H %d, W %d, mask channels %d)", who, g.L, g.H, g.W, g.Cm);
+  if (!GRID) {
+    if (g.n < 1) RNB_FAIL(RNB_E_INVALID, "%s: bad shape (B %lld)", who, (long long)g.n);
+    return RNB_OK;
+  }
+  if (g.Wl < 1 || Hl < 1) RNB_FAIL(RNB_E_INVALID, "%s: bad shape (grid %d x %d)", who, Hl, g.Wl);
+  if (g.first < 0 || g.n < 1 || g.first + g.n > (int64_t)Hl * g.Wl)
+    RNB_FAIL(RNB_E_INVALID, "%s: rays [%lld, %lld) outside the %d x %d grid", who, (long long)g.first,
+             (long long)(g.first + g.n), Hl, g.Wl);
+  const int L = MAPS ? source->n_lights : g.L;
+  if (g.light < -1 || g.light >= L)
+    RNB_FAIL(RNB_E_INVALID, "%s: light %d out of range (n_lights %d; -1 = all)", who, g.light, L);
+  return RNB_OK;
+}
+
+// The one launch path: the checks, then raygen_kernel<GRID, MAPS> over g.n rays.
+template <bool GRID, bool MAPS>
+static int launch_rays(const char* who, rnb::RayArgs g, const rnb_source_maps_t* source, int Hl, rnb_stream_t stream) {
+  using namespace rnb;
+  RNB_TRY((check_rays<GRID, MAPS>(who, g, source, Hl)));
+  if (MAPS) {
+    g.src = *source;
+    g.L = source->n_lights; g.H = source->H; g.W = source->W;
+  }
+  hipLaunchKernelGGL((raygen_kernel<GRID, MAPS>), dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
 RNB_API int rnb_gen_rays_at_view(const float* intrinsics_inv, const float* pose, const float* images,
                                  const float* images_warmup, const float* mask, int32_t mask_channels,
                                  const float* light_directions, const int64_t* pixels_x, const int64_t* pixels_y,
                                  int64_t B, int32_t n_lights, int32_t H, int32_t W, float* data, float* true_rgb,
                                  float* true_rgb_warmup, float* lights_dir, float* near, float* far,
                                  rnb_stream_t stream) {
-  using namespace rnb;
-  if (!intrinsics_inv || !pose || !mask || !pixels_x || !pixels_y || !data)
-    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_at_view: NULL pointer");
-  if ((true_rgb && !images) || (true_rgb_warmup && !images_warmup) || (lights_dir && !light_directions) ||
-      ((near == nullptr) != (far == nullptr)))
-    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_at_view: output requested without its source");
-  if (B < 1 || n_lights < 0 || H < 1 || W < 1 || mask_channels < 1)
-    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_at_view: bad shape (B %lld, L %d, H %d, W %d)", (long long)B, n_lights, H, W);
-  RayGenArgs g{intrinsics_inv, pose, images, images_warmup, mask, light_directions, pixels_x, pixels_y, B,
-               n_lights, H, W, mask_channels, data, true_rgb, true_rgb_warmup, lights_dir, near, far};
-  hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-  RNB_CHECK_LAUNCH();
-  return RNB_OK;
+  rnb::RayArgs g{intrinsics_inv, pose, pixels_x, pixels_y, B, n_lights, H, W, mask_channels, data, true_rgb, true_rgb_warmup,
+                 lights_dir, near, far, {}, nullptr, nullptr, nullptr, 0, 0, -1, images, images_warmup, mask, light_directions};
+  return launch_rays<false, false>("rnb_gen_rays_at_view", g, nullptr, 0, stream);
 }
 
 RNB_API int rnb_gen_rays_grid(const float* intrinsics_inv, const float* pose, const float* tx, const float* ty, int32_t Wl,
@@ -474,40 +436,18 @@ RNB_API int rnb_gen_rays_grid(const float* intrinsics_inv, const float* pose, co
                               const float* mask, int32_t mask_channels, const float* light_directions,
                               int32_t n_lights, int32_t light, int32_t H, int32_t W, float* data, float* true_rgb,
                               float* true_rgb_warmup, float* lights_dir, float* near, float* far, rnb_stream_t stream) {
-  using namespace rnb;
-  if (!intrinsics_inv || !pose || !tx || !ty || !data) RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid: NULL pointer");
-  if ((true_rgb && !images) || (true_rgb_warmup && !images_warmup) || (lights_dir && !light_directions) ||
-      ((near == nullptr) != (far == nullptr)))
-    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid: output requested without its source");
-  if (Wl < 1 || Hl < 1 || n_lights < 0 || H < 1 || W < 1 || (mask && mask_channels < 1))
-    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid: bad shape (grid %d x %d, L %d, H %d, W %d)", Hl, Wl, n_lights, H, W);
-  if (first < 0 || n < 1 || first + n > (int64_t)Hl * Wl)
-    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid: rays [%lld, %lld) outside the %d x %d grid", (long long)first,
-             (long long)(first + n), Hl, Wl);
-  if (light < -1 || light >= n_lights)
-    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid: light %d out of range (n_lights %d; -1 = all)", light, n_lights);
-  RayGridArgs g{intrinsics_inv, pose, tx, ty, images, images_warmup, mask, light_directions, first, n, Wl, n_lights,
-                light, H, W, mask_channels, data, true_rgb, true_rgb_warmup, lights_dir, near, far};
-  hipLaunchKernelGGL(raygen_grid_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-  RNB_CHECK_LAUNCH();
-  return RNB_OK;
+  rnb::RayArgs g{intrinsics_inv, pose, nullptr, nullptr, n, n_lights, H, W, mask_channels, data, true_rgb, true_rgb_warmup,
+                 lights_dir, near, far, {}, nullptr, tx, ty, first, Wl, light, images, images_warmup, mask, light_directions};
+  return launch_rays<true, false>("rnb_gen_rays_grid", g, nullptr, Hl, stream);
 }
 
 RNB_API int rnb_gen_rays_at_view_from_maps(const float* intrinsics_inv, const float* pose, const rnb_source_maps_t* source,
                                            const int64_t* pixels_x, const int64_t* pixels_y, int64_t B, float* data,
                                            float* true_rgb, float* true_rgb_warmup, float* lights_dir, float* near, float* far,
                                            rnb_stream_t stream) {
-  using namespace rnb;
-  if (!intrinsics_inv || !pose || !pixels_x || !pixels_y || !data)
-    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_at_view_from_maps: NULL pointer");
-  RNB_TRY(check_source_maps("rnb_gen_rays_at_view_from_maps", source));
-  if ((near == nullptr) != (far == nullptr))
-    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_at_view_from_maps: near and far come together");
-  if (B < 1) RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_at_view_from_maps: bad shape (B %lld)", (long long)B);
-  RayGenMapsArgs g{intrinsics_inv, pose, *source, pixels_x, pixels_y, B, data, true_rgb, true_rgb_warmup, lights_dir, near, far};
-  hipLaunchKernelGGL(raygen_maps_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-  RNB_CHECK_LAUNCH();
-  return RNB_OK;
+  rnb::RayArgs g{intrinsics_inv, pose, pixels_x, pixels_y, B, 0, 0, 0, 0, data, true_rgb, true_rgb_warmup, lights_dir, near, far,
+                 {}, nullptr, nullptr, nullptr, 0, 0, -1, nullptr, nullptr, nullptr, nullptr};
+  return launch_rays<false, true>("rnb_gen_rays_at_view_from_maps", g, source, 0, stream);
 }
 
 RNB_API int rnb_gen_rays_grid_from_maps(const float* intrinsics_inv, const float* pose, const float* view_pose,
@@ -515,21 +455,7 @@ RNB_API int rnb_gen_rays_grid_from_maps(const float* intrinsics_inv, const float
                                         const rnb_source_maps_t* source, int32_t light, float* data, float* true_rgb,
                                         float* true_rgb_warmup, float* lights_dir, float* near, float* far,
                                         rnb_stream_t stream) {
-  using namespace rnb;
-  if (!intrinsics_inv || !pose || !view_pose || !tx || !ty || !data)
-    RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid_from_maps: NULL pointer");
-  RNB_TRY(check_source_maps("rnb_gen_rays_grid_from_maps", source));
-  if ((near == nullptr) != (far == nullptr)) RNB_FAIL(RNB_E_NULL, "rnb_gen_rays_grid_from_maps: near and far come together");
-  if (Wl < 1 || Hl < 1) RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid_from_maps: bad shape (grid %d x %d)", Hl, Wl);
-  if (first < 0 || n < 1 || first + n > (int64_t)Hl * Wl)
-    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid_from_maps: rays [%lld, %lld) outside the %d x %d grid", (long long)first,
-             (long long)(first + n), Hl, Wl);
-  if (light < -1 || light >= source->n_lights)
-    RNB_FAIL(RNB_E_INVALID, "rnb_gen_rays_grid_from_maps: light %d out of range (n_lights %d; -1 = all)", light,
-             source->n_lights);
-  RayGridMapsArgs g{intrinsics_inv, pose, view_pose, tx, ty, *source, first, n, Wl, light, data, true_rgb, true_rgb_warmup,
-                    lights_dir, near, far};
-  hipLaunchKernelGGL(raygen_grid_maps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-  RNB_CHECK_LAUNCH();
-  return RNB_OK;
+  rnb::RayArgs g{intrinsics_inv, pose, nullptr, nullptr, n, 0, 0, 0, 0, data, true_rgb, true_rgb_warmup, lights_dir, near, far,
+                 {}, view_pose, tx, ty, first, Wl, light, nullptr, nullptr, nullptr, nullptr};
+  return launch_rays<true, true>("rnb_gen_rays_grid_from_maps", g, source, Hl, stream);
 }

@@ -10,15 +10,16 @@ a 200-view 1024^2 capture: 288 GB of HBM hold them all) and produces everything 
 `exp_runner.py:174-180` works unchanged on it; `pixels_x` / `pixels_y` may be passed in so that tests can use the
 reference's own draws.
 
-Whole views (`validate_image`, `render_novel_image`: exp_runner.py:389-558) come from one more kernel,
-`rnb_gen_rays_grid`: `gen_rays_at` / `gen_rays_between` are the reference's methods, `view_rays` gives any range of
+Whole views (`validate_image`, `render_novel_image`: exp_runner.py:389-558) come from the same kernel on its grid front
+(`rnb_gen_rays_grid`): `gen_rays_at` / `gen_rays_between` are the reference's methods, `view_rays` gives any range of
 a view's rays together with near / far and the gathers at the rounded pixel, one launch per call.
 
 Source mode (`DeviceRays.from_source_maps`): instead of the finished stacks of `Dataset.__init__` (27 floats and a mask
 float per pixel) the object keeps the capture's normal, albedo and mask maps in their own dtype (7 bytes per pixel as
-8-bit images) and the kernels `rnb_gen_rays_at_view_from_maps` / `rnb_gen_rays_grid_from_maps` compute lights and colours
-for the pixels they are asked for (include/rnbneus.h states the arithmetic).  Every method keeps its signature and return
-shapes.  `cameras_from_projections` is the reference's `load_K_Rt_from_P` without OpenCV."""
+8-bit images) and `rnb_gen_rays_at_view_from_maps` / `rnb_gen_rays_grid_from_maps` (the kernel's map targets) compute
+lights and colours for the pixels they are asked for (include/rnbneus.h states the arithmetic).  Every method keeps its
+signature and return shapes; all of them launch through `DeviceRays._ray_launch`.  `cameras_from_projections` is the
+reference's `load_K_Rt_from_P` without OpenCV."""
 from __future__ import annotations
 
 import ctypes as C
@@ -226,44 +227,65 @@ class DeviceRays:
                 torch._assert_async(ok.all())
         return pixels_x, pixels_y
 
-    def _launch(self, img_idx, pixels_x, pixels_y, want_rgb, want_warmup, want_lights, want_near_far, pose=None,
-                intrinsics_inv=None):
-        """`pose`, `intrinsics_inv`: [4,4] float32 contiguous device tensors used instead of the view's stored ones."""
-        B = pixels_x.numel()
-        L = self.n_lights
-        v = int(img_idx)
+    def _ray_launch(self, v, n, front, want_rgb, want_warmup, want_lights, want_near_far, pose=None, intrinsics_inv=None,
+                    view_pose=None, light=-1, targets=True):
+        """The one ray launch: `n` rays of view `v` from one of two fronts, `front` = (pixels_x, pixels_y) ([n] int64 device
+        tensors) or (tx, ty, first) (rays [first, first + n) of the row-major grid of the columns tx and the rows ty),
+        with the targets of the lights `light` (-1 = all; the pixel front always takes all).  `pose`,
+        `intrinsics_inv`, `view_pose` ([4,4] float32 contiguous device tensors): the camera of the rays and, for the grid
+        front in source mode, the pose that rotates the view's lights; None = the view's stored ones (`pose`: `view_pose`).
+        `targets` False: the pose-only view, no mask (0) and no gathers.  Allocates what is wanted and returns
+        (data [n,7], rgb, rgb_wu, lights [Lo,n,3], near, far [n,1]), None where not wanted."""
         if not 0 <= v < self.n_images:
             raise IndexError(f"img_idx {v} out of range (n_images {self.n_images})")
-        f32 = dict(dtype=torch.float32, device=self.device)
-        data = torch.empty(B, 7, **f32)
-        rgb = torch.empty(L, B, 3, **f32) if want_rgb else None
-        rgb_wu = torch.empty(L, B, 3, **f32) if want_warmup else None
-        lights = torch.empty(L, B, 3, **f32) if want_lights else None
-        near = torch.empty(B, 1, **f32) if want_near_far else None
-        far = torch.empty(B, 1, **f32) if want_near_far else None
-        pose = self.pose_all[v] if pose is None else pose
-        intrinsics_inv = self.intrinsics_all_inv[v] if intrinsics_inv is None else intrinsics_inv
-        if self.source_mode:
-            with native.on_device(data) as stream:
-                native.check(native.load().rnb_gen_rays_at_view_from_maps(
-                    native.ptr(intrinsics_inv), native.ptr(pose), C.byref(self._source(v)),
-                    native.ptr(pixels_x), native.ptr(pixels_y), B, native.ptr(data), native.ptr(rgb), native.ptr(rgb_wu),
-                    native.ptr(lights), native.ptr(near), native.ptr(far), stream))
-            return data, rgb, rgb_wu, lights, near, far
-        if want_warmup and self.images_warmup is None:
+        maps = targets and self.source_mode
+        if not maps and want_warmup and self.images_warmup is None:
             raise ValueError("DeviceRays was built without images_warmup")
-        if want_lights and self.light_directions is None:
+        if not maps and want_lights and self.light_directions is None:
             raise ValueError("DeviceRays was built without light_directions")
+        L, Lo = self.n_lights, (self.n_lights if light < 0 else 1)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        data = torch.empty(n, 7, **f32)
+        rgb = torch.empty(Lo, n, 3, **f32) if want_rgb else None
+        rgb_wu = torch.empty(Lo, n, 3, **f32) if want_warmup else None
+        lights = torch.empty(Lo, n, 3, **f32) if want_lights else None
+        near = torch.empty(n, 1, **f32) if want_near_far else None
+        far = torch.empty(n, 1, **f32) if want_near_far else None
+        view_pose = self.pose_all[v] if view_pose is None else view_pose
+        camera = (native.ptr(self.intrinsics_all_inv[v] if intrinsics_inv is None else intrinsics_inv),
+                  native.ptr(view_pose if pose is None else pose))
+        out = (native.ptr(data), native.ptr(rgb), native.ptr(rgb_wu), native.ptr(lights), native.ptr(near), native.ptr(far))
+        grid = len(front) == 3
+        if grid:
+            tx, ty, first, Wl, Hl = native.ptr(front[0]), native.ptr(front[1]), front[2], front[0].numel(), front[1].numel()
+        else:
+            px, py = native.ptr(front[0]), native.ptr(front[1])
+        lib = native.load()
         with native.on_device(data) as stream:
-            native.check(native.load().rnb_gen_rays_at_view(
-                native.ptr(intrinsics_inv), native.ptr(pose),
-                native.ptr(self.images[v]) if want_rgb else None,
-                native.ptr(self.images_warmup[v]) if want_warmup else None,
-                native.ptr(self.masks[v]), self.masks.shape[-1],
-                native.ptr(self.light_directions[v]) if want_lights else None,
-                native.ptr(pixels_x), native.ptr(pixels_y), B, L, self.H, self.W, native.ptr(data), native.ptr(rgb),
-                native.ptr(rgb_wu), native.ptr(lights), native.ptr(near), native.ptr(far), stream))
+            if maps:
+                source = C.byref(self._source(v))
+                if grid:
+                    rc = lib.rnb_gen_rays_grid_from_maps(*camera, native.ptr(view_pose), tx, ty, Wl, Hl, first, n, source, light,
+                                                         *out, stream)
+                else:
+                    rc = lib.rnb_gen_rays_at_view_from_maps(*camera, source, px, py, n, *out, stream)
+            else:
+                stacks = (native.ptr(self.images[v]) if want_rgb else None,
+                          native.ptr(self.images_warmup[v]) if want_warmup else None,
+                          native.ptr(self.masks[v]) if targets else None, self.masks.shape[-1],
+                          native.ptr(self.light_directions[v]) if want_lights else None)
+                if grid:
+                    rc = lib.rnb_gen_rays_grid(*camera, tx, ty, Wl, Hl, first, n, *stacks, L, light, self.H, self.W, *out, stream)
+                else:
+                    rc = lib.rnb_gen_rays_at_view(*camera, *stacks, px, py, n, L, self.H, self.W, *out, stream)
+            native.check(rc)
         return data, rgb, rgb_wu, lights, near, far
+
+    def _launch(self, img_idx, pixels_x, pixels_y, want_rgb, want_warmup, want_lights, want_near_far, pose=None,
+                intrinsics_inv=None):
+        """The pixel front (`pose`, `intrinsics_inv`: as `_ray_launch` takes them)."""
+        return self._ray_launch(int(img_idx), pixels_x.numel(), (pixels_x, pixels_y), want_rgb, want_warmup, want_lights,
+                                want_near_far, pose, intrinsics_inv)
 
     # ------------------------------------------------------------------ the reference's Dataset methods
     def ps_gen_random_rays_at_view_on_all_lights(self, img_idx, batch_size, pixels_x=None, pixels_y=None):
@@ -401,43 +423,20 @@ class DeviceRays:
         if not -1 <= li < L or (light is not None and li < 0):
             raise IndexError(f"light {light} out of range (n_lights {L})")
         Lo = L if li < 0 else 1
-        # the view's camera: the stored one, or the one `set_refinement` composes (forward only: detached)
-        with torch.no_grad():
-            view_pose, kinv, rot = self._camera(v)
-        view_pose = self.pose_all[v] if view_pose is None else _camera_matrix(view_pose, self.device)
-        kinv = self.intrinsics_all_inv[v] if kinv is None else _camera_matrix(kinv, self.device)
-        if pose is None:
-            if not gather:
-                raise ValueError("view_rays needs img_idx or pose")
-            pose_t = view_pose
-        else:
-            pose_t = torch.as_tensor(pose).to(device=self.device, dtype=torch.float32).reshape(4, 4).contiguous()
-        source = gather and self.source_mode
-        images = (self.images_warmup if warmup else self.images) if gather else None
-        if gather and warmup and images is None and not source:
-            raise ValueError("DeviceRays was built without images_warmup")
+        view_pose = kinv = rot = None       # the view's stored camera, unless `set_refinement` composes one
+        if self._refinement is not None:
+            with torch.no_grad():           # (forward only: detached)
+                view_pose, kinv, rot = self._camera(v)
+            view_pose = None if view_pose is None else _camera_matrix(view_pose, self.device)
+            kinv = None if kinv is None else _camera_matrix(kinv, self.device)
+        if pose is None and not gather:
+            raise ValueError("view_rays needs img_idx or pose")
+        if pose is not None:
+            pose = torch.as_tensor(pose).to(device=self.device, dtype=torch.float32).reshape(4, 4).contiguous()
         want_lights = gather and not warmup and self.has_lights()
-        f32 = dict(dtype=torch.float32, device=self.device)
-        data = torch.empty(n, 7, **f32)
-        near, far = torch.empty(n, 1, **f32), torch.empty(n, 1, **f32)
-        rgb = torch.empty(Lo, n, 3, **f32) if gather else None
-        lights = torch.empty(Lo, n, 3, **f32) if want_lights else None
-        with native.on_device(data) as stream:
-            if source:
-                native.check(native.load().rnb_gen_rays_grid_from_maps(
-                    native.ptr(kinv), native.ptr(pose_t), native.ptr(view_pose), native.ptr(tx),
-                    native.ptr(ty), Wl, Hl, first, n, C.byref(self._source(v)), li, native.ptr(data),
-                    None if warmup else native.ptr(rgb), native.ptr(rgb) if warmup else None, native.ptr(lights),
-                    native.ptr(near), native.ptr(far), stream))
-            else:
-                native.check(native.load().rnb_gen_rays_grid(
-                    native.ptr(kinv), native.ptr(pose_t), native.ptr(tx), native.ptr(ty), Wl, Hl, first,
-                    n, native.ptr(images[v]) if gather and not warmup else None,
-                    native.ptr(images[v]) if gather and warmup else None,
-                    native.ptr(self.masks[v]) if gather else None, self.masks.shape[-1],
-                    native.ptr(self.light_directions[v]) if want_lights else None, L, li, self.H, self.W, native.ptr(data),
-                    native.ptr(rgb) if gather and not warmup else None, native.ptr(rgb) if gather and warmup else None,
-                    native.ptr(lights), native.ptr(near), native.ptr(far), stream))
+        data, rgb, rgb_wu, lights, near, far = self._ray_launch(
+            v, n, (tx, ty, first), gather and not warmup, gather and warmup, want_lights, True, pose, kinv, view_pose, li, gather)
+        rgb = rgb_wu if warmup else rgb
         lights_dir = None
         if gather and warmup:
             if self.light_directions_warmup is None:
@@ -446,7 +445,7 @@ class DeviceRays:
             lw = lw if rot is None else _rotate(lw, rot)
             lights_dir = (lw if li < 0 else lw[li:li + 1]).reshape(Lo, 1, 1, 3)
         elif want_lights:
-            if rot is not None and not source:
+            if rot is not None and not self.source_mode:
                 lights = _rotate(lights, rot)
             lights_dir = lights.reshape(Lo, n, 1, 3)
         return {"rays_o": data[:, :3], "rays_d": data[:, 3:6], "mask": data[:, 6:7] if gather else None, "near": near,

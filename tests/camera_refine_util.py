@@ -1,5 +1,5 @@
 """Shared by tests/test_camera_refine_host.py and tests/test_gpu_camera_refine.py (not a test): a torch restatement, in
-whatever dtype its arguments have, of what the ray kernels make of a camera (csrc/raygen.hip ray_through + store_ray and
+whatever dtype its arguments have, of what the ray kernels make of a camera (csrc/raygen.hip pixel_ray + store_ray and
 the source-mode light rotation) and of `CameraRefinement.camera`, so that torch autograd in fp64 / fp32 gives the
 reference gradients; plus the fixtures' cameras and pixel draws.
 
@@ -42,7 +42,7 @@ def camera(delta, s, pose, kinv):
 
 
 def rays(kinv, pose, px, py):
-    """ray_through + store_ray: (rays_o [B,3], rays_d [B,3], near [B,1], far [B,1]) of the pixels (px, py)"""
+    """pixel_ray + store_ray: (rays_o [B,3], rays_d [B,3], near [B,1], far [B,1]) of the pixels (px, py)"""
     q = torch.stack([px.to(kinv.dtype), py.to(kinv.dtype), torch.ones(px.shape[0], dtype=kinv.dtype)], dim=-1)
     p = q @ kinv[:3, :3].T
     v = p / p.norm(dim=-1, keepdim=True)

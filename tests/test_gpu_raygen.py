@@ -1,12 +1,16 @@
 """GPU parity of the device-resident ray / target generation (rnb_gen_rays_at_view, DeviceRays) against the
 golden vectors of the reference's Dataset methods and against the oracle.  Gathers (colours, mask, lights) are
 bit-exact; ray directions / near / far within 1e-6 (a 3-term dot product whose fused / unfused evaluation is
-not specified by torch.matmul)."""
+not specified by torch.matmul); against the kernel's own stated arithmetic (tests/raygen_ref.py) they are bit-exact too."""
+import os
+
+import numpy as np
 import pytest
 import torch
 
 from oracle import rnb_oracle as O
-from tests.golden_util import load_raygen
+from tests import raygen_ref, source_maps_util
+from tests.golden_util import GOLDEN_DIR, load_raygen
 from tests.gpu_support import R  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -76,3 +80,55 @@ def test_device_draws_single_ray_and_bad_indices(R):
         dr.sample(0, 2, pixels_x=torch.tensor([0, dr.W]), pixels_y=torch.tensor([0, 0]))
     with pytest.raises(ValueError):
         dr.sample(0, 4, pixels_x=torch.tensor([1, 2]), pixels_y=torch.tensor([1, 2]))
+
+
+# ------------------------------------------------------------------------------------- the stated arithmetic, bit for bit
+def _ray_builds(R, front, targets):
+    """a DeviceRays on the fixture that drives one of the kernel's four instantiations"""
+    if targets == "maps":
+        fx = source_maps_util.load_fixture()
+        return R.DeviceRays.from_source_maps(fx["normals_u8"], fx["albedo_u8"], fx["masks_u8"], torch.from_numpy(
+            fx["intrinsics_inv"]), torch.from_numpy(fx["pose"]), "cuda:0")
+    if front == "list":
+        return _rays(R, load_raygen()[0])
+    z = np.load(os.path.join(GOLDEN_DIR, "image_rays_small.npz"), allow_pickle=False)
+    return _rays(R, {k: torch.from_numpy(z[k]) for k in z.files})
+
+
+def _assert_ray_bits(got, kinv, pose, x, y, what):
+    want = raygen_ref.pixel_rays(kinv.cpu().numpy(), np.asarray(pose.cpu() if torch.is_tensor(pose) else pose), x.cpu().numpy(),
+                                 y.cpu().numpy())
+    for k, w in zip(("rays_o", "rays_d", "near", "far"), want):
+        assert got[k].dtype == torch.float32 and torch.equal(got[k].cpu(), torch.from_numpy(w)), (what, k)
+
+
+@pytest.mark.parametrize("targets", ["stack", "maps"])
+@pytest.mark.parametrize("front", ["list", "grid"])
+def test_ray_bits_follow_the_stated_arithmetic(R, front, targets):
+    """rays_o, rays_d, near, far of every instantiation of the ray kernel (pixel list or grid range, stack gathers or
+    source maps) are the bits of tests/raygen_ref.py: float32, three-term sums left to right, IEEE sqrt and division, no
+    fused multiply-add.  List: B = 1, and B = 257 (a second 256-thread workgroup with one live lane).  Grid: a whole view
+    at level 1; at level 2 a range that starts and ends inside a row, with one light and with all; a pose-only call."""
+    dr = _ray_builds(R, front, targets)
+    if front == "list":
+        for v, B in ((0, 1), (2, 257)):
+            g = torch.Generator().manual_seed(5 + B)
+            px, py = torch.randint(0, dr.W, (B,), generator=g), torch.randint(0, dr.H, (B,), generator=g)
+            for warmup in (False, True):
+                s = dr.sample(v, B, warmup=warmup, pixels_x=px, pixels_y=py)
+                assert s["rays_d"].shape == (B, 3) and s["near"].shape == (B, 1)
+                _assert_ray_bits(s, dr.intrinsics_all_inv[v], dr.pose_all[v], px, py, (front, targets, B, warmup))
+        return
+    Wl = dr.W // 2
+    first, count = Wl + 2, 2 * Wl + 1          # starts at column 2 of row 1, ends after column 2 of row 3
+    assert first % Wl and (first + count) % Wl and first + count < (dr.H // 2) * Wl
+    calls = [(1, dict(resolution_level=1)), (0, dict(resolution_level=2, first=first, count=count, light=1)),
+             (2, dict(resolution_level=2, first=first, count=count))]
+    for v, kw in calls:
+        r = dr.view_rays(v, **kw)
+        assert r["rays_d"].shape[0] == kw.get("count", dr.H * dr.W) and r["true_rgb"].shape[0] == (1 if "light" in kw else 3)
+        _assert_ray_bits(r, dr.intrinsics_all_inv[v], dr.pose_all[v], r["pixels_x"], r["pixels_y"], (front, targets, kw))
+    pose = dr.pose_between(0, 2, 0.3)                                   # pose only: no mask, no targets (view 0's intrinsics)
+    r = dr.view_rays(pose=pose, resolution_level=2)
+    assert r["mask"] is None and r["true_rgb"] is None and r["rays_d"].shape[0] == (dr.H // 2) * Wl
+    _assert_ray_bits(r, dr.intrinsics_all_inv[0], pose, r["pixels_x"], r["pixels_y"], (front, targets, "pose only"))
