@@ -217,7 +217,7 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
                          hipStream_t s) {
   const Route& r = L.route;
   RNB_TRY(check_route_buffers(L, pb, parts));
-  RNB_TRY(dw_zero_partials(L, pb, parts, s));
+  RNB_TRY(dw_zero_partials(L, pb, s));
   // the weight-gradient jobs (dw.hip) follow every other launch of the backward; bf16_color_backward's are bf16_dw_backward's
   BwdParts dw_parts = parts;
   dw_parts.albedo = parts.albedo && r.color != COLOR_BF16;

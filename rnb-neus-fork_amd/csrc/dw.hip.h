@@ -63,9 +63,7 @@ struct DwJob {
   float* partb;
   int npairs, N, K, lddw, bias_pair, splits, rows_per_split, block_end;
 };
-constexpr int kMaxDwJobs = 12;
-constexpr int kMaxDwExtra = 2;   // reduce-only jobs (slabs written by other kernels) that ride in the reduction launch
-struct DwGroup {
+struct DwGroup {   // (kMaxDwJobs, kMaxDwExtra: dw_plan.h)
   DwJob job[kMaxDwJobs + kMaxDwExtra];
   int njobs, M;
 };
@@ -360,8 +358,7 @@ __global__ __launch_bounds__(256) void dw_reduce_kernel(const DwGroup g) {
 // next chunk's DMAs in flight while this one is multiplied.  The fragments are what the direct kernel loads from global: lane (i, h)
 // reads X[m + h][2i, 2i + 1] (8 bytes: the wave's two row tiles are the even / odd rows of its 64-row band) and
 // Y[m + h][i], Y[m + h][32 + i] — conflict-free ds_read_b64 / ds_read_b32.  Wave (wm, wn) = rows 64 wm.., columns 64 wn...
-constexpr int kStChunk = 32;                    // points per chunk
-constexpr int kStOpBytes = kStChunk * 256 * 4;  // one operand slab (32 KB)
+constexpr int kStOpBytes = kStChunk * 256 * 4;  // one operand slab (32 KB) of kStChunk points (dw_plan.h)
 constexpr int kStBufs = 2;                      // chunk c + 1 is copied while chunk c is multiplied
 
 __device__ inline void dw_staged_issue(const DwPair& p, int m_begin, int nchunks, int chunk, char* buf, int wave, int lane) {

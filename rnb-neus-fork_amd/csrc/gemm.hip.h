@@ -14,6 +14,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dw_plan.h"
+
 namespace rnb {
 
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -25,8 +27,7 @@ __device__ inline vf4 make_vf4(float a, float b, float c, float d) {
   return r;
 }
 
-constexpr int BM = 128;
-constexpr int BK = 32;
+constexpr int BM = 128;   // (BK, the points per main-loop step: dw_plan.h)
 constexpr int LDK = BK + 4;   // pitch (floats) of a k-contiguous tile  [rows][36]
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter,

@@ -204,7 +204,7 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
     }
     {
       const bool wc = (mode & PM_WITH_COLOR) != 0;
-      pb->dw_part_floats = dw_workspace_floats(L, M, wc);
+      pb->dw_part_floats = dw_workspace_floats(L, M, wc, &pb->dw_slab_off);
       pb->dw_part = c.take<float>(pb->dw_part_floats > 0 ? pb->dw_part_floats : 64);
       if (wc && L.route.color == COLOR_H2) pb->col_part = c.take<float>(color_h2_part_floats(L, M));
       pb->sdfh_part = c.take<float>((int64_t)kSdfHeadSlabs * (L.Hp + 1));

@@ -327,6 +327,7 @@ struct PointBufs {
                             // (float bits; zeroed by the first kernel of a render forward, grown by the forward sweeps)
   float* dw_part;           // partial slabs of the split-K weight-gradient GEMMs: [deterministic variant | staged kernel]
   int64_t dw_part_floats;
+  int64_t dw_slab_off;      // where the second part begins (floats): set with the buffer, read by dw_zero_partials / dw_backward
   unsigned* ac0_mask;       // fused albedo kernels: relu'(ac_0) as bits [tiles][256][2] (color_h2.hip)
   float* col_part;          // fused albedo backward: per-tile column sums of the output layer's gradient [tiles][Co][256] + [tiles][Co]
   float* sdfh_part;         // sdf-head row gradient: per-slab column sums [kSdfHeadSlabs][Hp] + [kSdfHeadSlabs]
@@ -402,12 +403,12 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
 int launch_sdf_xbar(const Layout& L, const float* packed, PointBufs& pb, bool with_normal, float* xbar, hipStream_t s);
 int launch_color_input_bwd(const Layout& L, const PointBufs& pb, float* pts_bar, float* nrm_bar, hipStream_t s);
 // ---- weight-gradient jobs of a backward (dw.hip) ----
-// floats of PointBufs::dw_part (carve_points) for a backward over M points
-int64_t dw_workspace_floats(const Layout& L, int64_t M, bool with_color);
+// floats of PointBufs::dw_part (carve_points) for a backward over M points, and the offset of its second part
+int64_t dw_workspace_floats(const Layout& L, int64_t M, bool with_color, int64_t* slab_off);
 // the one-workgroup-per-gradient kernel runs for this variant over M points (its slab reduction then sums the sdf-head row)
 bool dw_one_wg_runs(const Layout& L, int64_t M);
 // zeroes the deterministic variant's ordered-reduction slabs (before the backward's first launch)
-int dw_zero_partials(const Layout& L, const PointBufs& pb, const BwdParts& parts, hipStream_t s);
+int dw_zero_partials(const Layout& L, const PointBufs& pb, hipStream_t s);
 // queues and launches every weight-gradient job of a backward of these parts (its other launches are enqueued)
 int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, int sdfh_slabs, float* packed_grad, hipStream_t s);
 int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool store_ge = false);

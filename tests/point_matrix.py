@@ -5,21 +5,22 @@ runs it on the device through the direct network calls (SDFNetwork / RenderingNe
 along M are the fused sweeps (fused.hip, fused_bwd.hip: 32- or 64-point tiles over Mp = pad_rows(M)), the two albedo sweeps
 (color_h2.hip: 64-point tiles), and the weight gradients: gemm_dw_x3_kernel (dw.hip.h: one workgroup per (job, split), 16-point
 chunks, "the raw rows run TWO chunks ahead in two register sets") with its split plan (dw.hip dw_staged_plan, held to the slab
-room by DwBatch::flush_staged) and dw_reduce_kernel, or, when M is no multiple of kStChunk = 32, the guarded split-K kernels.
+room by dw_plan.h dw_make_plan) and dw_reduce_kernel, or, when M is no multiple of kStChunk = 32, the guarded split-K kernels.
 
 This module restates in Python the three rules that decide a row's path; it needs no library:
   pad_rows            rnb_internal.h kRowPad
   forward_family      fused.hip fused_forward: "64-point tiles when that still gives every CU >= 2 workgroups, 32-point tiles
                       for small batches", 8 waves while there is "at most one workgroup per CU"
-  staged_plan / plan  dw.hip dw_staged_plan and the loop of DwBatch::flush_staged over the jobs of dw_list, with the slab room
-                      of dw_sizes.  The job lists below are dw_list's for the descriptors the direct calls build
+  staged_plan / plan  dw_plan.h dw_staged_plan and the one-workgroup loop of dw_make_plan over the jobs of dw_list, with the slab
+                      room of its totals (DwPlan::slab_floats; tests/test_dw_plan_host.py holds both to the planner itself
+                      through tools/dw_plan_dump.hip).  The job lists below are dw_list's for the descriptors the direct calls build
                       (runtime.py: model_desc(net, None) with a 32-wide placeholder albedo net, whose layers are no x3 jobs;
                       _color_desc(net, 256, 6) with a one-layer placeholder SDF net).
 
 Backward kinds (KINDS): what one native backward runs.
   feature   rnb_sdf_backward, RNB_POINTS_FEATURE: the feature head and every hidden layer with ONE operand pair (zb_l / a_l-1);
             the workspace was sized for two pairs per hidden job, so layers 0 and 1 (the last the plan places) ask for more
-            slabs than are left: `splits > room` in flush_staged, from M = 1056 on
+            slabs than are left: `splits > room` in dw_make_plan, from M = 1056 on
   eikonal   rnb_sdf_backward, RNB_POINTS_NORMAL: every hidden layer with TWO pairs (gz_l / u_l and zb_l / in_l); the workspace
             is sized for exactly these jobs
   color     rnb_color_backward alone: three jobs (lin1; lin0 as a 256-column and a 64-column range) in a workspace sized
@@ -89,7 +90,7 @@ class Kind:
     name: str
     flags: str          # the RNB_POINTS_* flag of the native call
     jobs: tuple         # the backward's x3 jobs (dw_list with its BwdParts)
-    sized: tuple        # the jobs dw_sizes carves slabs for (BwdParts::render(with_color, false) on the call's descriptor)
+    sized: tuple        # the jobs dw_workspace_floats sizes slabs for (BwdParts::render(with_color, false) on the call's descriptor)
 
 
 KINDS = {
@@ -136,13 +137,13 @@ class JobPlan:
 
 
 def slab_room_floats(m: int, kind: Kind) -> int:
-    """dw_sizes' staged_floats: the slab part of PointBufs::dw_part"""
+    """DwPlan::slab_floats of the sized jobs: the slab part of PointBufs::dw_part"""
     total = sum(job_units(n, w) for w, n in kind.sized)
     return sum(staged_plan(m, job_units(n, w), total)[0] * (N_ROWS * w + N_ROWS) for w, n in kind.sized)
 
 
 def plan_kind(m: int, kind_name: str):
-    """The (job, split) layout of one backward of `kind_name` over m points (a multiple of 32): DwBatch::flush_staged."""
+    """The (job, split) layout of one backward of `kind_name` over m points (a multiple of 32): the one-workgroup group of dw_make_plan."""
     assert runs_x3(m)
     kind = KINDS[kind_name]
     jobs = list(reversed(kind.jobs))          # "most recently produced operands first"

@@ -234,7 +234,7 @@ def test_sample_rays_end_to_end_aggregate_rate(R):
 def test_more_weight_gradient_jobs_than_one_launch_group_holds(R):
     """A 12-hidden-layer SDF network and a 4-hidden-layer albedo network, all 256 wide: 17 weight-gradient jobs of the
     256-row kernel, more than the 12 one launch group carries, so the group is flushed mid-way and its slab workspace
-    must be handed to the next group (DwBatch::flush_staged).  One end-to-end step in a live state (tests/shape_matrix.py
+    must be handed to the next group (dw_plan.h dw_make_plan).  One end-to-end step in a live state (tests/shape_matrix.py
     live_params: no zero block, the PE columns of lin0 and the skip layer non-zero), every output and every parameter
     gradient against the oracle in fp64 with the calibrated bounds (gpu_support.step_against_fp64)."""
     from tests.shape_matrix import live_params

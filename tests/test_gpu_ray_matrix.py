@@ -225,7 +225,7 @@ def test_train_step_fused_sweeps(R, row):
 @pytest.mark.parametrize("B", [16, 32])
 def test_train_step_fused_sweeps_with_one_split_per_weight_gradient_job(R, B):
     """2+0 at 16 and 32 rays: 32 and 64 points, where every job of the one-workgroup weight-gradient kernel has a single
-    split and the slab workspace holds exactly one slab of each.  (Found by the z_vals.grad case at S = 2: DwBatch's
+    split and the slab workspace holds exactly one slab of each.  (Found by the z_vals.grad case at S = 2: the room clamp's
     equal-share rule computed a share of zero for a 256-column job followed by 64-column ones and refused the backward
     with "weight-gradient slab workspace exhausted".)  This state renders a surface at both sizes (weight_sum 0.49, 0.47)."""
     classes = _row_step(R, FUSED, M.BY_NAME["2+0"], B)

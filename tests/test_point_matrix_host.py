@@ -2,11 +2,13 @@
 cover every class of weight-gradient job the one-workgroup kernel distinguishes, both sides of each forward-family boundary
 appear, and the library's workspace query accepts every row for every flag set and variant tests/test_gpu_point_matrix.py uses.
 
-The limit of this file: the split plan restated in tests/point_matrix.py (dw_staged_plan and flush_staged's room clamp) is
-host code of the library with no entry point of its own.  What can be pinned here is its slab room: dw_sizes' share of
-rnb_points_grad_workspace_bytes, as the difference between two rows of one padded size
-(test_slab_room_matches_the_workspace_query).  The (job, split) layout itself meets the library only on the device, through
-the route assertion of tests/test_gpu_point_matrix.py (which kernel classes ran) and through the gradients those splits give."""
+The limit of this file: it needs nothing but the built library, and the split plan restated in tests/point_matrix.py
+(dw_plan.h dw_staged_plan and dw_make_plan's room clamp) is no entry point of it.  What is pinned here is its slab room: the
+plan's slab total in rnb_points_grad_workspace_bytes, as the difference between two rows of one padded size
+(test_slab_room_matches_the_workspace_query).  The (job, split) layout itself meets the planner in
+tests/test_dw_plan_host.py, which prints dw_make_plan's plan for the restated job shapes on the host (tools/dw_plan_dump.hip)
+and compares it with plan_kind row by row; on the device it is met again through the route assertion of
+tests/test_gpu_point_matrix.py (which kernel classes ran) and through the gradients those splits give."""
 import ctypes as C
 
 import pytest

@@ -1,6 +1,6 @@
 // Stand-alone timing of gemm_dw_x3_kernel (development aid; not part of the library).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/dwx3_bench.hip -o tools/dwx3_bench && tools/dwx3_bench [points]
-// 16 operand pairs of 256 x 256 gradients over M points, split like DwBatch::flush_staged (one round of 256 workgroups),
+// 16 operand pairs of 256 x 256 gradients over M points, split like the one-workgroup group of dw_make_plan (one round of 256 workgroups),
 // random operands.  Prints the launch time, the matrix-pipe share it implies at 2.4 GHz, and (stamped build of the same
 // kernel, DUMMY = 1) where wave 0 of a workgroup spends its clocks: barrier wait / chunk issue / load issue.
 #include <hip/hip_runtime.h>
