@@ -469,6 +469,51 @@ int rnb_marching_cubes_emit(const float* volume, int32_t nx, int32_t ny, int32_t
                             void* workspace, size_t workspace_bytes, int64_t n_vertices, int64_t n_triangles,
                             double* vertices, int32_t* triangles, rnb_stream_t stream);
 
+/* ---- Per-vertex attributes of validate_mesh_texture --------------------------------------------------
+ * What Runner.validate_mesh_texture (exp_runner.py:584-625) computes for every mesh vertex with sdf_network(v),
+ * sdf_network.gradient(v) and color_network(v, g, g, feat) in chunks on the host side: SDF, gradient, unit normal, albedo
+ * and the 8-bit vertex colour, for ANY number of vertices, in one call on the device.
+ * Vertices come either as `grid_vertices` (float64 grid-index coordinates, the array rnb_marching_cubes_emit writes; they
+ * are rescaled to the bounding box as models/renderer.py:34 does, then rounded to fp32:
+ *     p = (float)(v / (resolution - 1.0) * (double)(bound_max - bound_min) + (double)bound_min),
+ * bound_max - bound_min taken in fp32, multiply and add unfused — bit for bit the host's numpy expression followed by
+ * torch's conversion to float32) or as fp32 model-space `points` (copied).
+ * The library loops over chunks of `chunk` vertices (a positive multiple of 64) through ONE workspace of
+ * rnb_mesh_vertex_workspace_bytes(desc, chunk, flags) bytes, whatever V (stream order makes the reuse safe).  Per chunk:
+ * forward sweep (state saved) + reverse sweep on the model's kernel route; `refine` Newton steps towards the level set
+ *     p <- p - t g,   t = (sdf - level) / |g|^2,   displacement |t| |g| clamped to max_step,
+ * each followed by the two sweeps again (a point whose sdf or g is not finite, or with |g|^2 < 1e-12, is left where it
+ * is; max_step bounds the distance between the stored fp32 points, so the clamp is max_step less half an ulp of every
+ * coordinate); the albedo network ONCE at the final points, with g as its normal input, when RNB_MESH_ALBEDO is set; one epilogue
+ * kernel that writes the requested outputs.  Nothing is launched for V == 0.
+ *   rgb_out = (uint8) rintf(255 * min(max(a, 0), 1)) in fp32, channel order [2,1,0] with RNB_MESH_SWAP_RB (the reference's
+ *   BGR -> RGB swap); col_d_out == 1 replicates the one channel.
+ * RNB_E_INVALID before any launch: chunk not a positive multiple of 64; unknown flag bits; RNB_MESH_ALBEDO on a model
+ * without an albedo network; albedo_out or rgb_out without RNB_MESH_ALBEDO; rgb_out with col_d_out other than 1 or 3;
+ * refine < 0, or refine > 0 with max_step <= 0; V < 0; grid_vertices with resolution < 2; every output pointer NULL.
+ * RNB_E_NULL: both grid_vertices and points NULL (V > 0).  RNB_E_WORKSPACE: ws_bytes below the query's answer. */
+enum { RNB_MESH_ALBEDO = 1, RNB_MESH_SWAP_RB = 2 };
+typedef struct rnb_mesh_vertex_args {
+  const double* grid_vertices;  /* [V,3] grid-index coordinates as rnb_marching_cubes_emit writes them, or NULL */
+  const float* points;          /* [V,3] model-space points; read when grid_vertices is NULL */
+  int64_t V;
+  float bound_min[3], bound_max[3];
+  int32_t resolution;           /* bounds and resolution: used with grid_vertices only */
+  float level;                  /* SDF value of the surface: -threshold (the volume holds -sdf) */
+  int32_t refine;               /* Newton steps (0: evaluate where the vertices are) */
+  float max_step;               /* largest displacement of one Newton step (model units) */
+  int32_t flags;                /* RNB_MESH_* */
+  float* points_out;            /* [V,3] the points the attributes were evaluated at (after refinement) */
+  float* sdf_out;               /* [V] */
+  float* gradient_out;          /* [V,3] d sdf / d x, unnormalised (what the reference feeds the albedo net) */
+  float* normal_out;            /* [V,3] gradient / |gradient|; (0,0,0) where |gradient| is 0 or not finite */
+  float* albedo_out;            /* [V,col_d_out] raw network output */
+  uint8_t* rgb_out;             /* [V,3] */
+} rnb_mesh_vertex_args;         /* every output pointer may be NULL; at least one must not be */
+int rnb_mesh_vertex_workspace_bytes(const rnb_model_desc* desc, int64_t chunk, int32_t flags, int64_t* bytes);
+int rnb_mesh_vertex_attrs(const rnb_model_desc* desc, const float* packed, const rnb_mesh_vertex_args* args,
+                          int64_t chunk, void* ws, size_t ws_bytes, rnb_stream_t stream);
+
 /* The four rnb_gen_rays_* calls below that make rays are one kernel (csrc/raygen.hip) behind one set of checks: a front, the
  * pixel list of a train step (_at_view) or a range of a whole view's grid (_grid), and the targets, gathered from the finished
  * stacks or computed from the view's source maps (_from_maps).  The pixel-to-ray arithmetic exists once; it is unfused float32

@@ -21,10 +21,12 @@ from .optim import FlatAdam  # noqa: F401
 from .raygen import DeviceRays, cameras_from_projections  # noqa: F401
 from .mcubes import marching_cubes  # noqa: F401
 from .camera_refine import CameraRefinement  # noqa: F401
+from . import mesh_io  # noqa: F401
+from .mesh_io import read_ply, write_ply  # noqa: F401
 
 __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetwork", "NeRF", "get_embedder",
            "native", "build_from_named_params", "rnb_loss", "FlatAdam", "DeviceRays", "cameras_from_projections",
-           "marching_cubes", "CameraRefinement"]
+           "marching_cubes", "CameraRefinement", "mesh_io", "write_ply", "read_ply"]
 
 
 def build_from_named_params(mc, params, device):

@@ -331,6 +331,99 @@ RNB_API int rnb_color_backward(const rnb_model_desc* desc, const float* packed, 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// per-vertex mesh attributes (validate_mesh_texture): kernels in mesh_attrs.hip
+// ---------------------------------------------------------------------------------------------------
+struct MeshBufs {
+  float* pts;     // [chunk,3] the chunk's points (the Newton steps move them in place)
+  PointBufs pb;   // per-point state of `chunk` points: a forward-only render's (normal + colour)
+};
+
+static int check_mesh_chunk(int64_t chunk, int32_t flags) {
+  if (chunk <= 0 || chunk % 64 != 0) RNB_FAIL(RNB_E_INVALID, "mesh vertices: chunk must be a positive multiple of 64 (%lld)", (long long)chunk);
+  if (flags & ~(RNB_MESH_ALBEDO | RNB_MESH_SWAP_RB)) RNB_FAIL(RNB_E_INVALID, "mesh vertices: unknown flag bits (0x%x)", flags);
+  return RNB_OK;
+}
+
+static void carve_mesh(const Layout& L, Carver& c, int64_t chunk, MeshBufs* mb) {
+  mb->pts = c.take<float>(chunk * 3);
+  carve_points(L, c, chunk, kPointsMode, &mb->pb);
+}
+
+RNB_API int rnb_mesh_vertex_workspace_bytes(const rnb_model_desc* desc, int64_t chunk, int32_t flags, int64_t* bytes) {
+  RNB_REQUIRE(bytes, "bytes");
+  RNB_TRY(check_mesh_chunk(chunk, flags));
+  Layout L;
+  RNB_TRY(make_layout(desc, &L));
+  if ((flags & RNB_MESH_ALBEDO) && L.route.color == COLOR_NONE) RNB_FAIL(RNB_E_INVALID, "mesh vertices: RNB_MESH_ALBEDO on a model without an albedo network");
+  Carver c(nullptr, 0);
+  MeshBufs mb;
+  carve_mesh(L, c, chunk, &mb);
+  *bytes = (int64_t)c.off;
+  return RNB_OK;
+}
+
+RNB_API int rnb_mesh_vertex_attrs(const rnb_model_desc* desc, const float* packed, const rnb_mesh_vertex_args* a,
+                                  int64_t chunk, void* ws, size_t ws_bytes, rnb_stream_t stream) {
+  RNB_REQUIRE(packed, "packed");
+  RNB_REQUIRE(a, "args");
+  RNB_TRY(check_mesh_chunk(chunk, a->flags));
+  hipStream_t s = (hipStream_t)stream;
+  Layout L;
+  RNB_TRY(make_layout(desc, &L));
+  const bool albedo = (a->flags & RNB_MESH_ALBEDO) != 0;
+  if (albedo && L.route.color == COLOR_NONE) RNB_FAIL(RNB_E_INVALID, "mesh vertices: RNB_MESH_ALBEDO on a model without an albedo network");
+  if (!albedo && (a->albedo_out || a->rgb_out)) RNB_FAIL(RNB_E_INVALID, "mesh vertices: albedo_out / rgb_out without RNB_MESH_ALBEDO");
+  if (a->rgb_out && L.Co != 1 && L.Co != 3) RNB_FAIL(RNB_E_INVALID, "mesh vertices: rgb_out needs col_d_out 1 or 3 (%d)", L.Co);
+  if (a->refine < 0) RNB_FAIL(RNB_E_INVALID, "mesh vertices: refine < 0");
+  if (a->refine > 0 && !(a->max_step > 0.f)) RNB_FAIL(RNB_E_INVALID, "mesh vertices: refine > 0 needs max_step > 0 (%g)", (double)a->max_step);
+  if (a->V < 0) RNB_FAIL(RNB_E_INVALID, "mesh vertices: V < 0");
+  if (!(a->points_out || a->sdf_out || a->gradient_out || a->normal_out || a->albedo_out || a->rgb_out))
+    RNB_FAIL(RNB_E_INVALID, "mesh vertices: no output requested (every output pointer is NULL)");
+  if (a->grid_vertices && a->resolution < 2) RNB_FAIL(RNB_E_INVALID, "mesh vertices: grid_vertices of a resolution %d grid", a->resolution);
+  if (a->V == 0) return RNB_OK;
+  if (!a->grid_vertices) RNB_REQUIRE(a->points, "grid_vertices and points");
+  RNB_REQUIRE(ws, "workspace");
+  Carver c(ws, ws_bytes);
+  MeshBufs mb;
+  carve_mesh(L, c, chunk, &mb);
+  if (!c.ok) RNB_FAIL(RNB_E_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
+  MeshPointsSrc src;
+  memset(&src, 0, sizeof(src));
+  src.grid = a->grid_vertices;
+  src.pts = a->points;
+  src.rm1 = (double)a->resolution - 1.0;
+  for (int d = 0; d < 3; ++d) {
+    src.span[d] = a->bound_max[d] - a->bound_min[d];   // fp32, as the host's numpy does it
+    src.bmin[d] = a->bound_min[d];
+  }
+  MeshOut o;
+  memset(&o, 0, sizeof(o));
+  o.points = a->points_out; o.sdf = a->sdf_out; o.gradient = a->gradient_out; o.normal = a->normal_out;
+  o.albedo = a->albedo_out; o.rgb = a->rgb_out;
+  o.Co = L.Co;
+  o.swap_rb = (a->flags & RNB_MESH_SWAP_RB) ? 1 : 0;
+  // the state maxima of a saved forward, as a forward-only render keeps them (zeroed once: they only grow, nothing reads them)
+  RNB_CHECK_HIP(hipMemsetAsync(mb.pb.smax, 0, SMAX_SLOTS * sizeof(unsigned), s));
+  // every chunk through the one workspace: its kernels are enqueued behind the previous chunk's (stream order)
+  for (int64_t first = 0; first < a->V; first += chunk) {
+    const int64_t m = a->V - first < chunk ? a->V - first : chunk;
+    PointBufs pb = mb.pb;
+    pb.M = m;
+    pb.Mp = pad_rows(m);
+    RNB_TRY(launch_mesh_points(src, first, m, mb.pts, s));
+    for (int step = 0; step <= a->refine; ++step) {
+      if (step > 0) RNB_TRY(launch_mesh_newton(pb.sdf, pb.nrm, m, a->level, a->max_step, mb.pts, s));
+      // (the features feed the albedo network alone: only the sweep at the final points writes them)
+      RNB_TRY(forward_points(L, packed, mb.pts, m, pb, true, albedo && step == a->refine, true, nullptr, s));
+      RNB_TRY(reverse_points(L, packed, pb, false, s));
+    }
+    if (albedo) RNB_TRY(color_points(L, packed, pb, mb.pts, s));
+    RNB_TRY(launch_mesh_attrs(mb.pts, pb, first, m, o, s));
+  }
+  return RNB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // SDF grid (extract_fields)
 // ---------------------------------------------------------------------------------------------------
 constexpr int64_t kGridChunk = 1 << 20;   // points per pass of the generic (per-layer GEMM) path

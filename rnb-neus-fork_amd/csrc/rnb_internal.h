@@ -366,6 +366,32 @@ int launch_grid_points(const GridGen& g, int64_t first, int64_t n, float* pts, h
 int launch_scale_copy(const float* src, float scale, int64_t n, float* dst, hipStream_t s);
 int launch_grid_scatter(const GridGen& g, const float* src, int64_t first, int64_t n, float* dst, hipStream_t s);
 
+// ---- per-vertex mesh attributes (mesh_attrs.hip): the kernels around the point sweeps of rnb_mesh_vertex_attrs --------
+// where a chunk's points come from: grid-index float64 vertices (rescaled to the box: v / rm1 * span + bmin in float64,
+// span = bound_max - bound_min in fp32) or fp32 points (copied)
+struct MeshPointsSrc {
+  const double* grid;   // [V,3] or nullptr
+  const float* pts;     // [V,3], read when grid is nullptr
+  double rm1;           // resolution - 1
+  float span[3], bmin[3];
+};
+struct MeshOut {        // rnb_mesh_vertex_args' outputs (each may be nullptr)
+  float* points;
+  float* sdf;
+  float* gradient;
+  float* normal;
+  float* albedo;
+  uint8_t* rgb;
+  int Co;               // albedo width (col_d_out)
+  int swap_rb;
+};
+// vertices [first, first + n) -> pts [n,3]
+int launch_mesh_points(const MeshPointsSrc& src, int64_t first, int64_t n, float* pts, hipStream_t s);
+// one Newton step of pts [n,3] towards sdf = level, from the sweeps' sdf [n] and d sdf / d x [n,4]
+int launch_mesh_newton(const float* sdf, const float* nrm, int64_t n, float level, float max_step, float* pts, hipStream_t s);
+// rows [0, n) of the chunk's state (pb.sdf, pb.nrm, pb.alb) -> vertices [first, first + n) of the outputs
+int launch_mesh_attrs(const float* pts, const PointBufs& pb, int64_t first, int64_t n, const MeshOut& o, hipStream_t s);
+
 // ---- sparse SDF grid (sparse_grid.hip): brick bookkeeping around the forward sweeps' brick mode --------
 struct SparseGeom {
   int res, bs, nb, nl;   // grid samples, cells per brick edge, bricks and lattice points (nb + 1) per axis

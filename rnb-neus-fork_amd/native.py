@@ -25,6 +25,10 @@ POINTS_FEATURE = 1
 POINTS_NORMAL = 2
 POINTS_COLOR = 4
 
+# flags of rnb_mesh_vertex_attrs (include/rnbneus.h)
+MESH_ALBEDO = 1
+MESH_SWAP_RB = 2
+
 # rnb_model_desc.variant bits (include/rnbneus.h)
 VARIANT_BF16 = 1
 VARIANT_DETERMINISTIC = 2
@@ -89,6 +93,14 @@ class GridDesc(C.Structure):
 
 class SparseGridDesc(C.Structure):
     _fields_ = [("brick", C.c_int32), ("threshold", C.c_float), ("margin", C.c_float)]
+
+
+class MeshVertexArgs(C.Structure):
+    _fields_ = [("grid_vertices", C.c_void_p), ("points", C.c_void_p), ("V", C.c_int64),
+                ("bound_min", C.c_float * 3), ("bound_max", C.c_float * 3), ("resolution", C.c_int32),
+                ("level", C.c_float), ("refine", C.c_int32), ("max_step", C.c_float), ("flags", C.c_int32),
+                ("points_out", C.c_void_p), ("sdf_out", C.c_void_p), ("gradient_out", C.c_void_p),
+                ("normal_out", C.c_void_p), ("albedo_out", C.c_void_p), ("rgb_out", C.c_void_p)]
 
 
 SPARSE_BRICKS = (4, 8, 16, 32)
@@ -172,6 +184,9 @@ _SIGNATURES = {
                                            C.c_size_t, C.c_void_p, C.c_void_p]),
     "rnb_marching_cubes_emit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                           C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_vertex_workspace_bytes": (C.c_int, [_P(ModelDesc), C.c_int64, C.c_int32, _P(C.c_int64)]),
+    "rnb_mesh_vertex_attrs": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(MeshVertexArgs), C.c_int64, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
     "rnb_up_sample_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                      C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),

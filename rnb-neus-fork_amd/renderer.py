@@ -269,7 +269,8 @@ class NeuSRenderer:
         self.perturb = perturb
         # the reference reads self.color_depth without ever setting it (renderer.py:226; patched from
         # outside at exp_runner.py:125) — default it from the albedo network
-        self.color_depth = color_network.d_out
+        # (color_network None: a geometry-only renderer — extract_geometry, vertex_attributes without albedo)
+        self.color_depth = color_network.d_out if color_network is not None else None
         self.desc = model_desc(sdf_network, color_network, n_samples, n_importance, up_sample_steps)
         self.dp_group = None
         self.dp_exact = True
@@ -835,3 +836,92 @@ class NeuSRenderer:
             vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
         return vertices, triangles
+
+    # ------------------------------------------------------------------ textured mesh (validate_mesh_texture)
+    @torch.no_grad()
+    def vertex_attributes(self, points=None, *, grid_vertices=None, bounds=None, resolution=None, threshold=0.0, refine=0,
+                          max_step=None, albedo=None, chunk=65536):
+        """Per-vertex attributes on the device (`rnb_mesh_vertex_attrs`): what `validate_mesh_texture`
+        (exp_runner.py:601-613) gets from `sdf_network(v)`, `sdf_network.gradient(v)` and `color_network(v, g, g, feat)` per
+        host chunk — one forward, one reverse and one albedo sweep per chunk of `chunk` vertices on the model's kernel
+        route, through one workspace of the one-chunk size.
+        Vertices: fp32 model-space `points` [V,3], or float64 `grid_vertices` [V,3] as `marching_cubes` returns them with
+        `bounds` = (bound_min, bound_max) and `resolution` (rescaled on the device, bit for bit `extract_geometry`'s
+        expression converted to float32).  `refine` Newton steps move every vertex towards sdf = -threshold, each by at
+        most `max_step` (default with grid vertices: one cell diagonal; bare points must state it).
+        Returns device tensors `points` [V,3] (where the attributes were evaluated), `sdf` [V,1], `gradient` [V,3]
+        (unnormalised, the albedo net's normal input), `normal` [V,3] (unit, or 0) and, with the albedo network, `albedo`
+        [V,col_d_out] and `rgb` [V,3] uint8 = rint(255 clip(albedo[:, [2,1,0]], 0, 1)).  `albedo=None`: if the renderer has
+        the network.  Runs under no_grad whatever the caller's grad mode and is never collective under
+        `set_data_parallel`."""
+        if (points is None) == (grid_vertices is None):
+            raise ValueError("vertex_attributes: give either points or grid_vertices")
+        has_albedo = self.color_network is not None
+        albedo = has_albedo if albedo is None else bool(albedo)
+        if albedo and not has_albedo:
+            raise ValueError("vertex_attributes: albedo=True on a renderer without an albedo network")
+        refine = int(refine)
+        if refine < 0:
+            raise ValueError(f"vertex_attributes: refine must be >= 0, not {refine}")
+        lo = hi = None
+        if grid_vertices is not None:
+            if bounds is None or resolution is None:
+                raise ValueError("vertex_attributes: grid_vertices need bounds=(bound_min, bound_max) and resolution")
+            resolution = int(resolution)
+            if resolution < 2:
+                raise ValueError(f"vertex_attributes: a grid of resolution {resolution} has no cells")
+            lo, hi = ([float(b[d]) for d in range(3)] for b in bounds)
+            if max_step is None:
+                max_step = sum(((hi[d] - lo[d]) / (resolution - 1)) ** 2 for d in range(3)) ** 0.5
+        if refine > 0 and (max_step is None or not float(max_step) > 0.0):
+            raise ValueError("vertex_attributes: refine > 0 needs max_step > 0 (bare points have no cell size to default to)")
+        src = grid_vertices if grid_vertices is not None else points
+        dev = self.sdf_network.lin0.bias.device
+        if dev.type != "cuda":
+            raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+        if src.device != dev:
+            raise RuntimeError(f"NeuSRenderer: vertices live on {src.device} but the networks on {dev}")
+        return runtime.mesh_vertex_attrs(self.desc, self._pack(albedo), points=points, grid_vertices=grid_vertices,
+                                         bound_min=lo, bound_max=hi, resolution=resolution or 0, level=-float(threshold),
+                                         refine=refine, max_step=float(max_step) if max_step is not None else 0.0,
+                                         albedo=albedo, swap_rb=True, chunk=chunk)
+
+    @torch.no_grad()
+    def extract_textured_geometry(self, bound_min, bound_max, resolution, threshold=0.0, *, sparse=False, margin=1.0,
+                                  brick=None, refine=0, max_step=None, chunk=65536, to_host=True):
+        """`validate_mesh_texture` up to the export (exp_runner.py:584-613): SDF grid (dense, or `sparse=True` as in
+        `extract_geometry`), the native marching cubes, and `vertex_attributes` on the vertices where marching cubes left
+        them — they never leave the device in between.  Returns a dict:
+          `vertices` [V,3] float64 rescaled to the bounding box and `triangles` [T,3] int32 — with `refine == 0` the arrays
+          of `extract_geometry(..., backend="native")`; with `refine > 0` the float64 of the refined fp32 points (each moved
+          by at most `max_step`, default one cell diagonal, per step);
+          `normals` [V,3] float32 (unit); `sdf` [V,1]; and with the albedo network `albedo` [V,col_d_out] and `colors` [V,3]
+          uint8 RGB, the reference's `clip(albedo[:, [2,1,0]], 0, 1)` quantised by rint(255 x).
+        numpy arrays, or device tensors with `to_host=False` (then the only host synchronisations after the SDF grid are
+        the two marching-cubes counts).  `mesh_io.write_ply` writes the result."""
+        from .mcubes import marching_cubes
+        res = int(resolution)
+        if sparse:
+            u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, res, threshold, brick, margin,
+                                                                  to_host=False)
+        else:
+            u = self.extract_fields(bound_min, bound_max, res, to_host=False)
+        v, t = marching_cubes(u, threshold)
+        del u
+        at = self.vertex_attributes(grid_vertices=v, bounds=(bound_min, bound_max), resolution=res, threshold=threshold,
+                                    refine=refine, max_step=max_step, chunk=chunk)
+        if int(refine) > 0:
+            vertices = at["points"].double()
+        elif to_host:   # extract_geometry's rescaling, on the host as there
+            b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
+            vertices = v.cpu().numpy() / (res - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
+        else:           # the same expression on the device: float64, the box's extent taken in the bounds' precision first; an
+            #             element-wise division (a division by a Python scalar is a multiplication by its reciprocal there)
+            b_min, b_max = (b.detach().to(v.device) for b in (bound_min, bound_max))
+            vertices = v / torch.full_like(v, res - 1.0) * (b_max - b_min).double()[None, :] + b_min.double()[None, :]
+        out = {"vertices": vertices, "triangles": t, "normals": at["normal"], "sdf": at["sdf"]}
+        if "albedo" in at:
+            out["albedo"], out["colors"] = at["albedo"], at["rgb"]
+        if to_host:
+            out = {k: x.cpu().numpy() if isinstance(x, torch.Tensor) else x for k, x in out.items()}
+        return out

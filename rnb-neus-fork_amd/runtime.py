@@ -93,6 +93,51 @@ def color_forward(desc, packed, pts, normals, feats):
     return out
 
 
+def mesh_vertex_attrs(desc, packed, points=None, grid_vertices=None, bound_min=None, bound_max=None, resolution=0,
+                      level=0.0, refine=0, max_step=0.0, albedo=False, swap_rb=True, chunk=65536):
+    """rnb_mesh_vertex_attrs: per-vertex `points` [V,3], `sdf` [V,1], `gradient` [V,3], `normal` [V,3] and with `albedo`
+    `albedo` [V,col_d_out] and `rgb` [V,3] uint8, for fp32 `points` or float64 `grid_vertices` (+ bounds and resolution).
+    The library chunks the vertices through one workspace of min(chunk, V rounded up to 64) points."""
+    src = grid_vertices if grid_vertices is not None else points
+    _require_cuda(src, "vertices")
+    dev = src.device
+    gv = pts = None
+    if grid_vertices is not None:
+        gv = grid_vertices.detach().to(torch.float64).reshape(-1, 3).contiguous()
+    else:
+        pts = _f32c(points).reshape(-1, 3)
+    V = (gv if gv is not None else pts).shape[0]
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"points": torch.empty(V, 3, **f32), "sdf": torch.empty(V, 1, **f32), "gradient": torch.empty(V, 3, **f32),
+           "normal": torch.empty(V, 3, **f32)}
+    if albedo:
+        out["albedo"] = torch.empty(V, desc.col_d_out, **f32)
+        out["rgb"] = torch.empty(V, 3, dtype=torch.uint8, device=dev)
+    if V == 0:
+        return out
+    chunk = min(int(chunk), (V + 63) // 64 * 64)
+    a = native.MeshVertexArgs()
+    a.grid_vertices, a.points, a.V = native.ptr(gv), native.ptr(pts), V
+    if gv is not None:
+        for d in range(3):
+            a.bound_min[d], a.bound_max[d] = float(bound_min[d]), float(bound_max[d])
+        a.resolution = int(resolution)
+    a.level, a.refine, a.max_step = float(level), int(refine), float(max_step)
+    a.flags = (native.MESH_ALBEDO if albedo else 0) | (native.MESH_SWAP_RB if swap_rb else 0)
+    a.points_out, a.sdf_out = native.ptr(out["points"]), native.ptr(out["sdf"])
+    a.gradient_out, a.normal_out = native.ptr(out["gradient"]), native.ptr(out["normal"])
+    a.albedo_out, a.rgb_out = native.ptr(out.get("albedo")), native.ptr(out.get("rgb"))
+    lib = native.load()
+    nbytes = C.c_int64()
+    native.check(lib.rnb_mesh_vertex_workspace_bytes(C.byref(desc), chunk, a.flags, C.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    native.same_device(packed, gv, pts)
+    with native.on_device(dev) as stream:
+        native.check(lib.rnb_mesh_vertex_attrs(C.byref(desc), native.ptr(packed), C.byref(a), chunk, native.ptr(ws),
+                                               ws.numel(), stream))
+    return out
+
+
 class StandaloneSDF:
     """Context for calling an SDFNetwork outside a renderer (exp_runner.py:607-610 style)."""
 
