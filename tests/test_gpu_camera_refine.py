@@ -16,6 +16,7 @@ from oracle import rnb_oracle as O
 from tests import camera_refine_util as CU
 from tests.gpu_support import R  # noqa: F401
 from tests.gpu_support import device
+from tests.oracle_normal import graph_normal  # noqa: F401
 from tests.parity import GRAD_CAP, K_GRAD, check_grad, check_value, grad_bound, rel_l2
 from tests.ray_matrix import FLOAT_OUTS
 from tests.shape_matrix import BY_NAME, live_params
@@ -40,17 +41,6 @@ def rigs(R):
                           lights=ds["light_directions"], warm=ds["light_directions_warmup"]),
             "source": dict(dr=source, pose=pose, kinv=kinv, H=13, W=11, lights=torch.from_numpy(fx["l_cam"]),
                            warm=source.light_directions_warmup.cpu())}
-
-
-@pytest.fixture
-def graph_normal(monkeypatch):
-    def _graph_normal(p, conf, pts, create_graph=True):
-        x = pts if pts.requires_grad else pts.detach().requires_grad_(True)
-        with torch.enable_grad():
-            y = O.sdf_only(p, conf, x)
-            (g,) = torch.autograd.grad(y, x, torch.ones_like(y), create_graph=True, retain_graph=True)
-        return g
-    monkeypatch.setattr(O, "sdf_gradient", _graph_normal)
 
 
 def _restated(rig, mode, v, px, py, delta, s, dt, warmup=False):

@@ -4,7 +4,7 @@ gradients, bit-reproducibility, the bf16 refusal and the data-parallel shard rul
 
 The oracle's sdf_gradient detaches its input; the reference's gradient() (models/fields.py:114-127) keeps the graph to the
 points when they require grad, so the normal's Hessian-vector term is part of the reference's ray gradient.  Every oracle
-call here runs with a graph-keeping normal (_graph_normal, monkeypatched in)."""
+call here runs with a graph-keeping normal (the graph_normal fixture of tests/oracle_normal.py)."""
 import os
 from dataclasses import replace
 
@@ -16,6 +16,7 @@ import torch.multiprocessing as mp
 from oracle import rnb_oracle as O
 from tests.gpu_support import R  # noqa: F401
 from tests.gpu_support import device, explicit_depths, free_port
+from tests.oracle_normal import graph_normal  # noqa: F401
 from tests.parity import check_grad, check_value, grad_bound, rel_l2
 from tests.ray_matrix import FLOAT_OUTS, Z_GRAD_S
 from tests.shape_matrix import BY_NAME, live_params, step_batch
@@ -24,17 +25,6 @@ pytestmark = pytest.mark.gpu
 
 B = 64
 SHAPES = ["default_64x64", "feat128", "scale3"]
-
-
-@pytest.fixture
-def graph_normal(monkeypatch):
-    def _graph_normal(p, conf, pts, create_graph=True):
-        x = pts if pts.requires_grad else pts.detach().requires_grad_(True)
-        with torch.enable_grad():
-            y = O.sdf_only(p, conf, x)
-            (g,) = torch.autograd.grad(y, x, torch.ones_like(y), create_graph=True, retain_graph=True)
-        return g
-    monkeypatch.setattr(O, "sdf_gradient", _graph_normal)
 
 
 def _build(R, name, render=None):
