@@ -514,6 +514,52 @@ int rnb_mesh_vertex_workspace_bytes(const rnb_model_desc* desc, int64_t chunk, i
 int rnb_mesh_vertex_attrs(const rnb_model_desc* desc, const float* packed, const rnb_mesh_vertex_args* args,
                           int64_t chunk, void* ws, size_t ws_bytes, rnb_stream_t stream);
 
+/* ---- Mesh cleanup: connected components, per-component statistics, compaction ----------------------------
+ * The first thing done to a marching-cubes mesh after validate_mesh: keep the largest connected component, or drop the
+ * small ones (floaters, shell fragments at the box walls) — on the arrays rnb_marching_cubes_emit left in device memory.
+ *   triangles [T,3] int32, vertices [V,3] float64 (any coordinates), 0 <= V, T <= 2^31 - 1.
+ * Two vertices are connected when some triangle names both (degenerate triangles count like any other); a component is a
+ * class of the transitive closure over the vertices at least one triangle names.  Components are numbered 0 .. C-1 in
+ * increasing order of their smallest vertex index — independent of the schedule.  A vertex no triangle names is
+ * unreferenced: label -1, in no component, never kept.
+ * Every stage works in ONE workspace of rnb_mesh_clean_workspace_bytes(V, T) bytes (a stage may overwrite what the
+ * previous one left there, except that rnb_mesh_compact_emit reads what rnb_mesh_compact_count wrote).
+ *   rnb_mesh_components       labels [V] int32; counts[0] = C, counts[1] = 1 when some triangle holds an index outside
+ *                             [0, V) (device int64 [2]).  Such a triangle is skipped — every index is checked before it
+ *                             is used as an address — and the caller should treat the mesh as invalid.
+ *                             Lock-free union-find, one thread per triangle, the larger root hooked under the smaller
+ *                             (csrc/mesh_clean.hip has the termination argument: parent[x] <= x always).
+ *   -- the caller reads counts and allocates the [C] arrays --
+ *   rnb_mesh_component_stats  tri_count [C], vert_count [C] int64; with vertices != NULL also area [C] float64, the sum
+ *                             of 0.5 |(p1 - p0) x (p2 - p0)| over the component's triangles, and bbox_min / bbox_max
+ *                             [C,3] float64, the exact minimum / maximum.  No floating-point atomics: the area is
+ *                             accumulated as a 128-bit integer in units of 2^-54 of the power of two at or below the
+ *                             component's largest triangle (each triangle rounded to that unit: at most 2^-55 of the
+ *                             largest per triangle), so it is bit-reproducible from run to run.  A component with a NaN
+ *                             coordinate has NaN in that axis of its bbox, and a NaN area when the NaN reaches a triangle.
+ *   rnb_mesh_compact_count    keep [C] uint8 (device; non-zero = keep the component); counts[0] = kept vertices V',
+ *                             counts[1] = kept triangles T' (device int64 [2])
+ *   -- the caller reads counts and allocates the outputs --
+ *   rnb_mesh_compact_emit     vertices_out [V',3] (written when vertices != NULL), triangles_out [T',3] with the indices
+ *                             remapped, vertex_index [V'] int64 = the old index of every kept vertex.  Stable: kept
+ *                             vertices and triangles keep their relative order, triangles their corner order.
+ * RNB_E_INVALID before any launch: V or T negative or above 2^31 - 1, n_components outside [0, V], output sizes above
+ * the input sizes.  RNB_E_NULL: a required pointer is NULL.  RNB_E_WORKSPACE: workspace_bytes below the query's answer. */
+int rnb_mesh_clean_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int64_t* bytes);
+int rnb_mesh_components(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* workspace,
+                        size_t workspace_bytes, int32_t* labels, int64_t* counts, rnb_stream_t stream);
+int rnb_mesh_component_stats(const int32_t* triangles, int64_t n_triangles, const double* vertices, int64_t n_vertices,
+                             const int32_t* labels, int64_t n_components, void* workspace, size_t workspace_bytes,
+                             int64_t* tri_count, int64_t* vert_count, double* area, double* bbox_min, double* bbox_max,
+                             rnb_stream_t stream);
+int rnb_mesh_compact_count(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* labels,
+                           const uint8_t* keep, int64_t n_components, void* workspace, size_t workspace_bytes,
+                           int64_t* counts, rnb_stream_t stream);
+int rnb_mesh_compact_emit(const int32_t* triangles, int64_t n_triangles, const double* vertices, int64_t n_vertices,
+                          const int32_t* labels, const uint8_t* keep, int64_t n_components, void* workspace,
+                          size_t workspace_bytes, int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out,
+                          int32_t* triangles_out, int64_t* vertex_index, rnb_stream_t stream);
+
 /* The four rnb_gen_rays_* calls below that make rays are one kernel (csrc/raygen.hip) behind one set of checks: a front, the
  * pixel list of a train step (_at_view) or a range of a whole view's grid (_grid), and the targets, gathered from the finished
  * stacks or computed from the view's source maps (_from_maps).  The pixel-to-ray arithmetic exists once; it is unfused float32

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 HIP_SOURCES = ["api.hip", "layout.hip", "layers.hip", "backward.hip", "util.hip", "dw.hip", "weightnorm.hip", "sampling.hip", "composite.hip", "prof.hip", "fused.hip",
                "sweep_mv.hip", "fused_bwd.hip", "color_h2.hip", "bf16_sweeps.hip", "bf16_color.hip", "bf16_dw.hip", "train.hip", "raygen.hip", "mcubes.hip",
-               "sparse_grid.hip", "mesh_attrs.hip"]
+               "sparse_grid.hip", "mesh_attrs.hip", "mesh_clean.hip"]
 COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 EXTRA_FLAGS = {
     # sampling.hip must round like the reference's separate PyTorch ops (no fused multiply-add contraction)
@@ -20,6 +20,8 @@ EXTRA_FLAGS = {
     # the epilogue chains of the M/V sweeps' vector waves are written stage by stage (independent chains): the SLP
     # vectoriser would fuse neighbouring chains into packed fp32 instructions (slower beside the partner's MFMAs)
     "sweep_mv.hip": ["-fno-slp-vectorize"],
+    # triangle areas as the numpy reference evaluates them: every product and sum rounded on its own
+    "mesh_clean.hip": ["-ffp-contract=off"],
 }
 
 

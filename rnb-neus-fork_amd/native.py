@@ -187,6 +187,17 @@ _SIGNATURES = {
     "rnb_mesh_vertex_workspace_bytes": (C.c_int, [_P(ModelDesc), C.c_int64, C.c_int32, _P(C.c_int64)]),
     "rnb_mesh_vertex_attrs": (C.c_int, [_P(ModelDesc), C.c_void_p, _P(MeshVertexArgs), C.c_int64, C.c_void_p, C.c_size_t,
                                         C.c_void_p]),
+    "rnb_mesh_clean_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, _P(C.c_int64)]),
+    "rnb_mesh_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "rnb_mesh_component_stats": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "rnb_mesh_compact_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_compact_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "rnb_up_sample_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                      C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),

@@ -282,6 +282,7 @@ class NeuSRenderer:
         self.track_range = False
         self._range = None
         self.last_sparse_grid = None   # `info` of the last extract_geometry(sparse=True)
+        self.last_mesh_clean = None    # `info` of the last extract_geometry / extract_textured_geometry(clean=...)
 
     # ------------------------------------------------------------------ data parallel
     def set_data_parallel(self, group=None, enabled=True, exact=True):
@@ -785,7 +786,7 @@ class NeuSRenderer:
         return {"max_abs_weight": worst, "layer": where, "limit": 255.0, "ok": bool(worst < 255.0)}
 
     def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, backend=None, sparse=False, margin=1.0,
-                         brick=None):
+                         brick=None, clean=None):
         """models/renderer.py:1219-1224 / :27-36: SDF grid + marching cubes + rescaling to the bounding box; returns
         numpy `(vertices [V,3] float64, triangles [T,3])` as the reference does.
         `backend`: "native" — the library's own marching cubes on the volume still resident in HBM
@@ -799,7 +800,10 @@ class NeuSRenderer:
         only the bricks near the surface are evaluated, the mesh is the dense one for every component that passes through
         a seed brick (see there for what `margin` can miss) — and its `info` is kept in `self.last_sparse_grid`.  Marching
         cubes itself is unchanged and runs over the dense array; its limit of 2^32 grid points caps `resolution` at 1625
-        either way."""
+        either way.
+        `clean`: a dict of `mesh_clean.clean_mesh` keywords, e.g. `{"keep_largest": 1}` — the mesh is cleaned on the device
+        before the rescaling (areas are measured in grid-index units; with `backend="mcubes"` the host arrays are uploaded
+        for it) and the `info` of the cleaning is kept in `self.last_mesh_clean`.  None (default): no cleaning."""
         if backend is None:
             try:
                 import mcubes  # noqa: F401
@@ -815,6 +819,7 @@ class NeuSRenderer:
         self.last_mesh_backend = backend
         if backend not in ("native", "mcubes"):
             raise ValueError(f"extract_geometry: unknown backend {backend!r}")
+        self._check_clean(clean)
         b_max = bound_max.detach().cpu().numpy()
         b_min = bound_min.detach().cpu().numpy()
         if backend == "mcubes":
@@ -825,6 +830,11 @@ class NeuSRenderer:
             else:
                 u = self.extract_fields(bound_min, bound_max, resolution)
             vertices, triangles = mcubes.marching_cubes(u, threshold)
+            if clean is not None:
+                dev = self.sdf_network.lin0.bias.device
+                v, t = self._clean_mesh(torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev),
+                                        torch.as_tensor(np.ascontiguousarray(triangles).astype(np.int32)).to(dev), clean)
+                vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         else:
             from .mcubes import marching_cubes
             if sparse:
@@ -833,9 +843,29 @@ class NeuSRenderer:
             else:
                 u = self.extract_fields(bound_min, bound_max, resolution, to_host=False)
             v, t = marching_cubes(u, threshold)
+            if clean is not None:
+                del u
+                v, t = self._clean_mesh(v, t, clean)
             vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
         return vertices, triangles
+
+    @staticmethod
+    def _check_clean(clean):
+        """the `clean` argument of the two extract calls, checked before the grid is evaluated"""
+        from .mesh_clean import check_criteria
+        if clean is None:
+            return
+        if not isinstance(clean, dict) or not set(clean) <= {"by", "keep_largest", "min_fraction", "min_triangles"}:
+            raise ValueError("clean must be a dict of clean_mesh keywords (by, keep_largest, min_fraction, min_triangles)")
+        check_criteria("clean", has_vertices=True, **clean)
+
+    def _clean_mesh(self, v, t, clean):
+        """`clean_mesh(v, t, **clean)` for the two extract calls: the cleaned (vertices, triangles); `info` kept."""
+        from .mesh_clean import clean_mesh
+        out = clean_mesh(v, t, **clean)
+        self.last_mesh_clean = out["info"]
+        return out["vertices"], out["triangles"]
 
     # ------------------------------------------------------------------ textured mesh (validate_mesh_texture)
     @torch.no_grad()
@@ -888,7 +918,7 @@ class NeuSRenderer:
 
     @torch.no_grad()
     def extract_textured_geometry(self, bound_min, bound_max, resolution, threshold=0.0, *, sparse=False, margin=1.0,
-                                  brick=None, refine=0, max_step=None, chunk=65536, to_host=True):
+                                  brick=None, refine=0, max_step=None, chunk=65536, to_host=True, clean=None):
         """`validate_mesh_texture` up to the export (exp_runner.py:584-613): SDF grid (dense, or `sparse=True` as in
         `extract_geometry`), the native marching cubes, and `vertex_attributes` on the vertices where marching cubes left
         them — they never leave the device in between.  Returns a dict:
@@ -898,8 +928,12 @@ class NeuSRenderer:
           `normals` [V,3] float32 (unit); `sdf` [V,1]; and with the albedo network `albedo` [V,col_d_out] and `colors` [V,3]
           uint8 RGB, the reference's `clip(albedo[:, [2,1,0]], 0, 1)` quantised by rint(255 x).
         numpy arrays, or device tensors with `to_host=False` (then the only host synchronisations after the SDF grid are
-        the two marching-cubes counts).  `mesh_io.write_ply` writes the result."""
+        the two marching-cubes counts).  `mesh_io.write_ply` writes the result.
+        `clean`: a dict of `mesh_clean.clean_mesh` keywords, e.g. `{"keep_largest": 1}`; the cleaning runs between marching
+        cubes and `vertex_attributes`, so removed vertices are never evaluated (two more host synchronisations; `info` in
+        `self.last_mesh_clean`).  None (default): no cleaning."""
         from .mcubes import marching_cubes
+        self._check_clean(clean)
         res = int(resolution)
         if sparse:
             u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, res, threshold, brick, margin,
@@ -908,6 +942,8 @@ class NeuSRenderer:
             u = self.extract_fields(bound_min, bound_max, res, to_host=False)
         v, t = marching_cubes(u, threshold)
         del u
+        if clean is not None:
+            v, t = self._clean_mesh(v, t, clean)
         at = self.vertex_attributes(grid_vertices=v, bounds=(bound_min, bound_max), resolution=res, threshold=threshold,
                                     refine=refine, max_step=max_step, chunk=chunk)
         if int(refine) > 0:
