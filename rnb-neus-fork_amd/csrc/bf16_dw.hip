@@ -22,7 +22,6 @@ struct BfDwJob {
   float* part;      // deterministic: [splits][256][lddw] slabs (or nullptr: fp32 atomics)
   float* partb;     // deterministic: [splits][256]
 };
-constexpr int kMaxBfDwJobs = 16;
 struct BfDwGroup {
   BfDwJob job[kMaxBfDwJobs];
   int njobs, splits;
@@ -300,44 +299,57 @@ int bf16_sdf_head_bwd(const Layout& L, PointBufs& pb, float* packed_grad, hipStr
   return RNB_OK;
 }
 
-// The weight-gradient jobs of one bf16 backward, in launch order: the hidden layers 0 .. nh-1 (pairs gz_l / u_l and
-// zb_l / in_l), the feature head (with_color), and on the bf16 albedo route the albedo net's layers nc-1 .. 1 and its layer 0
-// as two jobs (the 256 feature columns, the encoding columns).  f(job, flops) gets every field but the slabs.  Sizing
-// lists a PointBufs without buffers and no packed gradient: the operands and targets are then null.
+// The weight-gradient jobs of one bf16 backward, in the launch order of bf16_dw_shapes (bf16_dw_plan.h: which jobs, their
+// column ranges and pitches): here each gets its operands and targets.  f(job, flops) gets every field but the slabs.
+// Sizing lists a PointBufs without buffers and no packed gradient: the operands and targets are then null.
 // (Not dw.hip's dw_list: other operands, formats, kernels and order.)
 template <class F>
-static void bf16_dw_list(const Layout& L, const PointBufs& pb, bool with_color, float* packed_grad, F f) {
+static void bf16_dw_list(const Layout& L, const PointBufs& pb, const BfDwShape* shape, int nshapes, float* packed_grad, F f) {
   const int64_t M = pb.M;
   auto bf = [](const void* p) { return reinterpret_cast<const bfraw*>(p); };
-  auto add = [&](const void* X1, const void* Y1, int Cy1, const void* X2, const void* Y2, int Cy2, int npairs, int K,
-                 const Lin& ln, int bias_pair, double fl, int ycol0 = 0, bool with_bias = true) {
+  for (int q = 0; q < nshapes; ++q) {
+    const BfDwShape& sh = shape[q];
+    const int l = sh.layer;
+    const void *X1 = nullptr, *Y1 = nullptr, *X2 = nullptr, *Y2 = nullptr;
+    int Cy = FH;
+    const Lin* ln = nullptr;
+    double fl = 0.0;
+    switch (sh.kind) {
+      case BF_DW_HIDDEN:   // pairs gz_l / u_l and zb_l / in_l
+        ln = &L.hid[l];
+        Cy = l == 0 ? L.Ep : FH;
+        X1 = pb.gz[l]; Y1 = l == 0 ? (const void*)pb.u0_k8 : (const void*)pb.u[l];
+        X2 = pb.zb[l]; Y2 = l == 0 ? (const void*)pb.e : (const void*)pb.a[l - 1];
+        fl = 4.0 * (double)M * ln->N * ln->K;
+        break;
+      case BF_DW_FEAT:
+        ln = &L.feat;
+        X1 = pb.fbar_k8; Y1 = pb.a[L.nh - 1];
+        fl = 2.0 * (double)M * ln->N * ln->K;
+        break;
+      case BF_DW_ALBEDO_HIDDEN:   // dW_l = zc_l^T in_l
+        ln = &L.col[l];
+        X1 = pb.zc8[l]; Y1 = pb.ac8[l - 1];
+        fl = 2.0 * (double)M * ln->N * ln->K;
+        break;
+      default:   // the albedo net's layer 0 on the Cinp-wide input: BF_DW_ALBEDO_IN_FEAT (its flops count the whole layer), _PE
+        ln = &L.col[0];
+        Cy = L.Cinp;
+        X1 = pb.zc8[0]; Y1 = pb.cin8;
+        fl = sh.kind == BF_DW_ALBEDO_IN_FEAT ? 2.0 * (double)M * ln->N * ln->K : 0.0;
+        break;
+    }
     BfDwJob J;
     memset(&J, 0, sizeof(J));
-    J.X[0] = bf(X1); J.Y[0] = bf(Y1); J.Cy[0] = Cy1; J.ycol0[0] = ycol0;
-    J.X[1] = bf(X2); J.Y[1] = bf(Y2); J.Cy[1] = Cy2; J.ycol0[1] = ycol0;
-    J.npairs = npairs; J.K = K; J.lddw = ln.Kp; J.bias_pair = bias_pair;
+    J.X[0] = bf(X1); J.Y[0] = bf(Y1); J.Cy[0] = Cy; J.ycol0[0] = sh.ycol0;
+    J.X[1] = bf(X2); J.Y[1] = bf(Y2); J.Cy[1] = sh.npairs == 2 ? Cy : 0; J.ycol0[1] = sh.ycol0;
+    J.npairs = sh.npairs; J.K = sh.K; J.lddw = sh.lddw; J.bias_pair = sh.bias_pair;
     if (packed_grad != nullptr) {
-      J.dW = packed_grad + ln.w_off + ycol0;      // a column range [ycol0, ycol0 + K) of the layer's [256 x Kp] gradient
-      J.db = with_bias ? packed_grad + ln.b_off : nullptr;
+      J.dW = packed_grad + ln->w_off + sh.ycol0;      // a column range [ycol0, ycol0 + K) of the layer's [256 x Kp] gradient
+      J.db = sh.with_bias ? packed_grad + ln->b_off : nullptr;
     }
     f(J, fl);
-  };
-  for (int l = 0; l < L.nh; ++l) {
-    const Lin& ln = L.hid[l];
-    const void* in = l == 0 ? (const void*)pb.e : (const void*)pb.a[l - 1];
-    const void* uin = l == 0 ? (const void*)pb.u0_k8 : (const void*)pb.u[l];
-    const int Cy = l == 0 ? L.Ep : FH;
-    add(pb.gz[l], uin, Cy, pb.zb[l], in, Cy, 2, ln.Kp, ln, 1, 4.0 * (double)M * ln.N * ln.K);
   }
-  if (!with_color) return;
-  add(pb.fbar_k8, pb.a[L.nh - 1], FH, nullptr, nullptr, 0, 1, L.feat.Kp, L.feat, 0, 2.0 * (double)M * L.feat.N * L.feat.K);
-  if (L.route.color != COLOR_BF16) return;
-  // the albedo net's hidden layers: dW_l = zc_l^T in_l
-  for (int l = L.nc - 1; l >= 1; --l)
-    add(pb.zc8[l], pb.ac8[l - 1], FH, nullptr, nullptr, 0, 1, L.col[l].Kp, L.col[l], 0, 2.0 * (double)M * L.col[l].N * L.col[l].K);
-  // layer 0 reads the Cinp-wide input: its 256 feature columns and its 64 pe columns are two jobs
-  add(pb.zc8[0], pb.cin8, L.Cinp, nullptr, nullptr, 0, 1, FH, L.col[0], 0, 2.0 * (double)M * L.col[0].N * L.col[0].K);
-  add(pb.zc8[0], pb.cin8, L.Cinp, nullptr, nullptr, 0, 1, L.Cinp - FH, L.col[0], 0, 0.0, FH, false);
 }
 
 // The one plan of the grouped launch: what is launched, how the points are split and where each job's slabs lie.
@@ -352,22 +364,18 @@ struct BfDwPlan {
 static BfDwPlan bf16_dw_plan(const Layout& L, const PointBufs& pb, bool with_color, float* packed_grad) {
   BfDwPlan P;
   memset(&P, 0, sizeof(P));
-  const int64_t M = pb.M;
-  P.grp.M = M;
-  bf16_dw_list(L, pb, with_color, packed_grad, [&](const BfDwJob& J, double fl) {
-    if (P.njobs < kMaxBfDwJobs) P.grp.job[P.grp.njobs++] = J;
-    ++P.njobs;
-    P.total += J.lddw + 1;   // (x splits x 256 below)
+  P.grp.M = pb.M;
+  BfDwShape shape[kBfDwListed];
+  P.njobs = bf16_dw_shapes(bf16_dw_net(L), with_color, shape);
+  bf16_dw_list(L, pb, shape, P.njobs, packed_grad, [&](const BfDwJob& J, double fl) {
+    if (P.grp.njobs < kMaxBfDwJobs) P.grp.job[P.grp.njobs++] = J;
     P.flops += fl;
   });
-  // points per workgroup: enough workgroups to fill the chip (njobs x splits >= ~2 per CU), ranges a multiple of 64
-  const int want = (512 + P.njobs - 1) / P.njobs;
-  const int64_t rows = ((M + want - 1) / want + 63) / 64 * 64;
-  P.grp.rows_per_split = rows;
-  P.grp.splits = (int)((M + rows - 1) / rows);
-  const int64_t slab = (int64_t)P.grp.splits * FH;   // floats per column of lddw + 1
-  P.total *= slab;
-  for (int q = 1; q < P.grp.njobs; ++q) P.slab_off[q] = P.slab_off[q - 1] + slab * (P.grp.job[q - 1].lddw + 1);
+  const BfDwSplit S = bf16_dw_split(shape, P.njobs, pb.M);
+  P.grp.rows_per_split = S.rows_per_split;
+  P.grp.splits = S.splits;
+  P.total = S.total;
+  for (int q = 0; q < kMaxBfDwJobs; ++q) P.slab_off[q] = S.slab_off[q];
   return P;
 }
 

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/rnbneus.h"
+#include "bf16_dw_plan.h"
 
 namespace rnb {
 
@@ -502,6 +503,18 @@ int bf16_sdf_head_bwd(const Layout& L, PointBufs& pb, float* packed_grad, hipStr
 int bf16_dw_backward(const Layout& L, PointBufs& pb, bool with_color, float* packed_grad, hipStream_t s);
 // floats of bf16_dw_backward's ordered-reduction slabs over M points (deterministic variant)
 int64_t bf16_dw_floats(const Layout& L, int64_t M, bool with_color);
+// the two networks as the plan of that launch reads them (bf16_dw_plan.h)
+inline BfDwNet bf16_dw_net(const Layout& L) {
+  BfDwNet n{};
+  n.nh = L.nh;
+  for (int l = 0; l < L.nh; ++l) n.hid_Kp[l] = L.hid[l].Kp;
+  n.feat_Kp = L.feat.Kp;
+  n.bf16_color = L.route.color == COLOR_BF16;
+  n.nc = L.nc;
+  for (int l = 0; l < L.nc; ++l) n.col_Kp[l] = L.col[l].Kp;
+  n.Cinp = L.Cinp;
+  return n;
+}
 
 // ---- sampling / composite ------------------------------------------------------------------------
 int launch_up_sample_step(const float* rays_o, const float* rays_d, const float* z_in, const float* sdf_old,

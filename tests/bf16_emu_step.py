@@ -6,6 +6,7 @@ import torch
 from oracle import rnb_oracle as O
 from oracle.bf16_emu import Bf16FinePass, packed_layout, weights_from_packed
 from tests.golden_util import Golden
+from tests.bf16_point_matrix import weighted_rnb_loss
 from tests.gpu_support import device
 from tests.parity import rel_l2
 
@@ -59,6 +60,11 @@ class Check:
         mx = lambda a: float((a - ref).abs().max())
         self.rows.append((name + " max", mx(dev), max(mx(o) for o in others), old_bound / 2))
 
+    def worst(self):
+        """the largest device / emu32 ratio over the calibrated rows (rms, loss, gradients) and the largest share of a bound"""
+        cal = [(e / max(e32, 1e-30), n) for n, e, e32, _ in self.rows if not n.endswith(" max")]
+        return {"worst_ratio": max(cal), "worst_of_bound": max((e / b, n) for n, e, _, b in self.rows)}
+
     def finish(self):
         for name, e, e32, bound in self.rows:
             print(f"BF16EMU {self.tag} {name}: device {e:.3e}, emu32 {e32:.3e}, ratio {e / max(e32, 1e-30):.2f}, "
@@ -67,7 +73,11 @@ class Check:
         assert not bad, f"{self.tag}: " + "; ".join(bad)
 
 
-def step_loss(api, out, b):
+def step_loss(api, out, b, rw=None):
+    """`rw` [B]: per-ray weights of the colour and mask terms (tests/bf16_point_matrix.py weighted_rnb_loss; render_rnb only)"""
+    if rw is not None:
+        assert api == "render_rnb"
+        return weighted_rnb_loss(out, b["true_rgb"], b["mask"], rw)
     if api == "render":
         return (out["color_fine"] - b["true_rgb"][0]).abs().mean() + 0.1 * out["gradient_error"] \
             + 0.1 * torch.nn.functional.binary_cross_entropy(out["weight_sum"].clip(1e-3, 1 - 1e-3),
@@ -75,7 +85,7 @@ def step_loss(api, out, b):
     return O.rnb_loss(out, b["true_rgb"], b["mask"])[0]
 
 
-def emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order):
+def emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order, rw=None):
     fp = Bf16FinePass(p, mc, w, dtype=dt, order=order)
     warm = api == "render_rnb_warmup"
     if api == "render":
@@ -86,33 +96,58 @@ def emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order):
                          relu_shading=warm, no_albedo=no_albedo, mvps=True)
     leaves = {k: out[k].detach().clone().requires_grad_(True) for k in ("color_fine", "weight_sum", "gradient_error")}
     bt = {k: v.to(dt) for k, v in batch.items()}
-    loss = step_loss(api, {**out, **leaves}, bt)
+    loss = step_loss(api, {**out, **leaves}, bt, rw)
     loss.backward()
     grads = fp.backward({k: v.grad for k, v in leaves.items()})
     return out, float(loss), grads
 
 
-def step(R, mc, B, api="render_rnb", no_albedo=False, sharpen=True, seed=2, tag="", params=None, **variant):
+def tail_ray_weight(p, mc, w, batch, z, api, no_albedo, key):
+    """the weight of the LAST ray at which, in the fp64 emulation, it carries half of the norm of `key`'s gradient: two
+    backward passes, with the last ray alone and with the rest alone (the loss is linear in the ray weights)"""
+    B = z.shape[0]
+    last = torch.zeros(B, dtype=torch.float64)
+    last[B - 1] = 1.0
+    g_last = emulated_step(p, mc, w, batch, z, api, no_albedo, None, torch.float64, "mm", rw=last)[2][key]
+    g_rest = emulated_step(p, mc, w, batch, z, api, no_albedo, None, torch.float64, "mm", rw=1.0 - last)[2][key]
+    n_last, n_rest = float(g_last.norm()), float(g_rest.norm())
+    assert n_last > 0 and n_rest > 0, f"the last ray or the rest carries no gradient of {key}"
+    rw = torch.ones(B, dtype=torch.float64)
+    rw[B - 1] = n_rest / n_last
+    return rw
+
+
+def step(R, mc, B, api="render_rnb", no_albedo=False, sharpen=True, seed=2, tag="", params=None, batch=None, z_vals=None,
+         tail_key=None, info=None, **variant):
+    """`batch`: the rays (else the synthetic batch of B); `z_vals` [B, S]: explicit depths instead of sampling; `tail_key`
+    (with z_vals): the last ray's loss weight is set by tail_ray_weight on that gradient; `info`: a dict that receives the
+    worst device / emu32 ratios and the ray weight."""
     p, sdf, dev, col, ren = model(R, mc, seed=seed, sharpen=sharpen, params=params, **variant)
     warm = api == "render_rnb_warmup"
-    batch = O.synthetic_batch(B, seed=40 + B, step=1, warmup=warm)
+    if batch is None:
+        batch = O.synthetic_batch(B, seed=40 + B, step=1, warmup=warm)
     b = {k: v.to(device()) for k, v in batch.items()}
+    depths = dict(t_rand=b["t_rand"]) if z_vals is None else dict(z_vals=z_vals.to(device()))
+    rw = None
+    if tail_key is not None:
+        packed, total = packed_weights(ren, mc)
+        rw = tail_ray_weight(p, mc, weights_from_packed(packed[:total], mc), batch, z_vals, api, no_albedo, tail_key)
     bg = None
     if api == "render":
         bg = torch.tensor([0.2, 0.5, 0.8])
         out = ren.render(b["rays_o"], b["rays_d"], b["near"], b["far"], background_rgb=bg.to(device()), cos_anneal_ratio=1.0,
-                         t_rand=b["t_rand"])
+                         **depths)
     else:
         fn = ren.render_rnb_warmup if warm else ren.render_rnb
-        out = fn(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0, t_rand=b["t_rand"],
-                 no_albedo=no_albedo)
-    loss = step_loss(api, out, b)
+        out = fn(b["rays_o"], b["rays_d"], b["near"], b["far"], b["lights_dir"], cos_anneal_ratio=1.0, no_albedo=no_albedo,
+                 **depths)
+    loss = step_loss(api, out, b, rw)
     loss.backward()
     torch.cuda.synchronize()
     z = ren.last_z_vals.cpu()
     packed, total = packed_weights(ren, mc)
     w = weights_from_packed(packed[:total], mc)
-    emu = [emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order)
+    emu = [emulated_step(p, mc, w, batch, z, api, no_albedo, bg, dt, order, rw)
            for dt, order in ((torch.float64, "mm"),) + MODES]
     (o64, l64, g64), rest = emu[0], emu[1:]
     chk = Check(tag or f"{api} B={B} S={z.shape[1]} no_albedo={no_albedo} {variant}")
@@ -137,6 +172,8 @@ def step(R, mc, B, api="render_rnb", no_albedo=False, sharpen=True, seed=2, tag=
         chk.add(k, rel_l2(v.grad.detach().cpu(), ref), [rel_l2(g[k].reshape(v.shape).detach(), ref) for _, _, g in rest],
                 FLOOR_GRAD, OLD["grad"] / 10)
         n_checked += 1
+    if info is not None:
+        info.update(chk.worst(), ray_weight=None if rw is None else float(rw[-1]))
     chk.finish()
     return n_checked
 

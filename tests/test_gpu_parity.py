@@ -832,7 +832,10 @@ def test_uninitialised_workspace_is_never_read(R, variant):
     reproduce the clean run bit for bit.  (Round 2 saw four GPU faults traced to NaN depths whose origin was never
     pinned down: a kernel reading a slab or a padded row it had not written is the class of bug this catches.)"""
     g = Golden("full_main_sharp")
-    batch = O.synthetic_batch(200, seed=5, step=1)        # ragged: 25,600 points, padded rows in every tile family
+    # 200 rays x 128 samples = 25,600 points: a multiple of the 128-row pad, so NO padded row exists here (workspace slabs,
+    # packed buffers and outputs are what this case poisons); point counts with padded rows, and counts that end inside an
+    # 8-point unit of the bf16 route, are tests/test_gpu_bf16_point_matrix.py part C
+    batch = O.synthetic_batch(200, seed=5, step=1)
     runs = []
     orig_empty, orig_empty_like = torch.empty, torch.empty_like
 

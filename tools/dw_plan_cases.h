@@ -86,15 +86,20 @@ struct CaseIn {
   BwdParts parts;
   int mode, slabs;
 };
-// the rest of a "D" line
-inline bool read_case(CaseIn* c) {
-  int32_t* f[] = {&c->desc.sdf_d_in, &c->desc.sdf_d_out, &c->desc.sdf_d_hidden, &c->desc.sdf_n_layers, &c->desc.sdf_skip_in,
-                  &c->desc.sdf_multires, &c->desc.sdf_weight_norm, &c->desc.col_d_feature, &c->desc.col_d_in, &c->desc.col_d_out,
-                  &c->desc.col_d_hidden, &c->desc.col_n_layers, &c->desc.col_multires_view, &c->desc.col_squeeze_out,
-                  &c->desc.col_weight_norm, &c->desc.n_samples, &c->desc.n_importance, &c->desc.up_sample_steps, &c->desc.variant};
-  c->desc.sdf_scale = 1.f;
+// the 19 int fields of a descriptor
+inline bool read_desc(rnb_model_desc* d) {
+  int32_t* f[] = {&d->sdf_d_in, &d->sdf_d_out, &d->sdf_d_hidden, &d->sdf_n_layers, &d->sdf_skip_in,
+                  &d->sdf_multires, &d->sdf_weight_norm, &d->col_d_feature, &d->col_d_in, &d->col_d_out,
+                  &d->col_d_hidden, &d->col_n_layers, &d->col_multires_view, &d->col_squeeze_out,
+                  &d->col_weight_norm, &d->n_samples, &d->n_importance, &d->up_sample_steps, &d->variant};
+  d->sdf_scale = 1.f;
   for (int32_t* p : f)
     if (scanf("%d", p) != 1) return false;
+  return true;
+}
+// the rest of a "D" line
+inline bool read_case(CaseIn* c) {
+  if (!read_desc(&c->desc)) return false;
   int b[5];
   if (scanf("%lld %d %d %d %d %d %d %d", &c->M, &b[0], &b[1], &b[2], &b[3], &b[4], &c->mode, &c->slabs) != 8) return false;
   c->parts = BwdParts{b[0] != 0, b[1] != 0, b[2] != 0, b[3] != 0, b[4] != 0};

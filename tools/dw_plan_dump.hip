@@ -2,7 +2,9 @@
 //   D <descriptor> M <BwdParts> <carve mode> sdfh_slabs   the plan dw_backward launches (line format: dw_plan_cases.h)
 //   J M x3 h2 one_wg lds det det_room slab_base slab_room n {N K npairs} x n
 //                                                         dw_make_plan of bare job shapes (a negative room: unbounded)
-// tests/test_dw_plan_host.py builds and runs it.  Not part of the library:
+//   B <descriptor> M with_color                           the grouped launch of the bf16 route (csrc/bf16_dw_plan.h): per job
+//                                                         [kind, layer, K, lddw, npairs, bias_pair, ycol0, with_bias, slab_off]
+// tests/test_dw_plan_host.py and tests/test_bf16_point_matrix_host.py build and run it.  Not part of the library:
 //   hipcc --cuda-host-only -std=c++17 -I rnb-neus-fork_amd/csrc tools/dw_plan_dump.hip rnb-neus-fork_amd/csrc/layout.hip -o dw_plan_dump
 #include <hip/hip_runtime.h>
 #undef hipLaunchKernelGGL
@@ -44,10 +46,41 @@ static void dump_plan(const DwPlan& P, const DwListed* job, const PointBufs* pb,
 }
 }  // namespace rnb
 
+// a "B" line: the bf16 route's plan of (descriptor, M, with_color)
+static bool dump_bf16_case() {
+  using namespace rnb;
+  rnb_model_desc desc;
+  long long M;
+  int with_color;
+  if (!read_desc(&desc) || scanf("%lld %d", &M, &with_color) != 2) return false;
+  Layout L;
+  const int rc = make_layout(&desc, &L);
+  if (rc != RNB_OK) {
+    printf("{\"refused\":%d,\"error\":\"%s\"}\n", rc, last_error());
+    return true;
+  }
+  BfDwShape shape[kBfDwListed];
+  const int n = bf16_dw_shapes(bf16_dw_net(L), with_color != 0, shape);
+  const BfDwSplit S = bf16_dw_split(shape, n, M);
+  printf("{\"njobs\":%d,\"want\":%d,\"rows\":%lld,\"splits\":%d,\"total\":%lld,\"sdf_route\":%d,\"color_route\":%d,\"jobs\":[", n, S.want,
+         (long long)S.rows_per_split, S.splits, (long long)S.total, (int)L.route.sdf, (int)L.route.color);
+  for (int q = 0; q < n; ++q) {
+    const BfDwShape& j = shape[q];
+    printf("%s[%d,%d,%d,%d,%d,%d,%d,%d,%lld]", q ? "," : "", j.kind, j.layer, j.K, j.lddw, j.npairs, j.bias_pair, j.ycol0, (int)j.with_bias,
+           q < kMaxBfDwJobs ? (long long)S.slab_off[q] : -1LL);
+  }
+  printf("]}\n");
+  return true;
+}
+
 int main() {
   using namespace rnb;
   char tag[8];
   while (scanf("%7s", tag) == 1) {
+    if (tag[0] == 'B') {
+      if (!dump_bf16_case()) { fprintf(stderr, "bad bf16 line\n"); return 2; }
+      continue;
+    }
     DumpCase out;
     DwPlan P;
     if (tag[0] == 'D') {
