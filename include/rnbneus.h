@@ -560,6 +560,96 @@ int rnb_mesh_compact_emit(const int32_t* triangles, int64_t n_triangles, const d
                           size_t workspace_bytes, int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out,
                           int32_t* triangles_out, int64_t* vertex_index, rnb_stream_t stream);
 
+/* ---- Mesh evaluation: triangle bins, closest points on a mesh, area-weighted surface samples ----------------
+ * What a reconstruction is judged by — how far is this mesh from that one (Chamfer, F-score) — needs two things for
+ * many points at once: the exact nearest point ON a triangle mesh, and points spread evenly over a surface.  Both work
+ * on the arrays of rnb_marching_cubes_emit / rnb_mesh_compact_emit in device memory:
+ *   vertices [V,3] float64, triangles [T,3] int32, 0 <= V, T <= 2^31 - 1; queries [N,3] float64, N <= 2^31 - 1.
+ * A triangle with a vertex index outside [0, V) or a non-finite coordinate is SKIPPED: never binned, never closest, area
+ * 0, never sampled; every index is checked before it is used as an address.  Means, maxima and threshold counts over the
+ * results are the caller's reductions: there is no reduction kernel, and no floating-point atomic anywhere.
+ *
+ * Bins.  rnb_mesh_bins is a uniform grid of cubic cells: cell (ix, iy, iz), linear index (iz * dims[1] + iy) * dims[0] + ix,
+ * covers origin + [i, i + 1) * cell_size per axis; a coordinate maps to clamp(floor((x - origin) / cell_size), 0, dim - 1),
+ * so the grid need not cover the mesh (what lies outside belongs to the boundary cells).  At most 2^24 cells.  A
+ * triangle is entered into every cell its axis-aligned box overlaps.
+ *   rnb_mesh_bins_count      cell_start [n_cells + 1] int64: the exclusive scan of the per-cell counts (the last element
+ *                            is E); counts[0] = E, the number of entries; counts[1]: bit 0 (1) set when a triangle was
+ *                            skipped, bit 1 (2) set when a binned triangle reaches outside the grid's box
+ *                            origin + [0, dims] * cell_size (it is binned all the same) (device int64 [2]).
+ *                            Workspace: rnb_mesh_bins_workspace_bytes(n_cells).
+ *   -- the caller reads counts, decides whether the grid is too fine for this mesh, and allocates entries [E] --
+ *   rnb_mesh_bins_emit       entries [E] int32 (the triangles of cell c are entries[cell_start[c] .. cell_start[c + 1]),
+ *                            in an order that may differ from run to run: integer atomics on per-cell cursors) and
+ *                            corners [T,9] float64, the three corners of every triangle side by side (zeros for a skipped
+ *                            one), so that a query reads a triangle with one indirection.  Same grid, mesh and workspace
+ *                            size as the count.
+ *
+ * Closest points.  rnb_mesh_closest_points: for every query the minimum over ALL binned triangles, under the
+ * lexicographic order (dist2 as computed, triangle index), of the squared distance point-triangle:
+ *     the minimum of |p - q|^2 over q = the closest point of each of the three edge SEGMENTS (parameter clamped to [0, 1];
+ *     a zero-length edge is its end point) and, where the triangle has a normal and the projection of p onto its plane
+ *     has barycentric weights >= 0, that projection — so a zero-area triangle is the segment or point it degenerates to.
+ * Each pair's value is a pure function of its four points (tests/mesh_distance_ref.py is the same expression in numpy),
+ * so the answer does not depend on the order of the entries or on the grid, and is bit-equal from run to run; the grid
+ * only decides how many pairs are evaluated.  Search: Chebyshev shells of cells around the query's (clamped) cell,
+ * stopped when everything outside the block searched so far is provably farther than the best so far
+ * (csrc/mesh_eval.hip has the bound, valid for queries outside the box too, and the termination argument: every trip
+ * count comes from the grid dims and E).  One lane per query: a caller who sorts the queries by cell makes neighbouring
+ * lanes read the same entries.  flags: RNB_MESH_BINS_COVER states that bit 1 of counts[1] came back clear — no binned
+ * triangle reaches outside the grid's box — which lets the bound count a query's distance to the box as well (fewer shells
+ * for queries outside it, the same answers); it must not be set otherwise.
+ *   dist2 [N] float64, closest [N,3] float64, triangle [N] int32: each may be NULL, not all.  A query with a non-finite
+ *   coordinate: dist2 = NaN, closest = NaN, triangle = -1.  No binned triangle (E == 0): dist2 = +inf, closest = NaN,
+ *   triangle = -1.  Nothing is launched for N == 0.
+ *
+ * Surface samples, area-weighted and deterministic (systematic sampling).
+ *   rnb_mesh_sample_areas    cum_area [T] float64: C_t = inclusive sum of A_t = 0.5 |(b - a) x (c - a)| (0 for a skipped
+ *                            triangle), in a fixed order: non-decreasing, C_t == C_{t-1} bit for bit where A_t == 0,
+ *                            the same bits on every run; total [1] float64 (device) = A = C_{T-1} (0 for T == 0).  The
+ *                            caller checks that A is positive and finite.  Workspace: rnb_mesh_sample_workspace_bytes(T).
+ *   rnb_mesh_sample_surface  sample k of n:  u_k = ((k + xi) * A) / n, lowered to the largest double below A if it rounds up
+ *                            to A; triangle t = the first with C_t > u_k (binary search, at most 32 steps): a triangle
+ *                            of zero area is never chosen, and triangle t receives n A_t / A samples up to rounding.
+ *                            The integer mixer, on unsigned 64-bit integers (the finaliser of splitmix64):
+ *                                mix(z):  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                                         z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *                                unit(z) = (z >> 11) * 2^-53
+ *                                s = mix(seed);  xi = unit(s);  r1 = unit(mix(s ^ (2k)));  r2 = unit(mix(s ^ (2k + 1)))
+ *                            (r1, r2) -> (1 - r1, 1 - r2) when r1 + r2 > 1 (decided exactly, as 1 - r1 < r2).
+ *                            bary = (1 - r1 - r2, r1, r2): exact, >= 0, sum 1.  The point a + r1 (b - a) + r2 (c - a)
+ *                            is evaluated as the convex combination (bary0 a + bary1 b) + bary2 c, each operation rounded
+ *                            on its own.  points [n,3], bary [n,3], normal [n,3] float64 (the unit face normal
+ *                            (b - a) x (c - a) / |.|; zero when undefined), triangle [n] int32: each may be NULL, not all.
+ *                            If A is not positive and finite: triangle = -1 and zeros.  Nothing is launched for n == 0.
+ * RNB_E_INVALID before any launch: a size negative or above 2^31 - 1, dims < 1 or more than 2^24 cells, cell_size or
+ * origin not positive / finite, unknown flag bits, samples of a mesh without triangles.  RNB_E_NULL: a required pointer is NULL.
+ * RNB_E_WORKSPACE: workspace_bytes below the query's answer.  Nothing is allocated and no device-wide synchronisation
+ * happens inside these calls. */
+enum { RNB_MESH_BINS_COVER = 1 };
+typedef struct rnb_mesh_bins {
+  double origin[3];
+  double cell_size;   /* cubic cells */
+  int32_t dims[3];
+  int32_t reserved_;
+} rnb_mesh_bins;
+int rnb_mesh_bins_workspace_bytes(int64_t n_cells, int64_t* bytes);
+int rnb_mesh_bins_count(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                        const rnb_mesh_bins* bins, void* workspace, size_t workspace_bytes, int64_t* cell_start,
+                        int64_t* counts, rnb_stream_t stream);
+int rnb_mesh_bins_emit(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                       const rnb_mesh_bins* bins, void* workspace, size_t workspace_bytes, const int64_t* cell_start,
+                       int64_t n_entries, int32_t* entries, double* corners, rnb_stream_t stream);
+int rnb_mesh_closest_points(const double* queries, int64_t n_queries, const rnb_mesh_bins* bins, const int64_t* cell_start,
+                            const int32_t* entries, int64_t n_entries, const double* corners, int64_t n_triangles,
+                            int32_t flags, double* dist2, double* closest, int32_t* triangle, rnb_stream_t stream);
+int rnb_mesh_sample_workspace_bytes(int64_t n_triangles, int64_t* bytes);
+int rnb_mesh_sample_areas(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                          void* workspace, size_t workspace_bytes, double* cum_area, double* total, rnb_stream_t stream);
+int rnb_mesh_sample_surface(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                            const double* cum_area, const double* total, int64_t n_samples, int64_t seed, double* points,
+                            int32_t* triangle, double* bary, double* normal, rnb_stream_t stream);
+
 /* The four rnb_gen_rays_* calls below that make rays are one kernel (csrc/raygen.hip) behind one set of checks: a front, the
  * pixel list of a train step (_at_view) or a range of a whole view's grid (_grid), and the targets, gathered from the finished
  * stacks or computed from the view's source maps (_from_maps).  The pixel-to-ray arithmetic exists once; it is unfused float32

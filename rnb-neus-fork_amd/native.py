@@ -103,6 +103,16 @@ class MeshVertexArgs(C.Structure):
                 ("normal_out", C.c_void_p), ("albedo_out", C.c_void_p), ("rgb_out", C.c_void_p)]
 
 
+class MeshBins(C.Structure):
+    """rnb_mesh_bins: the uniform grid of the triangle bins (origin, cubic cell size, cells per axis)"""
+    _fields_ = [("origin", C.c_double * 3), ("cell_size", C.c_double), ("dims", C.c_int32 * 3), ("reserved_", C.c_int32)]
+
+
+MESH_BINS_MAX_CELLS = 1 << 24
+# flags of rnb_mesh_closest_points; bits of rnb_mesh_bins_count's counts[1] (include/rnbneus.h)
+MESH_BINS_COVER = 1
+MESH_BINS_SKIPPED, MESH_BINS_OUTSIDE = 1, 2
+
 SPARSE_BRICKS = (4, 8, 16, 32)
 
 
@@ -198,6 +208,18 @@ _SIGNATURES = {
     "rnb_mesh_compact_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "rnb_mesh_bins_workspace_bytes": (C.c_int, [C.c_int64, _P(C.c_int64)]),
+    "rnb_mesh_bins_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(MeshBins), C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_bins_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(MeshBins), C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_closest_points": (C.c_int, [C.c_void_p, C.c_int64, _P(MeshBins), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_sample_workspace_bytes": (C.c_int, [C.c_int64, _P(C.c_int64)]),
+    "rnb_mesh_sample_areas": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "rnb_mesh_sample_surface": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnb_up_sample_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                      C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
