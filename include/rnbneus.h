@@ -650,6 +650,48 @@ int rnb_mesh_sample_surface(const double* vertices, int64_t n_vertices, const in
                             const double* cum_area, const double* total, int64_t n_samples, int64_t seed, double* points,
                             int32_t* triangle, double* bary, double* normal, rnb_stream_t stream);
 
+/* ---- Mesh ray casting: the first hit of every ray with a binned mesh ------------------------------------------
+ * What a camera sees of a mesh — depth, normal and silhouette per pixel, or whether a point is visible from an eye —
+ * on the bins, entries and corners [T,9] of rnb_mesh_bins_count / rnb_mesh_bins_emit above (csrc/mesh_raycast.hip).
+ *   origins, directions [N,3] float64; t_min, t_max [N] float64, each may be NULL (0 and +inf); N <= 2^31 - 1.
+ * The hit point of a ray is o + t d with d AS GIVEN (not normalised).  rnb_mesh_raycast: for every ray the minimum over
+ * ALL binned triangles, under the lexicographic order (t as computed, triangle index), over the triangles the ray hits
+ * with t_min <= t <= t_max, both ends inclusive.  The pair test is the watertight one of Woop, Benthin and Wald
+ * ("Watertight Ray/Triangle Intersection", JCGT 2013) in fp64, every operation rounded on its own:
+ *     kz = argmax |d| (the first maximum); kx, ky = the next two axes cyclically, swapped when d[kz] < 0;
+ *     Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz];
+ *     per corner (A, then B and C alike), translated by -o:  Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz], Az = Sz * A[kz];
+ *     U = Cx * By - Cy * Bx,  V = Ax * Cy - Ay * Cx,  W = Bx * Ay - By * Ax;
+ *     a hit needs (U >= 0 && V >= 0 && W >= 0) || (U <= 0 && V <= 0 && W <= 0), then det = (U + V) + W != 0, then
+ *     t = ((U * Az + V * Bz) + W * Cz) / det inside the range;  bary = (U, V, W) / det, the weights of (A, B, C).
+ * ZERO COUNTS AS INSIDE (fp64 has no wider type to fall back on): a hit on an edge is reported by both neighbours and
+ * the index order breaks the tie, so a closed surface has no pinholes.  A zero-area triangle has det == 0 and is never
+ * hit: exactly so with two or three equal corners; with collinear, distinct corners det is zero up to rounding, and a
+ * ray through the triangle's own segment (to within rounding) may be given a t inside the triangle's extent along the
+ * ray.  Each pair's value is a pure function of the ray and the three corners (tests/mesh_raycast_ref.py is the same
+ * expression in numpy), so the answer does not depend on the order of the entries and is bit-equal from run to run; it
+ * does not depend on the grid either, the grid only deciding how many pairs are evaluated, FOR EVERY HIT WHOSE OWN POINT
+ * sum of bary_k x corner_k LIES ON ITS RAY: within the widening below of o + t d.  That is every hit on a triangle with
+ * |det| >= r^3 / (1024 S) (corners within r of the ray, S = the grid's magnitude + max |o|), i.e. not seen edge-on to
+ * within its size over 1024 scene sizes.  A hit beyond that (the collinear triangle above is the extreme) is found by
+ * a one-cell grid and may be missed by a finer one.  Search: one lane per ray, by layers of cells along
+ * the major axis in the ray's direction, testing in each layer the cells under the ray's footprint widened by
+ * 4096 x 2^-52 x (the grid's magnitude + max |o|), stopped at the first layer that starts behind the best t so far
+ * (csrc/mesh_raycast.hip has the argument for why no hit is skipped, what it asks of a triangle seen edge-on, and why
+ * every trip count comes from the grid dims and E).
+ * flags MUST carry RNB_MESH_BINS_COVER (bit 1 of counts[1] came back clear: no binned triangle reaches outside the
+ * grid's box): the walk visits only the cells under the ray, and a triangle outside the box sits in a boundary cell
+ * far from where a ray meets it.  Without it the call is RNB_E_INVALID.
+ *   t [N] float64, triangle [N] int32, bary [N,3] float64: each may be NULL, not all.  No hit: t = +inf, triangle = -1,
+ *   bary = NaN.  A ray with a non-finite origin or direction, a zero direction or a NaN bound: t = NaN, triangle = -1,
+ *   bary = NaN.  No binned triangle (E == 0): every ray misses.  Nothing is launched for N == 0.
+ * RNB_E_INVALID before any launch: unknown flag bits, RNB_MESH_BINS_COVER missing, a size outside [0, 2^31 - 1], bins as
+ * for the calls above.  RNB_E_NULL: a required pointer is NULL.  Nothing is allocated, no device-wide synchronisation. */
+int rnb_mesh_raycast(const double* origins, const double* directions, const double* t_min, const double* t_max,
+                     int64_t n_rays, const rnb_mesh_bins* bins, const int64_t* cell_start, const int32_t* entries,
+                     int64_t n_entries, const double* corners, int64_t n_triangles, int32_t flags, double* t,
+                     int32_t* triangle, double* bary, rnb_stream_t stream);
+
 /* The four rnb_gen_rays_* calls below that make rays are one kernel (csrc/raygen.hip) behind one set of checks: a front, the
  * pixel list of a train step (_at_view) or a range of a whole view's grid (_grid), and the targets, gathered from the finished
  * stacks or computed from the view's source maps (_from_maps).  The pixel-to-ray arithmetic exists once; it is unfused float32

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from . import native
+from . import mesh_raycast, native
 from .mesh_clean import _check_sizes
 
 _MAX_CELLS = native.MESH_BINS_MAX_CELLS
@@ -82,7 +82,8 @@ class MeshIndex:
     (True when a triangle with a non-finite vertex was left out), `covers` (the grid's box holds every binned triangle:
     always, for the grids built here; the query's bound uses it), `n_triangles`, `n_vertices`.
     `grid=(origin, cell_size, dims)` places the bins by hand (any box, covering the mesh or not: what lies outside goes
-    to the boundary cells, and no result changes), without coarsening.
+    to the boundary cells, and no result of `closest` changes), without coarsening.  `raycast`, `interpolate` and `visible`
+    (mesh_raycast.py) cast rays at the same bins; they need `covers`.
     ValueError for wrong shapes / dtypes and for a triangle index outside [0, V); RuntimeError for CPU tensors.
     Host synchronisations: one for the bounding box, one per counting pass."""
 
@@ -198,6 +199,18 @@ class MeshIndex:
                     native.MESH_BINS_COVER if self.covers else 0, native.ptr(d2s), native.ptr(cls), native.ptr(trs), stream))
             dist2[order], closest[order], triangle[order] = d2s, cls, trs
         return {"distance": torch.sqrt(dist2), "dist2": dist2, "closest": closest, "triangle": triangle}
+
+    def raycast(self, origins, directions, t_min=None, t_max=None):
+        """The first hit of every ray with the mesh: `mesh_raycast.raycast` has the contract."""
+        return mesh_raycast.raycast(self, origins, directions, t_min, t_max)
+
+    def interpolate(self, hits, vertex_values):
+        """Per-vertex values at the hits of `raycast`, barycentrically: `mesh_raycast.interpolate`."""
+        return mesh_raycast.interpolate(self, hits, vertex_values)
+
+    def visible(self, points, eye, rel_tol=mesh_raycast.VISIBLE_REL_TOL):
+        """Which points the eye sees past the mesh: `mesh_raycast.visible`."""
+        return mesh_raycast.visible(self, points, eye, rel_tol)
 
 
 @torch.no_grad()

@@ -215,6 +215,9 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnb_mesh_closest_points": (C.c_int, [C.c_void_p, C.c_int64, _P(MeshBins), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_raycast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _P(MeshBins), C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "rnb_mesh_sample_workspace_bytes": (C.c_int, [C.c_int64, _P(C.c_int64)]),
     "rnb_mesh_sample_areas": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
