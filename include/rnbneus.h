@@ -560,6 +560,58 @@ int rnb_mesh_compact_emit(const int32_t* triangles, int64_t n_triangles, const d
                           size_t workspace_bytes, int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out,
                           int32_t* triangles_out, int64_t* vertex_index, rnb_stream_t stream);
 
+/* ---- Mesh simplification: vertex clustering on a uniform grid, to a cell size ------------------------------
+ * Makes a marching-cubes mesh smaller on the device (Rossignac-Borrel): the vertices of one grid cell become one vertex,
+ * which is ONE OF THEM (the member nearest the cell's mean), so every output vertex is an input vertex, per-vertex
+ * attributes carry over by a gather, and the result is defined bit for bit (tests/mesh_simplify_ref.py restates it in numpy).
+ *   vertices [V,3] float64, triangles [T,3] int32, 0 <= V, T <= 2^31 - 1; the grid: origin[3] (finite; host memory, or
+ *   NULL = per axis the minimum over the vertices whose three coordinates are finite, computed on the device; 0 when there
+ *   is none) and cell_size h (positive, finite).  The grid is unbounded, nothing is clamped, there is no per-cell array.
+ * Definition.
+ *   Cell of a coordinate   u = (x - origin) / h (two roundings), i = floor(u), f = u - i (exact, except that a negative u
+ *                          of tiny magnitude gives f = 1).  A vertex is USABLE when its three coordinates are finite and
+ *                          every i lies in [-2^20, 2^20); its cell key is (ix + 2^20) | (iy + 2^20) << 21 | (iz + 2^20) << 42.
+ *   Valid triangle         all three indices in [0, V) — every index is checked before it is used as an address — and all
+ *                          three vertices usable.  Any other triangle is skipped.  A vertex is REFERENCED when a valid
+ *                          triangle names it; only referenced vertices take part in anything below.
+ *   Cluster                the referenced vertices of one cell; its LEADER is its smallest vertex index.
+ *   Cluster mean           in cell units, from integer sums (independent of the order of accumulation): per axis
+ *                          q = (uint64) floor(f * 2^32), S = sum of q over the n members (64-bit), m = ((double) S /
+ *                          (double) n) * 2^-32.
+ *   Representative         the member that minimises (d2, vertex index) lexicographically, d2 = ((fx - mx)^2 + (fy - my)^2)
+ *                          + (fz - mz)^2 with every operation rounded on its own (d2 >= 0: its bits order as an integer).
+ *   Triangles              a valid triangle maps to the clusters of its corners, corner order kept.  It is DEGENERATE when
+ *                          two corners share a cluster: dropped.  Among the others, those with the same UNORDERED cluster
+ *                          triple are duplicates whatever their orientation: the one with the smallest input index survives.
+ *   Output                 surviving triangles in input order; the clusters at least one surviving triangle names, numbered
+ *                          in increasing order of leader; vertices_out[j] = vertices[representative of cluster j], bit for bit.
+ * Two calls in ONE workspace of rnb_mesh_simplify_workspace_bytes(V, T) bytes (a host function, monotone in both):
+ *   rnb_mesh_simplify_count  counts (device int64 [6]): [0] = V', [1] = T', [2] = degenerate triangles, [3] = duplicates
+ *                            removed ([1] + [2] + [3] = valid triangles), [4] = flag bits: 1 = a triangle was skipped for an
+ *                            index outside [0, V), 2 = one was skipped for a vertex that is not usable (4 = a table filled
+ *                            up, which its sizing excludes), [5] = clusters.
+ *   -- the caller reads counts and allocates the outputs --
+ *   rnb_mesh_simplify_emit   reads what the count left in the workspace: same mesh, same grid, same workspace size.
+ *                            vertices_out [V',3], triangles_out [T',3] int32, vertex_index [V'] int64 = the input index of
+ *                            every output vertex, vertex_cluster [V] int32 = the output index of every input vertex's
+ *                            cluster (-1: unreferenced, or its cluster is not in the output), triangle_index [T'] int64 =
+ *                            the input index of every surviving triangle.  vertex_cluster and triangle_index may be NULL.
+ * Two open-addressing tables of 32-bit slots (cells -> leader, cluster triples -> first triangle; csrc/mesh_simplify.hip
+ * has the argument why an insertion ends and a key ends in exactly one slot), integer atomics only, no floating-point
+ * atomic: the result does not depend on the schedule.
+ * RNB_E_INVALID before any launch: V or T negative or above 2^31 - 1, cell_size not positive and finite, origin not finite,
+ * output sizes above the input sizes.  RNB_E_NULL: a required pointer is NULL.  RNB_E_WORKSPACE: workspace_bytes below the
+ * query's answer.  Nothing is launched for T == 0: counts are zero, vertex_cluster is -1.  Nothing is allocated and no
+ * device-wide synchronisation happens inside these calls. */
+int rnb_mesh_simplify_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int64_t* bytes);
+int rnb_mesh_simplify_count(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                            const double* origin, double cell_size, void* workspace, size_t workspace_bytes,
+                            int64_t* counts, rnb_stream_t stream);
+int rnb_mesh_simplify_emit(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                           const double* origin, double cell_size, void* workspace, size_t workspace_bytes,
+                           int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out, int32_t* triangles_out,
+                           int64_t* vertex_index, int32_t* vertex_cluster, int64_t* triangle_index, rnb_stream_t stream);
+
 /* ---- Mesh evaluation: triangle bins, closest points on a mesh, area-weighted surface samples ----------------
  * What a reconstruction is judged by — how far is this mesh from that one (Chamfer, F-score) — needs two things for
  * many points at once: the exact nearest point ON a triangle mesh, and points spread evenly over a surface.  Both work

@@ -208,6 +208,12 @@ _SIGNATURES = {
     "rnb_mesh_compact_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "rnb_mesh_simplify_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, _P(C.c_int64)]),
+    "rnb_mesh_simplify_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p,
+                                          C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_simplify_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p,
+                                         C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "rnb_mesh_bins_workspace_bytes": (C.c_int, [C.c_int64, _P(C.c_int64)]),
     "rnb_mesh_bins_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(MeshBins), C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -283,6 +283,7 @@ class NeuSRenderer:
         self._range = None
         self.last_sparse_grid = None   # `info` of the last extract_geometry(sparse=True)
         self.last_mesh_clean = None    # `info` of the last extract_geometry / extract_textured_geometry(clean=...)
+        self.last_mesh_simplify = None  # `info` of the last extract_geometry / extract_textured_geometry(simplify=...)
 
     # ------------------------------------------------------------------ data parallel
     def set_data_parallel(self, group=None, enabled=True, exact=True):
@@ -786,7 +787,7 @@ class NeuSRenderer:
         return {"max_abs_weight": worst, "layer": where, "limit": 255.0, "ok": bool(worst < 255.0)}
 
     def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, backend=None, sparse=False, margin=1.0,
-                         brick=None, clean=None):
+                         brick=None, clean=None, simplify=None):
         """models/renderer.py:1219-1224 / :27-36: SDF grid + marching cubes + rescaling to the bounding box; returns
         numpy `(vertices [V,3] float64, triangles [T,3])` as the reference does.
         `backend`: "native" — the library's own marching cubes on the volume still resident in HBM
@@ -803,7 +804,10 @@ class NeuSRenderer:
         either way.
         `clean`: a dict of `mesh_clean.clean_mesh` keywords, e.g. `{"keep_largest": 1}` — the mesh is cleaned on the device
         before the rescaling (areas are measured in grid-index units; with `backend="mcubes"` the host arrays are uploaded
-        for it) and the `info` of the cleaning is kept in `self.last_mesh_clean`.  None (default): no cleaning."""
+        for it) and the `info` of the cleaning is kept in `self.last_mesh_clean`.  None (default): no cleaning.
+        `simplify`: a dict of `mesh_simplify.simplify_mesh` keywords (`cell_size` in grid-index units, i.e. voxels, or
+        `target_triangles`; `origin`) — the mesh is simplified on the device after the cleaning and before the rescaling;
+        `info` is kept in `self.last_mesh_simplify`.  None (default): no simplification."""
         if backend is None:
             try:
                 import mcubes  # noqa: F401
@@ -820,6 +824,7 @@ class NeuSRenderer:
         if backend not in ("native", "mcubes"):
             raise ValueError(f"extract_geometry: unknown backend {backend!r}")
         self._check_clean(clean)
+        self._check_simplify(simplify)
         b_max = bound_max.detach().cpu().numpy()
         b_min = bound_min.detach().cpu().numpy()
         if backend == "mcubes":
@@ -830,10 +835,14 @@ class NeuSRenderer:
             else:
                 u = self.extract_fields(bound_min, bound_max, resolution)
             vertices, triangles = mcubes.marching_cubes(u, threshold)
-            if clean is not None:
+            if clean is not None or simplify is not None:
                 dev = self.sdf_network.lin0.bias.device
-                v, t = self._clean_mesh(torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev),
-                                        torch.as_tensor(np.ascontiguousarray(triangles).astype(np.int32)).to(dev), clean)
+                v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev)
+                t = torch.as_tensor(np.ascontiguousarray(triangles).astype(np.int32)).to(dev)
+                if clean is not None:
+                    v, t = self._clean_mesh(v, t, clean)
+                if simplify is not None:
+                    v, t = self._simplify_mesh(v, t, simplify)
                 vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         else:
             from .mcubes import marching_cubes
@@ -843,9 +852,12 @@ class NeuSRenderer:
             else:
                 u = self.extract_fields(bound_min, bound_max, resolution, to_host=False)
             v, t = marching_cubes(u, threshold)
-            if clean is not None:
+            if clean is not None or simplify is not None:
                 del u
+            if clean is not None:
                 v, t = self._clean_mesh(v, t, clean)
+            if simplify is not None:
+                v, t = self._simplify_mesh(v, t, simplify)
             vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
         return vertices, triangles
@@ -865,6 +877,23 @@ class NeuSRenderer:
         from .mesh_clean import clean_mesh
         out = clean_mesh(v, t, **clean)
         self.last_mesh_clean = out["info"]
+        return out["vertices"], out["triangles"]
+
+    @staticmethod
+    def _check_simplify(simplify):
+        """the `simplify` argument of the two extract calls, checked before the grid is evaluated"""
+        from .mesh_simplify import check_arguments
+        if simplify is None:
+            return
+        if not isinstance(simplify, dict) or not set(simplify) <= {"cell_size", "target_triangles", "origin"}:
+            raise ValueError("simplify must be a dict of simplify_mesh keywords (cell_size, target_triangles, origin)")
+        check_arguments("simplify", **simplify)
+
+    def _simplify_mesh(self, v, t, simplify):
+        """`simplify_mesh(v, t, **simplify)` for the two extract calls: the simplified (vertices, triangles); `info` kept."""
+        from .mesh_simplify import simplify_mesh
+        out = simplify_mesh(v, t, **simplify)
+        self.last_mesh_simplify = out["info"]
         return out["vertices"], out["triangles"]
 
     # ------------------------------------------------------------------ textured mesh (validate_mesh_texture)
@@ -918,7 +947,8 @@ class NeuSRenderer:
 
     @torch.no_grad()
     def extract_textured_geometry(self, bound_min, bound_max, resolution, threshold=0.0, *, sparse=False, margin=1.0,
-                                  brick=None, refine=0, max_step=None, chunk=65536, to_host=True, clean=None):
+                                  brick=None, refine=0, max_step=None, chunk=65536, to_host=True, clean=None,
+                                  simplify=None):
         """`validate_mesh_texture` up to the export (exp_runner.py:584-613): SDF grid (dense, or `sparse=True` as in
         `extract_geometry`), the native marching cubes, and `vertex_attributes` on the vertices where marching cubes left
         them — they never leave the device in between.  Returns a dict:
@@ -931,9 +961,13 @@ class NeuSRenderer:
         the two marching-cubes counts).  `mesh_io.write_ply` writes the result.
         `clean`: a dict of `mesh_clean.clean_mesh` keywords, e.g. `{"keep_largest": 1}`; the cleaning runs between marching
         cubes and `vertex_attributes`, so removed vertices are never evaluated (two more host synchronisations; `info` in
-        `self.last_mesh_clean`).  None (default): no cleaning."""
+        `self.last_mesh_clean`).  None (default): no cleaning.
+        `simplify`: a dict of `mesh_simplify.simplify_mesh` keywords (`cell_size` in voxels, or `target_triangles`;
+        `origin`); the simplification runs after the cleaning and before `vertex_attributes`, which is evaluated on the
+        surviving vertices only (`info` in `self.last_mesh_simplify`).  None (default): no simplification."""
         from .mcubes import marching_cubes
         self._check_clean(clean)
+        self._check_simplify(simplify)
         res = int(resolution)
         if sparse:
             u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, res, threshold, brick, margin,
@@ -944,6 +978,8 @@ class NeuSRenderer:
         del u
         if clean is not None:
             v, t = self._clean_mesh(v, t, clean)
+        if simplify is not None:
+            v, t = self._simplify_mesh(v, t, simplify)
         at = self.vertex_attributes(grid_vertices=v, bounds=(bound_min, bound_max), resolution=res, threshold=threshold,
                                     refine=refine, max_step=max_step, chunk=chunk)
         if int(refine) > 0:
