@@ -707,7 +707,9 @@ __global__ __launch_bounds__(512, 1) void gemm_rows_x3m_kernel(const float* __re
 // The per-point kernels below compute (or consume) W consecutive columns of one matrix row per lane.
 // Touching global memory in that shape makes every access instruction hit 64 different rows; instead one
 // wave stages its 64 rows x W columns in LDS (pitch W + 1: conflict-free both ways) and moves them with
-// 16 bytes per lane along the rows.  W % 4 == 0, col0 % 4 == 0, ld % 4 == 0; one wave per workgroup.
+// 16 bytes per lane along the rows; the last W % 4 columns of a row move as single floats (an albedo input block
+// behind a feature width that is no multiple of 4: Cinp - F).  ld % 4 == 0; col0 % 4 == 0 keeps the 16-byte accesses
+// aligned (they are dword-aligned otherwise); one wave per workgroup.
 __device__ inline void tile_store64(float* __restrict__ dst, int ld, int64_t r0, int col0, int W,
                                     const float* __restrict__ tile, int lane) {
   const int g = W >> 2;   // 16-byte groups per row
@@ -715,6 +717,12 @@ __device__ inline void tile_store64(float* __restrict__ dst, int ld, int64_t r0,
     const int p = idx / g, c = (idx - p * g) * 4;
     const float* t = tile + p * (W + 1) + c;
     *reinterpret_cast<vf4*>(dst + (r0 + p) * ld + col0 + c) = make_vf4(t[0], t[1], t[2], t[3]);
+  }
+  if (const int rest = W & 3) {
+    for (int idx = lane; idx < 64 * rest; idx += 64) {
+      const int p = idx / rest, c = (W - rest) + (idx - p * rest);
+      dst[(r0 + p) * ld + col0 + c] = tile[p * (W + 1) + c];
+    }
   }
 }
 __device__ inline void tile_load64(const float* __restrict__ src, int ld, int64_t r0, int col0, int W,
@@ -725,6 +733,12 @@ __device__ inline void tile_load64(const float* __restrict__ src, int ld, int64_
     const vf4 v = *reinterpret_cast<const vf4*>(src + (r0 + p) * ld + col0 + c);
     float* t = tile + p * (W + 1) + c;
     t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+  }
+  if (const int rest = W & 3) {
+    for (int idx = lane; idx < 64 * rest; idx += 64) {
+      const int p = idx / rest, c = (W - rest) + (idx - p * rest);
+      tile[p * (W + 1) + c] = src[(r0 + p) * ld + col0 + c];
+    }
   }
 }
 

@@ -184,3 +184,15 @@ def target_grid(vertices):
     ok = np.isfinite(v).all(axis=1)
     lo, hi = v[ok].min(axis=0), v[ok].max(axis=0)
     return lo, float((hi - lo).max())
+
+
+def hub(double):
+    """4,096 fan triangles round vertex 0, every other vertex in a cell of its own at cell size 1"""
+    k = 4096
+    j = np.arange(2 * k)
+    others = np.stack([2.0 + (j % 128) + 0.25, 2.0 + (j // 128) + 0.5, np.full(2 * k, 3.75)], axis=1)
+    v = np.concatenate([[[0.5, 0.5, 0.5]], others])
+    t = np.stack([np.zeros(k, dtype=np.int64), 1 + 2 * np.arange(k), 2 + 2 * np.arange(k)], axis=1).astype(np.int32)
+    if double:                                                # every triangle twice, the copy turned round
+        t = np.stack([t, t[:, ::-1]], axis=1).reshape(-1, 3)
+    return v, t

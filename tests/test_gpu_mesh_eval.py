@@ -189,21 +189,7 @@ def test_degenerate_triangles_and_non_finite_input(R):
         index.closest(torch.from_numpy(q))
 
 
-def _spread_mesh():
-    """2,500 separate triangles (three scan tiles) whose areas span 10^6, with zero-area triangles at the places a scan can
-    get wrong: first, either side of a tile boundary, last"""
-    rng = np.random.default_rng(11)
-    T = 2500
-    size = np.sqrt(np.logspace(-3.0, 3.0, T))
-    rng.shuffle(size)
-    a = rng.uniform(-50.0, 50.0, (T, 3))
-    e1, e2 = rng.standard_normal((T, 3)), rng.standard_normal((T, 3))
-    b, c = a + size[:, None] * e1, a + size[:, None] * e2
-    zero = np.array([0, 1023, 1024, 1700, T - 1])
-    c[zero] = b[zero]                                             # two equal corners: the cross product is exactly 0
-    c[1700] = b[1700] = a[1700]                                   # a point
-    v = np.stack([a, b, c], axis=1).reshape(-1, 3)
-    return v, np.arange(3 * T, dtype=np.int32).reshape(-1, 3), zero
+_spread_mesh = F.spread_mesh
 
 
 def test_surface_samples(R):

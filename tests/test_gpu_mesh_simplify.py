@@ -182,15 +182,7 @@ def test_an_unreferenced_vertex_in_a_populated_cell_does_not_move_the_mean(R):
 
 
 # ---- a hub --------------------------------------------------------------------------------------------------------------
-def _hub(double):
-    k = 4096
-    j = np.arange(2 * k)
-    others = np.stack([2.0 + (j % 128) + 0.25, 2.0 + (j // 128) + 0.5, np.full(2 * k, 3.75)], axis=1)
-    v = np.concatenate([[[0.5, 0.5, 0.5]], others])
-    t = np.stack([np.zeros(k, dtype=np.int64), 1 + 2 * np.arange(k), 2 + 2 * np.arange(k)], axis=1).astype(np.int32)
-    if double:                                                # every triangle twice, the copy turned round
-        t = np.stack([t, t[:, ::-1]], axis=1).reshape(-1, 3)
-    return v, t
+_hub = S.hub
 
 
 @pytest.mark.parametrize("double", [False, True])
