@@ -110,7 +110,12 @@ typedef struct rnb_model_desc {
  *                             (from maxima the forward leaves in the workspace); loss adjoints' per tile / per launch from
  *                             their recorded maxima, so any loss scale works (a loss times 2^k gives gradients times 2^k bit
  *                             for bit, tested at k = +-40).  In the old range the SDF network's sweeps give the same bits as ABI 4's.  The RA
- *                             sweep is bound by its saved-state traffic and keeps the six bf16 terms. */
+ *                             sweep is bound by its saved-state traffic and keeps the six bf16 terms.
+ *   RNB_VARIANT_NO_DEAD_TILES the fused albedo backward (the default fp32 route) skips every 64-point tile whose colour adjoint
+ *                             is exactly zero — the rays outside the mask — and FB and the weight-gradient jobs skip those
+ *                             tiles with it: same outputs and gradients (a tile is skipped only where the full path would
+ *                             have produced exact zeros, NaN semantics included).  This bit forces the full path
+ *                             on every tile.  A/B switch; no effect on the other routes. */
 enum {
   RNB_VARIANT_BF16 = 1,
   RNB_VARIANT_DETERMINISTIC = 2,
@@ -126,7 +131,8 @@ enum {
   RNB_VARIANT_REG_TILE = 1 << 16,
   RNB_VARIANT_LDS_TILE = 1 << 17,
   RNB_VARIANT_X2H = 1 << 18,
-  RNB_VARIANT_NO_X2H = 1 << 19
+  RNB_VARIANT_NO_X2H = 1 << 19,
+  RNB_VARIANT_NO_DEAD_TILES = 1 << 20
 };
 
 /* Trainable leaves of one MLP in the reference's state_dict naming (linN.weight_g [out,1],
@@ -883,7 +889,9 @@ int rnb_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
  *   [0] max |effective weight| over the matrices of both networks (0 unless the default x2h arithmetic keeps its scale table)
  *   [1] max |hidden activation or encoded input| of the SDF network      [2] max |Jacobian row| of the normal's reverse sweep
  *   [3] max |input or hidden activation| of the albedo network           [4] max |loss adjoint| recorded by the backward (x2h)
- *   [5..7] 0 (reserved).
+ *   [5] after rnb_render_bwd: the number of 64-point tiles the fused albedo backward skipped because their colour adjoint was
+ *       exactly zero (0 where that path is off: RNB_VARIANT_NO_DEAD_TILES, other routes)
+ *   [6..7] 0 (reserved).
  * The default arithmetic (RNB_VARIANT_X2H) takes every fp16 operand scale from the data — per matrix, per tile and layer, per
  * launch — so none of these has a limit; the numbers document how far a model is from the fixed scales' old range (255 /
  * 1023), e.g. over a training run (tools/soak.py, profiles/r05_x2h_range.txt).  Costs one pass over the saved state: not

@@ -213,9 +213,21 @@ int sweep_backward(const Layout& L, const float* packed, PointBufs& pb, bool wit
 //                 zR_l is zero and the layers' weight gradients are the single zb/a pair
 //   color_inputs  cinb is left complete, encoding columns included, for the input adjoints
 // (pb.amax was zeroed by the composite backward, the first kernel of rnb_render_bwd, or by the point-wise entry point.)
-int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, const BwdParts& parts, float* packed_grad,
+// The zero-tile path (color_h2.hip): on in a render's backward of the fused fp32 route whose FB sweep skips
+// the tile too (fused_fb_h2_kernel) and where no caller waits for cinb's encoding columns (color_inputs: the tile's word lies
+// there).  Where the weight-gradient jobs skip the tile too (gemm_dw_x3_kernel: BwdParts::dead_dw) its rows of zc_l and cinb
+// stay unwritten; elsewhere (a point count that is no multiple of 32 goes to the split-K kernels) the dead tile stores zeros.
+bool dead_tiles_on(const Layout& L, const PointBufs& pb, const BwdParts& parts) {
+  return !(L.variant & RNB_VARIANT_NO_DEAD_TILES) && parts.albedo && parts.sdf && !parts.color_inputs && L.route.color == COLOR_H2 &&
+         L.route.h2 && pb.alb_dead != nullptr && pb.smax != nullptr && fused_fb_honours_dead(L);
+}
+
+int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, const BwdParts& parts_in, float* packed_grad,
                          hipStream_t s) {
   const Route& r = L.route;
+  BwdParts parts = parts_in;
+  parts.dead_tiles = dead_tiles_on(L, pb, parts_in);
+  parts.dead_dw = parts.dead_tiles && dw_honours_dead(L, pb.M);
   RNB_TRY(check_route_buffers(L, pb, parts));
   RNB_TRY(dw_zero_partials(L, pb, s));
   // the weight-gradient jobs (dw.hip) follow every other launch of the backward; bf16_color_backward's are bf16_dw_backward's
@@ -225,7 +237,7 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
   // (color_h2_backward is ONE fused sweep, which with parts.sdf also forms geb = J_pe(x) nbar_total)
   if (parts.albedo) switch (r.color) {
     case COLOR_BF16: RNB_TRY(bf16_color_backward(L, packed, pb, packed_grad, s)); break;
-    case COLOR_H2: RNB_TRY(color_h2_backward(L, packed, pb, s, parts.sdf, parts.color_inputs)); break;
+    case COLOR_H2: RNB_TRY(color_h2_backward(L, packed, pb, s, parts.sdf, parts.color_inputs, parts.dead_tiles, !parts.dead_dw)); break;
     case COLOR_LAYERS: RNB_TRY(layers_color_backward(L, packed, pb, packed_grad, s)); break;
     case COLOR_NONE: RNB_FAIL(RNB_E_INVALID, "backward: the model has no albedo network");
   }
@@ -259,7 +271,7 @@ int sweep_backward_parts(const Layout& L, const float* packed, PointBufs& pb, co
   // ---- FB: all zb_l (one launch on the fused and bf16 routes) ----------------------------------------
   switch (r.sdf) {
     case SDF_BF16: RNB_TRY(bf16_fb(L, packed, pb, parts.albedo, s)); break;
-    case SDF_FUSED: RNB_TRY(fused_fb(L, packed, pb, parts.feat, s)); break;
+    case SDF_FUSED: RNB_TRY(fused_fb(L, packed, pb, parts.feat, s, parts.dead_tiles)); break;
     case SDF_LAYERS: RNB_TRY(layers_fb(L, packed, pb, parts.feat, s)); break;
   }
   // ---- dW --------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@
 // the per-matrix scale of the mirror (H2Tab).
 // The gradient of the output layer (<= 4 rows) leaves as per-tile column sums (plain stores into a slab, summed in tile order
 // by dw_reduce_kernel): no atomics anywhere — the albedo network's gradients are bit-reproducible.
+// A tile whose colour adjoint is exactly zero (rays outside the mask) takes the backward's zero-tile path: no product, no weight
+// request; FB and the weight-gradient kernel skip the tile with it.
 #include <type_traits>
 
 #include "fused_common.hip.h"
@@ -42,6 +44,10 @@ struct ColH2Args {
                            // all the backward needs of ac_0 (2 MB instead of a 67 MB tile read with its latency exposed)
   float* alb;              // [Mp,4]
   unsigned* smax;          // PointBufs::smax (forward: slots SMAX_CIN, SMAX_AC + l grown) or nullptr
+  unsigned* alb_dead;      // PointBufs::alb_dead (stride alb_dead_stride): the backward leaves 1 for a tile it skipped (its colour
+  long long alb_dead_stride;   // adjoint is exactly zero), else 0 — written only with dead_on
+  int dead_on;             // backward: the zero-tile path may be taken (FB honours alb_dead)
+  int dead_zero;           // ... with weight-gradient kernels that read every row of zc_l / cinb: a dead tile stores its zeros
   // backward
   const float* albbar;     // [Mp,4]
   float* zc[2];            // [Mp,256]
@@ -77,10 +83,18 @@ __device__ inline void col_mask_push(unsigned& m, float a) {
 // all-ones / zero from the bit of element (ti, r) of a column tile's mask word
 __device__ inline unsigned col_mask_bit(unsigned m, int ti, int r) { return (unsigned)(((int)(m << (ti * 16 + r))) >> 31); }
 
+// nz stays +-0 while every x it has seen is finite and turns NaN at the first infinity or NaN (0 x inf = NaN), whatever
+// that value's sign: one fma per value.  (The maxima above are taken on bit patterns and miss a NaN with its sign bit set.)
+__device__ inline float fin_acc(float nz, float x) { return __builtin_fmaf(x, 0.f, nz); }
+// ... folded over the wave into a scalar at the end of each phase: nothing more to keep in a vector register across a matrix loop
+__device__ inline bool fin_bad(float nz) { return __builtin_amdgcn_ballot_w64(!(nz == 0.f)) != 0; }
+
 template <bool MASK>
 __device__ inline float col_fwd_epilogue(const v16f (&acc)[2][2], float inv, const float (&bias)[2], float* X,
-                                         float* __restrict__ out, int64_t row0, int n0, int lane, unsigned* __restrict__ mask_out) {
+                                         float* __restrict__ out, int64_t row0, int n0, int lane, unsigned* __restrict__ mask_out,
+                                         bool& bad) {
   const int h = lane >> 5, cl = lane & 31;
+  float nz = 0.f;
   const BufRsrc ro = tile_rsrc(out + (size_t)row0 * FH, CT * FH * 4);
   int amb = 0;   // (relu outputs are >= +0: their maximum on the bit patterns, h2_track2)
 #pragma unroll
@@ -100,12 +114,14 @@ __device__ inline float col_fwd_epilogue(const v16f (&acc)[2][2], float inv, con
         X[row * FP + col] = a0 * kH2ActScale;
         X[(row + 1) * FP + col] = a1 * kH2ActScale;
         h2_track2(amb, a0, a1);
+        nz = fin_acc(fin_acc(nz, a0), a1);
         if constexpr (MASK) { col_mask_push(mk, a0); col_mask_push(mk, a1); }
         bstore(ro, voff, rowc * FH * 4, a0);
         bstore(ro, voff, (rowc + 1) * FH * 4, a1);
       }
     if constexpr (MASK) mask_out[tj] = mk;
   }
+  bad |= fin_bad(nz);
   return __builtin_bit_cast(float, amb);
 }
 
@@ -150,6 +166,7 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
   const int wave = wave_id();
   const int64_t row0 = (int64_t)blockIdx.x * CT;
   const int n0 = wave * 64;
+  bool bad = false;        // (wave-uniform) this wave has put an infinity or a NaN into cin, ac_0 or ac_1
   const int nks0 = g.Cinp >> 4, ksF = g.F >> 4;   // weight steps per row of layer 0's matrix; first step of the encoding columns
   const x3raw* W0 = g.w2 + 2 * g.w_off[0];
   const x3raw* W1 = g.w2 + 2 * g.w_off[1];
@@ -188,6 +205,7 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
       xr[c + 3] = co * kH2ActScale;
     });
     pm = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));   // (the only unbounded entries of the encoding)
+    bad |= fin_bad(fin_acc(fin_acc(fin_acc(0.f, v[0]), v[1]), v[2]));   // (sines and cosines of finite arguments are finite)
     // (every wave leaves its own word: nothing to initialise; the layers' flags start from zero behind the same barrier)
     // (the ballot runs on every lane: under `lane == 0` it would see row 0 of the tile only)
     const bool any = __builtin_amdgcn_ballot_w64(pm >= kH2ActLimit) != 0;
@@ -221,14 +239,16 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
   mm.run_at<false>(X, W0, nks0, ksF, PW >> 4, n0, lane, acc, W0, nks0, 0, n0);   // acc = pe . W0[:, F ..]^T
   lds_barrier();   // every wave has finished reading the encoding columns
   // ---- features -> tile ----
-  float fm = 0.f;
+  float fm = 0.f, fnz = 0.f;
 #pragma unroll
   for (int i = 0; i < CT * (FH / 4) / NT; ++i) {
     const int idx = tid + NT * i;
     const vf4 v = fr[i];
     *reinterpret_cast<vf4*>(X + (idx >> 6) * FP + (idx & 63) * 4) = v * kH2ActScale;
     fm = fmaxf(fmaxf(fm, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    fnz = fin_acc(fin_acc(fin_acc(fin_acc(fnz, v.x), v.y), v.z), v.w);
   }
+  bad |= fin_bad(fnz);
   h2_raise_flag(fm, &ovf[0], lane);
   __syncthreads();
   float sa = kH2ActScale, isa = 1.f / kH2ActScale;
@@ -261,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
   {
     const float inv = isa * h2_iws_at(iwsv, g.id0);
     const float am = col_fwd_epilogue<true>(acc, inv, bc, X, g.ac[0], row0, n0, lane,
-                                            g.ac0_mask + ((size_t)blockIdx.x * NT + tid) * 2);
+                                            g.ac0_mask + ((size_t)blockIdx.x * NT + tid) * 2, bad);
     h2_raise_flag(am, &ovf[1], lane);
     lds_barrier();
     col_tile_rescale(&ovf[1], am, wmx, X, n0, lane, wave, g.smax ? g.smax + SMAX_AC : nullptr, tid, sa, isa);
@@ -282,8 +302,12 @@ __global__ __launch_bounds__(256, 2) void color_fwd_h2_kernel(ColH2Args g) {
   const float bo = g.packed[g.bo_off + min(lane, g.Co - 1)];   // (used by lanes < Co)
   {
     const float inv = isa * h2_iws_at(iwsv, g.id0 + 1);
-    const float am = col_fwd_epilogue<false>(acc, inv, bc, X, g.ac[1], row0, n0, lane, nullptr);
+    const float am = col_fwd_epilogue<false>(acc, inv, bc, X, g.ac[1], row0, n0, lane, nullptr, bad);
     h2_raise_flag(am, &ovf[0], lane);
+    // for the backward's zero-tile path: a product it skips is 0 x (these values), exactly zero only while they are finite.
+    // A wave that saw an infinity or a NaN raises SMAX_NONFIN (a path a sane network never takes: no atomic otherwise)
+    if (g.smax != nullptr && bad && lane == 0)
+      (void)__hip_atomic_fetch_max(g.smax + SMAX_NONFIN, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     lds_barrier();
     col_tile_rescale(&ovf[0], am, wmx, X, n0, lane, wave, g.smax ? g.smax + SMAX_AC + 1 : nullptr, tid, sa, isa);
   }
@@ -322,6 +346,7 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
   __shared__ __attribute__((aligned(16))) float X[CT * FP];
   __shared__ __attribute__((aligned(16))) float ZO[CT * 4];
   __shared__ float wm[2][4];
+  __shared__ int live_w[4];   // per wave: something forbids the zero-tile path
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = wave_id();
   const int64_t row0 = (int64_t)blockIdx.x * CT;
@@ -331,15 +356,31 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
   const x3raw* W1T = g.w2 + 2 * g.wT_off[1];
   const x3raw* W0T = g.w2 + 2 * g.wT_off[0];
   const float iwsv = h2_iws_load(g.h2tab, lane);
+  // The zero-tile path.  A ray outside the mask has a colour adjoint of exactly zero, so every product below
+  // is 0 x (saved state or weights): exactly zero while those are finite, NaN otherwise — and the NaN must stay.  What a
+  // dead tile would multiply with: alb (checked here), ac_1, ac_0, cin and through cin's feature columns a_{nh-1} (the
+  // forward's word SMAX_NONFIN: a non-finite a_{nh-1} makes its whole row of features non-finite), W_out (checked here), the
+  // two hidden matrices and the feature head (their maxima in the mirror's table; a NaN weight shows in SMAX_NONFIN).
+  bool veto = !g.dead_on;
+  if (g.dead_on) {   // (uniform)
+    const unsigned wmx = g.h2tab->wmax[lane < kH2TabSlots ? lane : 0];
+    const bool mine = lane >= g.id0 - 1 && lane <= g.id0 + 1 && wmx >= 0x7f800000u;
+    veto = g.smax[SMAX_NONFIN] != 0u || __builtin_amdgcn_ballot_w64(mine) != 0;
+  }
 
   // zo = albbar * sigmoid'  (rows >= M: 0)
+  bool keep = false;   // this lane's row carries a colour adjoint, or an albedo that is not finite
   if (tid < CT) {
     const int64_t row = row0 + tid;
     const vf4 a4 = *reinterpret_cast<const vf4*>(g.alb + row * 4);
     const vf4 g4 = *reinterpret_cast<const vf4*>(g.albbar + row * 4);
     vf4 z;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) z[c] = (c < g.Co && tid < rows_ok) ? g4[c] * (g.squeeze ? a4[c] * (1.f - a4[c]) : 1.f) : 0.f;
+    for (int c = 0; c < 4; ++c) {
+      const bool on = c < g.Co && tid < rows_ok;
+      z[c] = on ? g4[c] * (g.squeeze ? a4[c] * (1.f - a4[c]) : 1.f) : 0.f;
+      keep |= on && ((__builtin_bit_cast(unsigned, g4[c]) & 0x7fffffffu) != 0u || (g.squeeze && !(fabsf(a4[c]) < INFINITY)));
+    }
     *reinterpret_cast<vf4*>(ZO + tid * 4) = z;
   }
   // ac_1 arrives in two halves of 32 rows.  Everything this phase loads is requested BEFORE its stores: the vector-memory
@@ -358,7 +399,40 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
       const float w = g.packed[g.wo_off + (long long)min(c, g.Co - 1) * g.ldwo + n0 + tj * 32 + (lane & 31)];
       wo[tj][c] = c < g.Co ? w : 0.f;
     }
+  if (!veto) {   // (uniform) the tile is a candidate: the waves vote — wave 0 holds the rows, every wave 64 columns of W_out
+    float wnz = 0.f;
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) wnz = fin_acc(wnz, wo[tj][c]);
+    const bool any = __builtin_amdgcn_ballot_w64(keep || !(wnz == 0.f)) != 0;
+    if (lane == 0) live_w[wave] = any ? 1 : 0;
+  }
   __syncthreads();
+  const bool dead = !veto && (live_w[0] | live_w[1] | live_w[2] | live_w[3]) == 0;   // (workgroup-uniform)
+  if (tid == 0 && g.dead_on) {
+    g.alb_dead[(size_t)blockIdx.x * g.alb_dead_stride] = dead ? 1u : 0u;
+    if (blockIdx.x == 0) g.amax[AMAX_DEAD_RAN] = 1u;   // (the record that these words are this backward's)
+  }
+  if (dead) {
+    // No product runs, no weight is requested.  zc_1, zc_0 and cinb of this tile stay unwritten where their readers (FB, the
+    // weight-gradient jobs) skip the tile by the word above; where the weight-gradient kernels read every row, the exact zeros
+    // the full path would have left are stored.  The output layer's slabs are summed over every tile: this tile's sums are
+    // zero.  amax: untouched (max with zero).  What is left is geb = J_pe(x) nbar, below.
+    if (g.dead_zero) {   // (uniform)
+      const vf4 z4 = {0.f, 0.f, 0.f, 0.f};
+      for (int idx = tid; idx < CT * (FH / 4); idx += 256) {
+        const size_t r = (size_t)row0 + (idx >> 6);
+        const int c = (idx & 63) * 4;
+        *reinterpret_cast<vf4*>(g.zc[1] + r * FH + c) = z4;
+        *reinterpret_cast<vf4*>(g.zc[0] + r * FH + c) = z4;
+        *reinterpret_cast<vf4*>(g.cinb + r * g.Cinp + c) = z4;
+      }
+    }
+    if (tid == 0) g.amax[AMAX_ANY_DEAD] = 1u;   // (every dead tile stores the same word: no atomic)
+    if (tid < g.Co) g.dbo_part[(size_t)blockIdx.x * g.Co + tid] = 0.f;
+    for (int c = 0; c < g.Co; ++c) g.dwo_part[((size_t)blockIdx.x * g.Co + c) * FH + tid] = 0.f;
+  } else {
   if (tid < g.Co) {   // d b_out of this tile
     float t = 0.f;
     for (int r = 0; r < CT; ++r) t += ZO[r * 4 + tid];
@@ -483,6 +557,7 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) X[(rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * FP + 32 * ct + cl] = pacc[0][0][r] * unscale0;
   }
+  }   // (!dead)
   lds_barrier();
   if (g.keep_pe) {
     for (int idx = tid; idx < CT * 16; idx += 256) {
@@ -501,7 +576,7 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
     {
       const float* gq = X + p * FP + g.pev;   // the pe(n) block of the adjoint
       float t[3] = {0.f, 0.f, 0.f};
-      if (ok) pe_adjoint(g.nrm + row * 4, gq, g.multires_view, q, 4, t);
+      if (ok && !dead) pe_adjoint(g.nrm + row * 4, gq, g.multires_view, q, 4, t);
 #pragma unroll
       for (int d = 0; d < 3; ++d) part[q * 3 + d] = t[d];
     }
@@ -509,8 +584,10 @@ __global__ __launch_bounds__(256, 2) void color_bwd_h2_kernel(ColH2Args g) {
     float nb[3] = {0.f, 0.f, 0.f};
     if (ok) {
       const float* gq = X + p * FP + g.pev;
+      // (a dead tile: the pe(n) block of the adjoint is zero and the normal finite, so nbar_total = nbar)
 #pragma unroll
-      for (int d = 0; d < 3; ++d) nb[d] = g.nbar[row * 4 + d] + gq[d] + ((part[d] + part[3 + d]) + (part[6 + d] + part[9 + d]));
+      for (int d = 0; d < 3; ++d)
+        nb[d] = dead ? g.nbar[row * 4 + d] : g.nbar[row * 4 + d] + gq[d] + ((part[d] + part[3 + d]) + (part[6 + d] + part[9 + d]));
     }
     float* o = X + p * FP + 64;
     if (q == 0) {
@@ -584,7 +661,8 @@ int color_h2_forward(const Layout& L, const float* packed, PointBufs& pb, const 
 // floats of the per-tile slabs of the output layer's gradient
 int64_t color_h2_part_floats(const Layout& L, int64_t M) { return (pad_rows(M) / CT) * (int64_t)L.Co * (FH + 1); }
 
-int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool sdf, bool keep_pe) {
+int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool sdf, bool keep_pe, bool dead_tiles,
+                      bool dead_zero_fill) {
   ColH2Args g;
   col_fill(L, packed, pb, g);
   g.nrm = pb.nrm;
@@ -594,6 +672,15 @@ int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipSt
   g.nbar = pb.nbar;
   g.geb = sdf ? pb.geb : nullptr;
   g.keep_pe = keep_pe ? 1 : 0;
+  g.alb_dead = pb.alb_dead;
+  g.alb_dead_stride = pb.alb_dead_stride;
+  g.smax = pb.smax;
+  g.dead_zero = dead_zero_fill ? 1 : 0;
+  // (the one decision is dead_tiles_on, backward.hip; what it promises is held here: a backward that keeps cinb's encoding
+  // columns, where the tiles' words lie, or lacks a buffer the path reads, is refused instead of run)
+  if (dead_tiles && !(sdf && !keep_pe && pb.alb_dead != nullptr && pb.smax != nullptr && pb.amax != nullptr && g.h2tab != nullptr))
+    RNB_FAIL(RNB_E_INVALID, "albedo backward: the zero-tile path was asked for in a backward that cannot take it");
+  g.dead_on = dead_tiles ? 1 : 0;
   g.multires = L.multires;
   g.Ep = L.Ep;
   g.amax = pb.amax;

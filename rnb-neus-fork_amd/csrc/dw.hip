@@ -14,6 +14,15 @@ bool dw_one_wg_runs(const Layout& L, int64_t M) {
   return (is_x3(L) || (L.variant & RNB_VARIANT_DW_STAGED) != 0) && !(L.variant & RNB_VARIANT_DW_LDS) && M % kStChunk == 0;
 }
 
+// The jobs whose X operand the zero-tile path may leave unwritten — the albedo net's hidden layers and the feature head — all
+// go to gemm_dw_x3_kernel, the kernel that honours DwPair::dead.
+bool dw_honours_dead(const Layout& L, int64_t M) {
+  if (!dw_one_wg_runs(L, M) || !is_x3(L)) return false;
+  for (int l = 0; l < L.nc; ++l)
+    if (!x3_job_shape(true, L.col[l].Np, L.col[l].Kp)) return false;
+  return x3_job_shape(true, L.feat.Np, L.feat.Kp);
+}
+
 // One job of dw_list: dW[N x K] (+)= X1^T Y1 (+ X2^T Y2) over the points, with db = the column sums of X of pair
 // bias_pair; or, with splits > 0, a reduce-only job: `splits` slabs [N x K] + [N] at part / partb that another kernel
 // wrote, summed into dW / db by the reduction launch that follows the last group of weight-gradient jobs.
@@ -35,6 +44,10 @@ struct DwListed {
 template <class F>
 static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts, int sdfh_slabs, F f) {
   const int64_t M = pb.M;
+  // the albedo backward's zero-tile path ran: zc_l and cinb of its dead tiles are unwritten (exact zeros); the jobs that take
+  // them as X skip those tiles
+  const unsigned* dead = parts.dead_dw ? pb.alb_dead : nullptr;
+  const unsigned* any_dead = dead != nullptr ? pb.amax + AMAX_ANY_DEAD : nullptr;
   auto job = [&](const DwPair& p1, const DwPair& p2, int npairs, const Lin& ln, int bias_pair, double fl) {
     f(DwListed{p1, p2, npairs, ln.Np, ln.Kp, bias_pair, ln.w_off, ln.b_off, fl, nullptr, nullptr, 0});
   };
@@ -43,7 +56,8 @@ static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts,
       const float* in = l == 0 ? pb.cin : pb.ac[l - 1];
       const int ldin = l == 0 ? L.Cinp : L.Hcp;
       const DwPair p{pb.zc[l], L.Hcp, in, ldin, 0, h2_slot(L, pb.amax, AMAX_ZC + l),
-                     h2_slot(L, pb.smax, l == 0 ? SMAX_CIN : SMAX_AC + l - 1)};
+                     h2_slot(L, pb.smax, l == 0 ? SMAX_CIN : SMAX_AC + l - 1), dead, pb.alb_dead_stride,
+                     any_dead};
       job(p, p, 1, L.col[l], 0, mm_flops(M, L.col[l]));
     }
     if (L.route.color == COLOR_H2) {   // the output layer's gradient: per-tile column sums (color_h2_backward)
@@ -57,7 +71,8 @@ static void dw_list(const Layout& L, const PointBufs& pb, const BwdParts& parts,
     f(DwListed{{}, {}, 0, 1, L.Hp, 0, L.wsdf_off, L.bsdf_off, 0.0, pb.sdfh_part, pb.sdfh_part + (int64_t)sdfh_slabs * L.Hp,
                sdfh_slabs});
   if (parts.feat) {
-    const DwPair p{pb.cinb, L.Cinp, pb.a[L.nh - 1], L.Hp, 0, h2_slot(L, pb.amax, AMAX_CINB), h2_slot(L, pb.smax, SMAX_A + L.nh - 1)};
+    const DwPair p{pb.cinb, L.Cinp, pb.a[L.nh - 1], L.Hp, 0, h2_slot(L, pb.amax, AMAX_CINB), h2_slot(L, pb.smax, SMAX_A + L.nh - 1),
+                   parts.albedo ? dead : nullptr, pb.alb_dead_stride, any_dead};
     job(p, p, 1, L.feat, 0, mm_flops(M, L.feat));
   }
   for (int l = L.nh - 1; l >= 0; --l) {

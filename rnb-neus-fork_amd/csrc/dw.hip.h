@@ -22,6 +22,11 @@ struct DwPair {
   const unsigned* amax = nullptr;
   // ... and where the forward left max |.| of the OTHER operand (saved state: PointBufs::smax), or nullptr: the fixed 2^6
   const unsigned* smax = nullptr;
+  // gemm_dw_x3_kernel only: one word per 64-point tile, 1 = the tile's X rows were not written and stand for exact zeros (the
+  // albedo backward's zero-tile path, color_h2.hip): the tile's points are skipped, loads and MFMAs alike.  nullptr: none
+  const unsigned* dead = nullptr;
+  long long dead_stride = 0;   // (tile t's word is dead[t * dead_stride]: PointBufs::alb_dead)
+  const unsigned* any_dead = nullptr;   // with `dead`: one word, 0 = no tile of the launch is dead (PointBufs::amax, AMAX_ANY_DEAD)
 };
 
 template <bool GUARD, int KT>
@@ -613,8 +618,41 @@ __device__ inline void dw_x3_colsum(const vf4 (&x)[4], bool on, double (&bs)[4])
 
 // DUMMY == 1 (tools/dwx3_bench only): wave 0 sums the clocks it spends waiting at the barrier / issuing a chunk's
 // reads, MFMAs, split and stores / issuing the next loads, and leaves them in J.db (as uint64[8] per workgroup)
+// Pairs with DwPair::dead: the live 32-point units of a segment of the split, in ascending order, as a list in LDS.  The
+// chunk pipeline below then walks the list instead of the range, so the order of summation is a function of the flags (of
+// the inputs) alone.  A unit never straddles a tile (tiles are 64 points, splits begin on multiples of 32).
+constexpr int kDwLiveCap = 2048;   // units per segment (65,536 points); a longer split takes several segments
+struct DwLive {
+  int n;
+  unsigned short unit[kDwLiveCap];
+};
+// (read AS LDS: through a generic pointer the look-up would be a flat load, which waits on the vector-memory counter behind
+// the operand rows in flight — fused_common.hip.h, h2_flag_read)
+typedef __attribute__((address_space(3))) const DwLive lds_DwLive;
+// The list of units [0, nunits) of the segment that begins at point m0.  Every thread fetches the words of its units (independent
+// loads: one global round trip for the segment), then wave 0 compacts them in place (ballot + prefix count: ordered, no
+// atomics; a block of 64 is read before anything at or below it is written).
+__device__ inline void dw_live_build(DwLive* lv, const unsigned* __restrict__ dead, long long stride, int m0, int nunits, int tid) {
+  __syncthreads();   // every wave is done with the previous list
+  for (int u = tid; u < nunits; u += (int)blockDim.x)
+    lv->unit[u] = dead[(size_t)((m0 + 32 * u) >> 6) * stride] == 0u ? (unsigned short)1 : (unsigned short)0;
+  __syncthreads();
+  if (tid < 64) {
+    int n = 0;
+    for (int u0 = 0; u0 < nunits; u0 += 64) {
+      const int u = u0 + tid;
+      const bool live = u < nunits && lv->unit[u] != 0;
+      const unsigned long long mask = __builtin_amdgcn_ballot_w64(live);
+      if (live) lv->unit[n + __builtin_popcountll(mask & ((1ull << tid) - 1ull))] = (unsigned short)u;
+      n += __builtin_popcountll(mask);
+    }
+    if (tid == 0) lv->n = n;
+  }
+  __syncthreads();
+}
+
 template <int DUMMY, bool NARROW, int NP = 3>
-__device__ inline void dw_x3_body(const DwGroup& g, const DwJob& J, int split, char* lds) {
+__device__ inline void dw_x3_body(const DwGroup& g, const DwJob& J, int split, char* lds, DwLive* lv) {
   constexpr int kOp = dw_op_bytes<NP>(), kBuf = dw_buf_bytes<NP>();
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = wave_id();
@@ -622,7 +660,6 @@ __device__ inline void dw_x3_body(const DwGroup& g, const DwJob& J, int split, c
   const int m_begin = split * J.rows_per_split;
   const int m_end = min(g.M, m_begin + J.rows_per_split);
   if (m_begin >= m_end) return;   // (workgroup-uniform)
-  const int nchunks = (m_end - m_begin) / kX3Chunk;   // even: ranges are multiples of 32 points (host)
   // narrow job: the Y operand has 64 columns (J.K == 64); everything about X and the row split stays
   constexpr bool narrow = NARROW;
   // staging role of this thread: columns 4 cg .. + 4, points 4 pq .. + 4 of operand sop
@@ -666,16 +703,37 @@ __device__ inline void dw_x3_body(const DwGroup& g, const DwJob& J, int split, c
     const DwPair p = pi == 0 ? J.p1 : J.p2;
     const int ld = sop == 0 ? p.ldx : p.ldy;
     [[maybe_unused]] const float sc = NP == 2 ? (sop == p.adj ? s_adj : s_state) : 1.f;   // this thread's operand
-    // resource based at this split's first row: 32-bit offsets stay inside the split whatever the total point count
-    const BufRsrc src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>((sop == 0 ? p.X : p.Y) + (size_t)m_begin * ld), 0,
-                                                          0xfffffffc, 0x00020000);
     const unsigned voff = st_on ? 16u * (unsigned)cg : 0u;   // (lanes that stage nothing re-read column group 0)
     const bool do_bias = DUMMY == 0 && J.db != nullptr && pi == J.bias_pair && sop == 0;
+    // a pair without dead tiles: ONE segment, the whole split, its chunks in place.  With them: segments of kDwLiveCap units,
+    // each walked through its list of live units (all of this is workgroup-uniform)
+    // A segment in which every unit turns out live is walked in place too: no look-up per chunk, the loop of an unflagged pair.
+    // and a backward without a single dead tile reads one word: nothing else differs from an unflagged pair
+    const bool flagged = p.dead != nullptr && __builtin_amdgcn_readfirstlane((int)*p.any_dead) != 0;
+    const int seg_rows = flagged ? kDwLiveCap * 32 : m_end - m_begin;
+   for (int seg0 = m_begin; seg0 < m_end; seg0 += seg_rows) {
+    int nchunks = (min(m_end, seg0 + seg_rows) - seg0) / kX3Chunk;   // even: ranges are multiples of 32 points (host)
+    bool listed = false;
+    if (flagged) {
+      dw_live_build(lv, p.dead, p.dead_stride, seg0, nchunks / 2, tid);
+      const int nlive = __builtin_amdgcn_readfirstlane(((lds_DwLive*)lv)->n);
+      listed = 2 * nlive != nchunks;
+      nchunks = 2 * nlive;
+      if (nchunks == 0) continue;
+    }
+    // first row of chunk k (relative to the segment): in place, or through the list
+    auto row_of = [&](int k) -> int {
+      const int u = listed ? __builtin_amdgcn_readfirstlane((int)((lds_DwLive*)lv)->unit[k >> 1]) : (k >> 1);
+      return u * 32 + (k & 1) * kX3Chunk;
+    };
+    // resource based at this segment's first row: 32-bit offsets stay inside the split whatever the total point count
+    const BufRsrc src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>((sop == 0 ? p.X : p.Y) + (size_t)seg0 * ld), 0,
+                                                          0xfffffffc, 0x00020000);
     const int last = nchunks - 1;
-    const int r0 = 4 * pq;   // (rows relative to the split)
+    const int r0 = 4 * pq;   // (rows relative to the segment)
     vf4 x0[4], x1[4];   // raw rows of an even / odd chunk
-    dw_x3_load(src, voff, ld, r0, x0);
-    dw_x3_load(src, voff, ld, r0 + min(1, last) * kX3Chunk, x1);
+    dw_x3_load(src, voff, ld, r0 + row_of(0), x0);
+    dw_x3_load(src, voff, ld, r0 + row_of(min(1, last)), x1);
     __builtin_amdgcn_s_barrier();   // every wave is done with the buffers of the previous pair
     {
       vu2x pl[4][NP];
@@ -683,18 +741,19 @@ __device__ inline void dw_x3_body(const DwGroup& g, const DwJob& J, int split, c
       if (st_on) dw_x3_store<NP>(swr, pl);
       dw_x3_colsum(x0, do_bias, bs);
     }
-    dw_x3_load(src, voff, ld, r0 + min(2, last) * kX3Chunk, x0);
+    dw_x3_load(src, voff, ld, r0 + row_of(min(2, last)), x0);
     for (int c = 0; c < nchunks; c += 2) {
       // even chunk c from buffer 0; chunk c + 1 (x1) -> buffer 1; x1 <- chunk c + 3
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       [[maybe_unused]] const unsigned long long s0 = DUMMY == 1 ? __builtin_amdgcn_s_memtime() : 0;
       __builtin_amdgcn_s_barrier();
       [[maybe_unused]] const unsigned long long s1 = DUMMY == 1 ? __builtin_amdgcn_s_memtime() : 0;
+      const int row3 = row_of(min(c + 3, last)), row4 = row_of(min(c + 4, last));   // (looked up ahead of the chunk's own LDS reads)
       if constexpr (narrow) dw_x3_chunk_narrow<NP>(fx, fy, acc, x1, sc, swr + kBuf, st_on);
       else dw_x3_chunk<NP>(fx, fy, acc, x1, sc, swr + kBuf);
       dw_x3_colsum(x1, do_bias, bs);   // (nchunks even: chunk c + 1 always exists)
       [[maybe_unused]] const unsigned long long s2 = DUMMY == 1 ? __builtin_amdgcn_s_memtime() : 0;
-      dw_x3_load(src, voff, ld, r0 + min(c + 3, last) * kX3Chunk, x1);
+      dw_x3_load(src, voff, ld, r0 + row3, x1);
       if constexpr (DUMMY == 1) {
         const unsigned long long s3 = __builtin_amdgcn_s_memtime();
         t_bar += s1 - s0; t_chunk += s2 - s1; t_load += s3 - s2;
@@ -706,8 +765,9 @@ __device__ inline void dw_x3_body(const DwGroup& g, const DwJob& J, int split, c
       if constexpr (narrow) dw_x3_chunk_narrow<NP>(fx + kBuf, fy + kBuf, acc, x0, sc, swr, st_on);
       else dw_x3_chunk<NP>(fx + kBuf, fy + kBuf, acc, x0, sc, swr);
       dw_x3_colsum(x0, do_bias && c + 2 < nchunks, bs);
-      dw_x3_load(src, voff, ld, r0 + min(c + 4, last) * kX3Chunk, x0);
+      dw_x3_load(src, voff, ld, r0 + row4, x0);
     }
+   }   // (segments)
   }
   // accumulator (ti, tj, r) of lane (i, h) is dW[64 wm + 32 ti + rho][128 wn + 32 tj + i], rho = (r & 3) + 8 (r >> 2) + 4 h
   // slabs are compact [split][N][K] (K = the job's Y columns; dw_reduce_kernel scatters them into dW with lddw)
@@ -754,6 +814,7 @@ __device__ inline void dw_x3_body(const DwGroup& g, const DwJob& J, int split, c
 template <int DUMMY, int NP = 3>
 __global__ __launch_bounds__(512, 1) void gemm_dw_x3_kernel(const DwGroup g) {
   __shared__ __attribute__((aligned(16))) char lds[2 * dw_buf_bytes<NP>() > 8192 ? 2 * dw_buf_bytes<NP>() : 8192];   // 102 KB (NP = 2: 68 KB)
+  __shared__ DwLive live;   // 4 KB
   int ji = 0, begin = 0;
   for (int q = 0; q + 1 < g.njobs; ++q)
     if ((int)blockIdx.x >= g.job[q].block_end) { ji = q + 1; begin = g.job[q].block_end; }
@@ -761,8 +822,8 @@ __global__ __launch_bounds__(512, 1) void gemm_dw_x3_kernel(const DwGroup g) {
   const int split = (int)blockIdx.x - begin;
   if (split >= J.splits) return;
   // two bodies, one per job width (workgroup-uniform): separate accumulator sets, separate register allocation
-  if (J.K < 256) dw_x3_body<DUMMY, true, NP>(g, J, split, lds);
-  else dw_x3_body<DUMMY, false, NP>(g, J, split, lds);
+  if (J.K < 256) dw_x3_body<DUMMY, true, NP>(g, J, split, lds, &live);
+  else dw_x3_body<DUMMY, false, NP>(g, J, split, lds, &live);
 }
 
 }  // namespace rnb

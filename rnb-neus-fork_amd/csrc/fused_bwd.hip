@@ -40,6 +40,8 @@ struct FusedBwdArgs {
   const float* sbar;    // [Mp]        (FB)
   const float* fbar;    // [Mp,ld_fbar] first 256 columns, or nullptr (FB, no_albedo)
   int ld_fbar;
+  const unsigned* alb_dead;   // PointBufs::alb_dead or nullptr (FB, x2h form): 1 = the albedo backward skipped the 64-point tile:
+  long long alb_dead_stride;  // its fbar rows are exact zeros
   unsigned* amax;       // PointBufs::amax (RA: slots AMAX_U + l of the u_l it writes; FB: AMAX_ZB + l), or nullptr
   const H2Tab* h2tab;   // x2h: scales of the fp16 mirror's matrices (hidden layer l: id l, feature head: id nh)
   unsigned* smax;       // x2h R sweep of a render forward: PointBufs::smax (slots SMAX_GZ + l grown by the tile maxima), or nullptr
@@ -471,12 +473,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_fb_h2_kernel(F
   const long long left = g.M - row0;
   const int rows_ok = left >= BT ? BT : (int)(left < 0 ? 0 : left);
 
+  // a tile the albedo backward skipped (color_h2.hip): its feature adjoint is exactly zero and the feature head's matrix finite,
+  // so ab_{nh-1} starts from the sdf head's term alone, as without an albedo network (workgroup-uniform)
+  const float* const fbar = (g.fbar != nullptr && g.alb_dead != nullptr && g.alb_dead[(size_t)blockIdx.x * g.alb_dead_stride] != 0u) ? nullptr : g.fbar;
+
   v16f acc[TI][TJ];
   AuxTile<TI, TJ> aD, aZ;
   X3Mma<TI, TJ, 2> mm;
   constexpr bool LATE = TJ == 2;   // 64 x 64-output waves: operand tiles requested after the matrix loop
   if constexpr (!LATE) {
-    if (g.fbar != nullptr) mm.request(g.w3 + 2 * g.net.wfT_off, FH, n0, lane);
+    if (fbar != nullptr) mm.request(g.w3 + 2 * g.net.wfT_off, FH, n0, lane);
     else if (g.net.nh > 1) mm.request(g.w3 + 2 * g.net.wT_off[g.net.nh - 1], FH, n0, lane);
     prefetch_tile<TI, TJ>(g.D[g.net.nh - 1], row0, n0, lane, aD);
     prefetch_tile<TI, TJ>(g.zR[g.net.nh - 1], row0, n0, lane, aZ);
@@ -484,8 +490,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void fused_fb_h2_kernel(F
   for (int ti_ = 0; ti_ < TI; ++ti_) for (int tj_ = 0; tj_ < TJ; ++tj_) for (int r_ = 0; r_ < 16; ++r_) acc[ti_][tj_][r_] = 0.f;
   float unscale = 1.f;   // accumulator -> ab (true units)
   const float iwsv = h2_iws_load(g.h2tab, lane);
-  if (g.fbar != nullptr) {   // ab_{nh-1} = fbar W_feat (+ the sdf-head term below)
-    const float* fb = g.fbar + (size_t)row0 * g.ld_fbar;
+  if (fbar != nullptr) {   // ab_{nh-1} = fbar W_feat (+ the sdf-head term below)
+    const float* fb = fbar + (size_t)row0 * g.ld_fbar;
     float m = 0.f;
     for (int idx = tid; idx < BT * FH / 4; idx += NT) {
       const int r = idx >> 6, c4 = idx & 63;
@@ -602,11 +608,22 @@ static void fill_args(const Layout& L, const float* packed, PointBufs& pb, Fused
 // point (32-point tiles ran at the CU's 64 B/clk fill rate, the matrix pipe 28-34 % busy) and the split work per MFMA;
 // the operand tiles of the epilogue are requested after the matrix loop, into the registers it frees, and travel while
 // the CU's other workgroup multiplies.
-// pick_tile: that choice (knobs, else the defaults above) as f(TI, NW, grid, block) with TI, NW as constants
+// tile_choice: that choice (knobs, else the defaults above); pick_tile: the same as f(TI, NW, grid, block) with TI, NW as constants
+static void tile_choice(const Layout& L, int* ti, int* nw) {
+  const int kt = L.knob(RNB_VARIANT_BWD_TI_SHIFT), kw = L.knob(RNB_VARIANT_BWD_NW_SHIFT);
+  *ti = kt == 1 || kt == 2 ? kt : (is_x3(L) ? 2 : 1);
+  *nw = kw == 1 ? 4 : kw == 2 ? 8 : (is_x3(L) ? 4 : 8);
+}
+// FB runs as fused_fb_h2_kernel (fused_fb below: 64-point tiles of the x2h route), the form that honours PointBufs::alb_dead
+static bool fb_runs_h2(const Layout& L) {
+  int ti, nw;
+  tile_choice(L, &ti, &nw);
+  return ti == 2 && is_x2h(L);
+}
 template <class F>
 static void pick_tile(const Layout& L, const PointBufs& pb, F&& f) {
-  const int kt = L.knob(RNB_VARIANT_BWD_TI_SHIFT), kw = L.knob(RNB_VARIANT_BWD_NW_SHIFT);
-  const int ti = kt == 1 || kt == 2 ? kt : (is_x3(L) ? 2 : 1), nw = kw == 1 ? 4 : kw == 2 ? 8 : (is_x3(L) ? 4 : 8);
+  int ti, nw;
+  tile_choice(L, &ti, &nw);
   pick_c<2, 1>(ti, [&](auto ti_c) {
     pick_c<8, 4>(nw, [&](auto nw_c) { f(ti_c, nw_c, dim3((unsigned)(pb.Mp / (32 * ti_c))), dim3(64 * nw_c)); });
   });
@@ -653,7 +670,9 @@ int fused_ra(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s,
   return RNB_OK;
 }
 
-int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_color, hipStream_t s) {
+bool fused_fb_honours_dead(const Layout& L) { return fb_runs_h2(L); }
+
+int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_color, hipStream_t s, bool dead_tiles) {
   FusedBwdArgs g;
   fill_args(L, packed, pb, g);
   g.fbar = with_color ? pb.cinb : nullptr;
@@ -662,16 +681,20 @@ int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_colo
   pick_tile(L, pb, [&](auto ti_c, auto nw_c, dim3 grid, dim3 block) {
     constexpr int TI = decltype(ti_c)::value, NW = decltype(nw_c)::value;
     if constexpr (TI == 2) {
-      if (is_x2h(L)) {   // three fp16 terms, per-tile scales (64-point tiles only: the in-place form)
+      if (fb_runs_h2(L)) {   // three fp16 terms, per-tile scales (64-point tiles only: the in-place form)
         g.w3 = x2h_mirror(L, packed);
+        g.alb_dead = with_color && dead_tiles ? pb.alb_dead : nullptr;
+        g.alb_dead_stride = pb.alb_dead_stride;
         hipLaunchKernelGGL((fused_fb_h2_kernel<NW>), grid, block, 0, s, g);
         return;
       }
     }
+    if (dead_tiles) return;   // (refused below: this kernel reads every row of cinb)
     pick_c<1, 0>(is_x3(L), [&](auto x3_c) {
       hipLaunchKernelGGL((fused_fb_kernel<TI, NW, decltype(x3_c)::value != 0>), grid, block, 0, s, g);
     });
   });
+  if (dead_tiles && !fb_runs_h2(L)) RNB_FAIL(RNB_E_INVALID, "FB: the zero-tile path needs the x2h kernel on 64-point tiles");
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }

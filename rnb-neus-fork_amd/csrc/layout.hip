@@ -44,7 +44,7 @@ int make_layout(const rnb_model_desc* d, Layout* L) {
   if (d->sdf_multires < 0 || d->sdf_multires > 16) RNB_FAIL(RNB_E_INVALID, "bad sdf_multires");
   if (!(d->sdf_scale > 0.f)) RNB_FAIL(RNB_E_INVALID, "sdf_scale must be positive");
   L->variant = d->variant;
-  if (d->variant & ~0xFFF7F) RNB_FAIL(RNB_E_INVALID, "unknown bits in rnb_model_desc.variant (0x%x)", d->variant);
+  if (d->variant & ~0x1FFF7F) RNB_FAIL(RNB_E_INVALID, "unknown bits in rnb_model_desc.variant (0x%x)", d->variant);
   L->nh = d->sdf_n_layers;
   L->multires = d->sdf_multires;
   L->pe = 3 * (1 + 2 * d->sdf_multires);
@@ -199,6 +199,10 @@ void carve_points(const Layout& L, Carver& c, int64_t M, int mode, PointBufs* pb
     if (mode & PM_WITH_COLOR) {
       for (int l = 0; l < L.nc; ++l) pb->zc[l] = c.take<float>(Mp * L.Hcp);
       pb->cinb = c.take<float>(Mp * L.Cinp);
+      if (L.route.color == COLOR_H2 && pb->cinb != nullptr) {   // (no room of its own: PointBufs::alb_dead)
+        pb->alb_dead = reinterpret_cast<unsigned*>(pb->cinb + L.F);
+        pb->alb_dead_stride = (int64_t)64 * L.Cinp;
+      }
       if (L.route.color == COLOR_BF16)
         for (int l = 0; l < L.nc; ++l) pb->zc8[l] = c.take<uint16_t>(Mp * L.Hcp);
     }

@@ -330,15 +330,28 @@ struct PointBufs {
   int64_t dw_part_floats;
   int64_t dw_slab_off;      // where the second part begins (floats): set with the buffer, read by dw_zero_partials / dw_backward
   unsigned* ac0_mask;       // fused albedo kernels: relu'(ac_0) as bits [tiles][256][2] (color_h2.hip)
+  unsigned* alb_dead;       // fused albedo backward: one word per 64-point tile, 1 = the tile's colour adjoint is exactly zero and
+  int64_t alb_dead_stride;  // the tile was skipped: no product ran, its zc_l and cinb rows are NOT written (BwdParts::dead_dw; else
+                            // they hold stored zeros), and FB and the weight-gradient jobs skip the tile by this word.  Tile t's word is alb_dead[t * alb_dead_stride]: it lies in cinb, in the first
+                            // encoding column of the tile's first row — columns F .. of cinb are written and read only by a
+                            // backward that leaves the input adjoints (BwdParts::color_inputs), which never skips a tile
   float* col_part;          // fused albedo backward: per-tile column sums of the output layer's gradient [tiles][Co][256] + [tiles][Co]
   float* sdfh_part;         // sdf-head row gradient: per-slab column sums [kSdfHeadSlabs][Hp] + [kSdfHeadSlabs]
 };
 
 // slots of PointBufs::amax: zb_l, u_l (u_0 = geb), zc_l, cinb
-enum { AMAX_ZB = 0, AMAX_U = RNB_MAX_LIN, AMAX_ZC = 2 * RNB_MAX_LIN + 1, AMAX_CINB = 3 * RNB_MAX_LIN + 1, AMAX_SLOTS = 3 * RNB_MAX_LIN + 2 };
-// slots of PointBufs::smax: a_l, gz_l (hidden layers), e (positional encoding), cin (albedo-net input), ac_l (its hidden layers)
+// AMAX_DEAD_RAN (no maximum): set to 1 by the fused albedo backward when its zero-tile path was on, i.e. when the words of
+// PointBufs::alb_dead were written by this backward (zeroed with the slots at the start of every backward); AMAX_ANY_DEAD: set to
+// 1 by every tile that took the path — while it is 0 the weight-gradient kernel does not even look at the tiles' words
+enum { AMAX_ZB = 0, AMAX_U = RNB_MAX_LIN, AMAX_ZC = 2 * RNB_MAX_LIN + 1, AMAX_CINB = 3 * RNB_MAX_LIN + 1, AMAX_MAXIMA = 3 * RNB_MAX_LIN + 2,
+       AMAX_DEAD_RAN = AMAX_MAXIMA, AMAX_ANY_DEAD = AMAX_MAXIMA + 1, AMAX_SLOTS = AMAX_MAXIMA + 2 };
+static_assert(AMAX_SLOTS * sizeof(unsigned) <= 256, "the slots fit the 256 bytes carve_points has always taken for them");
+// slots of PointBufs::smax: a_l, gz_l (hidden layers), e (positional encoding), cin (albedo-net input), ac_l (its hidden layers);
+// SMAX_NONFIN: raised to 1 by the fused albedo forward when a value of cin, ac_0 or ac_1 is an infinity or a NaN (the backward's
+// zero-tile path then stays off for the step: 0 x that value is not zero)
 enum { SMAX_A = 0, SMAX_GZ = RNB_MAX_LIN, SMAX_E = 2 * RNB_MAX_LIN, SMAX_CIN = 2 * RNB_MAX_LIN + 1, SMAX_AC = 2 * RNB_MAX_LIN + 2,
-       SMAX_SLOTS = 3 * RNB_MAX_LIN + 2 };
+       SMAX_NONFIN = 3 * RNB_MAX_LIN + 2, SMAX_SLOTS = 3 * RNB_MAX_LIN + 3 };
+static_assert(SMAX_SLOTS * sizeof(unsigned) <= 256, "the slots fit the 256 bytes carve_points has always taken for them");
 // slot i of an x2h maxima array (PointBufs::amax / ::smax) when the route records them, else nullptr (also for the
 // buffer-less PointBufs of a sizing query): a weight-gradient job then scales by the fixed 2^6, a GEMM records no maximum
 inline unsigned* h2_slot(const Layout& L, unsigned* slots, int i) { return L.route.h2 && slots != nullptr ? slots + i : nullptr; }
@@ -418,6 +431,10 @@ struct BwdParts {
   bool feat;           // cinb's feature columns seed FB (the feature head's adjoint)
   bool normal;         // pb.nbar is live: geb, RA and the gz/u weight-gradient pairs
   bool color_inputs;   // leave all of cinb, encoding columns included, for the input adjoints
+  bool dead_tiles = false;   // set by sweep_backward_parts (dead_tiles_on): the albedo backward skips tiles whose colour adjoint
+                             // is exactly zero, and FB skips them with it
+  bool dead_dw = false;      // ... and so do the weight-gradient jobs (dw_honours_dead): the tiles' zc_l / cinb rows then stay
+                             // unwritten; else the albedo backward stores zeros in the rows those jobs read
   // a render's backward; the SDF network alone (SDFNetwork.forward / .gradient); the albedo net alone (RenderingNetwork)
   static BwdParts render(bool with_color, bool keep_color_inputs) { return {with_color, true, with_color, true, keep_color_inputs}; }
   static BwdParts sdf_points(bool feat, bool normal) { return {false, true, feat, normal, false}; }
@@ -438,9 +455,15 @@ bool dw_one_wg_runs(const Layout& L, int64_t M);
 int dw_zero_partials(const Layout& L, const PointBufs& pb, hipStream_t s);
 // queues and launches every weight-gradient job of a backward of these parts (its other launches are enqueued)
 int dw_backward(const Layout& L, const PointBufs& pb, const BwdParts& parts, int sdfh_slabs, float* packed_grad, hipStream_t s);
+// every job that reads zc_l or cinb goes to the kernel that skips dead tiles (gemm_dw_x3_kernel)
+bool dw_honours_dead(const Layout& L, int64_t M);
+// FB runs as fused_fb_h2_kernel, which skips the feature-head seed of a dead tile
+bool fused_fb_honours_dead(const Layout& L);
+// the zero-tile path runs in a backward of these parts (RNB_VARIANT_NO_DEAD_TILES switches it off)
+bool dead_tiles_on(const Layout& L, const PointBufs& pb, const BwdParts& parts);
 int fused_reverse(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool store_ge = false);
 int fused_ra(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, int* u_tiles = nullptr);
-int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_color, hipStream_t s);
+int fused_fb(const Layout& L, const float* packed, PointBufs& pb, bool with_color, hipStream_t s, bool dead_tiles = false);
 
 // ---- fused sweeps for hidden width 256 (fused.hip) ---------------------------------------------------
 bool fused_supported(const Layout& L);
@@ -481,7 +504,8 @@ int x3_pack_weights(const Layout& L, float* packed, hipStream_t s);
 bool color_h2_supported(const Layout& L);
 int color_h2_forward(const Layout& L, const float* packed, PointBufs& pb, const float* pts, const float* nrm, hipStream_t s);
 // sdf == false: no geb (the albedo net alone); keep_pe: also store cinb's 64 encoding columns (input adjoints)
-int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool sdf = true, bool keep_pe = false);
+int color_h2_backward(const Layout& L, const float* packed, PointBufs& pb, hipStream_t s, bool sdf = true, bool keep_pe = false,
+                      bool dead_tiles = false, bool dead_zero_fill = false);
 int64_t color_h2_part_floats(const Layout& L, int64_t M);
 constexpr int kSdfHeadSlabs = 64;   // row slabs of sdf_head_bwd_kernel's partial sums (summed in slab order: no atomics)
 

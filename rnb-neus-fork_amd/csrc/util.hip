@@ -96,7 +96,17 @@ __global__ void range_fold_kernel(const unsigned* __restrict__ words, int n, int
   out[k] = __builtin_bit_cast(float, m);
 }
 
-// rnb_render_range: out[0..4] as documented in include/rnbneus.h.  The maxima of the saved state are taken by a pass over the
+// out[k] = how many of the n per-tile words (PointBufs::alb_dead) are set — rnb_render_range's count of skipped tiles
+// `ran`: the backward's own record that it wrote the words (AMAX_DEAD_RAN); 0: they hold something else, the count is 0
+__global__ void dead_count_kernel(const unsigned* __restrict__ words, long long stride, int n, const unsigned* __restrict__ ran, int k,
+                                  float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int c = 0;
+  for (int i = 0; i < n && *ran != 0u; ++i) c += words[(size_t)i * stride] != 0u ? 1 : 0;
+  out[k] = (float)c;
+}
+
+// rnb_render_range: out[0..5] as documented in include/rnbneus.h.  The maxima of the saved state are taken by a pass over the
 // buffers themselves (the hot path records them only for tiles beyond the fixed scales' range); out doubles as scratch.
 int launch_range_report(const Layout& L, const float* packed, const PointBufs& pb, bool with_color, bool with_backward, float* out,
                         hipStream_t s) {
@@ -120,7 +130,13 @@ int launch_range_report(const Layout& L, const float* packed, const PointBufs& p
     for (int l = 0; l < L.nc; ++l) RNB_TRY(launch_absmax_rows(pb.ac[l], pb.Mp * L.Hcp, w + 3, s));
   }
   if (with_backward && L.route.h2) {
-    hipLaunchKernelGGL(range_fold_kernel, dim3(1), dim3(64), 0, s, pb.amax, (int)AMAX_SLOTS, 4, out);
+    hipLaunchKernelGGL(range_fold_kernel, dim3(1), dim3(64), 0, s, pb.amax, (int)AMAX_MAXIMA, 4, out);
+    RNB_CHECK_LAUNCH();
+  }
+  // (the words exist only where the backward took the zero-tile path, which it records in amax: elsewhere the count is 0)
+  if (with_backward && with_color && pb.alb_dead != nullptr && pb.amax != nullptr) {
+    hipLaunchKernelGGL(dead_count_kernel, dim3(1), dim3(64), 0, s, pb.alb_dead, (long long)pb.alb_dead_stride, (int)((pb.M + 63) / 64),
+                       pb.amax + AMAX_DEAD_RAN, 5, out);   // (tiles with a real row)
     RNB_CHECK_LAUNCH();
   }
   return RNB_OK;

@@ -302,7 +302,7 @@ class NeuSRenderer:
 
     def set_variant(self, **kw):
         """Kernel / arithmetic variant bits of the model descriptor (include/rnbneus.h RNB_VARIANT_*):
-        bf16=, deterministic=, generic=, dw_lds=, bwd_ti=, bwd_nw=, fwd_ti=, fwd_nw=.  Returns self."""
+        bf16=, deterministic=, generic=, dw_lds=, bwd_ti=, bwd_nw=, fwd_ti=, fwd_nw=, dead_tiles=.  Returns self."""
         self.desc.variant = native.variant_bits(**kw)
         return self
 
@@ -758,14 +758,15 @@ class NeuSRenderer:
     def range_report(self):
         """Largest operand magnitudes of the last render made with `track_range = True` (one device-to-host copy):
         `max_abs_weight`, `max_abs_activation` (SDF network, incl. the encoded input), `max_abs_jacobian_row`,
-        `max_abs_albedo_activation`, `max_abs_adjoint` (after a backward; 0 for forward-only renders).  The default arithmetic
+        `max_abs_albedo_activation`, `max_abs_adjoint` (after a backward; 0 for forward-only renders), `dead_tiles` (64-point
+        tiles whose colour adjoint was exactly zero and which the backward skipped; 0 where it skips none).  The default arithmetic
         takes every operand scale from the data (include/rnbneus.h, RNB_VARIANT_X2H): none of these has a limit; the
         numbers say how far a model is from the range the fixed scales of ABI 4 assumed (weights 255, activations 1023)."""
         if self._range is None:
             raise RuntimeError("range_report(): set `track_range = True` and render first")
         r = [float(x) for x in self._range.cpu()]
         return {"max_abs_weight": r[0], "max_abs_activation": r[1], "max_abs_jacobian_row": r[2],
-                "max_abs_albedo_activation": r[3], "max_abs_adjoint": r[4]}
+                "max_abs_albedo_activation": r[3], "max_abs_adjoint": r[4], "dead_tiles": int(r[5])}
 
     def x2h_range_report(self):
         """Host-side (plain torch) maximum of |g v / ||v||| over every layer of both networks:
