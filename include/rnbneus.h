@@ -750,6 +750,70 @@ int rnb_mesh_raycast(const double* origins, const double* directions, const doub
                      int64_t n_entries, const double* corners, int64_t n_triangles, int32_t flags, double* t,
                      int32_t* triangle, double* bary, rnb_stream_t stream);
 
+/* ---- Texture baking: a per-triangle atlas, its lattice samples and the 8-bit images ----------------------------
+ * What a simplified mesh loses between its vertices goes into textures (csrc/texture_bake.hip).  The atlas gives every
+ * triangle a chart of the same size, so a texel's triangle follows from its coordinates by integer arithmetic alone; the
+ * field is evaluated at the samples by rnb_mesh_vertex_attrs between the two calls below.  tests/texture_bake_ref.py is
+ * this definition in numpy, and device and numpy agree bit for bit.
+ *   vertices [V,3] float64 (model space), triangles [T,3] int32; V, T <= 2^31 - 1.
+ * The atlas.  One parameter, the chart size s in [1, 255] (texel steps along a chart's legs); cell side c = s + 5.  Cell
+ * k = t / 2 holds triangle 2k (its LOWER half) and 2k + 1 (its UPPER half); the K = ceil(T / 2) cells lie row-major,
+ * `cols` per row, cell k with its top-left texel at ((k % cols) c, (k / cols) c) of a W x H image whose row 0 is the top
+ * row (x runs right, y down).  Inside a cell, texel indices (i, j) in [0, c), a texel index standing for its centre:
+ *                           lower half                       upper half
+ *     vertex 0              (1, 1)                           (c - 2, c - 2)
+ *     vertex 1              (1 + s, 1)                       (c - 2 - s, c - 2)
+ *     vertex 2              (1, 1 + s)                       (c - 2, c - 2 - s)
+ *     texels owned          i + j <= s + 3                   all others
+ *     a1                    clamp(i - 1, 0, s)               clamp(c - 2 - i, 0, s)
+ *     a2                    clamp(j - 1, 0, s - a1)          clamp(c - 2 - j, 0, s - a1)
+ * (a1, a2) are the texel's lattice coordinates, a1, a2 >= 0, a1 + a2 <= s: a guard texel repeats a lattice sample of its
+ * own triangle.  A texel is EMPTY when its triangle index is >= T (the upper half of the last cell for odd T, unused
+ * cells), when it lies right of cols c or below the last cell row, or when its triangle is bad (below).  With c = s + 5 a
+ * bilinear lookup at any point of a triangle's chart, edges and corners included, reads only texels that triangle owns
+ * (with s + 4 the two hypotenuses would share a texel diagonal).  Corner UVs: u = (x + 0.5) / W, v = 1 - (y + 0.5) / H
+ * with (x, y) the corner's texel in the image; both halves have the same, MIRRORED orientation in UV (vertex 0 -> 1 -> 2
+ * turns clockwise in the (u, v) plane for both: (u1 - u0)(v2 - v0) - (v1 - v0)(u2 - u0) < 0).
+ * Samples.  Triangle t has n_s = (s + 1)(s + 2) / 2 lattice samples, sample p = t n_s + r with
+ *     r(a1, a2) = a2 (s + 1) - a2 (a2 - 1) / 2 + a1          (rows of constant a2; no compaction, no counting pass)
+ * and the point, in fp64 with every quotient, product and sum rounded on its own, then converted to fp32:
+ *     w1 = a1 / s,  w2 = a2 / s,  w0 = (s - a1 - a2) / s  (one division of an integer by s each; never 1 - w1 - w2)
+ *     P = (w0 A + w1 B) + w2 C                             (A, B, C the corners 0, 1, 2)
+ * So a corner sample equals its vertex converted to fp32, and a sample on a shared edge comes out the same from both
+ * triangles (one weight is an exact zero, the other two are the same two quotients, a sum of two products commutes) — as
+ * numbers (==); the sign of a zero coordinate is the only exception.  Seams need no blending pass.
+ * A BAD triangle (an index outside [0, V), checked before use, or a non-finite corner) puts its samples at (0, 0, 0) and
+ * its texels come out empty.
+ *   rnb_texture_sample_points  points_out [count,3] float32 = the samples first .. first + count - 1 (a range may start
+ *                              and end inside a triangle).  bad_out (may be NULL): int64 [1] on the device, ADDED to
+ *                              (one integer add per wave): the bad triangles whose sample r = 0 lies in the range, so
+ *                              ranges that partition [0, T n_s) count every bad triangle once; the caller zeroes it.
+ *   rnb_texture_pack           one lane per texel.  rgb [T n_s,3] uint8 and normal [T n_s,3] float32: per-sample values
+ *                              (each may be NULL with its image).  texel_sample [H,W] int32: the texel's sample index,
+ *                              -1 where it is empty (the gather map for float channels).  albedo_image [H,W,4] uint8: the
+ *                              sample's rgb with alpha 255, or 0,0,0,0.  normal_image [H,W,4] uint8: per component
+ *                              rintf(255 (0.5 n + 0.5)) in fp32, every operation rounded on its own, clipped to
+ *                              [0, 255] (NaN: 0), alpha 255 — object-space normals in model space; a zero normal gives
+ *                              128; empty texels 0,0,0,0.  Each output may be NULL, not all; the images are written
+ *                              one 32-bit word per texel and must be 4-byte aligned.  T == 0: the outputs are cleared
+ *                              (images 0, texel_sample -1) without a kernel.
+ * RNB_E_INVALID before any launch: s outside [1, 255]; a size negative or above 2^31 - 1; first + count > T n_s;
+ * T n_s >= 2^31; W H >= 2^31; a layout whose cells do not hold T triangles inside W x H (cols c > W, or
+ * cols (H / c) < K); every output NULL.  RNB_E_NULL: a required input is NULL.  Nothing is launched for T == 0 or
+ * count == 0.  The one loop (the row of a rank) has s + 1 trips, fixed before it starts; no computed value becomes an
+ * address unchecked.  Nothing is allocated, no device-wide synchronisation. */
+typedef struct rnb_texture_layout {
+  int32_t s;      /* chart size */
+  int32_t cols;   /* cells per row */
+  int32_t W, H;   /* image size in texels */
+} rnb_texture_layout;
+int rnb_texture_sample_points(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                              int32_t s, int64_t first, int64_t count, float* points_out, int64_t* bad_out,
+                              rnb_stream_t stream);
+int rnb_texture_pack(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                     const rnb_texture_layout* layout, const uint8_t* rgb, const float* normal, uint8_t* albedo_image,
+                     uint8_t* normal_image, int32_t* texel_sample, rnb_stream_t stream);
+
 /* The four rnb_gen_rays_* calls below that make rays are one kernel (csrc/raygen.hip) behind one set of checks: a front, the
  * pixel list of a train step (_at_view) or a range of a whole view's grid (_grid), and the targets, gathered from the finished
  * stacks or computed from the view's source maps (_from_maps).  The pixel-to-ray arithmetic exists once; it is unfused float32

@@ -22,7 +22,8 @@ from .raygen import DeviceRays, cameras_from_projections  # noqa: F401
 from .mcubes import marching_cubes  # noqa: F401
 from .camera_refine import CameraRefinement  # noqa: F401
 from . import mesh_io  # noqa: F401
-from .mesh_io import read_ply, write_ply  # noqa: F401
+from .mesh_io import read_obj, read_png, read_ply, write_obj, write_png, write_ply  # noqa: F401
+from .texture_bake import AtlasLayout, atlas_layout, atlas_uv, sample_texture  # noqa: F401
 from .mesh_clean import clean_mesh, mesh_components  # noqa: F401
 from .mesh_simplify import simplify_mesh  # noqa: F401
 from .mesh_eval import MeshIndex, mesh_distance, sample_surface  # noqa: F401
@@ -31,7 +32,8 @@ from .mesh_raycast import mesh_view_maps, normal_angular_error  # noqa: F401
 __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetwork", "NeRF", "get_embedder",
            "native", "build_from_named_params", "rnb_loss", "FlatAdam", "DeviceRays", "cameras_from_projections",
            "marching_cubes", "CameraRefinement", "mesh_io", "write_ply", "read_ply", "mesh_components", "clean_mesh",
-           "MeshIndex", "sample_surface", "mesh_distance", "mesh_view_maps", "normal_angular_error", "simplify_mesh"]
+           "MeshIndex", "sample_surface", "mesh_distance", "mesh_view_maps", "normal_angular_error", "simplify_mesh",
+           "atlas_layout", "atlas_uv", "AtlasLayout", "sample_texture", "write_obj", "read_obj", "write_png", "read_png"]
 
 
 def build_from_named_params(mc, params, device):

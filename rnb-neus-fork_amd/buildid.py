@@ -12,7 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 HIP_SOURCES = ["api.hip", "layout.hip", "layers.hip", "backward.hip", "util.hip", "dw.hip", "weightnorm.hip", "sampling.hip", "composite.hip", "prof.hip", "fused.hip",
                "sweep_mv.hip", "fused_bwd.hip", "color_h2.hip", "bf16_sweeps.hip", "bf16_color.hip", "bf16_dw.hip", "train.hip", "raygen.hip", "mcubes.hip",
-               "sparse_grid.hip", "mesh_attrs.hip", "mesh_clean.hip", "mesh_eval.hip", "mesh_raycast.hip", "mesh_simplify.hip"]
+               "sparse_grid.hip", "mesh_attrs.hip", "mesh_clean.hip", "mesh_eval.hip", "mesh_raycast.hip", "mesh_simplify.hip",
+               "texture_bake.hip"]
 COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 EXTRA_FLAGS = {
     # sampling.hip must round like the reference's separate PyTorch ops (no fused multiply-add contraction)
@@ -29,6 +30,9 @@ EXTRA_FLAGS = {
     "mesh_raycast.hip": ["-ffp-contract=off"],
     # the cell fractions, the cluster mean and d2 as tests/mesh_simplify_ref.py evaluates them, one rounding per operation
     "mesh_simplify.hip": ["-ffp-contract=off"],
+    # the sample point (w0 A + w1 B) + w2 C and the normal quantisation as tests/texture_bake_ref.py evaluates them: a
+    # sample on a shared edge must round alike from both triangles
+    "texture_bake.hip": ["-ffp-contract=off"],
 }
 
 

@@ -109,6 +109,11 @@ class MeshBins(C.Structure):
     _fields_ = [("origin", C.c_double * 3), ("cell_size", C.c_double), ("dims", C.c_int32 * 3), ("reserved_", C.c_int32)]
 
 
+class TextureLayout(C.Structure):
+    """rnb_texture_layout: chart size, cells per row, image size in texels"""
+    _fields_ = [("s", C.c_int32), ("cols", C.c_int32), ("W", C.c_int32), ("H", C.c_int32)]
+
+
 MESH_BINS_MAX_CELLS = 1 << 24
 # flags of rnb_mesh_closest_points; bits of rnb_mesh_bins_count's counts[1] (include/rnbneus.h)
 MESH_BINS_COVER = 1
@@ -230,6 +235,10 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "rnb_mesh_sample_surface": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_texture_sample_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_texture_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(TextureLayout), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnb_up_sample_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                      C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),

@@ -947,9 +947,45 @@ class NeuSRenderer:
                                          albedo=albedo, swap_rb=True, chunk=chunk)
 
     @torch.no_grad()
+    def bake_textures(self, vertices, triangles, *, size=None, chart=None, refine=0, max_step=None, threshold=0.0,
+                      albedo=None, slab=1 << 20, chunk=65536, return_samples=False, to_host=True):
+        """Bakes the field into textures of a mesh, on the device (texture_bake.py; include/rnbneus.h "Texture baking").
+        vertices [V,3] float64 in MODEL space and triangles [T,3] int32, device tensors as
+        `extract_textured_geometry(to_host=False)` returns them.  Every triangle gets a chart of `chart` texel steps
+        (`texture_bake.atlas_layout(T, size, chart)`: `chart` alone sizes the image, `size` alone takes the largest chart
+        that fits size x size, neither: chart = 8) with (chart + 1)(chart + 2) / 2 lattice samples; per slab of `slab`
+        samples (a positive multiple of 64, so the 64-point tiles of the sweeps — and their per-tile scales — are the same
+        whatever the slab) `rnb_texture_sample_points` makes the fp32 points and `vertex_attributes(points, refine=,
+        max_step=, threshold=, chunk=)` evaluates them; one `rnb_texture_pack` writes the images.  `refine` > 0 (needs
+        `max_step`, model-space units) projects every sample onto the level set first, so the maps carry the detail the
+        simplification removed.  Returns a dict: `uv` [T,3,2] float64 (per corner; v up), `albedo_image` [H,W,4] uint8
+        (RGB of the per-vertex colour rule, alpha 255, empty texels 0; None without the albedo network: `albedo=None` means
+        "if the renderer has it", `albedo=True` raises without it), `normal_image` [H,W,4] uint8 (object-space unit normals
+        in model space, rint(255 (0.5 n + 0.5))), `texel_sample` [H,W] int32 (the sample of every texel, -1 where empty:
+        the gather map for float channels), `layout` (`AtlasLayout`), `info` (`samples`, `bad_triangles`: triangles with
+        an index outside [0, V) or a non-finite corner, whose texels are empty; `slabs`) and, with `return_samples`, the
+        per-sample `points` [N,3], `sdf` [N,1], `normal` [N,3] and `albedo` [N,C] float32.  numpy arrays, or device
+        tensors with `to_host=False`.  Runs under no_grad; one host read (the bad-triangle counter); never collective
+        under `set_data_parallel`."""
+        from .texture_bake import bake_textures
+        return bake_textures(self, vertices, triangles, size=size, chart=chart, refine=refine, max_step=max_step,
+                             threshold=threshold, albedo=albedo, slab=slab, chunk=chunk, return_samples=return_samples,
+                             to_host=to_host)
+
+    @staticmethod
+    def _check_bake(bake):
+        """the `bake` argument of extract_textured_geometry, checked before the grid is evaluated"""
+        from .texture_bake import BAKE_KEYWORDS, check_arguments
+        if bake is None:
+            return
+        if not isinstance(bake, dict) or not set(bake) <= set(BAKE_KEYWORDS):
+            raise ValueError(f"bake must be a dict of bake_textures keywords {BAKE_KEYWORDS}")
+        check_arguments("bake", **bake, need_max_step=False)
+
+    @torch.no_grad()
     def extract_textured_geometry(self, bound_min, bound_max, resolution, threshold=0.0, *, sparse=False, margin=1.0,
                                   brick=None, refine=0, max_step=None, chunk=65536, to_host=True, clean=None,
-                                  simplify=None):
+                                  simplify=None, bake=None):
         """`validate_mesh_texture` up to the export (exp_runner.py:584-613): SDF grid (dense, or `sparse=True` as in
         `extract_geometry`), the native marching cubes, and `vertex_attributes` on the vertices where marching cubes left
         them — they never leave the device in between.  Returns a dict:
@@ -965,10 +1001,15 @@ class NeuSRenderer:
         `self.last_mesh_clean`).  None (default): no cleaning.
         `simplify`: a dict of `mesh_simplify.simplify_mesh` keywords (`cell_size` in voxels, or `target_triangles`;
         `origin`); the simplification runs after the cleaning and before `vertex_attributes`, which is evaluated on the
-        surviving vertices only (`info` in `self.last_mesh_simplify`).  None (default): no simplification."""
+        surviving vertices only (`info` in `self.last_mesh_simplify`).  None (default): no simplification.
+        `bake`: a dict of `bake_textures` keywords (`size`, `chart`, `refine`, `max_step`, `threshold`, `albedo`, `slab`,
+        `chunk`, `return_samples`; `threshold` defaults to this call's, `max_step` to one cell diagonal); the bake runs last,
+        on the final vertices (cleaned, simplified and, where asked for, refined), and adds `uv` [T,3,2], `albedo_image`,
+        `normal_image` and `bake` (the rest of `bake_textures`' result) to the dict.  None (default): nothing is added."""
         from .mcubes import marching_cubes
         self._check_clean(clean)
         self._check_simplify(simplify)
+        self._check_bake(bake)
         res = int(resolution)
         if sparse:
             u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, res, threshold, brick, margin,
@@ -995,6 +1036,19 @@ class NeuSRenderer:
         out = {"vertices": vertices, "triangles": t, "normals": at["normal"], "sdf": at["sdf"]}
         if "albedo" in at:
             out["albedo"], out["colors"] = at["albedo"], at["rgb"]
+        baked = None
+        if bake is not None:
+            kw = dict(bake)
+            kw.setdefault("threshold", threshold)
+            if kw.get("max_step") is None:
+                lo, hi = ([float(b[d]) for d in range(3)] for b in (bound_min, bound_max))
+                kw["max_step"] = sum(((hi[d] - lo[d]) / (res - 1)) ** 2 for d in range(3)) ** 0.5
+            final = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(vertices).to(t.device)
+            baked = self.bake_textures(final, t, to_host=to_host, **kw)
         if to_host:
             out = {k: x.cpu().numpy() if isinstance(x, torch.Tensor) else x for k, x in out.items()}
+        if baked is not None:
+            for k in ("uv", "albedo_image", "normal_image"):
+                out[k] = baked.pop(k)
+            out["bake"] = baked
         return out

@@ -138,6 +138,31 @@ def mesh_vertex_attrs(desc, packed, points=None, grid_vertices=None, bound_min=N
     return out
 
 
+def texture_sample_points(vertices, triangles, s, first, count, points_out, bad_out=None):
+    """rnb_texture_sample_points: the lattice samples first .. first + count - 1 of the atlas with chart size s into
+    `points_out` [count,3] fp32 (enqueued; `bad_out` [1] int64 is added to)."""
+    native.same_device(vertices, triangles, points_out, bad_out)
+    with native.on_device(triangles) as stream:
+        native.check(native.load().rnb_texture_sample_points(native.ptr(vertices), vertices.shape[0], native.ptr(triangles),
+                                                             triangles.shape[0], int(s), int(first), int(count),
+                                                             native.ptr(points_out), native.ptr(bad_out), stream))
+
+
+def texture_pack(vertices, triangles, s, cols, W, H, rgb=None, normal=None, albedo=True, normals=True, texel_sample=True):
+    """rnb_texture_pack: (albedo_image [H,W,4] uint8 or None, normal_image [H,W,4] uint8 or None, texel_sample [H,W] int32
+    or None) from the per-sample `rgb` [N,3] uint8 and `normal` [N,3] fp32 (enqueued, no host read)."""
+    dev = native.same_device(vertices, triangles, rgb, normal)
+    lay = native.TextureLayout(int(s), int(cols), int(W), int(H))
+    a_img = torch.empty(H, W, 4, dtype=torch.uint8, device=dev) if albedo else None
+    n_img = torch.empty(H, W, 4, dtype=torch.uint8, device=dev) if normals else None
+    t_smp = torch.empty(H, W, dtype=torch.int32, device=dev) if texel_sample else None
+    with native.on_device(dev) as stream:
+        native.check(native.load().rnb_texture_pack(native.ptr(vertices), vertices.shape[0], native.ptr(triangles),
+                                                    triangles.shape[0], C.byref(lay), native.ptr(rgb), native.ptr(normal),
+                                                    native.ptr(a_img), native.ptr(n_img), native.ptr(t_smp), stream))
+    return a_img, n_img, t_smp
+
+
 class StandaloneSDF:
     """Context for calling an SDFNetwork outside a renderer (exp_runner.py:607-610 style)."""
 
