@@ -566,6 +566,25 @@ int rnb_mesh_compact_emit(const int32_t* triangles, int64_t n_triangles, const d
                           size_t workspace_bytes, int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out,
                           int32_t* triangles_out, int64_t* vertex_index, rnb_stream_t stream);
 
+/* Compaction by a per-triangle keep (what survives a culling, rnb_mesh_view_votes below): the two calls above with
+ * another rule of what is kept, in the same workspace of rnb_mesh_clean_workspace_bytes(V, T) bytes.
+ *   keep_t [T] uint8 (device).  A triangle is KEPT when keep_t[t] != 0 and its three indices lie in [0, V) — every index
+ *   is checked before it is used as an address; a vertex is KEPT when a kept triangle names it.
+ *   rnb_mesh_compact_triangles_count   counts[0] = V', counts[1] = T' (device int64 [2])
+ *   -- the caller reads counts and allocates the outputs --
+ *   rnb_mesh_compact_triangles_emit    as rnb_mesh_compact_emit (stable order, indices remapped, vertex_index [V'] int64),
+ *                                      and triangle_index [T'] int64 = the old index of every kept triangle.  Same mesh,
+ *                                      keep_t and workspace size as the count, whose block sums it reads.
+ * Errors as for rnb_mesh_compact_count / _emit. */
+int rnb_mesh_compact_triangles_count(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                                     const uint8_t* keep_t, void* workspace, size_t workspace_bytes, int64_t* counts,
+                                     rnb_stream_t stream);
+int rnb_mesh_compact_triangles_emit(const int32_t* triangles, int64_t n_triangles, const double* vertices,
+                                    int64_t n_vertices, const uint8_t* keep_t, void* workspace, size_t workspace_bytes,
+                                    int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out,
+                                    int32_t* triangles_out, int64_t* vertex_index, int64_t* triangle_index,
+                                    rnb_stream_t stream);
+
 /* ---- Mesh simplification: vertex clustering on a uniform grid, to a cell size ------------------------------
  * Makes a marching-cubes mesh smaller on the device (Rossignac-Borrel): the vertices of one grid cell become one vertex,
  * which is ONE OF THEM (the member nearest the cell's mean), so every output vertex is an input vertex, per-vertex
@@ -749,6 +768,42 @@ int rnb_mesh_raycast(const double* origins, const double* directions, const doub
                      int64_t n_rays, const rnb_mesh_bins* bins, const int64_t* cell_start, const int32_t* entries,
                      int64_t n_entries, const double* corners, int64_t n_triangles, int32_t flags, double* t,
                      int32_t* triangle, double* bary, rnb_stream_t stream);
+
+/* ---- Mesh culling by the cameras: per-(point, camera) status and per-point votes -----------------------------------
+ * What the cameras of a masked multi-view reconstruction support of a mesh: for every point (a vertex) and every camera
+ * whether the point projects into the frame, into the mask, and is not hidden by the mesh (csrc/mesh_cull.hip; one
+ * launch for all cameras; tests/mesh_cull_ref.py is the same rule in numpy, and device and numpy agree bit for bit).
+ *   points [N,3] float64; projections [C,3,4] float64 (P = K [R|t], world -> pixel, row-major); eyes [C,3] float64 (the
+ *   camera centres); masks [C,H,W] uint8 (non-zero = inside) or NULL; the frame is H x W pixels either way; the bins,
+ *   entries and corners of rnb_mesh_bins_count / rnb_mesh_bins_emit; N, C, E, T <= 2^31 - 1.
+ * The status of the pair (camera c, point i = (X, Y, Z)), every operation in fp64 and rounded on its own:
+ *   1. x = ((P00 X + P01 Y) + P02 Z) + P03, y and w alike from rows 1 and 2 of P_c.
+ *      0 RNB_CULL_OUT_OF_FRAME if X, Y or Z is not finite, if w is not finite, or if w is not > 0.  Otherwise
+ *      u = x / w, v = y / w, a = u + 0.5, b = v + 0.5, and status 0 unless 0 <= a < W and 0 <= b < H (tested in fp64,
+ *      before any conversion to an integer; a NaN fails).  The pixel is (px, py) = (floor(a), floor(b)): pixel centres sit
+ *      at integer coordinates, the convention of the ray generation, whose direction is Kinv (x, y, 1).
+ *   2. 1 RNB_CULL_OUTSIDE_MASK if masks != NULL and masks[c, py, px] == 0.
+ *   3. (skipped under RNB_CULL_NO_OCCLUSION: status 3.)  The segment o = eye_c, d = (X - ex, Y - ey, Z - ez), t_min = 0,
+ *      t_max = 1 is cast by THE WALK AND PAIR TEST OF rnb_mesh_raycast (one device function serves both).  With t the
+ *      first hit's parameter: 3 RNB_CULL_SEEN when t >= 1 - rel_tol (+inf, nothing met, counts), 2 RNB_CULL_OCCLUDED
+ *      otherwise — a NaN t (a segment that cannot be cast: point == eye, an eye that is not finite) included.  That is
+ *      what a cast of the segment through rnb_mesh_raycast followed by the same comparison answers, bit for bit.  With
+ *      E == 0 every segment that can be cast is SEEN.
+ *   counts [N,4] int32, ZEROED BY THE CALL: counts[i][k] = the number of cameras with status k, a row sums to C.
+ *   status [C,N] uint8 or NULL.  Integer atomics only: bit-equal from run to run, whatever the launch geometry.
+ * flags: RNB_MESH_BINS_COVER is required as for rnb_mesh_raycast; RNB_CULL_NO_OCCLUSION skips step 3 (eyes and the bins'
+ * arrays may then be NULL).  Lanes of a wavefront are consecutive points of one camera.
+ * RNB_E_INVALID before any launch: unknown flag bits, RNB_MESH_BINS_COVER missing, a size outside [0, 2^31 - 1], H or W
+ * negative, or below 1 with masks given, rel_tol outside [0, 1), bins as for the calls above.  RNB_E_NULL: a required
+ * pointer is NULL.  Nothing is launched for N == 0 or C == 0 (counts is zeroed for C == 0).  Nothing is allocated, no
+ * device-wide synchronisation. */
+enum { RNB_CULL_NO_OCCLUSION = 2 };   /* (shares the flag word with RNB_MESH_BINS_COVER = 1) */
+enum { RNB_CULL_OUT_OF_FRAME = 0, RNB_CULL_OUTSIDE_MASK = 1, RNB_CULL_OCCLUDED = 2, RNB_CULL_SEEN = 3 };
+int rnb_mesh_view_votes(const double* points, int64_t n_points, const double* projections, const double* eyes,
+                        int64_t n_cameras, const uint8_t* masks, int32_t height, int32_t width, const rnb_mesh_bins* bins,
+                        const int64_t* cell_start, const int32_t* entries, int64_t n_entries, const double* corners,
+                        int64_t n_triangles, double rel_tol, int32_t flags, int32_t* counts, uint8_t* status,
+                        rnb_stream_t stream);
 
 /* ---- Texture baking: a per-triangle atlas, its lattice samples and the 8-bit images ----------------------------
  * What a simplified mesh loses between its vertices goes into textures (csrc/texture_bake.hip).  The atlas gives every

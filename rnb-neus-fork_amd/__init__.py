@@ -28,12 +28,15 @@ from .mesh_clean import clean_mesh, mesh_components  # noqa: F401
 from .mesh_simplify import simplify_mesh  # noqa: F401
 from .mesh_eval import MeshIndex, mesh_distance, sample_surface  # noqa: F401
 from .mesh_raycast import mesh_view_maps, normal_angular_error  # noqa: F401
+from .mesh_clean import compact_triangles  # noqa: F401
+from .mesh_cull import binary_masks, camera_projections, cull_mesh  # noqa: F401
 
 __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetwork", "NeRF", "get_embedder",
            "native", "build_from_named_params", "rnb_loss", "FlatAdam", "DeviceRays", "cameras_from_projections",
            "marching_cubes", "CameraRefinement", "mesh_io", "write_ply", "read_ply", "mesh_components", "clean_mesh",
            "MeshIndex", "sample_surface", "mesh_distance", "mesh_view_maps", "normal_angular_error", "simplify_mesh",
-           "atlas_layout", "atlas_uv", "AtlasLayout", "sample_texture", "write_obj", "read_obj", "write_png", "read_png"]
+           "atlas_layout", "atlas_uv", "AtlasLayout", "sample_texture", "write_obj", "read_obj", "write_png", "read_png",
+           "cull_mesh", "camera_projections", "binary_masks", "compact_triangles"]
 
 
 def build_from_named_params(mc, params, device):

@@ -12,7 +12,8 @@
 //               128-bit fixed-point sum in units of 2^(e_c - 54), e_c the exponent of the component's largest triangle
 //               — integer addition is associative, so the sum has the same bits whatever the arrival order
 //   compaction  flag scans of "vertex kept" / "triangle kept" (count), then the same flags again with the block
-//               offsets: old -> new vertex map, vertices, old indices, remapped triangles (emit)
+//               offsets: old -> new vertex map, vertices, old indices, remapped triangles (emit); kept = in a kept
+//               component (rnb_mesh_compact_*) or by a per-triangle keep (rnb_mesh_compact_triangles_*)
 //
 // The flag scans follow mcubes.hip: per block of 1024 items a sum, one workgroup scans the block sums, the emit kernel
 // recomputes the flags and adds a block-local scan.  Output order = input order (stable), whatever the launch geometry.
@@ -420,6 +421,39 @@ struct TriangleEmit {
   }
 };
 
+// compaction by a per-triangle keep (rnb_mesh_compact_triangles_*): a triangle is kept when keep_t says so and its three
+// indices are in range; a vertex when a kept triangle names it.  The marks live in the workspace's old -> new map itself:
+// zeroed, then 1 for every corner of a kept triangle (plain stores of one value: any order gives the same bytes), read
+// by the flag of the vertex scan, and replaced by the new index in the emit, where entry v is read and written by the
+// one thread that owns v.
+struct KeptTriangle {
+  const int32_t* tri;
+  const uint8_t* keep_t;
+  int64_t V;
+  __device__ bool operator()(int64_t t) const {
+    if (keep_t[t] == 0) return false;
+    const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
+    return !(a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V);
+  }
+};
+struct MarkedVertex {
+  const int32_t* mark;
+  __device__ bool operator()(int64_t v) const { return mark[v] != 0; }
+};
+struct TriangleEmitIndexed {
+  TriangleEmit emit;
+  int64_t* tindex;
+  __device__ void operator()(int64_t t, bool fl, unsigned pos) const {
+    emit(t, fl, pos);
+    if (fl && (int64_t)pos < emit.n_out) tindex[pos] = t;
+  }
+};
+__global__ __launch_bounds__(kMkThreads) void mk_mark_kernel(KeptTriangle kept, int64_t T, int32_t* mark) {
+  const int64_t t = (int64_t)blockIdx.x * kMkThreads + threadIdx.x;
+  if (t >= T || !kept(t)) return;
+  mark[kept.tri[t * 3]] = 1; mark[kept.tri[t * 3 + 1]] = 1; mark[kept.tri[t * 3 + 2]] = 1;
+}
+
 // ---- workspaces: every stage carves from the start of the one workspace -------------------------------------------
 struct ComponentsWs { uint8_t* ref; unsigned* rank; unsigned* bsum; };
 struct StatsWs { unsigned* flags; unsigned long long* lo; unsigned long long* hi; };
@@ -621,6 +655,90 @@ RNB_API int rnb_mesh_compact_emit(const int32_t* triangles, int64_t n_triangles,
     hipLaunchKernelGGL((mk_flag_emit_kernel<TriangleKeep, TriangleEmit>), dim3((unsigned)mk_blocks(T)), dim3(kMkThreads), 0, s,
                        TriangleKeep{triangles, labels, keep, V, C},
                        TriangleEmit{triangles, w.newidx, triangles_out, n_triangles_out}, T, w.bsum_t);
+    RNB_CHECK_LAUNCH();
+  }
+  return RNB_OK;
+}
+
+namespace rnb {
+static int mk_compact_triangles_check(const char* who, const int32_t* triangles, int64_t T, int64_t V, const uint8_t* keep_t,
+                                      void* workspace, size_t workspace_bytes, CompactWs* w) {
+  RNB_TRY(mk_sizes(who, V, T));
+  if (T > 0 && (!triangles || !keep_t)) RNB_FAIL(RNB_E_NULL, "%s: NULL triangles / keep_t", who);
+  Carver cv(workspace, workspace_bytes);
+  *w = carve_compact(cv, V, T);
+  if (cv.off > 0 && !workspace) RNB_FAIL(RNB_E_NULL, "%s: NULL workspace", who);
+  if (!cv.ok) RNB_FAIL(RNB_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, cv.off);
+  return RNB_OK;
+}
+
+// the marks of the vertices a kept triangle names, in w.newidx
+static int mk_mark_vertices(const KeptTriangle& kept, int64_t T, int64_t V, const CompactWs& w, hipStream_t s) {
+  if (V > 0) RNB_CHECK_HIP(hipMemsetAsync(w.newidx, 0, (size_t)V * sizeof(int32_t), s));
+  if (V > 0 && T > 0) {
+    hipLaunchKernelGGL(mk_mark_kernel, dim3(mk_grid(T)), dim3(kMkThreads), 0, s, kept, T, w.newidx);
+    RNB_CHECK_LAUNCH();
+  }
+  return RNB_OK;
+}
+}  // namespace rnb
+
+RNB_API int rnb_mesh_compact_triangles_count(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                                             const uint8_t* keep_t, void* workspace, size_t workspace_bytes, int64_t* counts,
+                                             rnb_stream_t stream) {
+  using namespace rnb;
+  const char* who = "rnb_mesh_compact_triangles_count";
+  const int64_t T = n_triangles, V = n_vertices;
+  CompactWs w;
+  RNB_TRY(mk_compact_triangles_check(who, triangles, T, V, keep_t, workspace, workspace_bytes, &w));
+  if (!counts) RNB_FAIL(RNB_E_NULL, "%s: NULL counts", who);
+  hipStream_t s = (hipStream_t)stream;
+  const KeptTriangle kept{triangles, keep_t, V};
+  RNB_TRY(mk_mark_vertices(kept, T, V, w, s));
+  const int64_t nbv = mk_blocks(V), nbt = mk_blocks(T);
+  if (V > 0) {
+    hipLaunchKernelGGL(mk_flag_sum_kernel<MarkedVertex>, dim3((unsigned)nbv), dim3(kMkThreads), 0, s, MarkedVertex{w.newidx}, V,
+                       w.bsum_v);
+    RNB_CHECK_LAUNCH();
+  }
+  if (T > 0) {
+    hipLaunchKernelGGL(mk_flag_sum_kernel<KeptTriangle>, dim3((unsigned)nbt), dim3(kMkThreads), 0, s, kept, T, w.bsum_t);
+    RNB_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(mk_scan_kernel, dim3(1), dim3(1024), 0, s, w.bsum_v, nbv, w.bsum_t, nbt, 2, counts);
+  RNB_CHECK_LAUNCH();
+  return RNB_OK;
+}
+
+RNB_API int rnb_mesh_compact_triangles_emit(const int32_t* triangles, int64_t n_triangles, const double* vertices,
+                                            int64_t n_vertices, const uint8_t* keep_t, void* workspace, size_t workspace_bytes,
+                                            int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out,
+                                            int32_t* triangles_out, int64_t* vertex_index, int64_t* triangle_index,
+                                            rnb_stream_t stream) {
+  using namespace rnb;
+  const char* who = "rnb_mesh_compact_triangles_emit";
+  const int64_t T = n_triangles, V = n_vertices;
+  CompactWs w;
+  RNB_TRY(mk_compact_triangles_check(who, triangles, T, V, keep_t, workspace, workspace_bytes, &w));
+  if (n_vertices_out < 0 || n_vertices_out > V || n_triangles_out < 0 || n_triangles_out > T)
+    RNB_FAIL(RNB_E_INVALID, "%s: %lld of %lld vertices / %lld of %lld triangles", who, (long long)n_vertices_out, (long long)V,
+             (long long)n_triangles_out, (long long)T);
+  if ((n_vertices_out > 0 && (!vertex_index || (vertices && !vertices_out))) ||
+      (n_triangles_out > 0 && (!triangles_out || !triangle_index)))
+    RNB_FAIL(RNB_E_NULL, "%s: NULL output", who);
+  hipStream_t s = (hipStream_t)stream;
+  const KeptTriangle kept{triangles, keep_t, V};
+  RNB_TRY(mk_mark_vertices(kept, T, V, w, s));       // (the count's marks again: the emit needs only its block sums)
+  if (V > 0) {
+    hipLaunchKernelGGL((mk_flag_emit_kernel<MarkedVertex, VertexEmit>), dim3((unsigned)mk_blocks(V)), dim3(kMkThreads), 0, s,
+                       MarkedVertex{w.newidx}, VertexEmit{vertices, vertices_out, vertex_index, w.newidx, n_vertices_out}, V,
+                       w.bsum_v);
+    RNB_CHECK_LAUNCH();
+  }
+  if (T > 0) {
+    hipLaunchKernelGGL((mk_flag_emit_kernel<KeptTriangle, TriangleEmitIndexed>), dim3((unsigned)mk_blocks(T)), dim3(kMkThreads), 0,
+                       s, kept, TriangleEmitIndexed{TriangleEmit{triangles, w.newidx, triangles_out, n_triangles_out}, triangle_index},
+                       T, w.bsum_t);
     RNB_CHECK_LAUNCH();
   }
   return RNB_OK;

@@ -3,7 +3,8 @@
 component, or drop the small ones — on the arrays marching cubes left on the GPU; there is no CPU path.
 
 Connectivity: two vertices are connected when some triangle names both.  Components are numbered 0..C-1 in increasing
-order of their smallest vertex index; a vertex no triangle names has label -1 and is always dropped by cleaning."""
+order of their smallest vertex index; a vertex no triangle names has label -1 and is always dropped by cleaning.
+`compact_triangles` is the same compaction by a per-triangle keep (what `mesh_cull.cull_mesh` ends with)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -187,3 +188,51 @@ def clean_mesh(vertices, triangles, *, by="area", keep_largest=None, min_fractio
     return {"vertices": v_out, "triangles": t_out,
             "attributes": {k: a.index_select(0, index) for k, a in attributes.items()},
             "vertex_index": index, "info": info}
+
+
+@torch.no_grad()
+def compact_triangles(vertices, triangles, keep, attributes=None):
+    """Keeps the triangles a per-triangle mask selects, and the vertices they name, on the device.
+    vertices [V,3] float64, triangles [T,3] int32, `keep` [T] bool or uint8 (non-zero = keep) — device tensors.  A
+    triangle is kept when `keep` says so and its three indices lie in [0, V) (one that does not is dropped, no address is
+    formed from it); a vertex when a kept triangle names it.  Compaction is stable, as `clean_mesh`'s.
+    Returns a dict shaped like `clean_mesh`'s: `vertices` [V',3], `triangles` [T',3] (remapped), `attributes` (per-vertex
+    device tensors [V, ...] gathered with the same map), `vertex_index` [V'] int64 and `triangle_index` [T'] int64 (the
+    old index of every kept vertex / triangle), `info`: `n_vertices` / `n_triangles` as (before, after).
+    ValueError for wrong shapes / dtypes; RuntimeError for CPU tensors.  One host synchronisation (V' and T')."""
+    who = "compact_triangles"
+    if vertices is None:
+        raise ValueError(f"{who}: vertices is None (compaction needs the [V,3] coordinates)")
+    V = _check_sizes(who, triangles, None, vertices)
+    T = triangles.shape[0]
+    if not isinstance(keep, torch.Tensor) or keep.dim() != 1 or keep.shape[0] != T or keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{who}: keep must be a [T] bool or uint8 tensor with T = {T}, got "
+                         f"{(tuple(keep.shape), keep.dtype) if isinstance(keep, torch.Tensor) else type(keep).__name__}")
+    attributes = dict(attributes or {})
+    for name, a in attributes.items():
+        if not isinstance(a, torch.Tensor) or a.dim() < 1 or a.shape[0] != V:
+            raise ValueError(f"{who}: attribute {name!r} must be a tensor with first dimension V = {V}")
+    dev = native.same_device(triangles, vertices, keep, *attributes.values())
+    if dev is None:
+        raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+    lib = native.load()
+    tri, vts = triangles.detach().contiguous(), vertices.detach().contiguous()
+    keep8 = keep.detach().to(torch.uint8).contiguous()
+    ws = _workspace(lib, V, T, dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    with native.on_device(dev) as stream:
+        native.check(lib.rnb_mesh_compact_triangles_count(native.ptr(tri), T, V, native.ptr(keep8), native.ptr(ws), ws.numel(),
+                                                          native.ptr(counts), stream))
+    nv, nt = (int(c) for c in counts.cpu())
+    v_out = torch.empty(nv, 3, dtype=torch.float64, device=dev)
+    t_out = torch.empty(nt, 3, dtype=torch.int32, device=dev)
+    v_index = torch.empty(nv, dtype=torch.int64, device=dev)
+    t_index = torch.empty(nt, dtype=torch.int64, device=dev)
+    with native.on_device(dev) as stream:
+        native.check(lib.rnb_mesh_compact_triangles_emit(native.ptr(tri), T, native.ptr(vts), V, native.ptr(keep8), native.ptr(ws),
+                                                         ws.numel(), nv, nt, native.ptr(v_out), native.ptr(t_out),
+                                                         native.ptr(v_index), native.ptr(t_index), stream))
+    return {"vertices": v_out, "triangles": t_out,
+            "attributes": {k: a.index_select(0, v_index) for k, a in attributes.items()},
+            "vertex_index": v_index, "triangle_index": t_index,
+            "info": {"n_vertices": (V, nv), "n_triangles": (T, nt)}}

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from . import mesh_raycast, native
+from . import mesh_cull, mesh_raycast, native
 from .mesh_clean import _check_sizes
 
 _MAX_CELLS = native.MESH_BINS_MAX_CELLS
@@ -83,7 +83,7 @@ class MeshIndex:
     always, for the grids built here; the query's bound uses it), `n_triangles`, `n_vertices`.
     `grid=(origin, cell_size, dims)` places the bins by hand (any box, covering the mesh or not: what lies outside goes
     to the boundary cells, and no result of `closest` changes), without coarsening.  `raycast`, `interpolate` and `visible`
-    (mesh_raycast.py) cast rays at the same bins; they need `covers`.
+    (mesh_raycast.py) and `view_votes` (mesh_cull.py) cast rays at the same bins; they need `covers`.
     ValueError for wrong shapes / dtypes and for a triangle index outside [0, V); RuntimeError for CPU tensors.
     Host synchronisations: one for the bounding box, one per counting pass."""
 
@@ -211,6 +211,12 @@ class MeshIndex:
     def visible(self, points, eye, rel_tol=mesh_raycast.VISIBLE_REL_TOL):
         """Which points the eye sees past the mesh: `mesh_raycast.visible`."""
         return mesh_raycast.visible(self, points, eye, rel_tol)
+
+    def view_votes(self, points, projections, eyes, masks=None, *, image_size=None, occlusion=True,
+                   rel_tol=mesh_raycast.VISIBLE_REL_TOL, return_status=False):
+        """Per point how many cameras have it out of frame, outside the mask, occluded, seen: `mesh_cull.view_votes`."""
+        return mesh_cull.view_votes(self, points, projections, eyes, masks, image_size=image_size, occlusion=occlusion,
+                                    rel_tol=rel_tol, return_status=return_status)
 
 
 @torch.no_grad()

@@ -118,6 +118,9 @@ MESH_BINS_MAX_CELLS = 1 << 24
 # flags of rnb_mesh_closest_points; bits of rnb_mesh_bins_count's counts[1] (include/rnbneus.h)
 MESH_BINS_COVER = 1
 MESH_BINS_SKIPPED, MESH_BINS_OUTSIDE = 1, 2
+# flag and status codes of rnb_mesh_view_votes (include/rnbneus.h)
+CULL_NO_OCCLUSION = 2
+CULL_OUT_OF_FRAME, CULL_OUTSIDE_MASK, CULL_OCCLUDED, CULL_SEEN = 0, 1, 2, 3
 
 SPARSE_BRICKS = (4, 8, 16, 32)
 
@@ -230,6 +233,14 @@ _SIGNATURES = {
     "rnb_mesh_raycast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _P(MeshBins), C.c_void_p,
                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "rnb_mesh_view_votes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                      C.c_int32, _P(MeshBins), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                      C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_compact_triangles_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p, C.c_void_p]),
+    "rnb_mesh_compact_triangles_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
     "rnb_mesh_sample_workspace_bytes": (C.c_int, [C.c_int64, _P(C.c_int64)]),
     "rnb_mesh_sample_areas": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),

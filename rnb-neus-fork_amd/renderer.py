@@ -284,6 +284,7 @@ class NeuSRenderer:
         self.last_sparse_grid = None   # `info` of the last extract_geometry(sparse=True)
         self.last_mesh_clean = None    # `info` of the last extract_geometry / extract_textured_geometry(clean=...)
         self.last_mesh_simplify = None  # `info` of the last extract_geometry / extract_textured_geometry(simplify=...)
+        self.last_mesh_cull = None     # `info` of the last extract_geometry / extract_textured_geometry(cull=...)
 
     # ------------------------------------------------------------------ data parallel
     def set_data_parallel(self, group=None, enabled=True, exact=True):
@@ -788,7 +789,7 @@ class NeuSRenderer:
         return {"max_abs_weight": worst, "layer": where, "limit": 255.0, "ok": bool(worst < 255.0)}
 
     def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, backend=None, sparse=False, margin=1.0,
-                         brick=None, clean=None, simplify=None):
+                         brick=None, clean=None, simplify=None, cull=None):
         """models/renderer.py:1219-1224 / :27-36: SDF grid + marching cubes + rescaling to the bounding box; returns
         numpy `(vertices [V,3] float64, triangles [T,3])` as the reference does.
         `backend`: "native" — the library's own marching cubes on the volume still resident in HBM
@@ -808,7 +809,11 @@ class NeuSRenderer:
         for it) and the `info` of the cleaning is kept in `self.last_mesh_clean`.  None (default): no cleaning.
         `simplify`: a dict of `mesh_simplify.simplify_mesh` keywords (`cell_size` in grid-index units, i.e. voxels, or
         `target_triangles`; `origin`) — the mesh is simplified on the device after the cleaning and before the rescaling;
-        `info` is kept in `self.last_mesh_simplify`.  None (default): no simplification."""
+        `info` is kept in `self.last_mesh_simplify`.  None (default): no simplification.
+        `cull`: a dict of `mesh_cull.cull_mesh` keywords (`rays` or `projections` / `eyes` / `masks` / `image_size`; `views`,
+        `max_outside`, `min_seen`, `occlusion`, `dilate`, `threshold`, `rule`) — what the cameras do not support is removed
+        on the device after the cleaning and before the simplification; the votes are taken on the vertices rescaled to the
+        bounding box (the cameras' frame), `info` is kept in `self.last_mesh_cull`.  None (default): no culling."""
         if backend is None:
             try:
                 import mcubes  # noqa: F401
@@ -826,6 +831,7 @@ class NeuSRenderer:
             raise ValueError(f"extract_geometry: unknown backend {backend!r}")
         self._check_clean(clean)
         self._check_simplify(simplify)
+        self._check_cull(cull)
         b_max = bound_max.detach().cpu().numpy()
         b_min = bound_min.detach().cpu().numpy()
         if backend == "mcubes":
@@ -836,12 +842,14 @@ class NeuSRenderer:
             else:
                 u = self.extract_fields(bound_min, bound_max, resolution)
             vertices, triangles = mcubes.marching_cubes(u, threshold)
-            if clean is not None or simplify is not None:
+            if clean is not None or simplify is not None or cull is not None:
                 dev = self.sdf_network.lin0.bias.device
                 v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev)
                 t = torch.as_tensor(np.ascontiguousarray(triangles).astype(np.int32)).to(dev)
                 if clean is not None:
                     v, t = self._clean_mesh(v, t, clean)
+                if cull is not None:
+                    v, t = self._cull_mesh(v, t, cull, bound_min, bound_max, resolution)
                 if simplify is not None:
                     v, t = self._simplify_mesh(v, t, simplify)
                 vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
@@ -853,10 +861,12 @@ class NeuSRenderer:
             else:
                 u = self.extract_fields(bound_min, bound_max, resolution, to_host=False)
             v, t = marching_cubes(u, threshold)
-            if clean is not None or simplify is not None:
+            if clean is not None or simplify is not None or cull is not None:
                 del u
             if clean is not None:
                 v, t = self._clean_mesh(v, t, clean)
+            if cull is not None:
+                v, t = self._cull_mesh(v, t, cull, bound_min, bound_max, resolution)
             if simplify is not None:
                 v, t = self._simplify_mesh(v, t, simplify)
             vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
@@ -879,6 +889,26 @@ class NeuSRenderer:
         out = clean_mesh(v, t, **clean)
         self.last_mesh_clean = out["info"]
         return out["vertices"], out["triangles"]
+
+    @staticmethod
+    def _check_cull(cull):
+        """the `cull` argument of the two extract calls, checked before the grid is evaluated"""
+        from .mesh_cull import CULL_KEYWORDS, check_arguments
+        if cull is None:
+            return
+        if not isinstance(cull, dict) or not set(cull) <= set(CULL_KEYWORDS):
+            raise ValueError(f"cull must be a dict of cull_mesh keywords {CULL_KEYWORDS}")
+        check_arguments("cull", **cull)
+
+    def _cull_mesh(self, v, t, cull, bound_min, bound_max, resolution):
+        """`cull_mesh` for the two extract calls: `v` in grid-index units is voted on in the cameras' frame (the rescaling of
+        `extract_textured_geometry(to_host=False)`, bit for bit the host's) and comes back culled in grid-index units; `info` kept."""
+        from .mesh_cull import cull_mesh
+        b_min, b_max = (b.detach().to(v.device) for b in (bound_min, bound_max))
+        model = v / torch.full_like(v, float(resolution) - 1.0) * (b_max - b_min).double()[None, :] + b_min.double()[None, :]
+        out = cull_mesh(model, t, **cull)
+        self.last_mesh_cull = out["info"]
+        return v.index_select(0, out["vertex_index"]), out["triangles"]
 
     @staticmethod
     def _check_simplify(simplify):
@@ -985,7 +1015,7 @@ class NeuSRenderer:
     @torch.no_grad()
     def extract_textured_geometry(self, bound_min, bound_max, resolution, threshold=0.0, *, sparse=False, margin=1.0,
                                   brick=None, refine=0, max_step=None, chunk=65536, to_host=True, clean=None,
-                                  simplify=None, bake=None):
+                                  simplify=None, bake=None, cull=None):
         """`validate_mesh_texture` up to the export (exp_runner.py:584-613): SDF grid (dense, or `sparse=True` as in
         `extract_geometry`), the native marching cubes, and `vertex_attributes` on the vertices where marching cubes left
         them — they never leave the device in between.  Returns a dict:
@@ -1002,6 +1032,9 @@ class NeuSRenderer:
         `simplify`: a dict of `mesh_simplify.simplify_mesh` keywords (`cell_size` in voxels, or `target_triangles`;
         `origin`); the simplification runs after the cleaning and before `vertex_attributes`, which is evaluated on the
         surviving vertices only (`info` in `self.last_mesh_simplify`).  None (default): no simplification.
+        `cull`: a dict of `mesh_cull.cull_mesh` keywords, as in `extract_geometry`; the culling runs after the cleaning and
+        before the simplification, so what no camera supports is neither evaluated nor baked (`info` in
+        `self.last_mesh_cull`).  None (default): no culling.
         `bake`: a dict of `bake_textures` keywords (`size`, `chart`, `refine`, `max_step`, `threshold`, `albedo`, `slab`,
         `chunk`, `return_samples`; `threshold` defaults to this call's, `max_step` to one cell diagonal); the bake runs last,
         on the final vertices (cleaned, simplified and, where asked for, refined), and adds `uv` [T,3,2], `albedo_image`,
@@ -1010,6 +1043,7 @@ class NeuSRenderer:
         self._check_clean(clean)
         self._check_simplify(simplify)
         self._check_bake(bake)
+        self._check_cull(cull)
         res = int(resolution)
         if sparse:
             u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, res, threshold, brick, margin,
@@ -1020,6 +1054,8 @@ class NeuSRenderer:
         del u
         if clean is not None:
             v, t = self._clean_mesh(v, t, clean)
+        if cull is not None:
+            v, t = self._cull_mesh(v, t, cull, bound_min, bound_max, res)
         if simplify is not None:
             v, t = self._simplify_mesh(v, t, simplify)
         at = self.vertex_attributes(grid_vertices=v, bounds=(bound_min, bound_max), resolution=res, threshold=threshold,
