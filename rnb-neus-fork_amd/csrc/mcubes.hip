@@ -11,7 +11,8 @@
 // L1 / L2), one 4-byte word per grid point of workspace carries the vertex numbering between the two emit kernels.
 //
 //   pass 1  mc_count_kernel     per block of 1024 grid points: (# vertices, # triangles)          -> block sums
-//   pass 2  mc_scan_kernel      exclusive scan of the block sums (one workgroup), totals to `counts`
+//   pass 2  scan_block_sums_kernel<unsigned> (scan.hip.h): exclusive scan of the block sums (one workgroup), totals to
+//                               `counts`; 64-bit running totals, the offsets themselves fit 32 bits
 //           -- the caller reads the two totals and allocates the outputs --
 //   pass 3  mc_vertex_kernel    recompute, block-local scan + block offset: vertex ids; writes the vertices and, per
 //                               grid point, id of its first vertex | active-x << 30 | active-y << 31
@@ -20,6 +21,7 @@
 // Order of the outputs (deterministic, independent of the launch geometry): vertices by owning grid point
 // (x slowest, z fastest), then by edge axis x, y, z; triangles by cell in the same order, then in table order.
 #include "rnb_internal.h"
+#include "scan.hip.h"
 
 namespace rnb {
 
@@ -27,9 +29,9 @@ namespace rnb {
 #include "mc_tables.inc"
 #undef RNB_MC_TABLE
 
-constexpr int kMcThreads = 256;
-constexpr int kMcItems = 4;
-constexpr int kMcTile = kMcThreads * kMcItems;     // grid points per workgroup
+constexpr int kMcThreads = kScanThreads;
+constexpr int kMcItems = kScanItems;
+constexpr int kMcTile = kScanTile;                 // grid points per workgroup
 
 struct McGrid {
   const float* v;
@@ -92,28 +94,6 @@ struct McCursor {
   }
 };
 
-// exclusive prefix of `v` over the 256 threads of the workgroup (thread order); *total = sum over the workgroup
-__device__ inline unsigned block_exclusive_scan(unsigned v, unsigned* total, unsigned* red /* [4] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();                 // `red` may still be read by the previous call
-  if (lane == 63) red[wave] = inc;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kMcThreads / 64; ++w) {
-    if (w < wave) base += red[w];
-    tot += red[w];
-  }
-  *total = tot;
-  return base + inc - v;
-}
-
 __global__ __launch_bounds__(kMcThreads) void mc_count_kernel(McGrid g, unsigned* __restrict__ block_verts,
                                                               unsigned* __restrict__ block_tris) {
   __shared__ unsigned red[4];
@@ -135,41 +115,6 @@ __global__ __launch_bounds__(kMcThreads) void mc_count_kernel(McGrid g, unsigned
   if (threadIdx.x == 0) {
     block_verts[blockIdx.x] = tv;
     block_tris[blockIdx.x] = tt;
-  }
-}
-
-// exclusive scan of the two block-sum arrays in place (64-bit running totals; the offsets themselves fit 32 bits
-// whenever the totals pass the caller's range check); counts[0..1] = total vertices, total triangles
-__global__ __launch_bounds__(1024) void mc_scan_kernel(unsigned* __restrict__ block_verts,
-                                                       unsigned* __restrict__ block_tris, int64_t nblocks,
-                                                       int64_t* __restrict__ counts) {
-  __shared__ unsigned long long wsum[16];
-  __shared__ unsigned long long carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int which = 0; which < 2; ++which) {
-    unsigned* a = which == 0 ? block_verts : block_tris;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nblocks; base += 1024) {
-      const int64_t i = base + threadIdx.x;
-      const unsigned long long v = i < nblocks ? a[i] : 0;
-      unsigned long long inc = v;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
-      if (lane == 63) wsum[wave] = inc;
-      __syncthreads();
-      unsigned long long before = carry_s;
-      for (int w = 0; w < wave; ++w) before += wsum[w];
-      if (i < nblocks) a[i] = (unsigned)(before + inc - v);
-      __syncthreads();
-      if (threadIdx.x == 1023) carry_s = before + inc;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[which] = (int64_t)carry_s;
-    __syncthreads();
   }
 }
 
@@ -262,8 +207,6 @@ static int mc_check(const char* who, const void* volume, int nx, int ny, int nz)
   return RNB_OK;
 }
 
-static int64_t mc_blocks(int64_t n) { return (n + kMcTile - 1) / kMcTile; }
-
 }  // namespace rnb
 
 #define RNB_API extern "C" __attribute__((visibility("default")))
@@ -273,7 +216,7 @@ RNB_API int rnb_marching_cubes_workspace_bytes(int32_t nx, int32_t ny, int32_t n
   if (!bytes) RNB_FAIL(RNB_E_NULL, "rnb_marching_cubes_workspace_bytes: NULL");
   if (nx < 2 || ny < 2 || nz < 2) RNB_FAIL(RNB_E_INVALID, "rnb_marching_cubes_workspace_bytes: bad grid");
   const int64_t n = (int64_t)nx * ny * nz;
-  const int64_t nb = (mc_blocks(n) + 63) / 64 * 64;
+  const int64_t nb = (scan_blocks(n) + 63) / 64 * 64;
   *bytes = (2 * nb + n) * (int64_t)sizeof(unsigned);
   return RNB_OK;
 }
@@ -286,13 +229,13 @@ RNB_API int rnb_marching_cubes_count(const float* volume, int32_t nx, int32_t ny
   int64_t need;
   RNB_TRY(rnb_marching_cubes_workspace_bytes(nx, ny, nz, &need));
   if ((int64_t)workspace_bytes < need) RNB_FAIL(RNB_E_INVALID, "rnb_marching_cubes_count: workspace %zu < %lld bytes", workspace_bytes, (long long)need);
-  const int64_t n = (int64_t)nx * ny * nz, nb = mc_blocks(n), nbp = (nb + 63) / 64 * 64;
+  const int64_t n = (int64_t)nx * ny * nz, nb = scan_blocks(n), nbp = (nb + 63) / 64 * 64;
   unsigned* bv = (unsigned*)workspace;
   unsigned* bt = bv + nbp;
   McGrid g{volume, nx, ny, nz, n, threshold};
   hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)nb), dim3(kMcThreads), 0, (hipStream_t)stream, g, bv, bt);
   RNB_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bv, bt, nb, counts);
+  hipLaunchKernelGGL(scan_block_sums_kernel<unsigned>, dim3(1), dim3(1024), 0, (hipStream_t)stream, bv, nb, bt, nb, 2, counts);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -311,7 +254,7 @@ RNB_API int rnb_marching_cubes_emit(const float* volume, int32_t nx, int32_t ny,
   int64_t need;
   RNB_TRY(rnb_marching_cubes_workspace_bytes(nx, ny, nz, &need));
   if ((int64_t)workspace_bytes < need) RNB_FAIL(RNB_E_INVALID, "rnb_marching_cubes_emit: workspace too small");
-  const int64_t n = (int64_t)nx * ny * nz, nb = mc_blocks(n), nbp = (nb + 63) / 64 * 64;
+  const int64_t n = (int64_t)nx * ny * nz, nb = scan_blocks(n), nbp = (nb + 63) / 64 * 64;
   unsigned* bv = (unsigned*)workspace;
   unsigned* bt = bv + nbp;
   unsigned* voff = bt + nbp;

@@ -15,12 +15,14 @@
 //               offsets: old -> new vertex map, vertices, old indices, remapped triangles (emit); kept = in a kept
 //               component (rnb_mesh_compact_*) or by a per-triangle keep (rnb_mesh_compact_triangles_*)
 //
-// The flag scans follow mcubes.hip: per block of 1024 items a sum, one workgroup scans the block sums, the emit kernel
-// recomputes the flags and adds a block-local scan.  Output order = input order (stable), whatever the launch geometry.
-#include "rnb_internal.h"
-#include "mesh_scan.hip.h"
+// The flag scans are those of scan.hip.h with 32-bit positions: output order = input order (stable), whatever the launch
+// geometry.  The index guard and the size checks are those of mesh_common.hip.h.
+#include "mesh_common.hip.h"
+#include "scan.hip.h"
 
 namespace rnb {
+
+constexpr int kMkThreads = kScanThreads;   // the block of every kernel here
 
 // ---- components ---------------------------------------------------------------------------------------------------
 
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(kMkThreads) void mk_union_kernel(const int32_t* __r
   const int64_t t = (int64_t)blockIdx.x * kMkThreads + threadIdx.x;
   if (t >= T) return;
   const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
-  if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V) {
+  if (!mesh_indices_ok(a, b, c, V)) {
     atomicOr(bad, 1ull);
     return;
   }
@@ -228,7 +230,7 @@ struct TriangleSrc {
   int64_t V, C;
   __device__ int operator()(int64_t t, double* area) const {
     const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
-    if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V) return -1;
+    if (!mesh_indices_ok(a, b, c, V)) return -1;
     const int l = labels[a];
     if (l < 0 || l >= C) return -1;
     if (vertices) {
@@ -243,10 +245,10 @@ struct TriangleSrc {
     return l;
   }
 };
-__device__ inline bool mk_finite(double a) { return a == a && a <= 1.7976931348623157e308; }
 
 // first triangle pass: triangle counts, and per component the largest finite area (as bits: areas are >= 0) / the
-// not-finite flags
+// not-finite flags.  (An area is 0.5 sqrt(..): a number >= 0, +inf or NaN, so the two-sided mesh_finite says what a test
+// against the upper bound alone would.)
 struct CountAcc {
   unsigned long long n = 0, bits = 0;
   unsigned fl = 0;
@@ -275,7 +277,7 @@ struct CountItem {
     a.n = 1;
     if (src.vertices) {
       if (area != area) a.fl = MK_AREA_NAN;
-      else if (!mk_finite(area)) a.fl = MK_AREA_INF;
+      else if (!mesh_finite(area)) a.fl = MK_AREA_INF;
       else a.bits = (unsigned long long)__double_as_longlong(area);
     }
     return c;
@@ -311,7 +313,7 @@ struct AreaItem {
     const int c = src(t, &area);
     if (c < 0) return -1;
     const double amax = __longlong_as_double((long long)amax_bits[c]);
-    if (mk_finite(area) && amax > 0.0) a.lo = (unsigned long long)llrint(ldexp(area, 54 - ilogb(amax)));
+    if (mesh_finite(area) && amax > 0.0) a.lo = (unsigned long long)llrint(ldexp(area, 54 - ilogb(amax)));
     return c;
   }
 };
@@ -386,7 +388,7 @@ struct TriangleKeep {
   int64_t V, C;
   __device__ bool operator()(int64_t t) const {
     const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
-    if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V) return false;
+    if (!mesh_indices_ok(a, b, c, V)) return false;
     const int l = labels[a];
     return l >= 0 && l < C && keep[l] != 0;
   }
@@ -433,7 +435,7 @@ struct KeptTriangle {
   __device__ bool operator()(int64_t t) const {
     if (keep_t[t] == 0) return false;
     const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
-    return !(a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V);
+    return mesh_indices_ok(a, b, c, V);
   }
 };
 struct MarkedVertex {
@@ -463,7 +465,7 @@ static ComponentsWs carve_components(Carver& c, int64_t V) {
   ComponentsWs w;
   w.ref = c.take<uint8_t>(V);
   w.rank = c.take<unsigned>(V);
-  w.bsum = c.take<unsigned>(mk_pad64(mk_blocks(V)));
+  w.bsum = c.take<unsigned>(scan_pad64(scan_blocks(V)));
   return w;
 }
 static StatsWs carve_stats(Carver& c, int64_t C) {
@@ -476,17 +478,9 @@ static StatsWs carve_stats(Carver& c, int64_t C) {
 static CompactWs carve_compact(Carver& c, int64_t V, int64_t T) {
   CompactWs w;
   w.newidx = c.take<int32_t>(V);
-  w.bsum_v = c.take<unsigned>(mk_pad64(mk_blocks(V)));
-  w.bsum_t = c.take<unsigned>(mk_pad64(mk_blocks(T)));
+  w.bsum_v = c.take<unsigned>(scan_pad64(scan_blocks(V)));
+  w.bsum_t = c.take<unsigned>(scan_pad64(scan_blocks(T)));
   return w;
-}
-
-constexpr int64_t kMkMax = 2147483647;   // V and T are 31-bit: vertex ids are int32
-
-static int mk_sizes(const char* who, int64_t V, int64_t T) {
-  if (V < 0 || T < 0 || V > kMkMax || T > kMkMax)
-    RNB_FAIL(RNB_E_INVALID, "%s: %lld vertices / %lld triangles outside [0, 2^31 - 1]", who, (long long)V, (long long)T);
-  return RNB_OK;
 }
 
 static unsigned mk_grid(int64_t n) { return (unsigned)((n + kMkThreads - 1) / kMkThreads); }
@@ -499,7 +493,7 @@ static unsigned mk_stat_grid(int64_t n) { return (unsigned)((n + kMkThreads * kM
 RNB_API int rnb_mesh_clean_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int64_t* bytes) {
   using namespace rnb;
   if (!bytes) RNB_FAIL(RNB_E_NULL, "rnb_mesh_clean_workspace_bytes: NULL");
-  RNB_TRY(mk_sizes("rnb_mesh_clean_workspace_bytes", n_vertices, n_triangles));
+  RNB_TRY(mesh_sizes("rnb_mesh_clean_workspace_bytes", n_vertices, n_triangles));
   Carver a(nullptr, 0), b(nullptr, 0), c(nullptr, 0);
   carve_components(a, n_vertices);
   carve_stats(b, n_vertices);             // at most one component per vertex
@@ -513,7 +507,7 @@ RNB_API int rnb_mesh_components(const int32_t* triangles, int64_t n_triangles, i
                                 size_t workspace_bytes, int32_t* labels, int64_t* counts, rnb_stream_t stream) {
   using namespace rnb;
   const int64_t T = n_triangles, V = n_vertices;
-  RNB_TRY(mk_sizes("rnb_mesh_components", V, T));
+  RNB_TRY(mesh_sizes("rnb_mesh_components", V, T));
   if (!counts || (T > 0 && !triangles) || (V > 0 && !labels)) RNB_FAIL(RNB_E_NULL, "rnb_mesh_components: NULL triangles / labels / counts");
   if (V > 0 && !workspace) RNB_FAIL(RNB_E_NULL, "rnb_mesh_components: NULL workspace");
   Carver cv(workspace, workspace_bytes);
@@ -531,13 +525,13 @@ RNB_API int rnb_mesh_components(const int32_t* triangles, int64_t n_triangles, i
   }
   hipLaunchKernelGGL(mk_flatten_kernel, dim3(mk_grid(V)), dim3(kMkThreads), 0, s, labels, w.ref, V);
   RNB_CHECK_LAUNCH();
-  const int64_t nb = mk_blocks(V);
+  const int64_t nb = scan_blocks(V);
   const RootFlag flag{labels};
-  hipLaunchKernelGGL(mk_flag_sum_kernel<RootFlag>, dim3((unsigned)nb), dim3(kMkThreads), 0, s, flag, V, w.bsum);
+  hipLaunchKernelGGL((scan_sum_kernel<unsigned, RootFlag>), dim3((unsigned)nb), dim3(kMkThreads), 0, s, flag, V, w.bsum);
   RNB_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mk_scan_kernel, dim3(1), dim3(1024), 0, s, w.bsum, nb, (unsigned*)nullptr, (int64_t)0, 1, counts);
+  hipLaunchKernelGGL(scan_block_sums_kernel<unsigned>, dim3(1), dim3(1024), 0, s, w.bsum, nb, (unsigned*)nullptr, (int64_t)0, 1, counts);
   RNB_CHECK_LAUNCH();
-  hipLaunchKernelGGL((mk_flag_emit_kernel<RootFlag, RankEmit>), dim3((unsigned)nb), dim3(kMkThreads), 0, s, flag,
+  hipLaunchKernelGGL((scan_emit_kernel<unsigned, RootFlag, RankEmit>), dim3((unsigned)nb), dim3(kMkThreads), 0, s, flag,
                      RankEmit{w.rank}, V, w.bsum);
   RNB_CHECK_LAUNCH();
   hipLaunchKernelGGL(mk_relabel_kernel, dim3(mk_grid(V)), dim3(kMkThreads), 0, s, labels, w.rank, V);
@@ -551,7 +545,7 @@ RNB_API int rnb_mesh_component_stats(const int32_t* triangles, int64_t n_triangl
                                      double* bbox_min, double* bbox_max, rnb_stream_t stream) {
   using namespace rnb;
   const int64_t T = n_triangles, V = n_vertices, C = n_components;
-  RNB_TRY(mk_sizes("rnb_mesh_component_stats", V, T));
+  RNB_TRY(mesh_sizes("rnb_mesh_component_stats", V, T));
   if (C < 0 || C > V) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_component_stats: %lld components of %lld vertices", (long long)C, (long long)V);
   if (C == 0) return RNB_OK;
   if (!labels || !tri_count || !vert_count || (T > 0 && !triangles))
@@ -594,7 +588,7 @@ RNB_API int rnb_mesh_component_stats(const int32_t* triangles, int64_t n_triangl
 namespace rnb {
 static int mk_compact_check(const char* who, const int32_t* triangles, int64_t T, int64_t V, const int32_t* labels,
                             const uint8_t* keep, int64_t C, void* workspace, size_t workspace_bytes, CompactWs* w) {
-  RNB_TRY(mk_sizes(who, V, T));
+  RNB_TRY(mesh_sizes(who, V, T));
   if (C < 0 || C > V) RNB_FAIL(RNB_E_INVALID, "%s: %lld components of %lld vertices", who, (long long)C, (long long)V);
   if ((T > 0 && !triangles) || (V > 0 && !labels) || (C > 0 && !keep)) RNB_FAIL(RNB_E_NULL, "%s: NULL triangles / labels / keep", who);
   Carver cv(workspace, workspace_bytes);
@@ -614,18 +608,18 @@ RNB_API int rnb_mesh_compact_count(const int32_t* triangles, int64_t n_triangles
   RNB_TRY(mk_compact_check("rnb_mesh_compact_count", triangles, T, V, labels, keep, C, workspace, workspace_bytes, &w));
   if (!counts) RNB_FAIL(RNB_E_NULL, "rnb_mesh_compact_count: NULL counts");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t nbv = mk_blocks(V), nbt = mk_blocks(T);
+  const int64_t nbv = scan_blocks(V), nbt = scan_blocks(T);
   if (V > 0) {
-    hipLaunchKernelGGL(mk_flag_sum_kernel<VertexKeep>, dim3((unsigned)nbv), dim3(kMkThreads), 0, s,
+    hipLaunchKernelGGL((scan_sum_kernel<unsigned, VertexKeep>), dim3((unsigned)nbv), dim3(kMkThreads), 0, s,
                        VertexKeep{labels, keep, C}, V, w.bsum_v);
     RNB_CHECK_LAUNCH();
   }
   if (T > 0) {
-    hipLaunchKernelGGL(mk_flag_sum_kernel<TriangleKeep>, dim3((unsigned)nbt), dim3(kMkThreads), 0, s,
+    hipLaunchKernelGGL((scan_sum_kernel<unsigned, TriangleKeep>), dim3((unsigned)nbt), dim3(kMkThreads), 0, s,
                        TriangleKeep{triangles, labels, keep, V, C}, T, w.bsum_t);
     RNB_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(mk_scan_kernel, dim3(1), dim3(1024), 0, s, w.bsum_v, nbv, w.bsum_t, nbt, 2, counts);
+  hipLaunchKernelGGL(scan_block_sums_kernel<unsigned>, dim3(1), dim3(1024), 0, s, w.bsum_v, nbv, w.bsum_t, nbt, 2, counts);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -646,13 +640,13 @@ RNB_API int rnb_mesh_compact_emit(const int32_t* triangles, int64_t n_triangles,
     RNB_FAIL(RNB_E_NULL, "rnb_mesh_compact_emit: NULL output");
   hipStream_t s = (hipStream_t)stream;
   if (V > 0) {
-    hipLaunchKernelGGL((mk_flag_emit_kernel<VertexKeep, VertexEmit>), dim3((unsigned)mk_blocks(V)), dim3(kMkThreads), 0, s,
+    hipLaunchKernelGGL((scan_emit_kernel<unsigned, VertexKeep, VertexEmit>), dim3((unsigned)scan_blocks(V)), dim3(kMkThreads), 0, s,
                        VertexKeep{labels, keep, C}, VertexEmit{vertices, vertices_out, vertex_index, w.newidx, n_vertices_out},
                        V, w.bsum_v);
     RNB_CHECK_LAUNCH();
   }
   if (T > 0) {
-    hipLaunchKernelGGL((mk_flag_emit_kernel<TriangleKeep, TriangleEmit>), dim3((unsigned)mk_blocks(T)), dim3(kMkThreads), 0, s,
+    hipLaunchKernelGGL((scan_emit_kernel<unsigned, TriangleKeep, TriangleEmit>), dim3((unsigned)scan_blocks(T)), dim3(kMkThreads), 0, s,
                        TriangleKeep{triangles, labels, keep, V, C},
                        TriangleEmit{triangles, w.newidx, triangles_out, n_triangles_out}, T, w.bsum_t);
     RNB_CHECK_LAUNCH();
@@ -663,7 +657,7 @@ RNB_API int rnb_mesh_compact_emit(const int32_t* triangles, int64_t n_triangles,
 namespace rnb {
 static int mk_compact_triangles_check(const char* who, const int32_t* triangles, int64_t T, int64_t V, const uint8_t* keep_t,
                                       void* workspace, size_t workspace_bytes, CompactWs* w) {
-  RNB_TRY(mk_sizes(who, V, T));
+  RNB_TRY(mesh_sizes(who, V, T));
   if (T > 0 && (!triangles || !keep_t)) RNB_FAIL(RNB_E_NULL, "%s: NULL triangles / keep_t", who);
   Carver cv(workspace, workspace_bytes);
   *w = carve_compact(cv, V, T);
@@ -695,17 +689,17 @@ RNB_API int rnb_mesh_compact_triangles_count(const int32_t* triangles, int64_t n
   hipStream_t s = (hipStream_t)stream;
   const KeptTriangle kept{triangles, keep_t, V};
   RNB_TRY(mk_mark_vertices(kept, T, V, w, s));
-  const int64_t nbv = mk_blocks(V), nbt = mk_blocks(T);
+  const int64_t nbv = scan_blocks(V), nbt = scan_blocks(T);
   if (V > 0) {
-    hipLaunchKernelGGL(mk_flag_sum_kernel<MarkedVertex>, dim3((unsigned)nbv), dim3(kMkThreads), 0, s, MarkedVertex{w.newidx}, V,
+    hipLaunchKernelGGL((scan_sum_kernel<unsigned, MarkedVertex>), dim3((unsigned)nbv), dim3(kMkThreads), 0, s, MarkedVertex{w.newidx}, V,
                        w.bsum_v);
     RNB_CHECK_LAUNCH();
   }
   if (T > 0) {
-    hipLaunchKernelGGL(mk_flag_sum_kernel<KeptTriangle>, dim3((unsigned)nbt), dim3(kMkThreads), 0, s, kept, T, w.bsum_t);
+    hipLaunchKernelGGL((scan_sum_kernel<unsigned, KeptTriangle>), dim3((unsigned)nbt), dim3(kMkThreads), 0, s, kept, T, w.bsum_t);
     RNB_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(mk_scan_kernel, dim3(1), dim3(1024), 0, s, w.bsum_v, nbv, w.bsum_t, nbt, 2, counts);
+  hipLaunchKernelGGL(scan_block_sums_kernel<unsigned>, dim3(1), dim3(1024), 0, s, w.bsum_v, nbv, w.bsum_t, nbt, 2, counts);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -730,13 +724,13 @@ RNB_API int rnb_mesh_compact_triangles_emit(const int32_t* triangles, int64_t n_
   const KeptTriangle kept{triangles, keep_t, V};
   RNB_TRY(mk_mark_vertices(kept, T, V, w, s));       // (the count's marks again: the emit needs only its block sums)
   if (V > 0) {
-    hipLaunchKernelGGL((mk_flag_emit_kernel<MarkedVertex, VertexEmit>), dim3((unsigned)mk_blocks(V)), dim3(kMkThreads), 0, s,
+    hipLaunchKernelGGL((scan_emit_kernel<unsigned, MarkedVertex, VertexEmit>), dim3((unsigned)scan_blocks(V)), dim3(kMkThreads), 0, s,
                        MarkedVertex{w.newidx}, VertexEmit{vertices, vertices_out, vertex_index, w.newidx, n_vertices_out}, V,
                        w.bsum_v);
     RNB_CHECK_LAUNCH();
   }
   if (T > 0) {
-    hipLaunchKernelGGL((mk_flag_emit_kernel<KeptTriangle, TriangleEmitIndexed>), dim3((unsigned)mk_blocks(T)), dim3(kMkThreads), 0,
+    hipLaunchKernelGGL((scan_emit_kernel<unsigned, KeptTriangle, TriangleEmitIndexed>), dim3((unsigned)scan_blocks(T)), dim3(kMkThreads), 0,
                        s, kept, TriangleEmitIndexed{TriangleEmit{triangles, w.newidx, triangles_out, n_triangles_out}, triangle_index},
                        T, w.bsum_t);
     RNB_CHECK_LAUNCH();

@@ -32,7 +32,7 @@ struct CvArgs {
   const uint8_t* masks;       // [C,H,W] or nullptr
   int64_t N, C;
   int H, W;
-  RcMesh mesh;
+  BinnedMesh mesh;
   double t_seen;              // 1 - rel_tol
   int occlusion;
   int32_t* counts;            // [N,4]
@@ -48,11 +48,11 @@ __global__ __launch_bounds__(kCvThreads) void cv_kernel(CvArgs a) {
     const double X = a.points[i * 3], Y = a.points[i * 3 + 1], Z = a.points[i * 3 + 2];
     const double* __restrict__ P = a.proj + c * 12;
     int st = RNB_CULL_OUT_OF_FRAME;
-    if (rc_finite(X) && rc_finite(Y) && rc_finite(Z)) {
+    if (mesh_finite(X) && mesh_finite(Y) && mesh_finite(Z)) {
       const double x = ((P[0] * X + P[1] * Y) + P[2] * Z) + P[3];
       const double y = ((P[4] * X + P[5] * Y) + P[6] * Z) + P[7];
       const double w = ((P[8] * X + P[9] * Y) + P[10] * Z) + P[11];
-      if (rc_finite(w) && w > 0.0) {
+      if (mesh_finite(w) && w > 0.0) {
         const double u = x / w, v = y / w;
         const double pa = u + 0.5, pb = v + 0.5;
         if (pa >= 0.0 && pa < (double)a.W && pb >= 0.0 && pb < (double)a.H) {
@@ -85,34 +85,26 @@ RNB_API int rnb_mesh_view_votes(const double* points, int64_t n_points, const do
                                 int32_t* counts, uint8_t* status, rnb_stream_t stream) {
   using namespace rnb;
   const char* who = "rnb_mesh_view_votes";
-  const int64_t N = n_points, C = n_cameras, E = n_entries, T = n_triangles;
-  if (flags & ~(RNB_MESH_BINS_COVER | RNB_CULL_NO_OCCLUSION)) RNB_FAIL(RNB_E_INVALID, "%s: unknown flag bits 0x%x", who, (unsigned)flags);
-  if (!(flags & RNB_MESH_BINS_COVER))
-    RNB_FAIL(RNB_E_INVALID, "%s: the bins must cover the mesh (RNB_MESH_BINS_COVER): a triangle outside the grid's box sits in a "
-                            "boundary cell the walk does not visit", who);
-  if (N < 0 || N > kRcMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld points outside [0, 2^31 - 1]", who, (long long)N);
-  if (C < 0 || C > kRcMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld cameras outside [0, 2^31 - 1]", who, (long long)C);
-  if (T < 0 || T > kRcMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld triangles outside [0, 2^31 - 1]", who, (long long)T);
-  if (E < 0 || E > kRcMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld entries outside [0, 2^31 - 1]", who, (long long)E);
+  const int64_t N = n_points, C = n_cameras;
+  RNB_TRY(mesh_count(who, N, "points"));
+  RNB_TRY(mesh_count(who, C, "cameras"));
   if (height < 0 || width < 0 || (masks && (height < 1 || width < 1)))
     RNB_FAIL(RNB_E_INVALID, "%s: a frame of %d x %d pixels%s", who, height, width, masks ? " with masks given" : "");
   if (!(rel_tol >= 0.0 && rel_tol < 1.0)) RNB_FAIL(RNB_E_INVALID, "%s: rel_tol = %g outside [0, 1)", who, rel_tol);
   CvArgs a;
-  RNB_TRY(rc_mesh_from_bins(who, bins, &a.mesh));
+  const bool occlusion = !(flags & RNB_CULL_NO_OCCLUSION);
+  RNB_TRY(mesh_binned(who, bins, cell_start, entries, n_entries, corners, n_triangles, flags,
+                      RNB_MESH_BINS_COVER | RNB_CULL_NO_OCCLUSION, true, occlusion && N > 0 && C > 0, &a.mesh));
   if (N == 0) return RNB_OK;
   if (!counts) RNB_FAIL(RNB_E_NULL, "%s: NULL counts", who);
-  const bool occlusion = !(flags & RNB_CULL_NO_OCCLUSION);
   if (C > 0) {
     if (!points || !projections) RNB_FAIL(RNB_E_NULL, "%s: NULL points / projections", who);
     if (occlusion && !eyes) RNB_FAIL(RNB_E_NULL, "%s: NULL eyes", who);
-    if (occlusion && E > 0 && (!cell_start || !entries || !corners)) RNB_FAIL(RNB_E_NULL, "%s: NULL cell_start / entries / corners", who);
   }
   hipStream_t s = (hipStream_t)stream;
   RNB_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)N * 4 * sizeof(int32_t), s));
   if (C == 0) return RNB_OK;
   a.points = points; a.proj = projections; a.eyes = eyes; a.masks = masks; a.N = N; a.C = C; a.H = height; a.W = width;
-  a.mesh.cell_start = (const unsigned long long*)cell_start; a.mesh.entries = entries; a.mesh.E = E; a.mesh.corners = corners;
-  a.mesh.T = T;
   a.t_seen = 1.0 - rel_tol;
   a.occlusion = occlusion ? 1 : 0;
   a.counts = counts; a.status = status;

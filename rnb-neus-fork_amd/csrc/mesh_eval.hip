@@ -2,7 +2,8 @@
 // (rnb_mesh_bins_*, rnb_mesh_closest_points, rnb_mesh_sample_* in include/rnbneus.h; DESIGN.md "Mesh evaluation").
 //
 //   bins     me_bin_kernel<false>   one thread per triangle: range / finiteness check, +1 on every cell its box overlaps
-//            scan (3 kernels)       exclusive 64-bit scan of the n_cells + 1 counts in place -> cell_start, E to counts[0]
+//            scan (3 kernels)       exclusive 64-bit scan of the n_cells + 1 counts in place, an instance of the weight
+//                                   scans of scan.hip.h -> cell_start, E to counts[0]
 //            me_bin_kernel<true>    the same walk again: entries[cell_start[c] + cursor[c]++] = t, and corners[t] (9 doubles)
 //   query    me_closest_kernel      one lane per query: Chebyshev shells of cells around the query's (clamped) cell
 //   samples  me_area_kernel         A_t and the sum of each tile of 1024 triangles
@@ -13,17 +14,19 @@
 // Integer atomics on the cell counters and cursors only; no floating-point atomics anywhere.  The file is compiled with
 // -ffp-contract=off: every product and sum rounds on its own, as the numpy reference evaluates them.
 //
-// THE CELL OF A COORDINATE is me_cell(x) = clamp(floor((x - origin) / cell), 0, dim - 1): subtraction, division by a
-// positive number, floor and clamp are all monotone, so me_cell is monotone in x.  A triangle is entered into the cells
-// [me_cell(lo), me_cell(hi)] of its box per axis.  What the query relies on (k = 1 .. dim - 1, plane(k) = origin + k cell):
-//     me_cell(x) >= k      =>  x >= plane(k) - slack          me_cell(x) <= k - 1  =>  x <= plane(k) + slack
-// with slack = 2^-48 (max |origin| + max dim x cell): floor(fl(fl(x - o) / cell)) >= k gives x - o >= k cell (1 - 2^-52)^2,
+// THE CELL OF A COORDINATE is mesh_cell(x) = clamp(floor((x - origin) / cell), 0, dim - 1) of mesh_common.hip.h:
+// subtraction, division by a positive number, floor and clamp are all monotone, so mesh_cell is monotone in x.  A triangle
+// is entered into the cells [mesh_cell(lo), mesh_cell(hi)] of its box per axis.  What the query relies on
+// (k = 1 .. dim - 1, plane(k) = origin + k cell):
+//     mesh_cell(x) >= k    =>  x >= plane(k) - slack          mesh_cell(x) <= k - 1  =>  x <= plane(k) + slack
+// with slack = mesh_slack(grid) = 2^-48 (max |origin| + max dim x cell): floor(fl(fl(x - o) / cell)) >= k gives
+// x - o >= k cell (1 - 2^-52)^2,
 // and fl(o + fl(k cell)) is within 2^-52 (|o| + 2 k cell) of o + k cell — a few 2^-52 of the grid's magnitude, against 16.
 // Clamping does not touch either implication (k >= 1 on the left, k - 1 <= dim - 2 on the right).
 //
 // WHY THE SHELL SEARCH IS EXACT.  After the shells 0 .. R around the query's cell q, every triangle entered into a cell of
 // the block [q - R, q + R]^3 has been evaluated.  A triangle that was not has, on some axis, its whole box on one side of
-// the block: every one of its points has me_cell >= q + R + 1 or <= q - R - 1 there, hence lies beyond plane(q + R + 1) or
+// the block: every one of its points has mesh_cell >= q + R + 1 or <= q - R - 1 there, hence lies beyond plane(q + R + 1) or
 // plane(q - R) up to slack, hence is at least  lower = min over the sides that still have cells of (|plane - p| - slack)
 // away from the query p (times 1 - 2^-48 for the rounding of the difference and of the square).  The search stops when
 // lower^2 > best, strictly: a triangle at exactly the best distance is always evaluated, so the tie rule (smaller index)
@@ -37,65 +40,30 @@
 // WHY IT CANNOT HANG.  R runs over 0 .. max(dims) - 1, the cell loops over the block clipped to the grid, the entry loop
 // over [cell_start[c], cell_start[c + 1]) clipped to [0, E): every trip count is bounded by the grid dims and E before the
 // loop starts, none depends on the data converging.  A query with a non-finite coordinate leaves before the loops.
-#include "rnb_internal.h"
+#include "mesh_common.hip.h"
+#include "scan.hip.h"
 
 namespace rnb {
 
 constexpr int kMeThreads = 256;
-constexpr int kMeItems = 4;
-constexpr int kMeTile = kMeThreads * kMeItems;
-constexpr int64_t kMeMax = 2147483647;       // V, T, N, n: 31-bit
-constexpr int64_t kMeMaxCells = 1 << 24;
-
-struct MeGrid {
-  double o[3];
-  double cell;
-  int d[3];
-  double slack;
-};
-
-__device__ inline bool me_finite(double a) { return a == a && a <= 1.7976931348623157e308 && a >= -1.7976931348623157e308; }
+constexpr int kMeItems = kScanItems;          // the area scan walks the tiles of the integer scans
+constexpr int kMeTile = kScanTile;
 
 // the far side of the grid's box on axis d: the same expression wherever it is needed
-__device__ inline double me_box_hi(const MeGrid& g, int d) { return g.o[d] + (double)g.d[d] * g.cell; }
-
-__device__ inline int me_cell(double x, double o, double cell, int dim) {
-  const double f = floor((x - o) / cell);
-  if (!(f >= 0.0)) return 0;
-  if (f >= (double)dim) return dim - 1;
-  return (int)f;
-}
-
-// the three corners of triangle t, or false: an index outside [0, V) (checked before it is used) or a non-finite coordinate
-__device__ inline bool me_corners(const double* __restrict__ vertices, int64_t V, const int32_t* __restrict__ tri, int64_t t,
-                                  double (&p)[9]) {
-  const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
-  if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V) return false;
-  const int idx[3] = {a, b, c};
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const double x = vertices[(int64_t)idx[k] * 3 + d];
-      p[k * 3 + d] = x;
-      ok = ok && me_finite(x);
-    }
-  return ok;
-}
+__device__ inline double me_box_hi(const MeshGrid& g, int d) { return g.o[d] + (double)g.d[d] * g.cell; }
 
 // ---- bins -----------------------------------------------------------------------------------------------------------
 
 template <bool kEmit>
 __global__ __launch_bounds__(kMeThreads) void me_bin_kernel(const double* __restrict__ vertices, int64_t V,
-                                                            const int32_t* __restrict__ tri, int64_t T, MeGrid g,
+                                                            const int32_t* __restrict__ tri, int64_t T, MeshGrid g,
                                                             unsigned long long* cell_start, unsigned* cursor, int64_t E,
                                                             int32_t* __restrict__ entries, double* __restrict__ corners,
                                                             unsigned long long* skipped) {
   const int64_t t = (int64_t)blockIdx.x * kMeThreads + threadIdx.x;
   if (t >= T) return;
   double p[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const bool ok = me_corners(vertices, V, tri, t, p);
+  const bool ok = mesh_corners(vertices, V, tri, t, p);
   if (kEmit) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) corners[t * 9 + k] = ok ? p[k] : 0.0;
@@ -106,12 +74,13 @@ __global__ __launch_bounds__(kMeThreads) void me_bin_kernel(const double* __rest
   }
   int lo[3], hi[3];
   bool inside = true;
+  const double slack = mesh_slack(g);
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     const double mn = fmin(p[d], fmin(p[3 + d], p[6 + d])), mx = fmax(p[d], fmax(p[3 + d], p[6 + d]));
-    lo[d] = me_cell(mn, g.o[d], g.cell, g.d[d]);
-    hi[d] = me_cell(mx, g.o[d], g.cell, g.d[d]);
-    inside = inside && mn >= g.o[d] - g.slack && mx <= me_box_hi(g, d) + g.slack;
+    lo[d] = mesh_cell(mn, g.o[d], g.cell, g.d[d]);
+    hi[d] = mesh_cell(mx, g.o[d], g.cell, g.d[d]);
+    inside = inside && mn >= g.o[d] - slack && mx <= me_box_hi(g, d) + slack;
   }
   if (!kEmit && !inside) atomicOr(skipped, 2ull);            // binned all the same, into the boundary cells
   for (int cz = lo[2]; cz <= hi[2]; ++cz)
@@ -127,88 +96,15 @@ __global__ __launch_bounds__(kMeThreads) void me_bin_kernel(const double* __rest
       }
 }
 
-// exclusive prefix of `v` over the 256 threads of the workgroup (thread order); *total = sum over the workgroup
-__device__ inline unsigned long long me_block_scan(unsigned long long v, unsigned long long* total, unsigned long long* red /* [4] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();
-  if (lane == 63) red[wave] = inc;
-  __syncthreads();
-  unsigned long long base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kMeThreads / 64; ++w) {
-    if (w < wave) base += red[w];
-    tot += red[w];
-  }
-  *total = tot;
-  return base + inc - v;
-}
-
-__global__ __launch_bounds__(kMeThreads) void me_scan_sum_kernel(const unsigned long long* __restrict__ a, int64_t n,
-                                                                 unsigned long long* __restrict__ bsum) {
-  __shared__ unsigned long long red[4];
-  const int64_t i0 = (int64_t)blockIdx.x * kMeTile + (int64_t)threadIdx.x * kMeItems;
-  unsigned long long s = 0;
-#pragma unroll
-  for (int k = 0; k < kMeItems; ++k)
-    if (i0 + k < n) s += a[i0 + k];
-  unsigned long long tot;
-  me_block_scan(s, &tot, red);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// exclusive scan in place of the block sums, one workgroup; *total = their sum
-__global__ __launch_bounds__(1024) void me_scan_blocks_kernel(unsigned long long* __restrict__ a, int64_t nblocks,
-                                                              int64_t* __restrict__ total) {
-  __shared__ unsigned long long wsum[16];
-  __shared__ unsigned long long carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < nblocks; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const unsigned long long v = i < nblocks ? a[i] : 0;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned long long t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned long long before = carry_s;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    if (i < nblocks) a[i] = before + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = before + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = (int64_t)carry_s;
-}
-
-__global__ __launch_bounds__(kMeThreads) void me_scan_apply_kernel(unsigned long long* a, int64_t n,
-                                                                   const unsigned long long* __restrict__ boff) {
-  __shared__ unsigned long long red[4];
-  const int64_t i0 = (int64_t)blockIdx.x * kMeTile + (int64_t)threadIdx.x * kMeItems;
-  unsigned long long v[kMeItems], s = 0;
-#pragma unroll
-  for (int k = 0; k < kMeItems; ++k) {
-    v[k] = i0 + k < n ? a[i0 + k] : 0;
-    s += v[k];
-  }
-  unsigned long long tot;
-  unsigned long long pos = boff[blockIdx.x] + me_block_scan(s, &tot, red);
-#pragma unroll
-  for (int k = 0; k < kMeItems; ++k) {
-    if (i0 + k < n) a[i0 + k] = pos;
-    pos += v[k];
-  }
-}
+// the scan of the per-cell counts in place: the emit writes the running sum over the count its weight read
+struct CellCount {
+  const unsigned long long* a;
+  __device__ unsigned long long operator()(int64_t c) const { return a[c]; }
+};
+struct CellStart {
+  unsigned long long* a;
+  __device__ void operator()(int64_t c, unsigned long long, unsigned long long pos) const { a[c] = pos; }
+};
 
 // ---- closest point --------------------------------------------------------------------------------------------------
 
@@ -287,15 +183,11 @@ __device__ inline double me_point_triangle(const double* p, const double* tri, d
 struct MeQuery {
   const double* queries;
   int64_t N;
-  MeGrid g;
-  const unsigned long long* cell_start;
-  const int32_t* entries;
-  int64_t E;
-  const double* corners;
-  int64_t T;
+  BinnedMesh m;
   double* dist2;
   double* closest;
   int32_t* triangle;
+  double slack;        // mesh_slack of the grid
   int covers;          // RNB_MESH_BINS_COVER: every binned triangle lies inside the grid's box
 };
 
@@ -312,7 +204,7 @@ __device__ inline double me_gap2(double gap, double slack) {
   return e > 0.0 ? e * e : 0.0;
 }
 
-__device__ inline void me_visit(const MeQuery& a, const double* p, int64_t c, MeBest& best) {
+__device__ inline void me_visit(const BinnedMesh& a, const double* p, int64_t c, MeBest& best) {
   unsigned long long s = a.cell_start[c], e = a.cell_start[c + 1];
   if (e > (unsigned long long)a.E) e = (unsigned long long)a.E;
   for (; s < e; ++s) {
@@ -339,17 +231,18 @@ __global__ __launch_bounds__(kMeThreads) void me_closest_kernel(MeQuery a) {
   best.d2 = inf;
   best.q[0] = best.q[1] = best.q[2] = nan;
   best.t = -1;
-  const MeGrid& g = a.g;
-  if (!(me_finite(p[0]) && me_finite(p[1]) && me_finite(p[2]))) {
+  const MeshGrid& g = a.m.g;
+  const double slack = a.slack;
+  if (!(mesh_finite(p[0]) && mesh_finite(p[1]) && mesh_finite(p[2]))) {
     best.d2 = nan;
-  } else if (a.E > 0) {
+  } else if (a.m.E > 0) {
     int qc[3];
 #pragma unroll
-    for (int d = 0; d < 3; ++d) qc[d] = me_cell(p[d], g.o[d], g.cell, g.d[d]);
+    for (int d = 0; d < 3; ++d) qc[d] = mesh_cell(p[d], g.o[d], g.cell, g.d[d]);
     double box2[3] = {0.0, 0.0, 0.0};
     if (a.covers) {
 #pragma unroll
-      for (int d = 0; d < 3; ++d) box2[d] = me_gap2(fmax(g.o[d] - p[d], p[d] - me_box_hi(g, d)), g.slack);
+      for (int d = 0; d < 3; ++d) box2[d] = me_gap2(fmax(g.o[d] - p[d], p[d] - me_box_hi(g, d)), slack);
     }
     const int max_r = max(g.d[0], max(g.d[1], g.d[2])) - 1;
     for (int R = 0; R <= max_r; ++R) {
@@ -360,10 +253,10 @@ __global__ __launch_bounds__(kMeThreads) void me_closest_kernel(MeQuery a) {
         for (int cy = y0; cy <= y1; ++cy) {
           const int64_t row = ((int64_t)cz * g.d[1] + cy) * g.d[0];
           if (cz - qc[2] == R || qc[2] - cz == R || cy - qc[1] == R || qc[1] - cy == R) {
-            for (int cx = x0; cx <= x1; ++cx) me_visit(a, p, row + cx, best);
+            for (int cx = x0; cx <= x1; ++cx) me_visit(a.m, p, row + cx, best);
           } else {                                           // (R > 0 here) the two x faces of the shell
-            if (qc[0] - R >= 0) me_visit(a, p, row + qc[0] - R, best);
-            if (qc[0] + R <= g.d[0] - 1) me_visit(a, p, row + qc[0] + R, best);
+            if (qc[0] - R >= 0) me_visit(a.m, p, row + qc[0] - R, best);
+            if (qc[0] + R <= g.d[0] - 1) me_visit(a.m, p, row + qc[0] + R, best);
           }
         }
       // the square of what every triangle outside the block [qc - R, qc + R] is at least away: per face with cells
@@ -373,8 +266,8 @@ __global__ __launch_bounds__(kMeThreads) void me_closest_kernel(MeQuery a) {
       for (int d = 0; d < 3; ++d) {
         const double across = box2[(d + 1) % 3] + box2[(d + 2) % 3];
         const int kh = qc[d] + R + 1, kl = qc[d] - R;
-        if (kh <= g.d[d] - 1) lower2 = fmin(lower2, me_gap2((g.o[d] + (double)kh * g.cell) - p[d], g.slack) + across);
-        if (kl >= 1) lower2 = fmin(lower2, me_gap2(p[d] - (g.o[d] + (double)kl * g.cell), g.slack) + across);
+        if (kh <= g.d[d] - 1) lower2 = fmin(lower2, me_gap2((g.o[d] + (double)kh * g.cell) - p[d], slack) + across);
+        if (kl >= 1) lower2 = fmin(lower2, me_gap2(p[d] - (g.o[d] + (double)kl * g.cell), slack) + across);
       }
       if (lower2 == inf) break;                              // no face has cells behind it: every cell is done
       if (lower2 > best.d2) break;
@@ -397,7 +290,7 @@ __global__ __launch_bounds__(kMeThreads) void me_closest_kernel(MeQuery a) {
 
 __device__ inline double me_area_of(const double* __restrict__ vertices, int64_t V, const int32_t* __restrict__ tri, int64_t t) {
   double p[9];
-  if (!me_corners(vertices, V, tri, t, p)) return 0.0;
+  if (!mesh_corners(vertices, V, tri, t, p)) return 0.0;
   const double u[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, v[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
   double n[3];
   me_cross(u, v, n);
@@ -485,13 +378,6 @@ __global__ __launch_bounds__(kMeThreads) void me_area_apply_kernel(double* __res
     if (i0 + k < T) cum[i0 + k] = off + inc[k];
 }
 
-// the integer mixer of the samples (include/rnbneus.h spells it out): the finaliser of splitmix64
-__device__ inline unsigned long long me_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __device__ inline double me_unit(unsigned long long z) { return (double)(z >> 11) * 1.1102230246251565e-16 /* 2^-53 */; }
 
 struct MeSample {
@@ -515,8 +401,8 @@ __global__ __launch_bounds__(kMeThreads) void me_sample_kernel(MeSample a) {
   const double A = *a.total;
   int64_t t = -1;
   double w[3] = {0, 0, 0}, pt[3] = {0, 0, 0}, nr[3] = {0, 0, 0};
-  if (A > 0.0 && me_finite(A)) {
-    const unsigned long long s = me_mix(a.seed);
+  if (A > 0.0 && mesh_finite(A)) {
+    const unsigned long long s = mesh_mix(a.seed);
     const double xi = me_unit(s);
     double u = (((double)k + xi) * A) / (double)a.n;
     const double below = __longlong_as_double(__double_as_longlong(A) - 1);   // the largest double under A = C_{T-1}
@@ -530,9 +416,9 @@ __global__ __launch_bounds__(kMeThreads) void me_sample_kernel(MeSample a) {
     }
     t = lo;
     double p[9];
-    if (t >= 0 && t < a.T && me_corners(a.vertices, a.V, a.tri, t, p)) {
-      double r1 = me_unit(me_mix(s ^ (2ull * (unsigned long long)k)));
-      double r2 = me_unit(me_mix(s ^ (2ull * (unsigned long long)k + 1ull)));
+    if (t >= 0 && t < a.T && mesh_corners(a.vertices, a.V, a.tri, t, p)) {
+      double r1 = me_unit(mesh_mix(s ^ (2ull * (unsigned long long)k)));
+      double r2 = me_unit(mesh_mix(s ^ (2ull * (unsigned long long)k + 1ull)));
       if (1.0 - r1 < r2) {                                                    // r1 + r2 > 1, decided exactly
         r1 = 1.0 - r1;
         r2 = 1.0 - r2;
@@ -549,7 +435,7 @@ __global__ __launch_bounds__(kMeThreads) void me_sample_kernel(MeSample a) {
       }
       me_cross(e1, e2, nr);
       const double len = sqrt(me_dot(nr, nr));
-      const bool ok = len > 0.0 && me_finite(len);
+      const bool ok = len > 0.0 && mesh_finite(len);
 #pragma unroll
       for (int d = 0; d < 3; ++d) nr[d] = ok ? nr[d] / len : 0.0;
     } else {
@@ -567,54 +453,21 @@ __global__ __launch_bounds__(kMeThreads) void me_sample_kernel(MeSample a) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static int64_t me_blocks(int64_t n) { return (n + kMeTile - 1) / kMeTile; }
 static unsigned me_grid(int64_t n) { return (unsigned)((n + kMeThreads - 1) / kMeThreads); }
 
 struct BinsWs { unsigned* cursor; unsigned long long* bsum; };
 static BinsWs carve_bins(Carver& c, int64_t n_cells) {
   BinsWs w;
   w.cursor = c.take<unsigned>(n_cells);
-  w.bsum = c.take<unsigned long long>(me_blocks(n_cells + 1));
+  w.bsum = c.take<unsigned long long>(scan_blocks(n_cells + 1));
   return w;
 }
 
-static bool host_finite(double x) { return x == x && x <= 1.7976931348623157e308 && x >= -1.7976931348623157e308; }
-
-// the grid of a call, checked: RNB_E_NULL / RNB_E_INVALID before anything else happens
-static int me_bins(const char* who, const rnb_mesh_bins* b, MeGrid* g, int64_t* n_cells) {
-  if (!b) RNB_FAIL(RNB_E_NULL, "%s: NULL bins", who);
-  int64_t n = 1;
-  double omax = 0.0;
-  int dmax = 1;
-  for (int d = 0; d < 3; ++d) {
-    if (!host_finite(b->origin[d])) RNB_FAIL(RNB_E_INVALID, "%s: bins origin is not finite", who);
-    if (b->dims[d] < 1 || b->dims[d] > kMeMaxCells) RNB_FAIL(RNB_E_INVALID, "%s: bins dims[%d] = %d outside [1, 2^24]", who, d, b->dims[d]);
-    n *= b->dims[d];
-    if (n > kMeMaxCells) RNB_FAIL(RNB_E_INVALID, "%s: more than 2^24 cells", who);
-    g->o[d] = b->origin[d];
-    g->d[d] = b->dims[d];
-    omax = fabs(b->origin[d]) > omax ? fabs(b->origin[d]) : omax;
-    dmax = b->dims[d] > dmax ? b->dims[d] : dmax;
-  }
-  if (!(b->cell_size > 0.0) || !host_finite(b->cell_size)) RNB_FAIL(RNB_E_INVALID, "%s: bins cell_size must be positive and finite", who);
-  g->cell = b->cell_size;
-  g->slack = (omax + (double)dmax * b->cell_size) * 3.552713678800501e-15;   // 2^-48 of the grid's magnitude
-  if (!host_finite(g->slack)) RNB_FAIL(RNB_E_INVALID, "%s: bins origin + dims x cell_size overflows", who);
-  *n_cells = n;
-  return RNB_OK;
-}
-
-static int me_sizes(const char* who, int64_t V, int64_t T) {
-  if (V < 0 || T < 0 || V > kMeMax || T > kMeMax)
-    RNB_FAIL(RNB_E_INVALID, "%s: %lld vertices / %lld triangles outside [0, 2^31 - 1]", who, (long long)V, (long long)T);
-  return RNB_OK;
-}
-
 static int me_bins_check(const char* who, const double* vertices, int64_t V, const int32_t* triangles, int64_t T,
-                         const rnb_mesh_bins* bins, void* workspace, size_t workspace_bytes, const void* cell_start, MeGrid* g,
+                         const rnb_mesh_bins* bins, void* workspace, size_t workspace_bytes, const void* cell_start, MeshGrid* g,
                          int64_t* n_cells, BinsWs* w) {
-  RNB_TRY(me_sizes(who, V, T));
-  RNB_TRY(me_bins(who, bins, g, n_cells));
+  RNB_TRY(mesh_sizes(who, V, T));
+  RNB_TRY(mesh_grid_from_bins(who, bins, g, n_cells));
   if ((T > 0 && !triangles) || (V > 0 && T > 0 && !vertices) || !cell_start) RNB_FAIL(RNB_E_NULL, "%s: NULL vertices / triangles / cell_start", who);
   if (!workspace) RNB_FAIL(RNB_E_NULL, "%s: NULL workspace", who);
   Carver cv(workspace, workspace_bytes);
@@ -626,7 +479,7 @@ static int me_bins_check(const char* who, const double* vertices, int64_t V, con
 struct SampleWs { double* bsum; };
 static SampleWs carve_sample(Carver& c, int64_t T) {
   SampleWs w;
-  w.bsum = c.take<double>(me_blocks(T));
+  w.bsum = c.take<double>(scan_blocks(T));
   return w;
 }
 
@@ -637,7 +490,7 @@ static SampleWs carve_sample(Carver& c, int64_t T) {
 RNB_API int rnb_mesh_bins_workspace_bytes(int64_t n_cells, int64_t* bytes) {
   using namespace rnb;
   if (!bytes) RNB_FAIL(RNB_E_NULL, "rnb_mesh_bins_workspace_bytes: NULL");
-  if (n_cells < 1 || n_cells > kMeMaxCells) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_bins_workspace_bytes: %lld cells outside [1, 2^24]", (long long)n_cells);
+  if (n_cells < 1 || n_cells > kMeshMaxCells) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_bins_workspace_bytes: %lld cells outside [1, 2^24]", (long long)n_cells);
   Carver c(nullptr, 0);
   carve_bins(c, n_cells);
   *bytes = (int64_t)c.off;
@@ -649,7 +502,7 @@ RNB_API int rnb_mesh_bins_count(const double* vertices, int64_t n_vertices, cons
                                 int64_t* counts, rnb_stream_t stream) {
   using namespace rnb;
   const int64_t V = n_vertices, T = n_triangles;
-  MeGrid g;
+  MeshGrid g;
   int64_t n_cells;
   BinsWs w;
   RNB_TRY(me_bins_check("rnb_mesh_bins_count", vertices, V, triangles, T, bins, workspace, workspace_bytes, cell_start, &g, &n_cells, &w));
@@ -662,12 +515,14 @@ RNB_API int rnb_mesh_bins_count(const double* vertices, int64_t n_vertices, cons
   hipLaunchKernelGGL(me_bin_kernel<false>, dim3(me_grid(T)), dim3(kMeThreads), 0, s, vertices, V, triangles, T, g, cs,
                      (unsigned*)nullptr, (int64_t)0, (int32_t*)nullptr, (double*)nullptr, (unsigned long long*)(counts + 1));
   RNB_CHECK_LAUNCH();
-  const int64_t n = n_cells + 1, nb = me_blocks(n);
-  hipLaunchKernelGGL(me_scan_sum_kernel, dim3((unsigned)nb), dim3(kMeThreads), 0, s, cs, n, w.bsum);
+  const int64_t n = n_cells + 1, nb = scan_blocks(n);
+  using u64 = unsigned long long;
+  hipLaunchKernelGGL((scan_sum_kernel<u64, CellCount>), dim3((unsigned)nb), dim3(kScanThreads), 0, s, CellCount{cs}, n, w.bsum);
   RNB_CHECK_LAUNCH();
-  hipLaunchKernelGGL(me_scan_blocks_kernel, dim3(1), dim3(1024), 0, s, w.bsum, nb, counts);
+  hipLaunchKernelGGL(scan_block_sums_kernel<u64>, dim3(1), dim3(1024), 0, s, w.bsum, nb, (u64*)nullptr, (int64_t)0, 1, counts);
   RNB_CHECK_LAUNCH();
-  hipLaunchKernelGGL(me_scan_apply_kernel, dim3((unsigned)nb), dim3(kMeThreads), 0, s, cs, n, w.bsum);
+  hipLaunchKernelGGL((scan_emit_kernel<u64, CellCount, CellStart>), dim3((unsigned)nb), dim3(kScanThreads), 0, s, CellCount{cs},
+                     CellStart{cs}, n, (const u64*)w.bsum);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -677,11 +532,11 @@ RNB_API int rnb_mesh_bins_emit(const double* vertices, int64_t n_vertices, const
                                int64_t n_entries, int32_t* entries, double* corners, rnb_stream_t stream) {
   using namespace rnb;
   const int64_t V = n_vertices, T = n_triangles, E = n_entries;
-  MeGrid g;
+  MeshGrid g;
   int64_t n_cells;
   BinsWs w;
   RNB_TRY(me_bins_check("rnb_mesh_bins_emit", vertices, V, triangles, T, bins, workspace, workspace_bytes, cell_start, &g, &n_cells, &w));
-  if (E < 0 || E > kMeMax) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_bins_emit: %lld entries outside [0, 2^31 - 1]", (long long)E);
+  RNB_TRY(mesh_count("rnb_mesh_bins_emit", E, "entries"));
   if ((E > 0 && !entries) || (T > 0 && !corners)) RNB_FAIL(RNB_E_NULL, "rnb_mesh_bins_emit: NULL entries / corners");
   if (T == 0) return RNB_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -697,20 +552,17 @@ RNB_API int rnb_mesh_closest_points(const double* queries, int64_t n_queries, co
                                     int64_t n_triangles, int32_t flags, double* dist2, double* closest, int32_t* triangle,
                                     rnb_stream_t stream) {
   using namespace rnb;
-  const int64_t N = n_queries, E = n_entries, T = n_triangles;
-  if (flags & ~RNB_MESH_BINS_COVER) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_closest_points: unknown flag bits 0x%x", (unsigned)flags);
-  if (N < 0 || N > kMeMax) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_closest_points: %lld queries outside [0, 2^31 - 1]", (long long)N);
-  RNB_TRY(me_sizes("rnb_mesh_closest_points", 0, T));
-  if (E < 0 || E > kMeMax) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_closest_points: %lld entries outside [0, 2^31 - 1]", (long long)E);
-  MeGrid g;
-  int64_t n_cells;
-  RNB_TRY(me_bins("rnb_mesh_closest_points", bins, &g, &n_cells));
+  const char* who = "rnb_mesh_closest_points";
+  const int64_t N = n_queries;
+  RNB_TRY(mesh_count(who, N, "queries"));
+  MeQuery a;
+  RNB_TRY(mesh_binned(who, bins, cell_start, entries, n_entries, corners, n_triangles, flags, RNB_MESH_BINS_COVER, false, N > 0, &a.m));
   if (N == 0) return RNB_OK;
-  if (!queries) RNB_FAIL(RNB_E_NULL, "rnb_mesh_closest_points: NULL queries");
-  if (E > 0 && (!cell_start || !entries || !corners)) RNB_FAIL(RNB_E_NULL, "rnb_mesh_closest_points: NULL cell_start / entries / corners");
-  if (!dist2 && !closest && !triangle) RNB_FAIL(RNB_E_NULL, "rnb_mesh_closest_points: every output is NULL");
-  const MeQuery a{queries, N, g, (const unsigned long long*)cell_start, entries, E, corners, T, dist2, closest, triangle,
-                  (flags & RNB_MESH_BINS_COVER) ? 1 : 0};
+  if (!queries) RNB_FAIL(RNB_E_NULL, "%s: NULL queries", who);
+  if (!dist2 && !closest && !triangle) RNB_FAIL(RNB_E_NULL, "%s: every output is NULL", who);
+  a.queries = queries; a.N = N; a.dist2 = dist2; a.closest = closest; a.triangle = triangle;
+  a.slack = mesh_slack(a.m.g);
+  a.covers = (flags & RNB_MESH_BINS_COVER) ? 1 : 0;
   hipLaunchKernelGGL(me_closest_kernel, dim3(me_grid(N)), dim3(kMeThreads), 0, (hipStream_t)stream, a);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
@@ -719,7 +571,7 @@ RNB_API int rnb_mesh_closest_points(const double* queries, int64_t n_queries, co
 RNB_API int rnb_mesh_sample_workspace_bytes(int64_t n_triangles, int64_t* bytes) {
   using namespace rnb;
   if (!bytes) RNB_FAIL(RNB_E_NULL, "rnb_mesh_sample_workspace_bytes: NULL");
-  RNB_TRY(me_sizes("rnb_mesh_sample_workspace_bytes", 0, n_triangles));
+  RNB_TRY(mesh_sizes("rnb_mesh_sample_workspace_bytes", 0, n_triangles));
   Carver c(nullptr, 0);
   carve_sample(c, n_triangles);
   *bytes = (int64_t)c.off;
@@ -730,7 +582,7 @@ RNB_API int rnb_mesh_sample_areas(const double* vertices, int64_t n_vertices, co
                                   void* workspace, size_t workspace_bytes, double* cum_area, double* total, rnb_stream_t stream) {
   using namespace rnb;
   const int64_t V = n_vertices, T = n_triangles;
-  RNB_TRY(me_sizes("rnb_mesh_sample_areas", V, T));
+  RNB_TRY(mesh_sizes("rnb_mesh_sample_areas", V, T));
   if (!total || (T > 0 && (!triangles || !cum_area)) || (V > 0 && T > 0 && !vertices))
     RNB_FAIL(RNB_E_NULL, "rnb_mesh_sample_areas: NULL vertices / triangles / cum_area / total");
   Carver cv(workspace, workspace_bytes);
@@ -742,7 +594,7 @@ RNB_API int rnb_mesh_sample_areas(const double* vertices, int64_t n_vertices, co
     RNB_CHECK_HIP(hipMemsetAsync(total, 0, sizeof(double), s));
     return RNB_OK;
   }
-  const int64_t nb = me_blocks(T);
+  const int64_t nb = scan_blocks(T);
   hipLaunchKernelGGL(me_area_kernel, dim3((unsigned)nb), dim3(kMeThreads), 0, s, vertices, V, triangles, T, cum_area, w.bsum);
   RNB_CHECK_LAUNCH();
   hipLaunchKernelGGL(me_area_blocks_kernel, dim3(1), dim3(1024), 0, s, w.bsum, nb, total);
@@ -757,8 +609,8 @@ RNB_API int rnb_mesh_sample_surface(const double* vertices, int64_t n_vertices, 
                                     int32_t* triangle, double* bary, double* normal, rnb_stream_t stream) {
   using namespace rnb;
   const int64_t V = n_vertices, T = n_triangles, n = n_samples;
-  RNB_TRY(me_sizes("rnb_mesh_sample_surface", V, T));
-  if (n < 0 || n > kMeMax) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_sample_surface: %lld samples outside [0, 2^31 - 1]", (long long)n);
+  RNB_TRY(mesh_sizes("rnb_mesh_sample_surface", V, T));
+  RNB_TRY(mesh_count("rnb_mesh_sample_surface", n, "samples"));
   if (n > 0 && T == 0) RNB_FAIL(RNB_E_INVALID, "rnb_mesh_sample_surface: samples of a mesh without triangles");
   if (n == 0) return RNB_OK;
   if (!vertices || !triangles || !cum_area || !total) RNB_FAIL(RNB_E_NULL, "rnb_mesh_sample_surface: NULL vertices / triangles / cum_area / total");

@@ -18,7 +18,7 @@ struct RcArgs {
   const double* t_min;
   const double* t_max;
   int64_t N;
-  RcMesh mesh;
+  BinnedMesh mesh;
   double* t;
   int32_t* triangle;
   double* bary;
@@ -51,23 +51,14 @@ RNB_API int rnb_mesh_raycast(const double* origins, const double* directions, co
                              int32_t* triangle, double* bary, rnb_stream_t stream) {
   using namespace rnb;
   const char* who = "rnb_mesh_raycast";
-  const int64_t N = n_rays, E = n_entries, T = n_triangles;
-  if (flags & ~RNB_MESH_BINS_COVER) RNB_FAIL(RNB_E_INVALID, "%s: unknown flag bits 0x%x", who, (unsigned)flags);
-  if (!(flags & RNB_MESH_BINS_COVER))
-    RNB_FAIL(RNB_E_INVALID, "%s: the bins must cover the mesh (RNB_MESH_BINS_COVER): a triangle outside the grid's box sits in a "
-                            "boundary cell the walk does not visit", who);
-  if (N < 0 || N > kRcMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld rays outside [0, 2^31 - 1]", who, (long long)N);
-  if (T < 0 || T > kRcMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld triangles outside [0, 2^31 - 1]", who, (long long)T);
-  if (E < 0 || E > kRcMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld entries outside [0, 2^31 - 1]", who, (long long)E);
+  const int64_t N = n_rays;
+  RNB_TRY(mesh_count(who, N, "rays"));
   RcArgs a;
-  RNB_TRY(rc_mesh_from_bins(who, bins, &a.mesh));
+  RNB_TRY(mesh_binned(who, bins, cell_start, entries, n_entries, corners, n_triangles, flags, RNB_MESH_BINS_COVER, true, N > 0, &a.mesh));
   if (N == 0) return RNB_OK;
   if (!origins || !directions) RNB_FAIL(RNB_E_NULL, "%s: NULL origins / directions", who);
-  if (E > 0 && (!cell_start || !entries || !corners)) RNB_FAIL(RNB_E_NULL, "%s: NULL cell_start / entries / corners", who);
   if (!t && !triangle && !bary) RNB_FAIL(RNB_E_NULL, "%s: every output is NULL", who);
   a.origins = origins; a.directions = directions; a.t_min = t_min; a.t_max = t_max; a.N = N;
-  a.mesh.cell_start = (const unsigned long long*)cell_start; a.mesh.entries = entries; a.mesh.E = E; a.mesh.corners = corners;
-  a.mesh.T = T;
   a.t = t; a.triangle = triangle; a.bary = bary;
   hipLaunchKernelGGL(rc_kernel, dim3((unsigned)((N + kRcThreads - 1) / kRcThreads)), dim3(kRcThreads), 0, (hipStream_t)stream, a);
   RNB_CHECK_LAUNCH();

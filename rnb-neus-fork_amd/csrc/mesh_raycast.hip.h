@@ -17,17 +17,18 @@
 //     pad = 4096 x 2^-52 x S      and      tau = pad / |d_m|   (pad as a ray parameter)
 // layer i stands for the m-coordinates [plane(i) - pad, plane(i + 1) + pad], plane(k) = origin + k cell.  Its parameter
 // interval [ta, tb] is cut to [t_min - tau, t_max + tau]; the other two coordinates u, v are evaluated at ta and at tb,
-// the interval between the two values is widened by pad and mapped to cells with the clamped, monotone rc_cell (the
-// me_cell of mesh_eval.hip).  |d_u|, |d_v| <= |d_m|: the ray moves at most one cell sideways per layer, so a layer costs
+// the interval between the two values is widened by pad and mapped to cells with the clamped, monotone mesh_cell of
+// mesh_common.hip.h.  |d_u|, |d_v| <= |d_m|: the ray moves at most one cell sideways per layer, so a layer costs
 // at most 2 cells per axis, 3 where the widening crosses a face.  Every entry of those cells is tested.
 //
 // WHY NO HIT IS SKIPPED.  Take a hit as the pair test computes it and let l = (U, V, W) / det as real numbers: l >= 0,
 // sum 1, so P = l0 A + l1 B + l2 C is a point of the triangle, inside its box.  The triangle is entered in the cell
-// (rc_cell(P_m), rc_cell(P_u), rc_cell(P_v)), because its cell range per axis is that of its box and rc_cell is monotone.
+// (mesh_cell(P_m), mesh_cell(P_u), mesh_cell(P_v)), because its cell range per axis is that of its box and mesh_cell is
+// monotone.
 //   * Along m: t is the l-weighted mean of Az = fl(Sz fl(A_m - o_m)) and its kin up to the rounding of three products,
 //     two sums and a division, so o_m + t d_m = P_m up to 16 x 2^-52 S, and t* = (P_m - o_m) / d_m is within
-//     16 x 2^-52 S / |d_m| of t.  rc_cell(x) = i implies plane(i) - slack <= x <= plane(i + 1) + slack with
-//     slack = 2^-48 |grid| (mesh_eval.hip shows it), so t* lies in the interval of layer i = rc_cell(P_m), and inside
+//     16 x 2^-52 S / |d_m| of t.  mesh_cell(x) = i implies plane(i) - slack <= x <= plane(i + 1) + slack with
+//     slack = 2^-48 |grid| (mesh_eval.hip shows it), so t* lies in the interval of layer i = mesh_cell(P_m), and inside
 //     [t_min - tau, t_max + tau] because t is inside [t_min, t_max].
 //   * Across: P_u - (o_u + t* d_u) = sum of l_k x (the exact sheared x of corner k) = sum of l_k A'_k,x + 8 x 2^-52 S,
 //     and sum of l_k A'_k = (eU A' + eV B' + eW C') / det, where eU .. are the rounding errors of the computed edge
@@ -50,29 +51,14 @@
 // WHY IT CANNOT HANG OR READ OUT OF BOUNDS.  The layer loop runs over a clamped range of [0, dim_m), the cell loops
 // over clamped ranges of [0, dim_u) x [0, dim_v), the entry loop over [cell_start[c], cell_start[c + 1]) cut to
 // [0, E), and a triangle index outside [0, T) is passed over: every trip count is fixed by the dims and E before its
-// loop starts, and every index is clamped before it is used, whatever the arithmetic in front of it produced (rc_cell
+// loop starts, and every index is clamped before it is used, whatever the arithmetic in front of it produced (mesh_cell
 // maps NaN to cell 0).  A ray with a non-finite origin or direction, a zero direction or a NaN bound leaves before the walk.
 #pragma once
-#include "rnb_internal.h"
+#include "mesh_common.hip.h"
 
 namespace rnb {
 
-constexpr int64_t kRcMax = 2147483647;       // N, E, T: 31-bit
-constexpr int64_t kRcMaxCells = 1 << 24;
 constexpr double kRcPad = 9.094947017729282e-13;   // 4096 x 2^-52 = 2^-40
-
-// the binned mesh a ray is cast at: the grid, the bins of rnb_mesh_bins_count / _emit and the corners [T,9]
-struct RcMesh {
-  double go[3];        // the grid: origin, cubic cell size, cells per axis, |grid|
-  double cell;
-  int gd[3];
-  double gmag;
-  const unsigned long long* cell_start;
-  const int32_t* entries;
-  int64_t E;
-  const double* corners;
-  int64_t T;
-};
 
 // what the pair test needs of a ray: the axis permutation, the translated origin, the shear
 struct RcRay {
@@ -88,21 +74,11 @@ struct RcBest {
   double U, V, W, det;
 };
 
-__device__ inline bool rc_finite(double a) { return a == a && a <= 1.7976931348623157e308 && a >= -1.7976931348623157e308; }
-
 template <class T>
 __device__ inline T rc_pick(T a0, T a1, T a2, int k) { return k == 0 ? a0 : (k == 1 ? a1 : a2); }
 
-// mesh_eval.hip's me_cell: clamp(floor((x - origin) / cell), 0, dim - 1), monotone in x, NaN -> 0
-__device__ inline int rc_cell(double x, double o, double cell, int dim) {
-  const double f = floor((x - o) / cell);
-  if (!(f >= 0.0)) return 0;
-  if (f >= (double)dim) return dim - 1;
-  return (int)f;
-}
-
 // every entry of cell c against the ray: tests/mesh_raycast_ref.py's ray_triangle, operation for operation
-__device__ inline void rc_visit(const RcMesh& a, const RcRay& r, int64_t c, RcBest& best) {
+__device__ inline void rc_visit(const BinnedMesh& a, const RcRay& r, int64_t c, RcBest& best) {
   unsigned long long s = a.cell_start[c], e = a.cell_start[c + 1];
   if (e > (unsigned long long)a.E) e = (unsigned long long)a.E;
   for (; s < e; ++s) {
@@ -131,7 +107,7 @@ __device__ inline void rc_visit(const RcMesh& a, const RcRay& r, int64_t c, RcBe
 // The first hit of the ray o + t d, t_min <= t <= t_max, with the mesh: best.t = +inf and best.tri = -1 when nothing is
 // met (always so with E == 0), best.t = NaN for a ray that cannot be cast (a non-finite origin or direction, a zero
 // direction, a NaN bound).
-__device__ inline RcBest rc_first_hit(const RcMesh& a, double o0, double o1, double o2, double d0, double d1, double d2,
+__device__ inline RcBest rc_first_hit(const BinnedMesh& a, double o0, double o1, double o2, double d0, double d1, double d2,
                                       double t_min, double t_max) {
   const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
   RcRay r;
@@ -141,7 +117,7 @@ __device__ inline RcBest rc_first_hit(const RcMesh& a, double o0, double o1, dou
   best.t = inf;
   best.tri = -1;
   best.U = best.V = best.W = best.det = nan;
-  const bool valid = rc_finite(o0) && rc_finite(o1) && rc_finite(o2) && rc_finite(d0) && rc_finite(d1) && rc_finite(d2) &&
+  const bool valid = mesh_finite(o0) && mesh_finite(o1) && mesh_finite(o2) && mesh_finite(d0) && mesh_finite(d1) && mesh_finite(d2) &&
                      (d0 != 0.0 || d1 != 0.0 || d2 != 0.0) && r.t_min == r.t_min && r.t_max == r.t_max;
   if (!valid) {
     best.t = nan;
@@ -162,26 +138,26 @@ __device__ inline RcBest rc_first_hit(const RcMesh& a, double o0, double o1, dou
     r.ox = rc_pick(o0, o1, o2, kx); r.oy = rc_pick(o0, o1, o2, ky); r.oz = rc_pick(o0, o1, o2, kz);
     r.Sx = du / dm; r.Sy = dv / dm; r.Sz = 1.0 / dm;
     // the grid along (u, v, m) = (kx, ky, kz)
-    const double gu = rc_pick(a.go[0], a.go[1], a.go[2], kx), gv = rc_pick(a.go[0], a.go[1], a.go[2], ky),
-                 gm = rc_pick(a.go[0], a.go[1], a.go[2], kz);
-    const int nu = rc_pick(a.gd[0], a.gd[1], a.gd[2], kx), nv = rc_pick(a.gd[0], a.gd[1], a.gd[2], ky),
-              nm = rc_pick(a.gd[0], a.gd[1], a.gd[2], kz);
-    const int64_t st1 = a.gd[0], st2 = (int64_t)a.gd[0] * a.gd[1];
+    const double gu = rc_pick(a.g.o[0], a.g.o[1], a.g.o[2], kx), gv = rc_pick(a.g.o[0], a.g.o[1], a.g.o[2], ky),
+                 gm = rc_pick(a.g.o[0], a.g.o[1], a.g.o[2], kz);
+    const int nu = rc_pick(a.g.d[0], a.g.d[1], a.g.d[2], kx), nv = rc_pick(a.g.d[0], a.g.d[1], a.g.d[2], ky),
+              nm = rc_pick(a.g.d[0], a.g.d[1], a.g.d[2], kz);
+    const int64_t st1 = a.g.d[0], st2 = (int64_t)a.g.d[0] * a.g.d[1];
     const int64_t su = rc_pick((int64_t)1, st1, st2, kx), sv = rc_pick((int64_t)1, st1, st2, ky), sm = rc_pick((int64_t)1, st1, st2, kz);
-    const double pad = (a.gmag + fmax(fabs(o0), fmax(fabs(o1), fabs(o2)))) * kRcPad;
+    const double cell = a.g.cell, pad = (a.g.mag + fmax(fabs(o0), fmax(fabs(o1), fabs(o2)))) * kRcPad;
     const double tau = pad * fabs(r.Sz);
     const double tlo = r.t_min - tau, thi = r.t_max + tau;
-    const double ulo_box = gu - pad, uhi_box = (gu + (double)nu * a.cell) + pad;
-    const double vlo_box = gv - pad, vhi_box = (gv + (double)nv * a.cell) + pad;
+    const double ulo_box = gu - pad, uhi_box = (gu + (double)nu * cell) + pad;
+    const double vlo_box = gv - pad, vhi_box = (gv + (double)nv * cell) + pad;
     const bool up = dm > 0.0;
     // the layers the cut parameter range can reach (the cut inside the loop is what decides; this only shortens it)
     const double m_first = r.oz + tlo * dm, m_last = r.oz + thi * dm;
-    const int first = rc_cell(up ? m_first - 2.0 * pad : m_first + 2.0 * pad, gm, a.cell, nm);
-    const int last = rc_cell(up ? m_last + 2.0 * pad : m_last - 2.0 * pad, gm, a.cell, nm);
+    const int first = mesh_cell(up ? m_first - 2.0 * pad : m_first + 2.0 * pad, gm, cell, nm);
+    const int last = mesh_cell(up ? m_last + 2.0 * pad : m_last - 2.0 * pad, gm, cell, nm);
     const int step = up ? 1 : -1;
     const int trips = (last - first) * step + 1;              // <= nm; none when the range is behind the ray
     for (int k = 0, layer = first; k < trips; ++k, layer += step) {
-      const double p0 = (gm + (double)layer * a.cell) - pad, p1 = (gm + (double)(layer + 1) * a.cell) + pad;
+      const double p0 = (gm + (double)layer * cell) - pad, p1 = (gm + (double)(layer + 1) * cell) + pad;
       double ta = ((up ? p0 : p1) - r.oz) * r.Sz, tb = ((up ? p1 : p0) - r.oz) * r.Sz;
       if (ta - tau > best.t) break;
       ta = fmax(ta, tlo);
@@ -190,38 +166,13 @@ __device__ inline RcBest rc_first_hit(const RcMesh& a, double o0, double o1, dou
       const double ua = r.ox + ta * du, ub = r.ox + tb * du, va = r.oy + ta * dv, vb = r.oy + tb * dv;
       const double ulo = fmin(ua, ub) - pad, uhi = fmax(ua, ub) + pad, vlo = fmin(va, vb) - pad, vhi = fmax(va, vb) + pad;
       if (uhi < ulo_box || ulo > uhi_box || vhi < vlo_box || vlo > vhi_box) continue;
-      const int cu0 = rc_cell(ulo, gu, a.cell, nu), cu1 = rc_cell(uhi, gu, a.cell, nu);
-      const int cv0 = rc_cell(vlo, gv, a.cell, nv), cv1 = rc_cell(vhi, gv, a.cell, nv);
+      const int cu0 = mesh_cell(ulo, gu, cell, nu), cu1 = mesh_cell(uhi, gu, cell, nu);
+      const int cv0 = mesh_cell(vlo, gv, cell, nv), cv1 = mesh_cell(vhi, gv, cell, nv);
       for (int cv = cv0; cv <= cv1; ++cv)
         for (int cu = cu0; cu <= cu1; ++cu) rc_visit(a, r, (int64_t)layer * sm + (int64_t)cv * sv + (int64_t)cu * su, best);
     }
   }
   return best;
-}
-
-static bool rc_host_finite(double x) { return x == x && x <= 1.7976931348623157e308 && x >= -1.7976931348623157e308; }
-
-// The checks of the bins every call that casts makes before it launches, and the grid of `m` filled from them.
-static int rc_mesh_from_bins(const char* who, const rnb_mesh_bins* bins, RcMesh* m) {
-  if (!bins) RNB_FAIL(RNB_E_NULL, "%s: NULL bins", who);
-  int64_t n_cells = 1;
-  double omax = 0.0;
-  int dmax = 1;
-  for (int d = 0; d < 3; ++d) {
-    if (!rc_host_finite(bins->origin[d])) RNB_FAIL(RNB_E_INVALID, "%s: bins origin is not finite", who);
-    if (bins->dims[d] < 1 || bins->dims[d] > kRcMaxCells) RNB_FAIL(RNB_E_INVALID, "%s: bins dims[%d] = %d outside [1, 2^24]", who, d, bins->dims[d]);
-    n_cells *= bins->dims[d];
-    if (n_cells > kRcMaxCells) RNB_FAIL(RNB_E_INVALID, "%s: more than 2^24 cells", who);
-    m->go[d] = bins->origin[d];
-    m->gd[d] = bins->dims[d];
-    omax = fabs(bins->origin[d]) > omax ? fabs(bins->origin[d]) : omax;
-    dmax = bins->dims[d] > dmax ? bins->dims[d] : dmax;
-  }
-  if (!(bins->cell_size > 0.0) || !rc_host_finite(bins->cell_size)) RNB_FAIL(RNB_E_INVALID, "%s: bins cell_size must be positive and finite", who);
-  m->cell = bins->cell_size;
-  m->gmag = omax + (double)dmax * bins->cell_size;
-  if (!rc_host_finite(m->gmag * 3.552713678800501e-15)) RNB_FAIL(RNB_E_INVALID, "%s: bins origin + dims x cell_size overflows", who);
-  return RNB_OK;
 }
 
 }  // namespace rnb

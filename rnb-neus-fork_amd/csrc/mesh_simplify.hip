@@ -14,8 +14,9 @@
 //          sp_dedupe_kernel      the non-degenerate triangles enter the triple table
 //          sp_survive_kernel    a triangle survives when its slot holds its own index; its three clusters are used
 //          flag scans            "v leads a used cluster" and "t survives" -> V', T' and the block offsets
-//   emit   the same two flags with the block offsets (mesh_scan.hip.h): cluster -> output index, representatives'
+//   emit   the same two flags with the block offsets (scan.hip.h): cluster -> output index, representatives'
 //          coordinates and indices, remapped triangles, input index of every surviving triangle, cluster of every vertex
+//   The index guard, the finiteness predicate, the mixer of the two tables and the size check: mesh_common.hip.h.
 //
 // Integer atomics only (compare-and-swap, min, add, or): every result is a function of the input alone, whatever the
 // schedule, and equals the numpy reference bit for bit.  The file is compiled with -ffp-contract=off: every product and
@@ -41,14 +42,14 @@
 // Termination.  Fewer than cap / 2 + 1 slots are ever filled (one per distinct key), so every walk meets an empty slot
 // or its own key after at most cap steps; the loop is bounded by cap all the same, and a walk that used them up would set
 // bit 2 of counts[4] and return.  No thread waits for another: there is no spin, no lock.
-#include "rnb_internal.h"
-#include "mesh_scan.hip.h"
+#include "mesh_common.hip.h"
+#include "scan.hip.h"
 
 namespace rnb {
 
 constexpr unsigned kSpEmpty = 0xffffffffu;
 constexpr unsigned long long kSpNoKey = ~0ull;
-constexpr int64_t kSpMax = 2147483647;   // V and T are 31-bit
+constexpr int kMkThreads = kScanThreads;   // the block of every kernel here
 enum { SP_BAD_INDEX = 1, SP_BAD_VERTEX = 2, SP_TABLE_FULL = 4 };
 
 struct SpGrid {
@@ -104,12 +105,10 @@ static SpWs sp_carve(Carver& c, int64_t V, int64_t T) {
   w.tslot = c.take<unsigned>(T);
   w.vtab = c.take<unsigned>((int64_t)w.cap_v);
   w.ttab = c.take<unsigned>((int64_t)w.cap_t);
-  w.bsum_v = c.take<unsigned>(mk_pad64(mk_blocks(V)));
-  w.bsum_t = c.take<unsigned>(mk_pad64(mk_blocks(T)));
+  w.bsum_v = c.take<unsigned>(scan_pad64(scan_blocks(V)));
+  w.bsum_t = c.take<unsigned>(scan_pad64(scan_blocks(T)));
   return w;
 }
-
-__device__ inline bool sp_finite(double a) { return a == a && a <= 1.7976931348623157e308 && a >= -1.7976931348623157e308; }
 
 // order-preserving map double -> uint64 (numbers only) and back
 __device__ inline unsigned long long sp_okey(double x) {
@@ -118,14 +117,6 @@ __device__ inline unsigned long long sp_okey(double x) {
 }
 __device__ inline double sp_unokey(unsigned long long k) {
   return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// the finaliser of splitmix64
-__device__ inline unsigned long long sp_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 // one add of the number of lanes with `pred` per wave
@@ -160,7 +151,7 @@ __global__ __launch_bounds__(kMkThreads) void sp_origin_kernel(const double* __r
   const int64_t v = (int64_t)blockIdx.x * kMkThreads + threadIdx.x;
   if (v < V) {
     const double x = vertices[v * 3], y = vertices[v * 3 + 1], z = vertices[v * 3 + 2];
-    if (sp_finite(x) && sp_finite(y) && sp_finite(z)) {
+    if (mesh_finite(x) && mesh_finite(y) && mesh_finite(z)) {
       atomicMin(&lmin[0], sp_okey(x));
       atomicMin(&lmin[1], sp_okey(y));
       atomicMin(&lmin[2], sp_okey(z));
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(kMkThreads) void sp_vertex_key_kernel(const double*
     const double x = vertices[v * 3 + d];
     int i = 0;
     double f;
-    ok = ok && sp_finite(x) && sp_cell(x, g.org(d), g.h, &i, &f);
+    ok = ok && mesh_finite(x) && sp_cell(x, g.org(d), g.h, &i, &f);
     key |= (unsigned long long)(unsigned)(i + 1048576) << (21 * d);
   }
   w.key[v] = ok ? key : kSpNoKey;
@@ -210,7 +201,7 @@ __global__ __launch_bounds__(kMkThreads) void sp_vertex_key_kernel(const double*
 __device__ inline bool sp_valid(const int32_t* __restrict__ tri, int64_t t, int64_t V, const unsigned long long* key,
                                 int* a, int* b, int* c, unsigned* why) {
   *a = tri[t * 3]; *b = tri[t * 3 + 1]; *c = tri[t * 3 + 2];
-  if (*a < 0 || *b < 0 || *c < 0 || *a >= V || *b >= V || *c >= V) { *why = SP_BAD_INDEX; return false; }
+  if (!mesh_indices_ok(*a, *b, *c, V)) { *why = SP_BAD_INDEX; return false; }
   if (key[*a] == kSpNoKey || key[*b] == kSpNoKey || key[*c] == kSpNoKey) { *why = SP_BAD_VERTEX; return false; }
   return true;
 }
@@ -234,7 +225,7 @@ __global__ __launch_bounds__(kMkThreads) void sp_cluster_kernel(int64_t V, SpWs 
   if (v >= V || !w.ref[v]) return;
   const unsigned long long k = w.key[v];
   const uint64_t mask = w.cap_v - 1;
-  uint64_t s = sp_mix(k) & mask;
+  uint64_t s = mesh_mix(k) & mask;
   for (uint64_t step = 0; step < w.cap_v; ++step, s = (s + 1) & mask) {
     const unsigned cur = atomicCAS(w.vtab + s, kSpEmpty, (unsigned)v);
     if (cur != kSpEmpty) {
@@ -344,7 +335,7 @@ __global__ __launch_bounds__(kMkThreads) void sp_dedupe_kernel(int64_t T, SpWs w
   const int x = w.triple[t * 3], y = w.triple[t * 3 + 1], z = w.triple[t * 3 + 2];
   if (x < 0) return;
   const uint64_t mask = w.cap_t - 1;
-  uint64_t s = sp_mix((unsigned long long)x + sp_mix((unsigned long long)y + sp_mix((unsigned long long)z))) & mask;
+  uint64_t s = mesh_mix((unsigned long long)x + mesh_mix((unsigned long long)y + mesh_mix((unsigned long long)z))) & mask;
   for (uint64_t step = 0; step < w.cap_t; ++step, s = (s + 1) & mask) {
     const unsigned cur = atomicCAS(w.ttab + s, kSpEmpty, (unsigned)t);
     if (cur != kSpEmpty) {
@@ -429,8 +420,7 @@ static unsigned sp_blocks(uint64_t n) { return (unsigned)((n + kMkThreads - 1) /
 // the checks the two stages share, before any launch
 static int sp_check(const char* who, const double* vertices, int64_t V, const int32_t* triangles, int64_t T,
                     const double* origin, double h, void* workspace, size_t workspace_bytes, SpGrid* g, SpWs* w) {
-  if (V < 0 || T < 0 || V > kSpMax || T > kSpMax)
-    RNB_FAIL(RNB_E_INVALID, "%s: %lld vertices / %lld triangles outside [0, 2^31 - 1]", who, (long long)V, (long long)T);
+  RNB_TRY(mesh_sizes(who, V, T));
   if (!(h > 0.0) || !std::isfinite(h)) RNB_FAIL(RNB_E_INVALID, "%s: cell_size %g is not positive and finite", who, h);
   g->h = h;
   g->dev_origin = nullptr;
@@ -455,9 +445,7 @@ static int sp_check(const char* who, const double* vertices, int64_t V, const in
 RNB_API int rnb_mesh_simplify_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int64_t* bytes) {
   using namespace rnb;
   if (!bytes) RNB_FAIL(RNB_E_NULL, "rnb_mesh_simplify_workspace_bytes: NULL");
-  if (n_vertices < 0 || n_triangles < 0 || n_vertices > kSpMax || n_triangles > kSpMax)
-    RNB_FAIL(RNB_E_INVALID, "rnb_mesh_simplify_workspace_bytes: %lld vertices / %lld triangles outside [0, 2^31 - 1]",
-             (long long)n_vertices, (long long)n_triangles);
+  RNB_TRY(mesh_sizes("rnb_mesh_simplify_workspace_bytes", n_vertices, n_triangles));
   Carver c(nullptr, 0);
   sp_carve(c, n_vertices, n_triangles);
   *bytes = (int64_t)c.off;
@@ -513,15 +501,15 @@ RNB_API int rnb_mesh_simplify_count(const double* vertices, int64_t n_vertices, 
   RNB_CHECK_LAUNCH();
   hipLaunchKernelGGL(sp_survive_kernel, dim3(sp_blocks(T)), blk, 0, s, T, w, cnt);
   RNB_CHECK_LAUNCH();
-  const int64_t nbv = mk_blocks(V), nbt = mk_blocks(T);
+  const int64_t nbv = scan_blocks(V), nbt = scan_blocks(T);
   if (V > 0) {
-    hipLaunchKernelGGL(mk_flag_sum_kernel<SpVertexFlag>, dim3((unsigned)nbv), blk, 0, s, SpVertexFlag{w.lead, w.used}, V,
+    hipLaunchKernelGGL((scan_sum_kernel<unsigned, SpVertexFlag>), dim3((unsigned)nbv), blk, 0, s, SpVertexFlag{w.lead, w.used}, V,
                        w.bsum_v);
     RNB_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(mk_flag_sum_kernel<SpTriangleFlag>, dim3((unsigned)nbt), blk, 0, s, SpTriangleFlag{w}, T, w.bsum_t);
+  hipLaunchKernelGGL((scan_sum_kernel<unsigned, SpTriangleFlag>), dim3((unsigned)nbt), blk, 0, s, SpTriangleFlag{w}, T, w.bsum_t);
   RNB_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mk_scan_kernel, dim3(1), dim3(1024), 0, s, w.bsum_v, nbv, w.bsum_t, nbt, 2, counts);
+  hipLaunchKernelGGL(scan_block_sums_kernel<unsigned>, dim3(1), dim3(1024), 0, s, w.bsum_v, nbv, w.bsum_t, nbt, 2, counts);
   RNB_CHECK_LAUNCH();
   return RNB_OK;
 }
@@ -549,7 +537,7 @@ RNB_API int rnb_mesh_simplify_emit(const double* vertices, int64_t n_vertices, c
   }
   const dim3 blk(kMkThreads);
   if (V > 0) {
-    hipLaunchKernelGGL((mk_flag_emit_kernel<SpVertexFlag, SpVertexEmit>), dim3((unsigned)mk_blocks(V)), blk, 0, s,
+    hipLaunchKernelGGL((scan_emit_kernel<unsigned, SpVertexFlag, SpVertexEmit>), dim3((unsigned)scan_blocks(V)), blk, 0, s,
                        SpVertexFlag{w.lead, w.used},
                        SpVertexEmit{vertices, w.rep, vertices_out, vertex_index, w.newidx, n_vertices_out}, V, w.bsum_v);
     RNB_CHECK_LAUNCH();
@@ -558,7 +546,7 @@ RNB_API int rnb_mesh_simplify_emit(const double* vertices, int64_t n_vertices, c
       RNB_CHECK_LAUNCH();
     }
   }
-  hipLaunchKernelGGL((mk_flag_emit_kernel<SpTriangleFlag, SpTriangleEmit>), dim3((unsigned)mk_blocks(T)), blk, 0, s,
+  hipLaunchKernelGGL((scan_emit_kernel<unsigned, SpTriangleFlag, SpTriangleEmit>), dim3((unsigned)scan_blocks(T)), blk, 0, s,
                      SpTriangleFlag{w}, SpTriangleEmit{triangles, w.lead, w.newidx, triangles_out, triangle_index, n_triangles_out},
                      T, w.bsum_t);
   RNB_CHECK_LAUNCH();

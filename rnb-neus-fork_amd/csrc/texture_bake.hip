@@ -11,14 +11,14 @@
 // the same expression in numpy).
 //
 // WHY NOTHING RUNS AWAY.  The only loop is the search of the row a2 of a rank r, s + 1 <= 256 trips fixed before it starts
-// (no break).  Every address is an index checked against its array: vertex indices against V before the vertices are read,
-// the sample index against T n_s before rgb / normal are read, the texel and the sample against the launch sizes.
-#include "rnb_internal.h"
+// (no break).  Every address is an index checked against its array: vertex indices against V before the vertices are read
+// (mesh_corners of mesh_common.hip.h), the sample index against T n_s before rgb / normal are read, the texel and the
+// sample against the launch sizes.
+#include "mesh_common.hip.h"
 
 namespace rnb {
 
 constexpr int kTbThreads = 256;
-constexpr int64_t kTbMax = 2147483647;
 
 struct TbMesh {
   const double* vertices;
@@ -26,25 +26,6 @@ struct TbMesh {
   const int32_t* tri;
   int64_t T;
 };
-
-__device__ inline bool tb_finite(double a) { return a == a && a <= 1.7976931348623157e308 && a >= -1.7976931348623157e308; }
-
-// the three corners of triangle t, or false: an index outside [0, V) (checked before it is used) or a non-finite coordinate
-__device__ inline bool tb_corners(const TbMesh& m, int64_t t, double (&p)[9]) {
-  const int a = m.tri[t * 3], b = m.tri[t * 3 + 1], c = m.tri[t * 3 + 2];
-  if (a < 0 || b < 0 || c < 0 || a >= m.V || b >= m.V || c >= m.V) return false;
-  const int idx[3] = {a, b, c};
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const double x = m.vertices[(int64_t)idx[k] * 3 + d];
-      p[k * 3 + d] = x;
-      ok = ok && tb_finite(x);
-    }
-  return ok;
-}
 
 // r(a1, a2) = a2 (s + 1) - a2 (a2 - 1) / 2 + a1: rows of constant a2, row a2 holds s + 1 - a2 samples
 __device__ inline int tb_rank(int s, int a1, int a2) { return a2 * (s + 1) - a2 * (a2 - 1) / 2 + a1; }
@@ -71,7 +52,7 @@ __global__ __launch_bounds__(kTbThreads) void tb_sample_kernel(TbMesh m, int s, 
       a2 = tb_rank(s, 0, row) <= r ? row : a2;
     const int a1 = r - tb_rank(s, 0, a2);
     double c[9];
-    if (t < m.T && tb_corners(m, t, c)) {
+    if (t < m.T && mesh_corners(m.vertices, m.V, m.tri, t, c)) {
       const double sd = (double)s;
       const double w0 = (double)(s - a1 - a2) / sd, w1 = (double)a1 / sd, w2 = (double)a2 / sd;
 #pragma unroll
@@ -118,7 +99,7 @@ __global__ __launch_bounds__(kTbThreads) void tb_pack_kernel(TbPack a) {
       a2 = a2 < 0 ? 0 : a2;
       a2 = a2 > a.s - a1 ? a.s - a1 : a2;
       double p[9];
-      if (tb_corners(a.m, t, p)) smp = t * a.n_s + tb_rank(a.s, a1, a2);
+      if (mesh_corners(a.m.vertices, a.m.V, a.m.tri, t, p)) smp = t * a.n_s + tb_rank(a.s, a1, a2);
     }
   }
   if (smp >= a.N) smp = -1;        // (cannot happen: t < T and r < n_s; an address is checked all the same)
@@ -142,12 +123,11 @@ static unsigned tb_grid(int64_t n) { return (unsigned)((n + kTbThreads - 1) / kT
 
 // V, T, s checked; *n_s and *N = T n_s < 2^31
 static int tb_sizes(const char* who, int64_t V, int64_t T, int32_t s, int* n_s, int64_t* N) {
-  if (V < 0 || T < 0 || V > kTbMax || T > kTbMax)
-    RNB_FAIL(RNB_E_INVALID, "%s: %lld vertices / %lld triangles outside [0, 2^31 - 1]", who, (long long)V, (long long)T);
+  RNB_TRY(mesh_sizes(who, V, T));
   if (s < 1 || s > 255) RNB_FAIL(RNB_E_INVALID, "%s: chart size s = %d outside [1, 255]", who, s);
   *n_s = (s + 1) * (s + 2) / 2;
   *N = T * (int64_t)*n_s;
-  if (*N > kTbMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld triangles x %d samples is not below 2^31", who, (long long)T, *n_s);
+  if (*N > kMeshMax) RNB_FAIL(RNB_E_INVALID, "%s: %lld triangles x %d samples is not below 2^31", who, (long long)T, *n_s);
   return RNB_OK;
 }
 
@@ -186,7 +166,7 @@ RNB_API int rnb_texture_pack(const double* vertices, int64_t n_vertices, const i
   int64_t N;
   RNB_TRY(tb_sizes("rnb_texture_pack", V, T, layout->s, &n_s, &N));
   const int64_t c = layout->s + 5, cols = layout->cols, W = layout->W, H = layout->H, K = (T + 1) / 2;
-  if (W < 0 || H < 0 || cols < 0 || W * H > kTbMax)
+  if (W < 0 || H < 0 || cols < 0 || W * H > kMeshMax)
     RNB_FAIL(RNB_E_INVALID, "rnb_texture_pack: layout %lld x %lld with %lld columns of cells: negative, or 2^31 texels or more",
              (long long)W, (long long)H, (long long)cols);
   if (cols * c > W || cols * (H / c) < K)

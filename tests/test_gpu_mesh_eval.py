@@ -122,6 +122,55 @@ def test_shapes_that_stress_the_bins(R):
     _same(twice, once, "duplicated triangles")
 
 
+def _bin_entries(v, t, origin, cell, dims):
+    """The cell rule of the bins in numpy (every triangle usable): the entries as (flat cell, triangle), sorted by both.
+    A triangle enters the cells clamp(floor((x - origin) / cell), 0, dim - 1) of its box's two corners and all between."""
+    corners, o, d = v[t], np.asarray(origin, dtype=np.float64), np.asarray(dims, dtype=np.int64)
+    lo = np.clip(np.floor((corners.min(axis=1) - o) / cell), 0, d - 1).astype(np.int64)
+    hi = np.clip(np.floor((corners.max(axis=1) - o) / cell), 0, d - 1).astype(np.int64)
+    cells, tris = [], []
+    for k in range(len(t)):
+        x, y, z = (np.arange(lo[k, a], hi[k, a] + 1) for a in range(3))
+        flat = ((z[:, None, None] * d[1] + y[None, :, None]) * d[0] + x[None, None, :]).ravel()
+        cells.append(flat)
+        tris.append(np.full(len(flat), k, dtype=np.int64))
+    cells, tris = np.concatenate(cells), np.concatenate(tris)
+    order = np.lexsort((tris, cells))
+    return cells[order], tris[order]
+
+
+def test_bins_past_the_first_chunk_of_the_block_sum_scan(R):
+    """More than 2^20 cells: the 64-bit scan of the per-cell counts has 1,041 tiles of 1,024, so the one workgroup that scans
+    the tile sums goes through a second chunk of 1,024 and its carry decides where every cell past 2^20 starts.  The torus
+    with its flat axis along x (the fastest cell index) under cells = (65, 128, 128): 1,064,960 cells, 371,408 entries,
+    3,950 of them in 1,942 non-empty cells at flat indices >= 2^20.  cell_start and the entries are compared as exact
+    integers with the cell rule in numpy (the order inside a cell comes from atomics: compared as sets), the queries bit
+    for bit with brute force."""
+    case = F.torus_case()
+    axes = [2, 0, 1]
+    v, t = np.ascontiguousarray(case["vertices"][:, axes]), case["triangles"]
+    q = np.ascontiguousarray(case["queries"][:, axes])
+    dims = (65, 128, 128)
+    n_cells = dims[0] * dims[1] * dims[2]
+    index, got = _query(R, v, t, q, cells=dims)
+    assert index.dims == dims and index.n_cells == n_cells == 1064960 and index.rounds == 1 and not index.skipped and index.covers
+    assert (n_cells + 1 + 1023) // 1024 == 1041, "the scan of n_cells + 1 counts has more than 1,024 tiles"
+    cells, tris = _bin_entries(v, t, index.origin, index.cell_size, dims)
+    counts = np.bincount(cells, minlength=n_cells)
+    past = cells >= 2 ** 20
+    print(f"{n_cells} cells, E = {len(cells)}; {int(past.sum())} entries in {len(np.unique(cells[past]))} cells past 2^20")
+    assert len(cells) == 371408 and int(past.sum()) == 3950 and len(np.unique(cells[past])) == 1942, "the fixture moved"
+    assert index.n_entries == len(cells)
+    start = index.cell_start.cpu().numpy()
+    assert start.dtype == np.int64 and np.array_equal(start, np.concatenate([[0], np.cumsum(counts)])), \
+        "cell_start is not the exclusive running sum of the per-cell counts"
+    entries = index.entries.cpu().numpy().astype(np.int64)
+    got_cells = np.repeat(np.arange(n_cells), np.diff(start))
+    order = np.lexsort((entries, got_cells))
+    assert np.array_equal(got_cells[order], cells) and np.array_equal(entries[order], tris), "a cell holds other triangles than numpy's"
+    _same(got, _query(R, v, t, q, cells=1)[1], "cells=(65, 128, 128) against brute force (cells=1)")
+
+
 def _segment_d2(p, a, b):
     ab = b - a
     s = np.clip(((p - a) @ ab) / (ab @ ab), 0.0, 1.0)
