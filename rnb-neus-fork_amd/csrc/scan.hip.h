@@ -48,7 +48,9 @@ __device__ inline T block_exclusive_scan(T v, T* total, T* red /* [4] */) {
 
 // Exclusive scan in place of `narr` (1 or 2) arrays of tile sums, one workgroup of 1024 going through them in chunks of
 // 1024; totals[k] = sum of array k.  The running carry is 64-bit whatever T: the offsets themselves fit T whenever the
-// totals pass the caller's range check.
+// totals pass the caller's range check.  The chunk loop's second trip (more than 2^20 items) is taken by
+// tests/test_gpu_mesh_second_trips.py (two arrays of different length, one array in four trips) and, for the 64-bit
+// instance, by tests/test_gpu_mesh_eval.py test_bins_past_the_first_chunk_of_the_block_sum_scan.
 template <class T>
 __global__ __launch_bounds__(1024) void scan_block_sums_kernel(T* __restrict__ a0, int64_t n0, T* __restrict__ a1, int64_t n1,
                                                                int narr, int64_t* __restrict__ totals) {

@@ -15,6 +15,7 @@ import torch
 from tests import guard_bands as GB
 from tests import mesh_cull_ref as F
 from tests import mesh_distance_ref as MD
+from tests import mesh_large_shapes as L
 from tests.gpu_support import R  # noqa: F401
 from tests.gpu_support import device
 
@@ -102,6 +103,24 @@ def test_compact_triangles(R):
     _made(s, "vertex_index", shape=(len(want[2]),), dtype=torch.int64)
     _made(s, "triangle_index", shape=(len(want[3]),), dtype=torch.int64)
     assert none["triangles"].shape == (0, 3) and every["triangles"].shape == (len(t), 3)
+
+
+def test_compact_triangles_past_the_first_chunk_of_the_block_sum_scan(R):
+    """SHEET of tests/mesh_large_shapes.py: 1,027 triangle tile sums and 515 vertex tile sums in the workspace, so the one
+    workgroup that scans them stores through a second chunk of the first array and none of the second"""
+    d = L.big("SHEET")
+    v, t = d["vertices"], d["triangles"]
+    assert L.tiles(len(t)) == 1027 and L.tiles(len(v)) == 515 and L.chunks(len(t)) == 2 and L.chunks(len(v)) == 1
+    keep = L.random_keep(len(t))
+    ws = C.c_int64()
+    R.native.check(R.native.load().rnb_mesh_clean_workspace_bytes(len(v), len(t), C.byref(ws)))
+    s, got = _twice("compact_triangles SHEET", lambda x: R.compact_triangles(x["v"], x["t"], x["keep"]), {"v": v, "t": t, "keep": keep})
+    nv, nt = got["info"]["n_vertices"][1], got["info"]["n_triangles"][1]
+    assert nt == int(keep.sum()) and int(got["triangle_index"][-1]) >= L.LINE
+    _made(s, "workspace", nbytes=ws.value, dtype=u8)
+    _made(s, "vertices", shape=(nv, 3), dtype=torch.float64)
+    _made(s, "triangles", shape=(nt, 3), dtype=torch.int32)
+    _made(s, "triangle_index", shape=(nt,), dtype=torch.int64)
 
 
 def test_cull_mesh(R):

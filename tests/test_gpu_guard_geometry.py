@@ -20,6 +20,7 @@ from tests import guard_bands as GB
 from tests import mesh_attrs_util as U
 from tests import mesh_components_ref as MC
 from tests import mesh_distance_ref as MD
+from tests import mesh_large_shapes as ML
 from tests import mesh_raycast_ref as MR
 from tests import mesh_simplify_ref as MS
 from tests import source_maps_util
@@ -239,6 +240,20 @@ def test_clean_mesh_small_meshes(R):
                {"v": v, "t": t})
 
 
+def test_clean_mesh_past_the_first_chunk_of_the_block_sum_scans(R):
+    """PREFIX of tests/mesh_large_shapes.py: 1,027 vertex tile sums (the root-rank scan and the vertex half of the compaction
+    scan store through a second chunk) and 489 triangle tile sums, all carved from the one workspace"""
+    d = ML.big("PREFIX")
+    v, t, n_loose = d["vertices"], d["triangles"], d["n_loose"]
+    assert ML.tiles(len(v)) == 1027 and ML.tiles(len(t)) == 489 and ML.chunks(len(v)) == 2 and ML.chunks(len(t)) == 1
+    s, out = _twice("clean_mesh PREFIX", lambda x: R.clean_mesh(x["v"], x["t"]), {"v": v, "t": t})
+    assert out["info"]["n_vertices"] == (len(v), len(v) - n_loose) and int(out["vertex_index"][0]) == n_loose
+    _made(s, "workspace", nbytes=_query(R, "rnb_mesh_clean_workspace_bytes", len(v), len(t)), dtype=u8)
+    _made(s, "labels", shape=(len(v),), dtype=torch.int32)
+    _made(s, "compacted vertices", shape=(len(v) - n_loose, 3), dtype=torch.float64)
+    _made(s, "vertex_index", shape=(len(v) - n_loose,), dtype=torch.int64)
+
+
 # ---------------------------------------------------------------------------------------------------------- simplification
 @pytest.mark.parametrize("double", [False, True])
 def test_simplify_mesh_hub(R, double):
@@ -312,6 +327,20 @@ def test_the_spread_mesh_crosses_scan_tiles(R):
     _made(s, "cum_area", shape=(len(t),), dtype=torch.float64)
     _made(s, "points", shape=(6000, 3), dtype=torch.float64)
     _made(s, "triangle", shape=(6000,), dtype=torch.int32)
+
+
+def test_sample_surface_past_the_first_chunk_of_the_area_scan(R):
+    """ISOLATED of tests/mesh_large_shapes.py: 1,029 fp64 tile sums in the sample workspace, the last five of them written
+    on the second trip of the one workgroup that chains them"""
+    d = ML.big("ISOLATED")
+    v, t = d["vertices"], d["triangles"]
+    assert ML.tiles(len(t)) == 1029 and ML.chunks(len(t)) == 2
+    s, out = _twice("sample_surface ISOLATED", lambda x: R.sample_surface(x["v"], x["t"], 4096, seed=3), {"v": v, "t": t})
+    assert int(out["triangle"].max()) >= ML.LINE, "a sample past triangle 2^20"
+    _made(s, "sample workspace", nbytes=_query(R, "rnb_mesh_sample_workspace_bytes", len(t)), dtype=u8)
+    _made(s, "cum_area", shape=(len(t),), dtype=torch.float64)
+    _made(s, "points", shape=(4096, 3), dtype=torch.float64)
+    _made(s, "triangle", shape=(4096,), dtype=torch.int32)
 
 
 def test_sample_surface_and_mesh_distance_on_the_torus(R):
