@@ -67,7 +67,7 @@ def _autograd_wanted(module: nn.Module, *inputs):
     return any(p.requires_grad for p in module.parameters()) or any(torch.is_tensor(t) and t.requires_grad for t in inputs)
 
 
-def _mlp_struct(lins, weight_norm, grads=None):
+def mlp_struct(lins, weight_norm, grads=None):
     """rnb_mlp_params / rnb_mlp_grads for a list of _WNLinear (grads: dict leaf -> tensor)."""
     s = native.MlpParams()
     s.n_lin = len(lins)
@@ -86,6 +86,9 @@ def _mlp_struct(lins, weight_norm, grads=None):
         s.v[i] = v.data_ptr()
         s.b[i] = b.data_ptr()
     return s
+
+
+_mlp_struct = mlp_struct    # the name this had while it was private: tests/test_gpu_weightnorm.py imports it
 
 
 class SDFNetwork(nn.Module):

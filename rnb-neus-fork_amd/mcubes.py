@@ -3,8 +3,6 @@ delegates to PyMCubes (`mcubes.marching_cubes(u, threshold)`).  All arithmetic i
 (csrc/mcubes.hip); there is no CPU path.  Parity with PyMCubes is unpinned (not importable here): see DESIGN.md."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import native
@@ -21,9 +19,7 @@ def marching_cubes(volume: torch.Tensor, threshold: float = 0.0):
     lib = native.load()
     u = volume.detach().to(torch.float32).contiguous()
     nx, ny, nz = u.shape
-    nbytes = C.c_int64()
-    native.check(lib.rnb_marching_cubes_workspace_bytes(nx, ny, nz, C.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=u.device)
+    ws = native.workspace("marching_cubes", u.device, nx, ny, nz)
     counts = torch.empty(2, dtype=torch.int64, device=u.device)
     with native.on_device(u) as stream:
         native.check(lib.rnb_marching_cubes_count(native.ptr(u), nx, ny, nz, float(threshold), native.ptr(ws),

@@ -7,62 +7,24 @@ order of their smallest vertex index; a vertex no triangle names has label -1 an
 `compact_triangles` is the same compaction by a per-triangle keep (what `mesh_cull.cull_mesh` ends with)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import native
+from .mesh_args import check_attributes, check_mesh
 
 _BY = ("area", "triangles")
-
-
-def _check_triangles(who, triangles):
-    if not isinstance(triangles, torch.Tensor) or triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"{who}: triangles must be a [T,3] tensor, got "
-                         f"{tuple(triangles.shape) if isinstance(triangles, torch.Tensor) else type(triangles).__name__}")
-    if triangles.dtype != torch.int32:
-        raise ValueError(f"{who}: triangles must be int32 (what marching_cubes returns), not {triangles.dtype}")
-
-
-def _check_vertices(who, vertices):
-    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"{who}: vertices must be a [V,3] tensor, got "
-                         f"{tuple(vertices.shape) if isinstance(vertices, torch.Tensor) else type(vertices).__name__}")
-    if vertices.dtype != torch.float64:
-        raise ValueError(f"{who}: vertices must be float64 (what marching_cubes returns), not {vertices.dtype}")
-
-
-def _check_sizes(who, triangles, n_vertices, vertices):
-    _check_triangles(who, triangles)
-    if vertices is not None:
-        _check_vertices(who, vertices)
-        if n_vertices is not None and int(n_vertices) != vertices.shape[0]:
-            raise ValueError(f"{who}: n_vertices = {n_vertices} but vertices has {vertices.shape[0]} rows")
-        n_vertices = vertices.shape[0]
-    if n_vertices is None:
-        raise ValueError(f"{who}: give n_vertices or vertices")
-    n_vertices = int(n_vertices)
-    if n_vertices < 0 or n_vertices > 2 ** 31 - 1 or triangles.shape[0] > 2 ** 31 - 1:
-        raise ValueError(f"{who}: {n_vertices} vertices / {triangles.shape[0]} triangles outside [0, 2^31 - 1]")
-    return n_vertices
-
-
-def _workspace(lib, V, T, device):
-    nbytes = C.c_int64()
-    native.check(lib.rnb_mesh_clean_workspace_bytes(V, T, C.byref(nbytes)))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+# what the renderer's `clean=` may hold: the selection keywords of `clean_mesh` (checked by `check_criteria`)
+CLEAN_KEYWORDS = ("by", "keep_largest", "min_fraction", "min_triangles")
 
 
 def _components(who, triangles, V, vertices):
     """labels, C, the statistics and the workspace.  One host synchronisation: C with the bad-index flag."""
-    dev = native.same_device(triangles, vertices)
-    if dev is None:
-        raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+    dev = native.gpu_device(triangles, vertices)
     lib = native.load()
     tri = triangles.detach().contiguous()
     vts = vertices.detach().contiguous() if vertices is not None else None
     T = tri.shape[0]
-    ws = _workspace(lib, V, T, dev)
+    ws = native.workspace("mesh_clean", dev, V, T)
     labels = torch.empty(V, dtype=torch.int32, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     with native.on_device(dev) as stream:
@@ -96,7 +58,7 @@ def mesh_components(triangles, n_vertices=None, vertices=None):
     `bbox_min`, `bbox_max` [C,3] float64.  A component with a NaN coordinate has a NaN area.
     ValueError for wrong shapes / dtypes and for a triangle index outside [0, V); RuntimeError for CPU tensors.  One host
     synchronisation.  Never collective under `set_data_parallel`."""
-    V = _check_sizes("mesh_components", triangles, n_vertices, vertices)
+    V = check_mesh("mesh_components", triangles, n_vertices, vertices)
     return _components("mesh_components", triangles, V, vertices)[0]
 
 
@@ -156,11 +118,8 @@ def clean_mesh(vertices, triangles, *, by="area", keep_largest=None, min_fractio
     check_criteria(who, by, keep_largest, min_fraction, min_triangles, vertices is not None)
     if vertices is None:
         raise ValueError(f"{who}: vertices is None (compaction needs the [V,3] coordinates)")
-    V = _check_sizes(who, triangles, None, vertices)
-    attributes = dict(attributes or {})
-    for name, a in attributes.items():
-        if not isinstance(a, torch.Tensor) or a.dim() < 1 or a.shape[0] != V:
-            raise ValueError(f"{who}: attribute {name!r} must be a tensor with first dimension V = {V}")
+    V = check_mesh(who, triangles, None, vertices)
+    attributes = check_attributes(who, attributes, V)
     dev = native.same_device(triangles, vertices, *attributes.values())
     comp, tri, vts, ws = _components(who, triangles, V, vertices)
     n_comp, T = comp["n_components"], tri.shape[0]
@@ -203,22 +162,17 @@ def compact_triangles(vertices, triangles, keep, attributes=None):
     who = "compact_triangles"
     if vertices is None:
         raise ValueError(f"{who}: vertices is None (compaction needs the [V,3] coordinates)")
-    V = _check_sizes(who, triangles, None, vertices)
+    V = check_mesh(who, triangles, None, vertices)
     T = triangles.shape[0]
     if not isinstance(keep, torch.Tensor) or keep.dim() != 1 or keep.shape[0] != T or keep.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f"{who}: keep must be a [T] bool or uint8 tensor with T = {T}, got "
                          f"{(tuple(keep.shape), keep.dtype) if isinstance(keep, torch.Tensor) else type(keep).__name__}")
-    attributes = dict(attributes or {})
-    for name, a in attributes.items():
-        if not isinstance(a, torch.Tensor) or a.dim() < 1 or a.shape[0] != V:
-            raise ValueError(f"{who}: attribute {name!r} must be a tensor with first dimension V = {V}")
-    dev = native.same_device(triangles, vertices, keep, *attributes.values())
-    if dev is None:
-        raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+    attributes = check_attributes(who, attributes, V)
+    dev = native.gpu_device(triangles, vertices, keep, *attributes.values())
     lib = native.load()
     tri, vts = triangles.detach().contiguous(), vertices.detach().contiguous()
     keep8 = keep.detach().to(torch.uint8).contiguous()
-    ws = _workspace(lib, V, T, dev)
+    ws = native.workspace("mesh_clean", dev, V, T)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     with native.on_device(dev) as stream:
         native.check(lib.rnb_mesh_compact_triangles_count(native.ptr(tri), T, V, native.ptr(keep8), native.ptr(ws), ws.numel(),

@@ -10,14 +10,13 @@ include/rnbneus.h defines the status of a pair operation for operation and tests
 device and numpy agree bit for bit, and the SEEN / OCCLUDED split is `MeshIndex.visible`'s.  There is no CPU path."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import native
 from .mesh_clean import compact_triangles
-from .mesh_raycast import VISIBLE_REL_TOL, _check_rays, _device_of
+from .mesh_args import check_points
+from .mesh_raycast import VISIBLE_REL_TOL, index_device
 
 STATUS_NAMES = ("out_of_frame", "outside_mask", "occluded", "seen")
 RULES = ("all", "any")
@@ -121,7 +120,7 @@ def view_votes(index, points, projections, eyes, masks=None, *, image_size=None,
     ValueError for wrong shapes / dtypes and for an index that does not cover its mesh (`covers == False`); RuntimeError
     for CPU points or masks, or another device.  No host synchronisation."""
     who = "MeshIndex.view_votes"
-    _check_rays(who, "points", points)
+    check_points(who, "points", points)
     if isinstance(rel_tol, bool) or not isinstance(rel_tol, (int, float)) or not 0.0 <= rel_tol < 1.0:
         raise ValueError(f"{who}: rel_tol must be a number in [0, 1), not {rel_tol!r}")
     if not index.covers:
@@ -138,7 +137,7 @@ def view_votes(index, points, projections, eyes, masks=None, *, image_size=None,
         size = (int(masks.shape[1]), int(masks.shape[2]))
     if size is None:
         raise ValueError(f"{who}: without masks the frame is unknown: give image_size=(H, W)")
-    dev = _device_of(who, index, points, masks)
+    dev = index_device(who, index, points, masks)
     P = _small(who, "projections", projections, (3, 4), dev)
     e = _small(who, "eyes", eyes, (3,), dev)
     n_cam = P.shape[0]
@@ -153,9 +152,8 @@ def view_votes(index, points, projections, eyes, masks=None, *, image_size=None,
     if N > 0:
         with native.on_device(dev) as stream:
             native.check(native.load().rnb_mesh_view_votes(
-                native.ptr(p), N, native.ptr(P), native.ptr(e), n_cam, native.ptr(m), size[0], size[1], C.byref(index.bins),
-                native.ptr(index.cell_start), native.ptr(index.entries), index.n_entries, native.ptr(index.corners),
-                index.n_triangles, float(rel_tol), flags, native.ptr(counts), native.ptr(status), stream))
+                native.ptr(p), N, native.ptr(P), native.ptr(e), n_cam, native.ptr(m), size[0], size[1], *index.native_args(),
+                float(rel_tol), flags, native.ptr(counts), native.ptr(status), stream))
     out = {name: counts[:, k] for k, name in enumerate(STATUS_NAMES)}
     out["counts"] = counts
     if return_status:

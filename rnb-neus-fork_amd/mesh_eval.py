@@ -14,27 +14,10 @@ import math
 import torch
 
 from . import mesh_cull, mesh_raycast, native
-from .mesh_clean import _check_sizes
+from .mesh_args import check_mesh, check_points, finite_box
 
 _MAX_CELLS = native.MESH_BINS_MAX_CELLS
 _COARSEN_ROUNDS = 8
-
-
-def _device_of(who, *tensors):
-    dev = native.same_device(*tensors)
-    if dev is None:
-        raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
-    return dev
-
-
-def _check_points(who, points):
-    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"{who}: points must be a [N,3] tensor, got "
-                         f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
-    if points.dtype != torch.float64:
-        raise ValueError(f"{who}: points must be float64 (the mesh's own precision), not {points.dtype}")
-    if points.shape[0] > 2 ** 31 - 1:
-        raise ValueError(f"{who}: {points.shape[0]} points outside [0, 2^31 - 1]")
 
 
 def _check_cells(who, cells):
@@ -89,7 +72,7 @@ class MeshIndex:
 
     def __init__(self, vertices, triangles, cells=None, grid=None):
         who = "MeshIndex"
-        V = _check_sizes(who, triangles, None, vertices)
+        V = check_mesh(who, triangles, None, vertices)
         forced = _check_cells(who, cells)
         if grid is not None:
             if cells is not None:
@@ -98,27 +81,17 @@ class MeshIndex:
             g_origin, g_cell, forced = [float(x) for x in g_origin], float(g_cell), _check_cells(who, tuple(g_dims))
             if len(g_origin) != 3 or not all(math.isfinite(x) for x in g_origin) or not (g_cell > 0.0 and math.isfinite(g_cell)):
                 raise ValueError(f"{who}: grid = (origin, cell_size, dims) needs a finite origin and a positive cell size")
-        dev = _device_of(who, triangles, vertices)
+        dev = native.gpu_device(triangles, vertices)
         lib = native.load()
         self.vertices = vertices.detach().contiguous()
         self.triangles = triangles.detach().contiguous()
         self.n_vertices, self.n_triangles, self.device = V, self.triangles.shape[0], dev
         T = self.n_triangles
-        # the box of the finite vertices (a non-finite one only ever belongs to skipped triangles)
-        box = torch.zeros(2, 3, dtype=torch.float64, device=dev)
-        if V > 0:
-            fin = torch.isfinite(self.vertices).all(dim=1, keepdim=True)
-            big = torch.finfo(torch.float64).max
-            lo = torch.where(fin, self.vertices, torch.full_like(self.vertices, big)).min(dim=0).values
-            hi = torch.where(fin, self.vertices, torch.full_like(self.vertices, -big)).max(dim=0).values
-            box = torch.stack([lo, hi])
         bad = ((self.triangles < 0) | (self.triangles >= V)).any().to(torch.float64).reshape(1, 1).expand(1, 3)
-        host = torch.cat([box, bad]).cpu()
+        host = torch.cat([torch.stack(finite_box(self.vertices)), bad]).cpu()     # (the box and the flag in one read)
         if float(host[2, 0]) != 0.0:
             raise ValueError(f"{who}: a triangle holds a vertex index outside [0, {V})")
         lo, hi = host[0].tolist(), host[1].tolist()
-        if any(h < l for l, h in zip(lo, hi)):        # no finite vertex
-            lo, hi = [0.0] * 3, [0.0] * 3
         extent = [h - l for l, h in zip(lo, hi)]
         if not all(math.isfinite(e) for e in extent):
             raise ValueError(f"{who}: the mesh's bounding box overflows float64")
@@ -134,9 +107,7 @@ class MeshIndex:
             rounds += 1
             n_cells = dims[0] * dims[1] * dims[2]
             bins = native.MeshBins((C.c_double * 3)(*lo), cell, (C.c_int32 * 3)(*dims), 0)
-            nbytes = C.c_int64()
-            native.check(lib.rnb_mesh_bins_workspace_bytes(n_cells, C.byref(nbytes)))
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            ws = native.workspace("mesh_bins", dev, n_cells)
             cell_start = torch.empty(n_cells + 1, dtype=torch.int64, device=dev)
             with native.on_device(dev) as stream:
                 native.check(lib.rnb_mesh_bins_count(native.ptr(self.vertices), V, native.ptr(self.triangles), T, C.byref(bins),
@@ -164,6 +135,12 @@ class MeshIndex:
         self._origin_t = torch.tensor(lo, dtype=torch.float64, device=dev)
         self._dims_t = torch.tensor(dims, dtype=torch.float64, device=dev)
 
+    def native_args(self):
+        """the six arguments by which the native calls take these bins: the grid, the cells' first entries, the entries and
+        their count, the triangles' corners and their count"""
+        return (C.byref(self.bins), native.ptr(self.cell_start), native.ptr(self.entries), self.n_entries,
+                native.ptr(self.corners), self.n_triangles)
+
     def _cell_order(self, q):
         """the permutation that sorts the queries by cell: neighbouring lanes of the query kernel then read the same entries
         (locality only: no result depends on it)"""
@@ -179,8 +156,8 @@ class MeshIndex:
         `triangle` [N] int32 (ties to the smaller index).  A query with a non-finite coordinate: NaN, NaN, -1; a mesh without
         a usable triangle: +inf, NaN, -1.  No host synchronisation."""
         who = "MeshIndex.closest"
-        _check_points(who, points)
-        dev = _device_of(who, points)
+        check_points(who, "points", points, dtypes=(torch.float64,), noun="points")
+        dev = native.gpu_device(points)
         if dev != self.device:
             raise RuntimeError(f"{who}: points live on {dev}, the mesh on {self.device}")
         q = points.detach().contiguous()
@@ -194,9 +171,8 @@ class MeshIndex:
             d2s, cls, trs = torch.empty_like(dist2), torch.empty_like(closest), torch.empty_like(triangle)
             with native.on_device(dev) as stream:
                 native.check(native.load().rnb_mesh_closest_points(
-                    native.ptr(qs), N, C.byref(self.bins), native.ptr(self.cell_start), native.ptr(self.entries),
-                    self.n_entries, native.ptr(self.corners), self.n_triangles,
-                    native.MESH_BINS_COVER if self.covers else 0, native.ptr(d2s), native.ptr(cls), native.ptr(trs), stream))
+                    native.ptr(qs), N, *self.native_args(), native.MESH_BINS_COVER if self.covers else 0,
+                    native.ptr(d2s), native.ptr(cls), native.ptr(trs), stream))
             dist2[order], closest[order], triangle[order] = d2s, cls, trs
         return {"distance": torch.sqrt(dist2), "dist2": dist2, "closest": closest, "triangle": triangle}
 
@@ -229,7 +205,7 @@ def sample_surface(vertices, triangles, n, seed=0):
     ValueError for wrong shapes / dtypes, a triangle index outside [0, V), n < 0, or a total area that is zero or not
     finite; RuntimeError for CPU tensors.  One host synchronisation (A with the bad-index flag)."""
     who = "sample_surface"
-    V = _check_sizes(who, triangles, None, vertices)
+    V = check_mesh(who, triangles, None, vertices)
     if isinstance(n, bool) or int(n) != n or not 0 <= int(n) <= 2 ** 31 - 1:
         raise ValueError(f"{who}: n must be an integer in [0, 2^31 - 1], not {n!r}")
     if isinstance(seed, bool) or int(seed) != seed:
@@ -237,13 +213,11 @@ def sample_surface(vertices, triangles, n, seed=0):
     n = int(n)
     seed = int(seed) & (2 ** 64 - 1)
     seed = seed - 2 ** 64 if seed >= 2 ** 63 else seed
-    dev = _device_of(who, triangles, vertices)
+    dev = native.gpu_device(triangles, vertices)
     lib = native.load()
     vts, tri = vertices.detach().contiguous(), triangles.detach().contiguous()
     T = tri.shape[0]
-    nbytes = C.c_int64()
-    native.check(lib.rnb_mesh_sample_workspace_bytes(T, C.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ws = native.workspace("mesh_sample", dev, T)
     cum = torch.empty(T, dtype=torch.float64, device=dev)
     head = torch.empty(2, dtype=torch.float64, device=dev)     # A, the bad-index flag
     with native.on_device(dev) as stream:
@@ -298,8 +272,8 @@ def mesh_distance(va, ta, vb, tb, n_samples=1_000_000, thresholds=(), seed=0, re
     thresholds = tuple(float(t) for t in thresholds)
     if any(not t >= 0.0 for t in thresholds):
         raise ValueError(f"{who}: thresholds must be >= 0, not {thresholds!r}")
-    _check_sizes(who, ta, None, va)
-    _check_sizes(who, tb, None, vb)
+    check_mesh(who, ta, None, va)
+    check_mesh(who, tb, None, vb)
     index_a, index_b = MeshIndex(va, ta), MeshIndex(vb, tb)
     if index_a.device != index_b.device:
         raise RuntimeError(f"{who}: the meshes live on different devices ({index_a.device} and {index_b.device})")

@@ -11,11 +11,10 @@ noise of the pair test that a one-cell grid reports and a finer one may not (inc
 Gradients do not flow through a hit."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import native
+from .mesh_args import check_points
 
 # `MeshIndex.visible`: the target point lies ON the mesh, so the segment eye -> point meets the point's own triangle (and
 # its neighbours at an edge or a vertex) at t = 1 up to the rounding of the hit, a few 2^-52 of the scene's size over the
@@ -24,23 +23,12 @@ from . import native
 VISIBLE_REL_TOL = 1e-6
 
 
-def _device_of(who, index, *tensors):
-    dev = native.same_device(*tensors)
-    if dev is None:
-        raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+def index_device(who, index, *tensors):
+    """the GPU the given tensors share (`native.gpu_device`), which must be the mesh's"""
+    dev = native.gpu_device(*tensors)
     if dev != index.device:
         raise RuntimeError(f"{who}: the rays live on {dev}, the mesh on {index.device}")
     return dev
-
-
-def _check_rays(who, name, x):
-    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"{who}: {name} must be a [N,3] tensor, got "
-                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-    if x.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{who}: {name} must be float64 (or float32, widened exactly), not {x.dtype}")
-    if x.shape[0] > 2 ** 31 - 1:
-        raise ValueError(f"{who}: {x.shape[0]} rays outside [0, 2^31 - 1]")
 
 
 def _check_bound(who, name, b, N):
@@ -59,7 +47,7 @@ def _bound(who, name, b, N, dev):
         return None
     if isinstance(b, torch.Tensor):
         if not b.is_cuda:
-            raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+            raise RuntimeError(native.NO_CPU_PATH)
         if b.device != dev:
             raise RuntimeError(f"{who}: {name} lives on {b.device}, the rays on {dev}")
         return b.detach().to(torch.float64).reshape(-1).expand(N).contiguous()
@@ -68,8 +56,8 @@ def _bound(who, name, b, N, dev):
 
 def _cast(who, index, origins, directions, t_min, t_max, want_bary=True):
     """the checks and the launch: (o, d as float64, t [N], triangle [N], bary [N,3] or None)"""
-    _check_rays(who, "origins", origins)
-    _check_rays(who, "directions", directions)
+    check_points(who, "origins", origins)
+    check_points(who, "directions", directions)
     if origins.shape != directions.shape:
         raise ValueError(f"{who}: origins {tuple(origins.shape)} and directions {tuple(directions.shape)} differ in shape")
     if not index.covers:
@@ -77,7 +65,7 @@ def _cast(who, index, origins, directions, t_min, t_max, want_bary=True):
     N = origins.shape[0]
     _check_bound(who, "t_min", t_min, N)
     _check_bound(who, "t_max", t_max, N)
-    dev = _device_of(who, index, origins, directions)
+    dev = index_device(who, index, origins, directions)
     o = origins.detach().to(torch.float64).contiguous()
     d = directions.detach().to(torch.float64).contiguous()
     lo, hi = _bound(who, "t_min", t_min, N, dev), _bound(who, "t_max", t_max, N, dev)
@@ -87,9 +75,8 @@ def _cast(who, index, origins, directions, t_min, t_max, want_bary=True):
     if N > 0:
         with native.on_device(dev) as stream:
             native.check(native.load().rnb_mesh_raycast(
-                native.ptr(o), native.ptr(d), native.ptr(lo), native.ptr(hi), N, C.byref(index.bins),
-                native.ptr(index.cell_start), native.ptr(index.entries), index.n_entries, native.ptr(index.corners),
-                index.n_triangles, native.MESH_BINS_COVER, native.ptr(t), native.ptr(tri), native.ptr(bary), stream))
+                native.ptr(o), native.ptr(d), native.ptr(lo), native.ptr(hi), N, *index.native_args(),
+                native.MESH_BINS_COVER, native.ptr(t), native.ptr(tri), native.ptr(bary), stream))
     return o, d, t, tri, bary
 
 
@@ -161,13 +148,13 @@ def visible(index, points, eye, rel_tol=VISIBLE_REL_TOL):
     met at t = 1 up to rounding: `rel_tol` (default 1e-6 of the segment, see VISIBLE_REL_TOL) keeps that hit from hiding
     it.  A point with a non-finite coordinate, or equal to its eye, is not visible.  No host synchronisation."""
     who = "MeshIndex.visible"
-    _check_rays(who, "points", points)
+    check_points(who, "points", points)
     if not isinstance(eye, torch.Tensor) or eye.dtype not in (torch.float64, torch.float32) or (
             tuple(eye.shape) != (3,) and eye.shape != points.shape):
         raise ValueError(f"{who}: eye must be a float [3] or [N,3] tensor")
     if isinstance(rel_tol, bool) or not isinstance(rel_tol, (int, float)) or not 0.0 <= rel_tol < 1.0:
         raise ValueError(f"{who}: rel_tol must be a number in [0, 1), not {rel_tol!r}")
-    _device_of(who, index, points, eye)
+    index_device(who, index, points, eye)
     p = points.detach().to(torch.float64)
     e = eye.detach().to(torch.float64).expand_as(p).contiguous()
     t = _cast(who, index, e, p - e, 0.0, 1.0, want_bary=False)[2]           # only t: no point, normal or bary is built
@@ -194,8 +181,8 @@ def mesh_view_maps(index, rays_o, rays_d=None, shape=None, vertex_normals=None, 
         rays = {}
     if rays_d is None:
         raise ValueError(f"{who}: rays_d is missing")
-    _check_rays(who, "rays_o", rays_o)
-    _check_rays(who, "rays_d", rays_d)
+    check_points(who, "rays_o", rays_o)
+    check_points(who, "rays_d", rays_d)
     if shape is None and "H" in rays and "W" in rays and rays_o.shape[0] == int(rays["H"]) * int(rays["W"]):
         shape = (int(rays["H"]), int(rays["W"]))
     if shape is not None:

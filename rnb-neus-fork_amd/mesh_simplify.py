@@ -15,20 +15,12 @@ import numbers
 import torch
 
 from . import native
-from .mesh_clean import _check_sizes
+from .mesh_args import check_attributes, check_mesh, finite_box
 
 MAX_RESOLUTION = 2 ** 20 - 1     # cell indices are 21-bit
 FLAG_BAD_INDEX, FLAG_BAD_VERTEX, FLAG_TABLE_FULL = 1, 2, 4
-
-
-def _finite_box(vts):
-    """(min [3], max [3]) over the vertices with all-finite coordinates, on the device; (0, 0) when there is none"""
-    ok = torch.isfinite(vts).all(dim=1, keepdim=True)
-    inf = torch.full_like(vts, float("inf"))
-    lo = torch.where(ok, vts, inf).amin(dim=0) if vts.shape[0] else inf.new_full((3,), float("inf"))
-    hi = torch.where(ok, vts, -inf).amax(dim=0) if vts.shape[0] else inf.new_full((3,), float("-inf"))
-    none = torch.isinf(lo)
-    return torch.where(none, torch.zeros_like(lo), lo), torch.where(none, torch.zeros_like(hi), hi)
+# what the renderer's `simplify=` may hold: the keywords of `simplify_mesh` that `check_arguments` checks
+SIMPLIFY_KEYWORDS = ("cell_size", "target_triangles", "origin")
 
 
 class _Pass:
@@ -39,9 +31,7 @@ class _Pass:
         self.V, self.T = vts.shape[0], tri.shape[0]
         self.dev = vts.device
         self.lib = native.load()
-        nbytes = C.c_int64()
-        native.check(self.lib.rnb_mesh_simplify_workspace_bytes(self.V, self.T, C.byref(nbytes)))
-        self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+        self.ws = native.workspace("mesh_simplify", self.dev, self.V, self.T)
         self.counts = torch.empty(6, dtype=torch.int64, device=self.dev)
         self.grid = None
 
@@ -135,21 +125,16 @@ def simplify_mesh(vertices, triangles, *, cell_size=None, target_triangles=None,
     org = check_arguments(who, cell_size, target_triangles, origin)
     if vertices is None:
         raise ValueError(f"{who}: vertices is None")
-    V = _check_sizes(who, triangles, None, vertices)
-    attributes = dict(attributes or {})
-    for name, a in attributes.items():
-        if not isinstance(a, torch.Tensor) or a.dim() < 1 or a.shape[0] != V:
-            raise ValueError(f"{who}: attribute {name!r} must be a tensor with first dimension V = {V}")
-    dev = native.same_device(triangles, vertices, *attributes.values())
-    if dev is None:
-        raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+    V = check_mesh(who, triangles, None, vertices)
+    attributes = check_attributes(who, attributes, V)
+    dev = native.gpu_device(triangles, vertices, *attributes.values())
     tri, vts = triangles.detach().contiguous(), vertices.detach().contiguous()
     T = tri.shape[0]
     if target_triangles is None:
         run = _Pass(who, vts, tri)
         h = float(cell_size)
         c = run.count(org, h)
-        origin_t = torch.tensor(org, dtype=torch.float64, device=dev) if org is not None else _finite_box(vts)[0]
+        origin_t = torch.tensor(org, dtype=torch.float64, device=dev) if org is not None else finite_box(vts)[0]
         return _result(*run.emit(c[0], c[1]), attributes, _info(h, origin_t, V, T, c, []))
     n = int(target_triangles)
     if T <= n:      # small enough already: only unreferenced vertices go
@@ -159,11 +144,11 @@ def simplify_mesh(vertices, triangles, *, cell_size=None, target_triangles=None,
         cluster = torch.full((V,), -1, dtype=torch.int32, device=dev)
         cluster[index] = torch.arange(index.shape[0], dtype=torch.int32, device=dev)
         nv = index.shape[0]
-        info = _info(None, _finite_box(vts)[0] if org is None else torch.tensor(org, dtype=torch.float64, device=dev), V, T,
+        info = _info(None, finite_box(vts)[0] if org is None else torch.tensor(org, dtype=torch.float64, device=dev), V, T,
                      [nv, T, 0, 0, 0, nv], [])
         return _result(out["vertices"], out["triangles"], index, cluster, torch.arange(T, dtype=torch.int64, device=dev),
                        attributes, info)
-    lo_t, hi_t = _finite_box(vts)
+    lo_t, hi_t = finite_box(vts)
     box = torch.stack([lo_t, hi_t]).cpu()
     L = float((box[1] - box[0]).max())
     if not (0.0 < L < math.inf):

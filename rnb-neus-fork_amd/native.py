@@ -345,6 +345,22 @@ def check(rc: int):
         raise NativeError(f"librnbneus_hip error {rc}: {msg.decode() if msg else '?'}")
 
 
+def workspace_bytes(name, *size_args, floor=0):
+    """max(bytes, floor) with `rnb_<name>_workspace_bytes(*size_args, &bytes)` asked (a host function) and its return
+    code checked"""
+    nbytes = C.c_int64()
+    check(getattr(load(), f"rnb_{name}_workspace_bytes")(*size_args, C.byref(nbytes)))
+    return max(nbytes.value, floor)
+
+
+def workspace(name, device, *size_args, floor=0):
+    """The byte tensor of a native call's workspace: `workspace_bytes(name, *size_args, floor=floor)` uint8 on `device`.
+    (Two callers allocate that size themselves, `runtime.mesh_vertex_attrs` and `NeuSRenderer._maps_begin`: the
+    guard-band tests find a buffer by the function that allocated it.)"""
+    import torch
+    return torch.empty(workspace_bytes(name, *size_args, floor=floor), dtype=torch.uint8, device=device)
+
+
 def variant_bits(bf16=False, deterministic=False, generic=False, dw_lds=False, dw_staged=False, bwd_ti=0, bwd_nw=0,
                  fwd_ti=0, fwd_nw=0, x3=False, f32_mfma=False, reg_tile=False, lds_tile=False, x2h=None, dead_tiles=True) -> int:
     """rnb_model_desc.variant from keyword switches (tile heights: 0/1/2; waves: 0/4/8; x2h: None = the library's default
@@ -360,6 +376,9 @@ def variant_bits(bf16=False, deterministic=False, generic=False, dw_lds=False, d
             | (0 if dead_tiles else VARIANT_NO_DEAD_TILES))
 
 
+NO_CPU_PATH = "librnbneus_hip.so works on GPU tensors only (there is no CPU path)"
+
+
 class on_device:
     """Context for one native call: makes the tensors' device the current HIP device (the library launches on
     the stream it is given and never calls hipSetDevice) and yields that device's current torch stream as the
@@ -371,7 +390,7 @@ class on_device:
         if isinstance(device, torch.Tensor):
             device = device.device
         if device.type != "cuda":
-            raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+            raise RuntimeError(NO_CPU_PATH)
         self._torch = torch
         self.device = device
         self._ctx = torch.cuda.device(device)
@@ -391,11 +410,19 @@ def same_device(*tensors):
         if t is None:
             continue
         if not t.is_cuda:
-            raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+            raise RuntimeError(NO_CPU_PATH)
         if dev is None:
             dev = t.device
         elif t.device != dev:
             raise RuntimeError(f"tensors of one native call live on different devices ({dev} and {t.device})")
+    return dev
+
+
+def gpu_device(*tensors):
+    """`same_device` for a call that needs at least one tensor: the GPU they share, RuntimeError when none is given"""
+    dev = same_device(*tensors)
+    if dev is None:
+        raise RuntimeError(NO_CPU_PATH)
     return dev
 
 

@@ -31,8 +31,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import native, parallel, runtime
-from .fields import _mlp_struct, model_desc
+from . import mesh_pipeline, native, parallel, runtime
+from .fields import mlp_struct, model_desc
 from .parallel import allreduce_mean_, allreduce_sum_
 
 _MESH_BACKEND_LOGGED = False
@@ -122,9 +122,7 @@ class _FinePass(torch.autograd.Function):
             extras["sdf"] = torch.empty(B * S, 1, **f32)
             if not (mvps and (flags & native.FLAG_NO_ALBEDO)):
                 extras["sampled_albedo"] = torch.empty(B, S, Cd, **f32)
-        nbytes = C.c_int64()
-        native.check(lib.rnb_render_workspace_bytes(C.byref(desc), B, S, flags, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = native.workspace("render", dev, C.byref(desc), B, S, flags)
         args = native.RenderArgs()
         args.B, args.S, args.n_lights, args.flags = B, S, L, flags
         args.cos_anneal_ratio = float(call["cos_anneal_ratio"])
@@ -228,11 +226,11 @@ class _FinePass(torch.autograd.Function):
         if renderer.track_range:
             renderer._collect_range(desc, call["packed"], ctx.ws, ctx.args.B, ctx.args.S, ctx.args.flags)
         sdf_net, col_net = renderer.sdf_network, renderer.color_network
-        sp = _mlp_struct(sdf_net.lins(), sdf_net.weight_norm)
-        sg = _mlp_struct(sdf_net.lins(), sdf_net.weight_norm, grads=views)
+        sp = mlp_struct(sdf_net.lins(), sdf_net.weight_norm)
+        sg = mlp_struct(sdf_net.lins(), sdf_net.weight_norm, grads=views)
         use_col = call["train_color"]
-        cp = _mlp_struct(col_net.lins(), col_net.weight_norm) if use_col else None
-        cg = _mlp_struct(col_net.lins(), col_net.weight_norm, grads=views) if use_col else None
+        cp = mlp_struct(col_net.lins(), col_net.weight_norm) if use_col else None
+        cg = mlp_struct(col_net.lins(), col_net.weight_norm, grads=views) if use_col else None
         with native.on_device(dev) as stream:
             native.check(lib.rnb_weightnorm_bwd(C.byref(desc), C.byref(sp), C.byref(cp) if cp is not None else None,
                                                 native.ptr(packed_grad), C.byref(sg),
@@ -341,9 +339,7 @@ class NeuSRenderer:
             t_rand = None
         S = self.n_samples + self.n_importance
         z = torch.empty(B, S, dtype=torch.float32, device=dev)
-        nbytes = C.c_int64()
-        native.check(lib.rnb_sample_workspace_bytes(C.byref(self.desc), B, C.byref(nbytes)))
-        ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=dev)
+        ws = native.workspace("sample", dev, C.byref(self.desc), B, floor=256)
         near = near.to(torch.float32).reshape(B).contiguous()
         far = far.to(torch.float32).reshape(B).contiguous()
         native.same_device(packed, rays_o, rays_d, near, far, t_rand)
@@ -478,14 +474,12 @@ class NeuSRenderer:
         out = {m: torch.empty(shapes[m], **f32) for m in maps}
         if keep_z:
             out["z_vals"] = torch.empty(n_rays, S, **f32)
-        nbytes = C.c_int64()
-        native.check(native.load().rnb_render_workspace_bytes(C.byref(self.desc), chunk, S, flags | native.FLAG_FORWARD_ONLY,
-                                                              C.byref(nbytes)))
+        ws_bytes = native.workspace_bytes("render", C.byref(self.desc), chunk, S, flags | native.FLAG_FORWARD_ONLY, floor=256)
         bg = None
         if background_rgb is not None and not mvps:
             bg = background_rgb.detach().to(device=dev, dtype=torch.float32).reshape(3).contiguous()
         return dict(flags=flags, mvps=mvps, maps=maps, out=out, chunk=chunk, S=S, L=n_lights, Cd=Cd, dev=dev, bg=bg,
-                    packed=self._pack(use_color), ws=torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=dev),
+                    packed=self._pack(use_color), ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev),
                     cos=float(cos_anneal_ratio), variance=self.deviation_network.variance.detach().reshape(1))
 
     def _maps_chunk(self, st, i0, rays_o, rays_d, z_vals, lights):
@@ -548,7 +542,7 @@ class NeuSRenderer:
         The rays run in chunks of `chunk_rays` through ONE workspace of the one-chunk size, allocated once (stream order
         makes the reuse safe), and every chunk's maps are written straight into rows of the preallocated outputs — except
         [L,B,C] colour, whose per-chunk [L,n,C] block is copied into its columns (the kernel has no output stride).
-        Workspace: `rnb_render_workspace_bytes(desc, chunk_rays, S, flags | RNB_FLAG_FORWARD_ONLY)` — about 30 KB per
+        Workspace: `rnb_render_workspace_bytes` of (desc, chunk_rays, S, flags | RNB_FLAG_FORWARD_ONLY) — about 30 KB per
         sample point at the shipped shape (256-wide, 8 layers), i.e. ~4 GB per 1024-ray chunk of 128 samples, whatever the
         image size.  Runs under no_grad whatever the caller's grad mode (outputs carry no grad_fn, no `.grad` is touched),
         for every `set_variant`, and is never collective under `set_data_parallel`."""
@@ -665,17 +659,11 @@ class NeuSRenderer:
         group = group if group is not None else self.dp_group
         rank, world = (dist.get_rank(group), dist.get_world_size(group)) if group is not None else (0, 1)
         per, x0, x1 = parallel.grid_slab(res, rank, world)   # x-planes per rank (the last slabs may be shorter, or empty)
-        gd = native.GridDesc()
-        for d in range(3):
-            gd.bound_min[d] = float(bound_min[d])
-            gd.bound_max[d] = float(bound_max[d])
-        gd.resolution, gd.x_begin, gd.x_end, gd.out_scale = res, x0, x1, -1.0
+        gd = mesh_pipeline.grid_desc(bound_min, bound_max, res, x0, x1)
         slab = torch.empty(per, res, res, dtype=torch.float32, device=dev)     # padded to `per` planes for the gather
         with torch.no_grad():
             if x1 > x0:
-                nbytes = C.c_int64()
-                native.check(lib.rnb_sdf_grid_workspace_bytes(C.byref(self.desc), C.byref(gd), C.byref(nbytes)))
-                ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=dev)
+                ws = native.workspace("sdf_grid", dev, C.byref(self.desc), C.byref(gd), floor=256)
                 with native.on_device(dev) as stream:
                     native.check(lib.rnb_sdf_grid(C.byref(self.desc), native.ptr(packed), C.byref(gd), native.ptr(slab),
                                                   native.ptr(ws), ws.numel(), stream))
@@ -715,20 +703,14 @@ class NeuSRenderer:
                              "(extract_fields serves set_data_parallel)")
         dev = self.sdf_network.lin0.bias.device
         if dev.type != "cuda":
-            raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+            raise RuntimeError(native.NO_CPU_PATH)
         lib = native.load()
-        gd = native.GridDesc()
-        for d in range(3):
-            gd.bound_min[d] = float(bound_min[d])
-            gd.bound_max[d] = float(bound_max[d])
-        gd.resolution, gd.x_begin, gd.x_end, gd.out_scale = res, 0, res, -1.0
+        gd = mesh_pipeline.grid_desc(bound_min, bound_max, res, 0, res)
         sd = native.SparseGridDesc(brick, threshold, margin)
         nb = geo["nb"]
         with torch.no_grad():
             packed = self._pack(False)
-            nbytes = C.c_int64()
-            native.check(lib.rnb_sdf_grid_sparse_workspace_bytes(C.byref(self.desc), C.byref(gd), C.byref(sd), C.byref(nbytes)))
-            ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=dev)
+            ws = native.workspace("sdf_grid_sparse", dev, C.byref(self.desc), C.byref(gd), C.byref(sd), floor=256)
             u = torch.empty(res, res, res, dtype=torch.float32, device=dev)
             mask = torch.empty(nb, nb, nb, dtype=torch.uint8, device=dev)
             n_listed = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -829,103 +811,22 @@ class NeuSRenderer:
         self.last_mesh_backend = backend
         if backend not in ("native", "mcubes"):
             raise ValueError(f"extract_geometry: unknown backend {backend!r}")
-        self._check_clean(clean)
-        self._check_simplify(simplify)
-        self._check_cull(cull)
-        b_max = bound_max.detach().cpu().numpy()
-        b_min = bound_min.detach().cpu().numpy()
+        options = {"clean": clean, "simplify": simplify, "cull": cull}
+        mesh_pipeline.check_options(**options)
         if backend == "mcubes":
             import mcubes
-            if sparse:
-                u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, resolution, threshold, brick,
-                                                                      margin, to_host=True)
-            else:
-                u = self.extract_fields(bound_min, bound_max, resolution)
+            u = mesh_pipeline.volume(self, bound_min, bound_max, resolution, threshold, sparse, brick, margin, to_host=True)
             vertices, triangles = mcubes.marching_cubes(u, threshold)
-            if clean is not None or simplify is not None or cull is not None:
+            if any(o is not None for o in options.values()):     # the stages run on the device: the host arrays go up for them
                 dev = self.sdf_network.lin0.bias.device
                 v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev)
                 t = torch.as_tensor(np.ascontiguousarray(triangles).astype(np.int32)).to(dev)
-                if clean is not None:
-                    v, t = self._clean_mesh(v, t, clean)
-                if cull is not None:
-                    v, t = self._cull_mesh(v, t, cull, bound_min, bound_max, resolution)
-                if simplify is not None:
-                    v, t = self._simplify_mesh(v, t, simplify)
+                v, t = mesh_pipeline.run_stages(self, v, t, (bound_min, bound_max, resolution), options)
                 vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         else:
-            from .mcubes import marching_cubes
-            if sparse:
-                u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, resolution, threshold, brick,
-                                                                      margin, to_host=False)
-            else:
-                u = self.extract_fields(bound_min, bound_max, resolution, to_host=False)
-            v, t = marching_cubes(u, threshold)
-            if clean is not None or simplify is not None or cull is not None:
-                del u
-            if clean is not None:
-                v, t = self._clean_mesh(v, t, clean)
-            if cull is not None:
-                v, t = self._cull_mesh(v, t, cull, bound_min, bound_max, resolution)
-            if simplify is not None:
-                v, t = self._simplify_mesh(v, t, simplify)
+            v, t = mesh_pipeline.device_mesh(self, bound_min, bound_max, resolution, threshold, sparse, brick, margin, options)
             vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
-        vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
-        return vertices, triangles
-
-    @staticmethod
-    def _check_clean(clean):
-        """the `clean` argument of the two extract calls, checked before the grid is evaluated"""
-        from .mesh_clean import check_criteria
-        if clean is None:
-            return
-        if not isinstance(clean, dict) or not set(clean) <= {"by", "keep_largest", "min_fraction", "min_triangles"}:
-            raise ValueError("clean must be a dict of clean_mesh keywords (by, keep_largest, min_fraction, min_triangles)")
-        check_criteria("clean", has_vertices=True, **clean)
-
-    def _clean_mesh(self, v, t, clean):
-        """`clean_mesh(v, t, **clean)` for the two extract calls: the cleaned (vertices, triangles); `info` kept."""
-        from .mesh_clean import clean_mesh
-        out = clean_mesh(v, t, **clean)
-        self.last_mesh_clean = out["info"]
-        return out["vertices"], out["triangles"]
-
-    @staticmethod
-    def _check_cull(cull):
-        """the `cull` argument of the two extract calls, checked before the grid is evaluated"""
-        from .mesh_cull import CULL_KEYWORDS, check_arguments
-        if cull is None:
-            return
-        if not isinstance(cull, dict) or not set(cull) <= set(CULL_KEYWORDS):
-            raise ValueError(f"cull must be a dict of cull_mesh keywords {CULL_KEYWORDS}")
-        check_arguments("cull", **cull)
-
-    def _cull_mesh(self, v, t, cull, bound_min, bound_max, resolution):
-        """`cull_mesh` for the two extract calls: `v` in grid-index units is voted on in the cameras' frame (the rescaling of
-        `extract_textured_geometry(to_host=False)`, bit for bit the host's) and comes back culled in grid-index units; `info` kept."""
-        from .mesh_cull import cull_mesh
-        b_min, b_max = (b.detach().to(v.device) for b in (bound_min, bound_max))
-        model = v / torch.full_like(v, float(resolution) - 1.0) * (b_max - b_min).double()[None, :] + b_min.double()[None, :]
-        out = cull_mesh(model, t, **cull)
-        self.last_mesh_cull = out["info"]
-        return v.index_select(0, out["vertex_index"]), out["triangles"]
-
-    @staticmethod
-    def _check_simplify(simplify):
-        """the `simplify` argument of the two extract calls, checked before the grid is evaluated"""
-        from .mesh_simplify import check_arguments
-        if simplify is None:
-            return
-        if not isinstance(simplify, dict) or not set(simplify) <= {"cell_size", "target_triangles", "origin"}:
-            raise ValueError("simplify must be a dict of simplify_mesh keywords (cell_size, target_triangles, origin)")
-        check_arguments("simplify", **simplify)
-
-    def _simplify_mesh(self, v, t, simplify):
-        """`simplify_mesh(v, t, **simplify)` for the two extract calls: the simplified (vertices, triangles); `info` kept."""
-        from .mesh_simplify import simplify_mesh
-        out = simplify_mesh(v, t, **simplify)
-        self.last_mesh_simplify = out["info"]
-        return out["vertices"], out["triangles"]
+        return mesh_pipeline.rescale_to_bounds_host(vertices, bound_min, bound_max, resolution), triangles
 
     # ------------------------------------------------------------------ textured mesh (validate_mesh_texture)
     @torch.no_grad()
@@ -962,13 +863,13 @@ class NeuSRenderer:
                 raise ValueError(f"vertex_attributes: a grid of resolution {resolution} has no cells")
             lo, hi = ([float(b[d]) for d in range(3)] for b in bounds)
             if max_step is None:
-                max_step = sum(((hi[d] - lo[d]) / (resolution - 1)) ** 2 for d in range(3)) ** 0.5
+                max_step = mesh_pipeline.cell_diagonal(lo, hi, resolution)
         if refine > 0 and (max_step is None or not float(max_step) > 0.0):
             raise ValueError("vertex_attributes: refine > 0 needs max_step > 0 (bare points have no cell size to default to)")
         src = grid_vertices if grid_vertices is not None else points
         dev = self.sdf_network.lin0.bias.device
         if dev.type != "cuda":
-            raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+            raise RuntimeError(native.NO_CPU_PATH)
         if src.device != dev:
             raise RuntimeError(f"NeuSRenderer: vertices live on {src.device} but the networks on {dev}")
         return runtime.mesh_vertex_attrs(self.desc, self._pack(albedo), points=points, grid_vertices=grid_vertices,
@@ -1002,16 +903,6 @@ class NeuSRenderer:
                              threshold=threshold, albedo=albedo, slab=slab, chunk=chunk, return_samples=return_samples,
                              to_host=to_host)
 
-    @staticmethod
-    def _check_bake(bake):
-        """the `bake` argument of extract_textured_geometry, checked before the grid is evaluated"""
-        from .texture_bake import BAKE_KEYWORDS, check_arguments
-        if bake is None:
-            return
-        if not isinstance(bake, dict) or not set(bake) <= set(BAKE_KEYWORDS):
-            raise ValueError(f"bake must be a dict of bake_textures keywords {BAKE_KEYWORDS}")
-        check_arguments("bake", **bake, need_max_step=False)
-
     @torch.no_grad()
     def extract_textured_geometry(self, bound_min, bound_max, resolution, threshold=0.0, *, sparse=False, margin=1.0,
                                   brick=None, refine=0, max_step=None, chunk=65536, to_host=True, clean=None,
@@ -1039,36 +930,18 @@ class NeuSRenderer:
         `chunk`, `return_samples`; `threshold` defaults to this call's, `max_step` to one cell diagonal); the bake runs last,
         on the final vertices (cleaned, simplified and, where asked for, refined), and adds `uv` [T,3,2], `albedo_image`,
         `normal_image` and `bake` (the rest of `bake_textures`' result) to the dict.  None (default): nothing is added."""
-        from .mcubes import marching_cubes
-        self._check_clean(clean)
-        self._check_simplify(simplify)
-        self._check_bake(bake)
-        self._check_cull(cull)
+        mesh_pipeline.check_options(clean=clean, simplify=simplify, bake=bake, cull=cull)
         res = int(resolution)
-        if sparse:
-            u, self.last_sparse_grid = self.extract_fields_sparse(bound_min, bound_max, res, threshold, brick, margin,
-                                                                  to_host=False)
-        else:
-            u = self.extract_fields(bound_min, bound_max, res, to_host=False)
-        v, t = marching_cubes(u, threshold)
-        del u
-        if clean is not None:
-            v, t = self._clean_mesh(v, t, clean)
-        if cull is not None:
-            v, t = self._cull_mesh(v, t, cull, bound_min, bound_max, res)
-        if simplify is not None:
-            v, t = self._simplify_mesh(v, t, simplify)
+        v, t = mesh_pipeline.device_mesh(self, bound_min, bound_max, res, threshold, sparse, brick, margin,
+                                         {"clean": clean, "simplify": simplify, "cull": cull})
         at = self.vertex_attributes(grid_vertices=v, bounds=(bound_min, bound_max), resolution=res, threshold=threshold,
                                     refine=refine, max_step=max_step, chunk=chunk)
         if int(refine) > 0:
             vertices = at["points"].double()
         elif to_host:   # extract_geometry's rescaling, on the host as there
-            b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
-            vertices = v.cpu().numpy() / (res - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
-        else:           # the same expression on the device: float64, the box's extent taken in the bounds' precision first; an
-            #             element-wise division (a division by a Python scalar is a multiplication by its reciprocal there)
-            b_min, b_max = (b.detach().to(v.device) for b in (bound_min, bound_max))
-            vertices = v / torch.full_like(v, res - 1.0) * (b_max - b_min).double()[None, :] + b_min.double()[None, :]
+            vertices = mesh_pipeline.rescale_to_bounds_host(v.cpu().numpy(), bound_min, bound_max, res)
+        else:
+            vertices = mesh_pipeline.rescale_to_bounds_device(v, bound_min, bound_max, res)
         out = {"vertices": vertices, "triangles": t, "normals": at["normal"], "sdf": at["sdf"]}
         if "albedo" in at:
             out["albedo"], out["colors"] = at["albedo"], at["rgb"]
@@ -1077,8 +950,7 @@ class NeuSRenderer:
             kw = dict(bake)
             kw.setdefault("threshold", threshold)
             if kw.get("max_step") is None:
-                lo, hi = ([float(b[d]) for d in range(3)] for b in (bound_min, bound_max))
-                kw["max_step"] = sum(((hi[d] - lo[d]) / (res - 1)) ** 2 for d in range(3)) ** 0.5
+                kw["max_step"] = mesh_pipeline.cell_diagonal(bound_min, bound_max, res)
             final = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(vertices).to(t.device)
             baked = self.bake_textures(final, t, to_host=to_host, **kw)
         if to_host:

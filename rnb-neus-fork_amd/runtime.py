@@ -8,7 +8,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import native
-from .fields import RenderingNetwork, SDFNetwork, _mlp_struct, model_desc
+from .fields import RenderingNetwork, SDFNetwork, mlp_struct, model_desc
 
 
 def _require_cuda(t, name):
@@ -32,8 +32,8 @@ def pack_weights(desc, sdf: SDFNetwork | None, color: RenderingNetwork | None, d
     network are zeros instead of uninitialised memory)."""
     lib = native.load()
     packed = (torch.zeros if zero else torch.empty)(packed_floats(desc), dtype=torch.float32, device=device)
-    sp = _mlp_struct(sdf.lins(), sdf.weight_norm) if sdf is not None else None
-    cp = _mlp_struct(color.lins(), color.weight_norm) if color is not None else None
+    sp = mlp_struct(sdf.lins(), sdf.weight_norm) if sdf is not None else None
+    cp = mlp_struct(color.lins(), color.weight_norm) if color is not None else None
     with native.on_device(packed) as stream:
         native.check(lib.rnb_weightnorm_fwd(C.byref(desc), C.byref(sp) if sp is not None else None,
                                             C.byref(cp) if cp is not None else None, native.ptr(packed), stream))
@@ -41,9 +41,7 @@ def pack_weights(desc, sdf: SDFNetwork | None, color: RenderingNetwork | None, d
 
 
 def points_workspace(desc, n, device):
-    b = C.c_int64()
-    native.check(native.load().rnb_points_workspace_bytes(C.byref(desc), n, C.byref(b)))
-    return torch.empty(b.value, dtype=torch.uint8, device=device)
+    return native.workspace("points", device, C.byref(desc), n)
 
 
 def sdf_forward(desc, packed, pts, with_feature):
@@ -128,9 +126,7 @@ def mesh_vertex_attrs(desc, packed, points=None, grid_vertices=None, bound_min=N
     a.gradient_out, a.normal_out = native.ptr(out["gradient"]), native.ptr(out["normal"])
     a.albedo_out, a.rgb_out = native.ptr(out.get("albedo")), native.ptr(out.get("rgb"))
     lib = native.load()
-    nbytes = C.c_int64()
-    native.check(lib.rnb_mesh_vertex_workspace_bytes(C.byref(desc), chunk, a.flags, C.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ws = torch.empty(native.workspace_bytes("mesh_vertex", C.byref(desc), chunk, a.flags), dtype=torch.uint8, device=dev)
     native.same_device(packed, gv, pts)
     with native.on_device(dev) as stream:
         native.check(lib.rnb_mesh_vertex_attrs(C.byref(desc), native.ptr(packed), C.byref(a), chunk, native.ptr(ws),
@@ -209,9 +205,7 @@ def standalone_color(color: RenderingNetwork, pts, normals, feats):
 # (rnb_sdf_backward / rnb_color_backward), + rnb_weightnorm_bwd to the leaves, as in renderer._FinePass
 # ---------------------------------------------------------------------------------------------------------------------
 def points_grad_workspace(desc, n, flags, device):
-    b = C.c_int64()
-    native.check(native.load().rnb_points_grad_workspace_bytes(C.byref(desc), n, flags, C.byref(b)))
-    return torch.empty(b.value, dtype=torch.uint8, device=device)
+    return native.workspace("points_grad", device, C.byref(desc), n, flags)
 
 
 def _leaf_grads(desc, net, packed_grad, color):
@@ -222,8 +216,8 @@ def _leaf_grads(desc, net, packed_grad, color):
     for p in leaves:
         views[id(p)] = flat[off:off + p.numel()]
         off += p.numel()
-    params = _mlp_struct(net.lins(), net.weight_norm)
-    grads = _mlp_struct(net.lins(), net.weight_norm, grads=views)
+    params = mlp_struct(net.lins(), net.weight_norm)
+    grads = mlp_struct(net.lins(), net.weight_norm, grads=views)
     sp, sg = (None, None) if color else (C.byref(params), C.byref(grads))
     cp, cg = (C.byref(params), C.byref(grads)) if color else (None, None)
     with native.on_device(packed_grad) as stream:

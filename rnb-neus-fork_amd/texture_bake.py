@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import native, runtime
-from .mesh_clean import _check_sizes
+from .mesh_args import check_mesh
 
 DEFAULT_CHART = 8
 MAX_CHART = 255
@@ -117,16 +117,14 @@ def bake_textures(renderer, vertices, triangles, *, size=None, chart=None, refin
         raise ValueError(f"{who}: albedo=True on a renderer without an albedo network")
     if vertices is None:
         raise ValueError(f"{who}: vertices is None")
-    V = _check_sizes(who, triangles, None, vertices)
+    check_mesh(who, triangles, None, vertices)
     T = triangles.shape[0]
     lay = atlas_layout(T, size, chart)
     n_s = lay.samples_per_triangle
     N = T * n_s
     if N >= 2 ** 31:
         raise ValueError(f"{who}: {T} triangles x {n_s} samples is not below 2^31: use a smaller chart")
-    dev = native.same_device(triangles, vertices)
-    if dev is None:
-        raise RuntimeError("librnbneus_hip.so works on GPU tensors only (there is no CPU path)")
+    dev = native.gpu_device(triangles, vertices)
     vts, tri = vertices.detach().contiguous(), triangles.detach().contiguous()
     f32 = dict(dtype=torch.float32, device=dev)
     normal = torch.empty(N, 3, **f32)

@@ -201,7 +201,10 @@ def test_python_argument_checks_fire_on_the_host():
     with pytest.raises(RuntimeError, match="GPU tensors only"):                  # valid arguments: there is no CPU path
         R.cull_mesh(v, t, projections=P, eyes=e, masks=masks)
     # the renderer's cull=: the same checks, before the grid is evaluated
-    check = R.NeuSRenderer._check_cull
+    from rnb_neus_fork_amd.mesh_pipeline import check_options
+
+    def check(cull):
+        check_options(cull=cull)
     check(None)
     check({"projections": P, "eyes": e, "masks": masks, "min_seen": 2, "rule": "any"})
     for bad, match in (({"rule": "all"}, "no cameras"), ({"projections": P, "eyes": e, "rule": "some"}, "rule"),
