@@ -637,6 +637,72 @@ int rnb_mesh_simplify_emit(const double* vertices, int64_t n_vertices, const int
                            int64_t n_vertices_out, int64_t n_triangles_out, double* vertices_out, int32_t* triangles_out,
                            int64_t* vertex_index, int32_t* vertex_cluster, int64_t* triangle_index, rnb_stream_t stream);
 
+/* ---- Mesh topology audit: edges, boundaries, watertightness ---------------------------------------------------
+ * What the stages that change connectivity (culling, clustering, a surface that leaves the box) did to a mesh: is it closed,
+ * how many holes, is it oriented consistently — on the device, defined bit for bit (tests/mesh_topology_ref.py restates it
+ * in numpy).
+ *   triangles [T,3] int32, V vertices, optionally vertices [V,3] float64; 0 <= V <= 2^31 - 1, 0 <= T <= 1,431,655,764
+ *   (3 T <= 2^32 - 4: a half-edge index fits a 32-bit table slot).
+ * Definition.
+ *   Triangle classes    INVALID: an index outside [0, V) — every index is checked before it is used as an address.  A valid
+ *                       triangle is DEGENERATE when two of its indices are equal.  The others are PROPER: only they have edges.
+ *   Half-edges          proper triangle t = (a, b, c) has the half-edges 3t + 0 = (a, b), 3t + 1 = (b, c), 3t + 2 = (c, a).
+ *   Edge key            the undirected edge of half-edge (p, q) has the key min(p, q) * 2^31 + max(p, q); the half-edge is
+ *                       FORWARD when p < q, else BACKWARD.  n_fwd / n_bwd of an edge count its forward / backward half-edges.
+ *   Edge classes        BOUNDARY n_fwd + n_bwd == 1; MANIFOLD n_fwd == n_bwd == 1; FLIPPED (2, 0) or (0, 2): two triangles
+ *                       that disagree about the orientation; NON-MANIFOLD three or more uses.
+ *   Leader              the smallest half-edge index of an edge.  Edges are listed in increasing order of leader (no sort).
+ *   Triangle flags      uint8: 1 = has a boundary edge, 2 = a flipped edge, 4 = a non-manifold edge, 8 = degenerate, 16 = invalid.
+ *   Vertex flags        uint8: 1 = on a boundary edge, 2 = on a flipped edge, 4 = on a non-manifold edge, 8 = named by no
+ *                       proper triangle.
+ *   Boundary components the classes of the transitive closure over the vertices a boundary edge joins, numbered in increasing
+ *                       order of their smallest vertex; boundary_labels[v] = -1 off the boundary.  boundary_degree[v] = the
+ *                       number of boundary edges at v; the boundary is SIMPLE when that is 2 at every boundary vertex: then
+ *                       every boundary component is one closed loop, one hole.
+ *   Component table     per component of rnb_mesh_components' labels (unchanged), int64 [C,8]: [0..3] boundary, manifold,
+ *                       flipped, non-manifold edges (an edge belongs to the component of its smaller vertex), [4] proper and
+ *                       [5] degenerate triangles (the component of the first corner), [6] boundary components (that of their
+ *                       smallest vertex; -1 when the count made none), [7] vertices a proper triangle names.
+ *   Signed volume       with vertices: the sum over the component's proper triangles of term = (((x0 cx + y0 cy) + z0 cz) / 6),
+ *                       cx = y1 z2 - z1 y2, cy = z1 x2 - x1 z2, cz = x1 y2 - y1 x2, every product, sum and the division
+ *                       rounded on its own.  Accumulated like the area of rnb_mesh_component_stats, signed: a 128-bit
+ *                       two's-complement integer in units of 2^(e_c - 54), e_c the exponent of the component's largest |term|
+ *                       (each term rounded to that unit: at most 2^-55 of the largest per triangle), converted with one
+ *                       rounding — bit-reproducible from run to run, no floating-point atomic.  NaN when a proper triangle
+ *                       of the component has a non-finite corner or a non-finite term.  It is the ENCLOSED volume only for
+ *                       a closed, consistently oriented component; its sign is the orientation (positive: counter-clockwise
+ *                       seen from outside).
+ *   NOT detected        vertex-manifoldness: a vertex where two fans touch (a "bow-tie") has only manifold edges.  Duplicate
+ *                       triangles show only through their edges (non-manifold, or flipped for a reversed copy of a
+ *                       boundary triangle).
+ * Three calls in ONE workspace of rnb_mesh_topology_workspace_bytes(V, T) bytes (a host function of the sizes alone):
+ *   rnb_mesh_topology_count       counts (device int64 [8]): E, boundary, manifold, flipped, non-manifold edges, degenerate
+ *                                 triangles, invalid triangles, boundary components; tri_flags [T], vert_flags [V];
+ *                                 boundary_labels [V] and boundary_degree [V] int32, both given or both NULL: with NULL no
+ *                                 boundary component is made and counts[7] = -1.  (counts[0] = -1: the edge table filled up,
+ *                                 which its sizing excludes.)
+ *   -- the caller reads counts and allocates the outputs --
+ *   rnb_mesh_topology_emit        same mesh and workspace, reading what the count left: edges [E,2] int32 (min, max), edge_use
+ *                                 [E,2] int32 (n_fwd, n_bwd), edge_triangle [E] int32 (the leader's triangle), in leader order.
+ *   rnb_mesh_topology_components  labels [V], C of rnb_mesh_components and the workspace of the count: table [C,8] int64 and,
+ *                                 with vertices != NULL, volume [C] float64.  It leaves what the emit reads alone.
+ * The edge table is the open-addressing table of the simplification (32-bit slots holding a half-edge index, two slots per
+ * half-edge, the argument in csrc/mesh_simplify.hip), the boundary components the lock-free union-find of the cleanup;
+ * integer atomics only: no result depends on the schedule.
+ * RNB_E_INVALID before any launch: V or T out of range, n_edges outside [0, 3T], n_components outside [0, V].  RNB_E_NULL: a
+ * required pointer (the workspace included) is NULL.  RNB_E_WORKSPACE: workspace_bytes below the query's answer.  Nothing is
+ * allocated and no device-wide synchronisation happens inside these calls. */
+int rnb_mesh_topology_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int64_t* bytes);
+int rnb_mesh_topology_count(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* workspace,
+                            size_t workspace_bytes, int64_t* counts, uint8_t* tri_flags, uint8_t* vert_flags,
+                            int32_t* boundary_labels, int32_t* boundary_degree, rnb_stream_t stream);
+int rnb_mesh_topology_emit(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* workspace,
+                           size_t workspace_bytes, int64_t n_edges, int32_t* edges, int32_t* edge_use, int32_t* edge_triangle,
+                           rnb_stream_t stream);
+int rnb_mesh_topology_components(const int32_t* triangles, int64_t n_triangles, const double* vertices, int64_t n_vertices,
+                                 const int32_t* labels, int64_t n_components, void* workspace, size_t workspace_bytes,
+                                 int64_t* table, double* volume, rnb_stream_t stream);
+
 /* ---- Mesh evaluation: triangle bins, closest points on a mesh, area-weighted surface samples ----------------
  * What a reconstruction is judged by — how far is this mesh from that one (Chamfer, F-score) — needs two things for
  * many points at once: the exact nearest point ON a triangle mesh, and points spread evenly over a surface.  Both work

@@ -42,12 +42,14 @@
 // Termination.  Fewer than cap / 2 + 1 slots are ever filled (one per distinct key), so every walk meets an empty slot
 // or its own key after at most cap steps; the loop is bounded by cap all the same, and a walk that used them up would set
 // bit 2 of counts[4] and return.  No thread waits for another: there is no spin, no lock.
+// The loop itself is mesh_table_insert of mesh_table.hip.h, which mesh_topology.hip uses for its edge table.
 #include "mesh_common.hip.h"
+#include "mesh_table.hip.h"
 #include "scan.hip.h"
 
 namespace rnb {
 
-constexpr unsigned kSpEmpty = 0xffffffffu;
+constexpr unsigned kSpEmpty = kTabEmpty;
 constexpr unsigned long long kSpNoKey = ~0ull;
 constexpr int kMkThreads = kScanThreads;   // the block of every kernel here
 enum { SP_BAD_INDEX = 1, SP_BAD_VERTEX = 2, SP_TABLE_FULL = 4 };
@@ -80,11 +82,7 @@ struct SpWs {
   uint64_t cap_v, cap_t;
 };
 
-static uint64_t sp_capacity(int64_t n) {
-  uint64_t c = 64;
-  while (c < 2 * (uint64_t)n) c <<= 1;
-  return c;
-}
+static uint64_t sp_capacity(int64_t n) { return mesh_table_capacity(n); }
 
 static SpWs sp_carve(Carver& c, int64_t V, int64_t T) {
   SpWs w;
@@ -224,15 +222,9 @@ __global__ __launch_bounds__(kMkThreads) void sp_cluster_kernel(int64_t V, SpWs 
   const int64_t v = (int64_t)blockIdx.x * kMkThreads + threadIdx.x;
   if (v >= V || !w.ref[v]) return;
   const unsigned long long k = w.key[v];
-  const uint64_t mask = w.cap_v - 1;
-  uint64_t s = mesh_mix(k) & mask;
-  for (uint64_t step = 0; step < w.cap_v; ++step, s = (s + 1) & mask) {
-    const unsigned cur = atomicCAS(w.vtab + s, kSpEmpty, (unsigned)v);
-    if (cur != kSpEmpty) {
-      if (w.key[cur] != k) continue;
-      atomicMin(w.vtab + s, (unsigned)v);
-    }
-    w.lead[v] = (int32_t)(uint32_t)s;  // (s < cap_v <= 2^32: kept as its 32 bits until sp_sum_kernel replaces it)
+  const uint64_t s = mesh_table_insert(w.vtab, w.cap_v, (unsigned)v, mesh_mix(k), [&](unsigned cur) { return w.key[cur] == k; });
+  if (s < w.cap_v) {
+    w.lead[v] = (int32_t)(uint32_t)s;    // (s < cap_v <= 2^32: kept as its 32 bits until sp_sum_kernel replaces it)
     return;
   }
   w.ref[v] = 0;                        // (cannot happen: takes no part)
@@ -334,15 +326,12 @@ __global__ __launch_bounds__(kMkThreads) void sp_dedupe_kernel(int64_t T, SpWs w
   if (t >= T) return;
   const int x = w.triple[t * 3], y = w.triple[t * 3 + 1], z = w.triple[t * 3 + 2];
   if (x < 0) return;
-  const uint64_t mask = w.cap_t - 1;
-  uint64_t s = mesh_mix((unsigned long long)x + mesh_mix((unsigned long long)y + mesh_mix((unsigned long long)z))) & mask;
-  for (uint64_t step = 0; step < w.cap_t; ++step, s = (s + 1) & mask) {
-    const unsigned cur = atomicCAS(w.ttab + s, kSpEmpty, (unsigned)t);
-    if (cur != kSpEmpty) {
-      const int32_t* o = w.triple + (int64_t)cur * 3;      // (cur < T: only triangle indices are ever stored)
-      if (o[0] != x || o[1] != y || o[2] != z) continue;
-      atomicMin(w.ttab + s, (unsigned)t);
-    }
+  const unsigned long long h = mesh_mix((unsigned long long)x + mesh_mix((unsigned long long)y + mesh_mix((unsigned long long)z)));
+  const uint64_t s = mesh_table_insert(w.ttab, w.cap_t, (unsigned)t, h, [&](unsigned cur) {
+    const int32_t* o = w.triple + (int64_t)cur * 3;        // (cur < T: only triangle indices are ever stored)
+    return o[0] == x && o[1] == y && o[2] == z;
+  });
+  if (s < w.cap_t) {
     w.tslot[t] = (unsigned)s;
     return;
   }

@@ -301,7 +301,25 @@ _SIGNATURES = {
     "rnb_profile_report": (C.c_int64, [C.c_char_p, C.c_int64]),
 }
 
-EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
+# The mesh topology audit (additive: the ABI stays 5).  A table of its own: tests/test_mesh_pipeline_host.py holds the size
+# queries of `_SIGNATURES` to its own list of arguments, and tests/test_mesh_topology_host.py makes the same checks of
+# `workspace` / `workspace_bytes` for this one.  `signature(name)` looks a symbol up in both.
+_TOPOLOGY_SIGNATURES = {
+    "rnb_mesh_topology_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, _P(C.c_int64)]),
+    "rnb_mesh_topology_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_topology_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_topology_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys()) + tuple(_TOPOLOGY_SIGNATURES.keys())
+
+
+def signature(name):
+    """(restype, argtypes) of an exported symbol"""
+    return _SIGNATURES[name] if name in _SIGNATURES else _TOPOLOGY_SIGNATURES[name]
 
 _lib = None
 
@@ -320,7 +338,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `python __graft_entry__.py` (hipcc, gfx950). "
             "There is no CPU fallback for the renderer.")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name in EXPORTED_SYMBOLS:
+        restype, argtypes = signature(name)
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

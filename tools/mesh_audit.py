@@ -1,0 +1,55 @@
+"""Topology audit of a mesh on the device: is it closed, how many holes, is it oriented consistently
+(`rnb_neus_fork_amd.mesh_topology`; edge-manifoldness — a vertex where two fans touch is not detected).
+
+  python tools/mesh_audit.py MESH.ply [--max-components N]
+
+MESH.ply as `write_ply` writes it.  Prints ONE JSON line: the totals (edges by class, degenerate and invalid triangles,
+boundary components, whether the boundary is simple, `watertight`) and, for the first --max-components components (in order
+of their smallest vertex), euler, genus (-1: undefined), holes, closed, area and signed volume.  Exits with status 2 on a
+mesh with vertex indices out of range (the totals are still printed; there is no per-component part)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("mesh")
+    ap.add_argument("--max-components", type=int, default=32, help="components listed one by one")
+    a = ap.parse_args(argv)
+    sys.path.insert(0, ROOT)
+    import rnb_neus_fork_amd as R
+
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/mesh_audit.py needs a GPU (there is no CPU path)")
+    dev = torch.device("cuda:0")
+    m = R.read_ply(a.mesh)
+    v = torch.from_numpy(np.ascontiguousarray(m["vertices"], dtype=np.float64)).to(dev)
+    t = torch.from_numpy(np.ascontiguousarray(m["triangles"], dtype=np.int32)).to(dev)
+    rep = R.mesh_topology(t, vertices=v)
+    out = {k: rep[k] for k in ("n_edges", "n_boundary", "n_manifold", "n_flipped", "n_nonmanifold", "n_degenerate", "n_invalid",
+                               "n_boundary_components", "boundary_simple")}
+    out.update(mesh=a.mesh, vertices=len(v), triangles=len(t), watertight=R.watertight(rep), build=R.native.build_id(),
+               unused_vertices=int((rep["vertex_flags"] & 8).ne(0).sum()))
+    if rep["n_invalid"] == 0:
+        c = rep["components"]
+        area = R.mesh_components(t, vertices=v)["area"]         # (the same labels: the components of the cleanup)
+        n = min(c["n_components"], a.max_components)
+        cols = {k: c[k][:n].cpu().tolist() for k in ("euler", "genus", "holes", "closed", "volume")}
+        cols["area"] = area[:n].cpu().tolist()
+        out.update(n_components=c["n_components"], n_closed=int(c["closed"].sum()),
+                   components=[{k: cols[k][i] for k in ("euler", "genus", "holes", "closed", "area", "volume")} for i in range(n)])
+    print(json.dumps(out))
+    if rep["n_invalid"]:
+        raise SystemExit(2)
+    return out
+
+
+if __name__ == "__main__":
+    main()
