@@ -703,6 +703,76 @@ int rnb_mesh_topology_components(const int32_t* triangles, int64_t n_triangles, 
                                  const int32_t* labels, int64_t n_components, void* workspace, size_t workspace_bytes,
                                  int64_t* table, double* volume, rnb_stream_t stream);
 
+/* ---- Mesh hole filling: ordered boundary loops, fan caps ------------------------------------------------------------
+ * What closes the holes the audit above reports (csrc/mesh_fill.hip; tests/mesh_fill_ref.py restates it in numpy): the
+ * boundary components as ordered polygons, and a fan of triangles around the centroid of every loop that can be walked.
+ *   Sizes as for the audit: 0 <= V <= 2^31 - 1, 0 <= T <= 1,431,655,764 (half-edge indices are 32-bit).
+ * Definition.
+ *   Boundary half-edge  the single use of a BOUNDARY edge: the half-edge p -> q of a proper triangle whose edge no other
+ *                       half-edge uses.  Invalid and degenerate triangles have none.
+ *   Loops               the boundary components of rnb_mesh_topology_count, in its numbering (by smallest vertex); loop l has
+ *                       the vertices with boundary_labels == l.
+ *   Status              0 SIMPLE: every vertex of the loop has boundary_degree 2, one outgoing and one incoming boundary
+ *                       half-edge: the loop is one closed polygon.  1 TANGLED: some vertex has boundary_degree != 2 (two
+ *                       holes that touch).  2 MISORIENTED: degree 2 everywhere, but some vertex has two outgoing or two
+ *                       incoming half-edges (the surface changes orientation along the hole).
+ *   loop_edges          the boundary edges of the loop: half the sum of its vertices' boundary degrees (= its number of
+ *                       vertices when it is SIMPLE).
+ *   Ordered loops       CSR: loop_offsets [L + 1] int64, loop_vertices [B] int32, B = the number of boundary vertices.  A SIMPLE
+ *                       loop of n vertices w[0..n): w[0] = its smallest vertex, w[j + 1] = the head of the boundary half-edge
+ *                       that leaves w[j].  A loop of another status lists its vertices in increasing index; it is not walked.
+ *   Loop mean           per loop and column the mean of a per-vertex array over the loop's vertices: every value enters a
+ *                       128-bit integer sum in units of 2^(e - 54), e the exponent of the largest |value| of that loop and
+ *                       column (an error of at most 2^-55 of the largest per vertex), the sum is converted with one rounding
+ *                       and divided by n in fp64; for float32 values the quotient is then rounded once to float32.  Integer
+ *                       atomics only: bit-equal from run to run.  NaN when a value of the loop is not finite.  The loop
+ *                       centroid is the loop mean of the vertex positions.
+ *   The cap             a loop is FILLED when it is SIMPLE and has at most max_edges edges (max_edges < 0: no limit).  The
+ *                       filled loops are ranked r = 0 .. F - 1 in loop order.  Loop r adds vertex V + r at its centroid and the
+ *                       n triangles (w[(j + 1) mod n], w[j], V + r), j = 0 .. n - 1, appended in that order, loop after loop,
+ *                       behind the T old triangles; old vertices and triangles are copied bit for bit, invalid and degenerate
+ *                       triangles and unreferenced vertices included.  Each rim edge is used once against its one existing
+ *                       use, so the cap inherits the surface's orientation.
+ * The calls, in the count / emit idiom.  A departure from one count and one emit over one workspace: the loops are found from
+ * what rnb_mesh_topology_count left — its workspace (read, never written) and its boundary_labels / boundary_degree — so
+ * the edge table is built once for an audit and a fill; and the means are a call of their own, which serves the centroid
+ * and any number of attribute arrays.  The fill's own workspace has rnb_mesh_fill_workspace_bytes(V, T) bytes.
+ *   rnb_mesh_loops_count  after rnb_mesh_topology_count on the same mesh with boundary arrays.  counts (device int64 [16]):
+ *                         [0] L loops, [1] B boundary vertices, [2] F filled loops, [3] N new triangles, [4] TANGLED,
+ *                         [5] MISORIENTED loops, [6] SIMPLE loops with more than max_edges edges, [7] the longest filled loop,
+ *                         [8] the longest SIMPLE loop, [9] the vertices of loops that are not SIMPLE, [10] -1 when the audit's
+ *                         edge table had filled up or a value was out of range (its sizing excludes both), [11..15] 0.
+ *   -- the caller reads counts and allocates the outputs --
+ *   rnb_mesh_loops_emit   with L, B, counts[8] and counts[9] as read: loop_offsets, loop_vertices, loop_status [L] uint8,
+ *                         loop_edges [L] int32.  The place of a vertex in a SIMPLE loop comes from pointer jumping over the B
+ *                         compacted boundary vertices, ceil(log2(longest SIMPLE loop)) rounds between two buffers; the other
+ *                         loops' vertices from a stable radix split by loop id, one bit per pass.  No thread walks a loop.
+ *   rnb_mesh_loops_mean   values [V,C] float64 (value_type 0) or float32 (1) -> means [L,C] of the same type, from the CSR
+ *                         arrays alone (a vertex index outside [0, V) in loop_vertices is skipped, never used as an address).
+ *   rnb_mesh_fill_emit    from the CSR arrays, loop_status and loop_centroid [L,3]: vertices_out [V + F,3], triangles_out
+ *                         [T + N,3], filled [F] int32 (the loop of every new vertex), with F = counts[2] and N = counts[3] of a
+ *                         count made with the same max_edges.
+ * RNB_E_INVALID before any launch: a size out of range, V + F or T + N above 2^31 - 1, an unknown value_type.  RNB_E_NULL: a
+ * required pointer (a workspace included) is NULL.  RNB_E_WORKSPACE: workspace_bytes below the query's answer.  Nothing is
+ * allocated and no device-wide synchronisation happens inside these calls; every trip count is fixed before its loop. */
+enum { RNB_LOOP_SIMPLE = 0, RNB_LOOP_TANGLED = 1, RNB_LOOP_MISORIENTED = 2 };
+int rnb_mesh_fill_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int64_t* bytes);
+int rnb_mesh_loops_count(int64_t n_triangles, int64_t n_vertices, const void* topology_workspace,
+                         size_t topology_workspace_bytes, const int32_t* boundary_labels, const int32_t* boundary_degree,
+                         int64_t max_edges, void* workspace, size_t workspace_bytes, int64_t* counts, rnb_stream_t stream);
+int rnb_mesh_loops_emit(int64_t n_triangles, int64_t n_vertices, const int32_t* boundary_labels, void* workspace,
+                        size_t workspace_bytes, int64_t n_loops, int64_t n_boundary_vertices, int64_t longest_simple,
+                        int64_t n_unwalked, int64_t* loop_offsets, int32_t* loop_vertices, uint8_t* loop_status,
+                        int32_t* loop_edges, rnb_stream_t stream);
+int rnb_mesh_loops_mean(const void* values, int32_t value_type, int64_t n_vertices, int64_t n_columns,
+                        const int64_t* loop_offsets, const int32_t* loop_vertices, int64_t n_loops,
+                        int64_t n_boundary_vertices, void* workspace, size_t workspace_bytes, void* means, rnb_stream_t stream);
+int rnb_mesh_fill_emit(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                       const int64_t* loop_offsets, const int32_t* loop_vertices, const uint8_t* loop_status,
+                       const double* loop_centroid, int64_t n_loops, int64_t n_boundary_vertices, int64_t max_edges,
+                       void* workspace, size_t workspace_bytes, int64_t n_filled, int64_t n_new_triangles,
+                       double* vertices_out, int32_t* triangles_out, int32_t* filled, rnb_stream_t stream);
+
 /* ---- Mesh evaluation: triangle bins, closest points on a mesh, area-weighted surface samples ----------------
  * What a reconstruction is judged by — how far is this mesh from that one (Chamfer, F-score) — needs two things for
  * many points at once: the exact nearest point ON a triangle mesh, and points spread evenly over a surface.  Both work

@@ -27,6 +27,7 @@ from .texture_bake import AtlasLayout, atlas_layout, atlas_uv, sample_texture  #
 from .mesh_clean import clean_mesh, mesh_components  # noqa: F401
 from .mesh_simplify import simplify_mesh  # noqa: F401
 from .mesh_topology import mesh_topology, watertight  # noqa: F401
+from .mesh_fill import boundary_loops, fill_holes  # noqa: F401
 from .mesh_eval import MeshIndex, mesh_distance, sample_surface  # noqa: F401
 from .mesh_raycast import mesh_view_maps, normal_angular_error  # noqa: F401
 from .mesh_clean import compact_triangles  # noqa: F401
@@ -37,7 +38,8 @@ __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetw
            "marching_cubes", "CameraRefinement", "mesh_io", "write_ply", "read_ply", "mesh_components", "clean_mesh",
            "MeshIndex", "sample_surface", "mesh_distance", "mesh_view_maps", "normal_angular_error", "simplify_mesh",
            "atlas_layout", "atlas_uv", "AtlasLayout", "sample_texture", "write_obj", "read_obj", "write_png", "read_png",
-           "cull_mesh", "camera_projections", "binary_masks", "compact_triangles", "mesh_topology", "watertight"]
+           "cull_mesh", "camera_projections", "binary_masks", "compact_triangles", "mesh_topology", "watertight",
+           "boundary_loops", "fill_holes"]
 
 
 def build_from_named_params(mc, params, device):

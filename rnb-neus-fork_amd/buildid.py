@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_SOURCES = ["api.hip", "layout.hip", "layers.hip", "backward.hip", "util.hip", "dw.hip", "weightnorm.hip", "sampling.hip", "composite.hip", "prof.hip", "fused.hip",
                "sweep_mv.hip", "fused_bwd.hip", "color_h2.hip", "bf16_sweeps.hip", "bf16_color.hip", "bf16_dw.hip", "train.hip", "raygen.hip", "mcubes.hip",
                "sparse_grid.hip", "mesh_attrs.hip", "mesh_clean.hip", "mesh_eval.hip", "mesh_raycast.hip", "mesh_simplify.hip",
-               "texture_bake.hip", "mesh_cull.hip", "mesh_topology.hip"]
+               "texture_bake.hip", "mesh_cull.hip", "mesh_topology.hip", "mesh_fill.hip"]
 COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 EXTRA_FLAGS = {
     # sampling.hip must round like the reference's separate PyTorch ops (no fused multiply-add contraction)
@@ -38,6 +38,8 @@ EXTRA_FLAGS = {
     "mesh_cull.hip": ["-ffp-contract=off"],
     # the signed-volume term as tests/mesh_topology_ref.py evaluates it, one rounding per operation
     "mesh_topology.hip": ["-ffp-contract=off"],
+    # the loop means: the conversion of the integer sum and the division by n, each rounded on its own
+    "mesh_fill.hip": ["-ffp-contract=off"],
 }
 
 

@@ -29,79 +29,16 @@
 // the table passes.
 #include "mesh_common.hip.h"
 #include "mesh_table.hip.h"
+#include "mesh_topology.hip.h"
 #include "scan.hip.h"
 #include "union_find.hip.h"
 
 namespace rnb {
 
 constexpr int kTpThreads = kScanThreads;
-constexpr unsigned long long kTpNoKey = ~0ull;
-constexpr unsigned kTpNone = 0xffffffffu;
-constexpr int64_t kTpMaxTriangles = 1431655764;        // 3 T <= 2^32 - 4: a half-edge index fits a 32-bit slot, all ones stays free
-enum { TP_BOUNDARY = 1, TP_FLIPPED = 2, TP_NONMANIFOLD = 4, TP_DEGENERATE = 8, TP_INVALID = 16 };   // triangle flags
-enum { TP_V_UNUSED = 8 };                                                                            // vertex flags: 1, 2, 4 as above
-enum { TP_INFO_BOUNDARY = 0, TP_INFO_ERROR = 1 };   // words of TpWs::info: boundary components were made; a table walk failed
 // columns of the per-component table
 enum { TP_C_BOUNDARY = 0, TP_C_MANIFOLD, TP_C_FLIPPED, TP_C_NONMANIFOLD, TP_C_PROPER, TP_C_DEGENERATE, TP_C_HOLES, TP_C_VERTICES };
 enum { TP_VOL_NAN = 1 };
-
-struct TpWs {
-  unsigned* info;             // [64]  see TP_INFO_*
-  unsigned long long* key;    // [3T]  edge key of the half-edge, all ones = its triangle is not proper
-  unsigned* lead;             // [3T]  smallest half-edge of the same edge, all ones = none
-  unsigned* nfwd;             // [3T]  (by leader) forward uses
-  unsigned* nbwd;             // [3T]  (by leader) backward uses
-  unsigned* tab;              // [cap] the edge table
-  unsigned* bsum;             // block sums of the leader scan
-  unsigned* vword;            // [V]   vertex flag word
-  uint8_t* vref;              // [V]   named by a proper triangle
-  uint8_t* broot;             // [V]   smallest vertex of its boundary component
-  unsigned* rank;             // [V]   dense id of a boundary root
-  unsigned* bsum_v;
-  // the component call's own part (the count and the emit never touch it)
-  unsigned long long* maxbits;  // [V] largest |term| of the component, as bits
-  unsigned long long* lo;       // [V] the fixed-point volume sum, low and high word
-  unsigned long long* hi;
-  unsigned* cflags;             // [V]
-  uint64_t cap;
-};
-
-static TpWs tp_carve(Carver& c, int64_t V, int64_t T) {
-  TpWs w;
-  const int64_t H = 3 * T;
-  w.cap = mesh_table_capacity(H);
-  w.info = c.take<unsigned>(64);
-  w.key = c.take<unsigned long long>(H);
-  w.lead = c.take<unsigned>(H);
-  w.nfwd = c.take<unsigned>(H);
-  w.nbwd = c.take<unsigned>(H);
-  w.tab = c.take<unsigned>((int64_t)w.cap);
-  w.bsum = c.take<unsigned>(scan_pad64(scan_blocks(H)));
-  w.vword = c.take<unsigned>(V);
-  w.vref = c.take<uint8_t>(V);
-  w.broot = c.take<uint8_t>(V);
-  w.rank = c.take<unsigned>(V);
-  w.bsum_v = c.take<unsigned>(scan_pad64(scan_blocks(V)));
-  w.maxbits = c.take<unsigned long long>(V);      // at most one component per vertex
-  w.lo = c.take<unsigned long long>(V);
-  w.hi = c.take<unsigned long long>(V);
-  w.cflags = c.take<unsigned>(V);
-  return w;
-}
-
-__device__ inline void tp_wave_count(long long* counter, bool pred) {
-  const unsigned long long m = __ballot(pred);
-  if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1))
-    atomicAdd((unsigned long long*)counter, (unsigned long long)__popcll(m));
-}
-
-// class bit of an edge used n_fwd times forward and n_bwd times backward (0: manifold)
-__device__ inline unsigned tp_class(unsigned nf, unsigned nb) {
-  const unsigned n = nf + nb;
-  if (n == 1) return TP_BOUNDARY;
-  if (n == 2) return nf == 1 ? 0u : TP_FLIPPED;
-  return TP_NONMANIFOLD;
-}
 
 // the two ends (p, q) of half-edge h = 3 t + k of a proper triangle: corners k and (k + 1) mod 3
 __device__ inline void tp_ends(const int32_t* __restrict__ tri, unsigned h, int* p, int* q) {
@@ -419,20 +356,13 @@ struct TpMaxItem {
   }
 };
 
-// every finite term in units of 2^(e_c - 54), e_c = exponent of the component's largest |term|: |scaled| < 2^55, rounded to
-// nearest (an error of at most 2^-55 of the largest per triangle), sign-extended to 128 bits and added as integers
+// every finite term in units of 2^(e_c - 54), e_c = exponent of the component's largest |term| (mesh_topology.hip.h has the
+// accumulator: wide_scaled, wide_add, wide_to_double)
 struct TpVolAcc {
   unsigned long long lo = 0, hi = 0;
   __device__ void store(const TpBufs& s, int c) const { s.lo[c] = lo; s.hi[c] = hi; }
   __device__ void load(const TpBufs& s, int c) { lo = s.lo[c]; hi = s.hi[c]; }
-  __device__ void flush(const TpBufs& s, int c) const {
-    unsigned long long carry = 0;
-    if (lo) {
-      const unsigned long long old = atomicAdd(s.lo + c, lo);
-      carry = old + lo < old ? 1ull : 0ull;
-    }
-    if (hi + carry) atomicAdd(s.hi + c, hi + carry);
-  }
+  __device__ void flush(const TpBufs& s, int c) const { wide_add(s.lo + c, s.hi + c, lo, hi); }
 };
 struct TpVolItem {
   TpTermSrc src;
@@ -444,7 +374,7 @@ struct TpVolItem {
     if (c < 0) return -1;
     const double tmax = __longlong_as_double((long long)maxbits[c]);
     if (finite && tmax > 0.0) {
-      const long long q = llrint(ldexp(term, 54 - ilogb(tmax)));
+      const long long q = wide_scaled(term, tmax);
       a.lo = (unsigned long long)q;
       a.hi = q < 0 ? ~0ull : 0ull;
     }
@@ -498,34 +428,14 @@ __global__ __launch_bounds__(kTpThreads) void tp_table_init_kernel(TpBufs s, TpW
   }
 }
 
-// the 128-bit two's-complement sum as a double with ONE rounding, times 2^(e_c - 54)
+// the 128-bit two's-complement sum as a double with ONE rounding (wide_to_double)
 __global__ __launch_bounds__(kTpThreads) void tp_volume_kernel(TpBufs s, double* __restrict__ volume) {
   const int64_t c = (int64_t)blockIdx.x * kTpThreads + threadIdx.x;
   if (c >= s.C) return;
   const double tmax = __longlong_as_double((long long)s.maxbits[c]);
   double v = 0.0;
   if (s.flags[c] & TP_VOL_NAN) v = __longlong_as_double(0x7ff8000000000000ll);
-  else if (tmax > 0.0) {
-    unsigned long long lo = s.lo[c], hi = s.hi[c];
-    const bool neg = (hi >> 63) != 0;
-    if (neg) {                                               // magnitude: two's-complement negation
-      lo = ~lo + 1ull;
-      hi = ~hi + (lo == 0 ? 1ull : 0ull);
-    }
-    double m;
-    int shift = 0;
-    if (hi == 0) m = (double)lo;
-    else {                                                   // the top 64 bits, what is below them as a sticky bit
-      const int lz = __clzll((long long)hi);
-      shift = 64 - lz;
-      unsigned long long top = lz ? (hi << lz) | (lo >> (64 - lz)) : hi;
-      const bool sticky = (lz ? (lo << lz) : lo) != 0;
-      top |= sticky ? 1ull : 0ull;
-      m = (double)top;
-    }
-    v = ldexp(m, shift + ilogb(tmax) - 54);
-    if (neg) v = -v;
-  }
+  else if (tmax > 0.0) v = wide_to_double(s.lo[c], s.hi[c], tmax);
   volume[c] = v;
 }
 

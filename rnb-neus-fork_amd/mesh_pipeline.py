@@ -8,7 +8,7 @@ from typing import Callable, NamedTuple, Optional
 
 import torch
 
-from . import mesh_clean, mesh_cull, mesh_simplify, native, texture_bake
+from . import mesh_clean, mesh_cull, mesh_fill, mesh_simplify, native, texture_bake
 from .mcubes import marching_cubes
 
 
@@ -84,11 +84,15 @@ STAGES = (
 # `bake=` of the textured call is checked like a stage's options and is not a stage: it runs on the final, rescaled mesh
 BAKE = Stage("bake", texture_bake.BAKE_KEYWORDS, partial(texture_bake.check_arguments, need_max_step=False),
              f"bake_textures keywords {texture_bake.BAKE_KEYWORDS}")
-_OPTIONS = {s.name: s for s in STAGES + (BAKE,)}
+# `fill=` closes the holes the stages leave: checked like a stage's options, run after the last stage and before the rescale
+# (`run_fill`), and not a row of `STAGES`, whose order and length an existing test holds fixed
+FILL = Stage("fill", mesh_fill.FILL_KEYWORDS, mesh_fill.check_arguments,
+             f"fill_holes keywords {mesh_fill.FILL_KEYWORDS}", info="last_mesh_fill")
+_OPTIONS = {s.name: s for s in STAGES + (BAKE, FILL)}
 
 
 def check_options(**options):
-    """The `clean`, `cull`, `simplify` and `bake` arguments of the extract calls, in the order given and before any grid
+    """The `clean`, `cull`, `simplify`, `bake` and `fill` arguments of the extract calls, in the order given and before any grid
     is evaluated: None, or a dict whose keys are the option's keywords and which its module's checker accepts."""
     for name, value in options.items():
         if value is None:
@@ -109,6 +113,16 @@ def run_stages(renderer, v, t, frame, options):
     return v, t
 
 
+def run_fill(renderer, v, t, fill):
+    """`fill_holes(v, t, **fill)` on device (v, t) in grid-index units when `fill` is a dict, its `info` left on the renderer;
+    (v, t) as they are for None"""
+    if fill is None:
+        return v, t
+    out = mesh_fill.fill_holes(v, t, **fill)
+    setattr(renderer, FILL.info, out["info"])
+    return out["vertices"], out["triangles"]
+
+
 # ------------------------------------------------------------------------------------------------------------- the chain
 def volume(renderer, bound_min, bound_max, res, threshold, sparse, brick, margin, to_host):
     """The SDF grid of the chain: `extract_fields`, or with `sparse` `extract_fields_sparse` (its `info` kept in
@@ -120,10 +134,10 @@ def volume(renderer, bound_min, bound_max, res, threshold, sparse, brick, margin
     return renderer.extract_fields(bound_min, bound_max, res, to_host=to_host)
 
 
-def device_mesh(renderer, bound_min, bound_max, res, threshold, sparse, brick, margin, options):
-    """Volume, native marching cubes and the stages without leaving the device: (v, t) in grid-index units.  The volume is
-    released before the first stage."""
+def device_mesh(renderer, bound_min, bound_max, res, threshold, sparse, brick, margin, options, fill=None):
+    """Volume, native marching cubes, the stages and the hole filling without leaving the device: (v, t) in grid-index
+    units.  The volume is released before the first stage."""
     u = volume(renderer, bound_min, bound_max, res, threshold, sparse, brick, margin, to_host=False)
     v, t = marching_cubes(u, threshold)
     del u
-    return run_stages(renderer, v, t, (bound_min, bound_max, res), options)
+    return run_fill(renderer, *run_stages(renderer, v, t, (bound_min, bound_max, res), options), fill)

@@ -314,12 +314,31 @@ _TOPOLOGY_SIGNATURES = {
                                                C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
-EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys()) + tuple(_TOPOLOGY_SIGNATURES.keys())
+# The hole filling (additive as well), in a table of its own for the same reason; tests/test_mesh_fill_host.py checks its
+# size query.
+_FILL_SIGNATURES = {
+    "rnb_mesh_fill_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, _P(C.c_int64)]),
+    "rnb_mesh_loops_count": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_loops_emit": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int64,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_loops_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rnb_mesh_fill_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+_TABLES = (_SIGNATURES, _TOPOLOGY_SIGNATURES, _FILL_SIGNATURES)
+EXPORTED_SYMBOLS = tuple(name for table in _TABLES for name in table)
 
 
 def signature(name):
     """(restype, argtypes) of an exported symbol"""
-    return _SIGNATURES[name] if name in _SIGNATURES else _TOPOLOGY_SIGNATURES[name]
+    for table in _TABLES:
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 _lib = None
 

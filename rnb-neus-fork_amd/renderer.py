@@ -283,6 +283,7 @@ class NeuSRenderer:
         self.last_mesh_clean = None    # `info` of the last extract_geometry / extract_textured_geometry(clean=...)
         self.last_mesh_simplify = None  # `info` of the last extract_geometry / extract_textured_geometry(simplify=...)
         self.last_mesh_cull = None     # `info` of the last extract_geometry / extract_textured_geometry(cull=...)
+        self.last_mesh_fill = None     # `info` of the last extract_geometry / extract_textured_geometry(fill=...)
 
     # ------------------------------------------------------------------ data parallel
     def set_data_parallel(self, group=None, enabled=True, exact=True):
@@ -771,7 +772,7 @@ class NeuSRenderer:
         return {"max_abs_weight": worst, "layer": where, "limit": 255.0, "ok": bool(worst < 255.0)}
 
     def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, backend=None, sparse=False, margin=1.0,
-                         brick=None, clean=None, simplify=None, cull=None):
+                         brick=None, clean=None, simplify=None, cull=None, fill=None):
         """models/renderer.py:1219-1224 / :27-36: SDF grid + marching cubes + rescaling to the bounding box; returns
         numpy `(vertices [V,3] float64, triangles [T,3])` as the reference does.
         `backend`: "native" — the library's own marching cubes on the volume still resident in HBM
@@ -795,7 +796,10 @@ class NeuSRenderer:
         `cull`: a dict of `mesh_cull.cull_mesh` keywords (`rays` or `projections` / `eyes` / `masks` / `image_size`; `views`,
         `max_outside`, `min_seen`, `occlusion`, `dilate`, `threshold`, `rule`) — what the cameras do not support is removed
         on the device after the cleaning and before the simplification; the votes are taken on the vertices rescaled to the
-        bounding box (the cameras' frame), `info` is kept in `self.last_mesh_cull`.  None (default): no culling."""
+        bounding box (the cameras' frame), `info` is kept in `self.last_mesh_cull`.  None (default): no culling.
+        `fill`: a dict of `mesh_fill.fill_holes` keywords (`max_edges`; `{}` fills every simple loop) — the holes the mesh has
+        after the stages are closed with centroid fans on the device, last before the rescaling; `info` is kept in
+        `self.last_mesh_fill`.  None (default): no filling."""
         if backend is None:
             try:
                 import mcubes  # noqa: F401
@@ -812,19 +816,21 @@ class NeuSRenderer:
         if backend not in ("native", "mcubes"):
             raise ValueError(f"extract_geometry: unknown backend {backend!r}")
         options = {"clean": clean, "simplify": simplify, "cull": cull}
-        mesh_pipeline.check_options(**options)
+        mesh_pipeline.check_options(**options, fill=fill)
         if backend == "mcubes":
             import mcubes
             u = mesh_pipeline.volume(self, bound_min, bound_max, resolution, threshold, sparse, brick, margin, to_host=True)
             vertices, triangles = mcubes.marching_cubes(u, threshold)
-            if any(o is not None for o in options.values()):     # the stages run on the device: the host arrays go up for them
+            if fill is not None or any(o is not None for o in options.values()):     # the stages run on the device: the host arrays go up for them
                 dev = self.sdf_network.lin0.bias.device
                 v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev)
                 t = torch.as_tensor(np.ascontiguousarray(triangles).astype(np.int32)).to(dev)
                 v, t = mesh_pipeline.run_stages(self, v, t, (bound_min, bound_max, resolution), options)
+                v, t = mesh_pipeline.run_fill(self, v, t, fill)
                 vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         else:
-            v, t = mesh_pipeline.device_mesh(self, bound_min, bound_max, resolution, threshold, sparse, brick, margin, options)
+            v, t = mesh_pipeline.device_mesh(self, bound_min, bound_max, resolution, threshold, sparse, brick, margin, options,
+                                             fill)
             vertices, triangles = v.cpu().numpy(), t.cpu().numpy()
         return mesh_pipeline.rescale_to_bounds_host(vertices, bound_min, bound_max, resolution), triangles
 
@@ -906,7 +912,7 @@ class NeuSRenderer:
     @torch.no_grad()
     def extract_textured_geometry(self, bound_min, bound_max, resolution, threshold=0.0, *, sparse=False, margin=1.0,
                                   brick=None, refine=0, max_step=None, chunk=65536, to_host=True, clean=None,
-                                  simplify=None, bake=None, cull=None):
+                                  simplify=None, bake=None, cull=None, fill=None):
         """`validate_mesh_texture` up to the export (exp_runner.py:584-613): SDF grid (dense, or `sparse=True` as in
         `extract_geometry`), the native marching cubes, and `vertex_attributes` on the vertices where marching cubes left
         them — they never leave the device in between.  Returns a dict:
@@ -929,11 +935,14 @@ class NeuSRenderer:
         `bake`: a dict of `bake_textures` keywords (`size`, `chart`, `refine`, `max_step`, `threshold`, `albedo`, `slab`,
         `chunk`, `return_samples`; `threshold` defaults to this call's, `max_step` to one cell diagonal); the bake runs last,
         on the final vertices (cleaned, simplified and, where asked for, refined), and adds `uv` [T,3,2], `albedo_image`,
-        `normal_image` and `bake` (the rest of `bake_textures`' result) to the dict.  None (default): nothing is added."""
-        mesh_pipeline.check_options(clean=clean, simplify=simplify, bake=bake, cull=cull)
+        `normal_image` and `bake` (the rest of `bake_textures`' result) to the dict.  None (default): nothing is added.
+        `fill`: a dict of `mesh_fill.fill_holes` keywords (`max_edges`), as in `extract_geometry`; the filling runs after the
+        last stage and before `vertex_attributes`, so the cap centroids get normals and colours, and `refine > 0` projects
+        them onto the level set, like every other vertex (`info` in `self.last_mesh_fill`).  None (default): no filling."""
+        mesh_pipeline.check_options(clean=clean, simplify=simplify, bake=bake, cull=cull, fill=fill)
         res = int(resolution)
         v, t = mesh_pipeline.device_mesh(self, bound_min, bound_max, res, threshold, sparse, brick, margin,
-                                         {"clean": clean, "simplify": simplify, "cull": cull})
+                                         {"clean": clean, "simplify": simplify, "cull": cull}, fill)
         at = self.vertex_attributes(grid_vertices=v, bounds=(bound_min, bound_max), resolution=res, threshold=threshold,
                                     refine=refine, max_step=max_step, chunk=chunk)
         if int(refine) > 0:

@@ -1,12 +1,15 @@
 """Topology audit of a mesh on the device: is it closed, how many holes, is it oriented consistently
 (`rnb_neus_fork_amd.mesh_topology`; edge-manifoldness — a vertex where two fans touch is not detected).
 
-  python tools/mesh_audit.py MESH.ply [--max-components N]
+  python tools/mesh_audit.py MESH.ply [--max-components N] [--fill OUT.ply [--max-edges N]]
 
 MESH.ply as `write_ply` writes it.  Prints ONE JSON line: the totals (edges by class, degenerate and invalid triangles,
 boundary components, whether the boundary is simple, `watertight`) and, for the first --max-components components (in order
 of their smallest vertex), euler, genus (-1: undefined), holes, closed, area and signed volume.  Exits with status 2 on a
-mesh with vertex indices out of range (the totals are still printed; there is no per-component part)."""
+mesh with vertex indices out of range (the totals are still printed; there is no per-component part).
+--fill OUT.ply closes the holes with `fill_holes` (simple loops of at most --max-edges edges; default: any length), writes the
+filled mesh (vertex colours and normals are not carried over) and adds to the JSON line a "fill" object, the `info` of the
+fill, and under "after" the audit of the filled mesh."""
 import argparse
 import json
 import os
@@ -18,10 +21,34 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def audit(R, v, t, max_components, named=None):
+    """the audit of device (v, t) as a dict, and the report it was made from; `named`: the file's name, for the line's head"""
+    rep = R.mesh_topology(t, vertices=v)
+    out = {k: rep[k] for k in ("n_edges", "n_boundary", "n_manifold", "n_flipped", "n_nonmanifold", "n_degenerate", "n_invalid",
+                               "n_boundary_components", "boundary_simple")}
+    if named is not None:
+        out.update(mesh=named)
+    out.update(vertices=len(v), triangles=len(t), watertight=R.watertight(rep))
+    if named is not None:
+        out.update(build=R.native.build_id())
+    out.update(unused_vertices=int((rep["vertex_flags"] & 8).ne(0).sum()))
+    if rep["n_invalid"] == 0:
+        c = rep["components"]
+        area = R.mesh_components(t, vertices=v)["area"]         # (the same labels: the components of the cleanup)
+        n = min(c["n_components"], max_components)
+        cols = {k: c[k][:n].cpu().tolist() for k in ("euler", "genus", "holes", "closed", "volume")}
+        cols["area"] = area[:n].cpu().tolist()
+        out.update(n_components=c["n_components"], n_closed=int(c["closed"].sum()),
+                   components=[{k: cols[k][i] for k in ("euler", "genus", "holes", "closed", "area", "volume")} for i in range(n)])
+    return out, rep
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("mesh")
     ap.add_argument("--max-components", type=int, default=32, help="components listed one by one")
+    ap.add_argument("--fill", metavar="OUT.ply", help="close the holes and write the filled mesh here")
+    ap.add_argument("--max-edges", type=int, default=None, help="with --fill: leave longer loops open")
     a = ap.parse_args(argv)
     sys.path.insert(0, ROOT)
     import rnb_neus_fork_amd as R
@@ -32,19 +59,12 @@ def main(argv=None):
     m = R.read_ply(a.mesh)
     v = torch.from_numpy(np.ascontiguousarray(m["vertices"], dtype=np.float64)).to(dev)
     t = torch.from_numpy(np.ascontiguousarray(m["triangles"], dtype=np.int32)).to(dev)
-    rep = R.mesh_topology(t, vertices=v)
-    out = {k: rep[k] for k in ("n_edges", "n_boundary", "n_manifold", "n_flipped", "n_nonmanifold", "n_degenerate", "n_invalid",
-                               "n_boundary_components", "boundary_simple")}
-    out.update(mesh=a.mesh, vertices=len(v), triangles=len(t), watertight=R.watertight(rep), build=R.native.build_id(),
-               unused_vertices=int((rep["vertex_flags"] & 8).ne(0).sum()))
-    if rep["n_invalid"] == 0:
-        c = rep["components"]
-        area = R.mesh_components(t, vertices=v)["area"]         # (the same labels: the components of the cleanup)
-        n = min(c["n_components"], a.max_components)
-        cols = {k: c[k][:n].cpu().tolist() for k in ("euler", "genus", "holes", "closed", "volume")}
-        cols["area"] = area[:n].cpu().tolist()
-        out.update(n_components=c["n_components"], n_closed=int(c["closed"].sum()),
-                   components=[{k: cols[k][i] for k in ("euler", "genus", "holes", "closed", "area", "volume")} for i in range(n)])
+    out, rep = audit(R, v, t, a.max_components, named=a.mesh)
+    if a.fill:
+        filled = R.fill_holes(v, t, max_edges=a.max_edges)
+        R.write_ply(a.fill, filled["vertices"].cpu().numpy(), filled["triangles"].cpu().numpy())
+        out["fill"] = dict(filled["info"], mesh=a.fill)
+        out["after"] = audit(R, filled["vertices"], filled["triangles"], a.max_components)[0]
     print(json.dumps(out))
     if rep["n_invalid"]:
         raise SystemExit(2)
